@@ -3,16 +3,20 @@
 3-D regulariser -> soft argmin, with its 2-D feature net) at the ETH3D shape 768x1152, 4 source views,
 256 depth planes, fp32 (BASELINE.json configs[2]), on N GPUs of one node as independent replicas.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 A step = one forward pass (one key view + V sources -> one depth map) on inputs already resident in HBM.
 Frames are sharded over the ranks (each rank runs K steps on its own frames, weak scaling); there is no
 data-path collective — the process group is only used for the barrier and the max-over-ranks time.
-Rank 0 prints ONE JSON line with the contract fields plus `roofline` (warp+variance kernel, HIP events
-around every launch of it inside the timed region), `cpu_baseline` (the CPU oracle port timed on this
-host, N=1 only) and `path_a` (the robust_mvd model at the same shape, same protocol).
+Rank 0 prints ONE JSON line with the contract fields.  A plain run measures the headline and nothing else;
+--full adds `roofline` (warp+variance kernel, HIP events around every launch of it inside the timed region,
+and the measured copy / streaming-store peaks), the extra blocks (other arithmetic, frames in flight, h2d,
+`path_a`: the robust_mvd model at the same shape, same protocol) and `cpu_baseline` (the CPU oracle port
+timed on this host, N=1 only).
+--dump-outputs DIR: rank 0 writes what the last timed step returned (the model's `pred` and `aux` tensors) as
+DIR/<name>.npy in float32; weights and frames are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -91,25 +95,49 @@ class StubModel:
         return {"depth": sum(float(im.double().mean()) for im in images)}, {}
 
 
-def timed_loop(model, samples, steps, warmup, world, dev, arm=None, cdev=None):
-    """W untimed + K timed forwards bracketed by barrier + synchronize; returns seconds (max over ranks)."""
+def timed_loop(model, samples, steps, warmup, world, dev, arm=None, cdev=None, last=None):
+    """W untimed + K timed forwards bracketed by barrier + synchronize; returns seconds (max over ranks).
+    `last` (a list): receives what the last timed forward returned."""
     import torch.distributed as dist
     from robustmvd_amd.sharding import timed_region
 
     def run(n, armed):
+        out = None
         with torch.no_grad():
             for i in range(n):
                 if armed and arm is not None:
                     arm(i)
-                model(**samples[i % len(samples)])
+                out = model(**samples[i % len(samples)])
+        return out
+
+    def timed():
+        out = run(steps, True)
+        if last is not None:
+            last.append(out)
 
     # set-up, not measurement: the first calls load code objects, run MIOpen's solver search for the adjacent 2-D
     # convolutions and bring the allocator and the clocks to steady state; then the W warm-up steps of the contract
     run(SETTLE_FORWARDS, False)
     device_sync(dev)
     run(warmup, False)
-    return timed_region(lambda: run(steps, True), sync=lambda: device_sync(dev),
-                        dist=dist if world > 1 else None, device=cdev or dev)
+    return timed_region(timed, sync=lambda: device_sync(dev), dist=dist if world > 1 else None, device=cdev or dev)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(model_output, out_dir):
+    """Writes a forward's (pred, aux) dicts as out_dir/<key>.npy (aux keys as aux_<key>), float32."""
+    pred, aux = model_output
+    arrays = dict(pred)
+    arrays.update({"aux_" + k: v for k, v in aux.items()})
+    arrays = {k: torch.as_tensor(v).detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def measured_copy_gbs(dev):
@@ -186,9 +214,12 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=2, help="index into BASELINE.json configs (default 2 = headline)")
     ap.add_argument("--fp32", action="store_true", help="run configs[3] on the fp32 path instead of its named fp16-feature variant")
-    ap.add_argument("--include-h2d", action="store_true", help="(kept for compatibility: h2d_inclusive is on by default)")
+    ap.add_argument("--include-h2d", action="store_true", help="(kept for compatibility: h2d_inclusive is on by default with --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-path-a", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the extra blocks and the CPU baseline (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float32)")
     args = ap.parse_args(argv)
 
     rank = int(os.environ.get("RANK", "0"))
@@ -237,9 +268,9 @@ def main(argv=None):
     else:
         samples = [adapted_sample(model, f, H, W, V, (np.float32(0.5), np.float32(10.0))) for f in my_frames]
 
-    # HIP events around every warp+variance launch inside the timed region
+    # --full: HIP events around every warp+variance launch inside the timed region (the roofline block)
     lib, ev = None, []
-    if not stub:
+    if not stub and args.full:
         from robustmvd_amd import _lib as L
         lib = L.load()
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
@@ -248,11 +279,15 @@ def main(argv=None):
         torch.cuda.synchronize(dev)
 
     def arm(i):
-        if stub or os.environ.get("MVD_BENCH_NO_ARM"):
+        if stub or not args.full or os.environ.get("MVD_BENCH_NO_ARM"):
             return
         lib.mvd_arm_kernel_timing(ev[i][0].cuda_event, ev[i][1].cuda_event)
 
-    dt = timed_loop(model, samples, args.steps, args.warmup, world, dev, arm, cdev)
+    last = []
+    dt = timed_loop(model, samples, args.steps, args.warmup, world, dev, arm, cdev, last)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last[0], args.dump_outputs)
+    del last
     k3_ms = float(np.mean([a.elapsed_time(b) for a, b in ev])) if ev else float("nan")
     # SURVEY.md 8(d), batch 1 per launch; the fp16-feature variant moves 2-byte features and a 2-byte volume
     k3_bytes = (2.0 if half else 4.0) * ((V + 1) * C * h * w + C * D * h * w)
@@ -274,7 +309,7 @@ def main(argv=None):
     }
     if stub:
         out["stub"] = "MVD_BENCH_STUB=1: control-flow rehearsal on CPU, the model is a stand-in; not a measurement"
-    if rank == 0 and not stub:
+    if rank == 0 and not stub and args.full:
         # `traffic` is NOT measured in this run: PMC counters need rocprofv3 passes of their own.  It is the constant
         # the last committed counter passes gave for this config (profiles/k3_traffic.json, with its source files)
         traffic, traffic_src = None, None
@@ -324,11 +359,12 @@ def main(argv=None):
                             "ms_per_step": dtp / args.steps * 1e3,
                             "note": "same workload and step count, two HIP streams per process; not the headline value"}
 
-    # Multi-rank runs (the driver's scaling curve) measure the headline and h2d_inclusive (which guards itself against a lone
-    # failing rank): the other extra blocks contain barriers too, so a failure on ONE rank would hang the others and lose the
-    # whole line.  MVD_BENCH_EXTRAS=1 forces all of them on, =0 turns every extra off at one rank too (clean kernel statistics
-    # under rocprofv3).
-    extras = ((world == 1 and os.environ.get("MVD_BENCH_EXTRAS", "") != "0") or os.environ.get("MVD_BENCH_EXTRAS", "0") == "1") and not stub
+    # Every extra block runs only with --full.  Multi-rank --full runs measure the headline and h2d_inclusive (which guards
+    # itself against a lone failing rank): the other extra blocks contain barriers too, so a failure on ONE rank would hang the
+    # others and lose the whole line.  MVD_BENCH_EXTRAS=1 forces all of them on, =0 turns every extra off at one rank too (clean
+    # kernel statistics under rocprofv3).
+    extras = args.full and ((world == 1 and os.environ.get("MVD_BENCH_EXTRAS", "") != "0")
+                            or os.environ.get("MVD_BENCH_EXTRAS", "0") == "1") and not stub
     if extras and os.environ.get("MVD_BENCH_PIPELINED", "1") == "1":
         guarded("pipelined", pipelined_block)
 
@@ -389,8 +425,8 @@ def main(argv=None):
                                 "note": "raw images in pinned host memory -> copy stream (overlapped with the previous "
                                         "frame) -> input_adapter on the device -> forward; not the headline value"}
 
-    # on by default at every rank count (MVD_BENCH_H2D=0 turns it off); it handles a failing rank itself, so it is not `guarded`
-    if os.environ.get("MVD_BENCH_H2D", "1") == "1" and os.environ.get("MVD_BENCH_EXTRAS", "") != "0":
+    # with --full on at every rank count (MVD_BENCH_H2D=0 turns it off); it handles a failing rank itself, so it is not `guarded`
+    if args.full and os.environ.get("MVD_BENCH_H2D", "1") == "1" and os.environ.get("MVD_BENCH_EXTRAS", "") != "0":
         h2d_inclusive_block()
 
     def fp32_conv0_block():
@@ -575,7 +611,7 @@ def main(argv=None):
     if extras and not args.no_path_a and args.config in (1, 2, 3):
         guarded("path_a", path_a_block)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not stub:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not stub:
         guarded("cpu_baseline", lambda: out.__setitem__("cpu_baseline", cpu_baseline(H, W, V, D, sd)))
     if rank == 0:
         print(json.dumps(out), flush=True)

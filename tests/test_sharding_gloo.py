@@ -80,7 +80,7 @@ def test_two_rank_frame_sharding():
         np.testing.assert_array_equal(seen[i], _frame_result(i))
 
 
-def _bench_worker(rank, world, port, q, fail_rank):
+def _bench_worker(rank, world, port, q, fail_rank, extra_args):
     """runs bench.py's own main() on a gloo rank with the model stubbed (MVD_BENCH_STUB=1)"""
     os.environ.update({"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "RANK": str(rank), "LOCAL_RANK": str(rank),
                        "WORLD_SIZE": str(world), "MVD_BENCH_STUB": "1", "MVD_BENCH_SETTLE": "1"})
@@ -92,15 +92,15 @@ def _bench_worker(rank, world, port, q, fail_rank):
     import bench
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        out = bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1"])
+        out = bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1"] + list(extra_args))
     q.put((rank, out, buf.getvalue()))
 
 
-def _run_bench(world, fail_rank=None):
+def _run_bench(world, fail_rank=None, extra_args=("--full",)):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_bench_worker, args=(r, world, port, q, fail_rank)) for r in range(world)]
+    procs = [ctx.Process(target=_bench_worker, args=(r, world, port, q, fail_rank, extra_args)) for r in range(world)]
     for p in procs:
         p.start()
     results = sorted((q.get(timeout=180) for _ in range(world)), key=lambda r: r[0])
@@ -132,3 +132,19 @@ def test_bench_h2d_block_survives_a_lone_failing_rank():
     (r0, out0, _), (r1, out1, _) = _run_bench(2, fail_rank=1)
     assert "skipped" in out0["h2d_inclusive"] and "skipped" in out1["h2d_inclusive"]
     assert out0["value"] > 0
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """a plain run (no --full) prints the headline fields and no extra block; --dump-outputs writes the last timed step's
+    outputs as float32 .npy files"""
+    import json
+    out_dir = tmp_path / "outputs"
+    [(r0, out0, text0)] = _run_bench(1, extra_args=("--dump-outputs", str(out_dir)))
+    line = json.loads(text0.strip())
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line
+    assert line["steps"] == 3 and line["n_gpus"] == 1
+    assert abs(line["value"] - 3 / (line["ms_per_step"] * 3e-3)) < 1e-6 * line["value"]
+    assert not {"h2d_inclusive", "roofline", "pipelined", "path_a", "cpu_baseline"} & set(line)
+    depth = np.load(out_dir / "depth.npy")
+    assert depth.dtype == np.float32 and np.isfinite(depth).all()
