@@ -346,6 +346,19 @@ int mvd_conv2d_head_f32(const float* image, const float* w0, const float* scale0
 int mvd_softmax_regress_f32(const float* cost, const float* depth_values, int B, int D, int h, int w,
                             float* depth_out, float* conf_out, mvd_stream_t stream);
 
+/* K5 for training — the forward of MVSNet.forward's soft argmin with autograd recording (rmvd/models/mvsnet.py:139-141,
+ * rmvd/models/blocks/utils.py:271-274).
+ * mvd_softmax_regress_stats_f32: depth_out and conf_out bit-identical to mvd_softmax_regress_f32's (same kernel body); also
+ *   stats_out (B,2,h,w): plane 0 = M = max_d cost, plane 1 = 1 / sum_d exp(cost_d - M).  conf_out may be NULL.
+ * mvd_softmax_regress_backward_f32: VJP w.r.t. the cost volume, from the forward's depth (B,h,w) and stats:
+ *   g_cost (B,D,h,w)[b,d,p] = exp(cost - M) * (1/se) * g_depth[b,p] * (depth_values[b,d] - depth[b,p]).
+ *   g_depth (B,h,w) NULL = zero gradient (g_cost is written with zeros).  No gradient to depth_values (the reference's samples
+ *   come from linspace of a range that carries none) and none through the confidence (computed under no_grad, mvsnet.py:143-160). */
+int mvd_softmax_regress_stats_f32(const float* cost, const float* depth_values, int B, int D, int h, int w,
+                                  float* depth_out, float* conf_out, float* stats_out, mvd_stream_t stream);
+int mvd_softmax_regress_backward_f32(const float* cost, const float* depth_values, const float* depth, const float* stats,
+                                     const float* g_depth, int B, int D, int h, int w, float* g_cost, mvd_stream_t stream);
+
 /* Measurement aid (bench.py's `measured_stream_peak_gbs`): fills n floats (n % 4 == 0, dst 16-byte aligned) with a pure
  * streaming-store pass, the access pattern an HBM-write-bound kernel can reach at best on this device. */
 int mvd_stream_fill_f32(float* dst, long long n, float value, mvd_stream_t stream);

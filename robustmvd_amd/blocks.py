@@ -285,12 +285,22 @@ class FeatureNet(nn.Module):
         """Reference layout: (N,3,H,W) -> (N,32,H/4,W/4)."""
         return self.forward_layout(x, L.LAYOUT_NCHW)
 
+    def forward_autograd(self, x):
+        """The reference's forward (mvsnet_components.py:60-64) on the module's own nn.Conv2d / nn.BatchNorm2d layers (vendor
+        library convolutions, BN in whatever mode the module is in): records an autograd graph, for training (MVSNet.forward)."""
+        x = self.conv1(self.conv0(x))
+        x = self.conv4(self.conv3(self.conv2(x)))
+        return self.feature(self.conv6(self.conv5(x)))
+
 
 class ConvBnReLU3D(nn.Module):
     def __init__(self, cin, cout, kernel_size=3, stride=1, pad=1):
         super().__init__()
         self.conv = nn.Conv3d(cin, cout, kernel_size, stride=stride, padding=pad, bias=False)
         self.bn = nn.BatchNorm3d(cout)
+
+    def forward(self, x):  # mvsnet_components.py:40-41 (CostRegNet.forward_autograd)
+        return F.relu(self.bn(self.conv(x)), inplace=True)
 
 
 def _deconv_block(cin, cout):
@@ -425,6 +435,19 @@ class CostRegNet(nn.Module):
     def forward(self, x):
         """Reference layout: (B,32,D,h,w) -> (B,1,D,h,w)."""
         return self.forward_channels_last(ops.to_channels_last_3d(x)).unsqueeze(1)
+
+    def forward_autograd(self, x):
+        """The reference's forward (mvsnet_components.py:111-123) on the module's own nn.Conv3d / nn.ConvTranspose3d /
+        nn.BatchNorm3d layers (vendor library convolutions, BN in whatever mode the module is in): (B,32,D,h,w) -> (B,1,D,h,w)
+        with an autograd graph, for training (MVSNet.forward)."""
+        conv0 = self.conv0(x)
+        conv2 = self.conv2(self.conv1(conv0))
+        conv4 = self.conv4(self.conv3(conv2))
+        x = self.conv6(self.conv5(conv4))
+        x = conv4 + self.conv7(x)
+        x = conv2 + self.conv9(x)
+        x = conv0 + self.conv11(x)
+        return self.prob(x)
 
 
 # ------------------------------------------------------------------------------------------------

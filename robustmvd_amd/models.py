@@ -193,7 +193,11 @@ class MVSNet(nn.Module):
         stays fp32.  Regressed depth within rtol 1e-2 of the fp32 path.  Plain IEEE fp16 without scaling:
         feature or variance magnitudes beyond 65504 become inf (include/mvd.h); meant for O(1) features.
         conv0_split (default True): the regulariser's first layer with split, range-scaled fp16 operands on fp16 MFMA
-        (CostRegNet); False = fp32 MFMA.  exact_grid: K3's sampling positions by the reference's own rounding chain."""
+        (CostRegNet); False = fp32 MFMA.  exact_grid: K3's sampling positions by the reference's own rounding chain.
+        Training: in training mode, or with autograd recording and a parameter that requires grad, forward takes the
+        differentiable path (_forward_autograd: the reference-form FeatureNet / CostRegNet on the vendor library's convolutions,
+        K3 and K5 with their VJP kernels); conv0_split and exact_grid apply to the inference path only, and half_features=True
+        raises there (the fp16 variant is inference-only)."""
         super().__init__()
         self.half_features = bool(half_features)
         if sample_in_inv_depth_space:
@@ -253,6 +257,11 @@ class MVSNet(nn.Module):
             out = list(packed.unbind(0))
         return out
 
+    def _records_graph(self):
+        """The differentiable path is taken in training mode, or when autograd is recording and a parameter requires grad
+        (e.g. fine-tuning with frozen BatchNorm in eval mode); every other call runs the inference engine."""
+        return self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))
+
     def forward(self, images, poses, intrinsics, keyview_idx, depth_range=None, **_):
         n = images[0].shape[0]
         device = images[0].device
@@ -262,6 +271,8 @@ class MVSNet(nn.Module):
         proj = self.projection_matrices(intrinsics, poses, key_pos, device)
         views = [select_by_index(images, kidx)] + exclude_index(images, kidx)
         projs = [select_by_index(proj, kidx)] + exclude_index(proj, kidx)
+        if self._records_graph():
+            return self._forward_autograd(views, projs, depth_samples, n)
 
         # K6 x 8: ((V+1)*B, h+3, w+3, 32), the last layer writing straight into K3's zero-bordered staging layout
         split = self.cost_regularization.conv0_split and not self.half_features
@@ -285,6 +296,19 @@ class MVSNet(nn.Module):
         cost = self.cost_regularization.forward_channels_last(var, x_absmax=amax)                               # K4
         del var
         depth, conf = ops.softmax_regress(cost, depth_samples)                                                  # K5
+        pred = {"depth": depth.unsqueeze(1), "depth_uncertainty": (1 - conf).unsqueeze(1)}
+        return pred, {}
+
+    def _forward_autograd(self, views, projs, depth_samples, n):
+        """mvsnet.py:117-168 with an autograd graph: FeatureNet and CostRegNet in the reference's form on the vendor library's
+        convolutions (BN in the module's mode), K3 and K5 on the engine with their VJP kernels (ops.warp_variance_autograd,
+        ops.softmax_regress_autograd).  Gradients reach every parameter; the uncertainty carries none (no_grad in the reference)."""
+        if self.half_features:
+            raise ValueError("MVSNet(half_features=True) is inference-only: call .eval() and run under torch.no_grad()")
+        feats = list(torch.split(self.feature.forward_autograd(_as_batch(views)), n, 0))                  # (B,32,h,w) per view
+        var = ops.warp_variance_autograd(feats[0], feats[1:], projs[1:], projs[0], depth_samples)         # K3 (B,32,D,h,w)
+        cost = self.cost_regularization.forward_autograd(var).squeeze(1)                                  # (B,D,h,w)
+        depth, conf = ops.softmax_regress_autograd(cost, depth_samples)                                   # K5
         pred = {"depth": depth.unsqueeze(1), "depth_uncertainty": (1 - conf).unsqueeze(1)}
         return pred, {}
 

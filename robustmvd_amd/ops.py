@@ -1034,5 +1034,47 @@ def fuse_views_autograd(corrs, masks, scores):
     return _FuseViews.apply(V, *corrs, *_views(masks, "masks", V), *_views(scores, "scores", V))
 
 
+class _SoftmaxRegress(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cost, depth_values):
+        lib = L.load()
+        c = L.as_f32(cost.detach(), "cost")
+        if c.dim() != 4:
+            raise ValueError("cost must be (B,D,h,w)")
+        B, D, h, w = c.shape
+        dv = L.as_f32(depth_values.detach(), "depth_values", (B, D), c.device)
+        depth = torch.empty((B, h, w), dtype=torch.float32, device=c.device)
+        conf = torch.empty((B, h, w), dtype=torch.float32, device=c.device)
+        stats = torch.empty((B, 2, h, w), dtype=torch.float32, device=c.device)
+        with torch.cuda.device(c.device):
+            rc = lib.mvd_softmax_regress_stats_f32(L.ptr(c), L.ptr(dv), B, D, h, w, L.ptr(depth), L.ptr(conf), L.ptr(stats),
+                                                   L.stream_of(c))
+        L.check(rc, "mvd_softmax_regress_stats_f32")
+        ctx.save_for_backward(c, dv, depth, stats)
+        ctx.mark_non_differentiable(conf)
+        return depth, conf
+
+    @staticmethod
+    def backward(ctx, g_depth, _g_conf):
+        lib = L.load()
+        c, dv, depth, stats = ctx.saved_tensors
+        B, D, h, w = c.shape
+        with torch.no_grad():
+            g = g_depth.float().contiguous() if g_depth is not None else None
+            g_cost = torch.empty_like(c)
+            with torch.cuda.device(c.device):
+                rc = lib.mvd_softmax_regress_backward_f32(L.ptr(c), L.ptr(dv), L.ptr(depth), L.ptr(stats), L.ptr(g), B, D, h, w,
+                                                          L.ptr(g_cost), L.stream_of(c))
+            L.check(rc, "mvd_softmax_regress_backward_f32")
+        return g_cost, None
+
+
+def softmax_regress_autograd(cost, depth_values):
+    """Differentiable K5: cost (B,D,h,w), depth_values (B,D) -> depth (B,h,w), confidence (B,h,w), depth bit-identical to
+    softmax_regress's.  The gradient flows to the cost volume only (mvd_softmax_regress_backward_f32); the confidence is
+    non-differentiable (the reference computes it under no_grad, mvsnet.py:143-160) and the depth samples are constants."""
+    return _SoftmaxRegress.apply(cost, depth_values)
+
+
 def needs_grad(*objs):
     return torch.is_grad_enabled() and any(t.requires_grad for t in _tensors(objs))
