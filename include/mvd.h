@@ -174,7 +174,9 @@ int mvd_warp_variance_absmax_f32(const float* key_feat, const float* const* src_
  * Sampling positions, bilinear weights, the blend and the variance are computed in fp32 exactly as in the f32 entry point
  * (the fp16 taps enter the same fmaf chain): the result equals the f32 kernel's on the same fp16-representable feature
  * values, rounded once (to nearest even) to fp16 on the way out.  Calibration stays fp32.
- * Algorithmic HBM bytes: 2*((V+1)*C*h*w + C*D*h*w)*B — the volume is stored fp16 (1,137.5 MB at configs[3]). */
+ * Algorithmic HBM bytes: 2*((V+1)*C*h*w + C*D*h*w)*B — the volume is stored fp16 (1,137.5 MB at configs[3]).
+ * Map size: h, w <= 65532 and h*w*64 < 2^31 (the range of the one kernel behind this entry point); larger maps return
+ * MVD_ERR_INVALID_ARG (mvd_warp_variance_f32 runs longer maps on another kernel). */
 size_t mvd_warp_variance_f16_workspace_bytes(int B);
 int mvd_warp_variance_f16(const void* key_feat, const void* const* src_feat, const float* const* src_proj,
                           const float* key_proj_inv, const float* depth_values, int B, int D, int h, int w, int V,

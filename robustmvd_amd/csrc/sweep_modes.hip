@@ -11,7 +11,7 @@
 // homography_warping samples at X/Z - 0.5 from positions x + 0.5, blocks/utils.py:154-186).
 // Per view the caller passes the 3x4 matrix [R | t] with (X,Y,Z) = R (x+o, y+o, 1)^T d + t.
 //
-// Generic and simple by design (the tuned, marching K3 is the hot path): thread = (pixel, unit), unit = channel quad
+// Generic and simple by design (the tuned K3 tile kernel is the hot path): thread = (pixel, unit), unit = channel quad
 // (variance modes) or channel group (group correlation); pixels are the fast index so that stores into the
 // reference's (B,C,D,h,w) layout are coalesced.  Gathers come from zero-bordered channel-last copies like K3's.
 #include "mvd_common.h"

@@ -78,11 +78,22 @@ __device__ __forceinline__ void store_b64(u32x2 v, __amdgpu_buffer_rsrc_t rsrc, 
 bool warp_tile_supported(const WarpParams& p, bool f16);
 int launch_warp_tile(const WarpParams& p0, hipStream_t st, int tw, int win, int nch, int sets, bool f16, bool exact);
 
+// gather kernel (warp_variance.hip): any C, either layout.  launch_gather launches one compiled form (LPP lanes per pixel, DPB
+// planes per workgroup), launch_warp_gather the product's form for C channels
+typedef void (*WarpKernel)(WarpParams);
+int launch_gather(const WarpParams& p0, int lpp, int dpb, WarpKernel kernel, hipStream_t st);
+int launch_warp_gather(const WarpParams& p, int C, bool warp_only, hipStream_t st);
+
 #ifdef MVD_EXPERIMENTS
-// experimental launchers (warp_variance_exp.hip); each returns an mvd_status
-int launch_warp_q8(const WarpParams& p0, hipStream_t st, int minw);
-int launch_warp_wave(const WarpParams& p0, hipStream_t st, int nd);
-int launch_warp_lds(const WarpParams& p0, hipStream_t st, int nd);
+// One of the gather kernel's experimental forms (C = 32, folded grid): REUSE 0 / 1 / 2 / 4 = MVD_K3_CFG "dpb,minw" / "r…" /
+// "u…" / "v…"
+struct GatherForm {
+    int reuse, dpb, minw;
+    WarpKernel kernel;
+};
+// The kernel MVD_K3_CFG = cfg selects for a complete WarpParams (warp_variance_exp.hip); returns an mvd_status
+int warp_variance_experiment(const char* cfg, const WarpParams& p, int C, bool warp_only, bool f16, hipStream_t st,
+                             const GatherForm* forms, int nforms);
 #endif
 
 }  // namespace mvd

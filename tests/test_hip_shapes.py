@@ -364,6 +364,80 @@ def test_warp_variance_experimental_variants_match_default(cfg, dev, monkeypatch
     assert torch.equal(got, ref)
 
 
+def beyond_tile_inputs(transposed, seed=65540):
+    """C = 32, V = 2, D = 8 on a 4 x 65540 map (65540 x 4 when transposed), longer than the tile kernel covers.  The
+    features are random across channels and along the short side, smooth along the long one (periods of 8192 px and more,
+    an envelope that meets the zero border without a step): at x ~ 65536 the reference's own grid chain resolves a sampling
+    position to about 1/256 px, which on white noise, or at a step, would show as 1e-2 differences between any two grid
+    formulas.  The poses keep the samples within the 4 rows and move them by up to ~15 px along the long side."""
+    B, C, h, w, D, V = 1, 32, 4, 65540, 8, 2
+    rng = np.random.default_rng(seed)
+    x = np.arange(w)
+    feats = []
+    for _ in range(V + 1):
+        amp = rng.standard_normal((B, C, h, 1))
+        period = rng.uniform(8192.0, 32768.0, (B, C, h, 1))
+        phase = rng.uniform(0.0, 2 * np.pi, (B, C, h, 1))
+        feats.append((amp * np.sin(np.pi * x / (w - 1)) * np.sin(2 * np.pi * x / period + phase)).astype(np.float32))
+    Ks = gc.synthetic_intrinsics(h, w).astype(np.float64)
+    swap = np.eye(4)[[1, 0, 2, 3]] if transposed else np.eye(4)  # exchanges the image axes
+
+    def proj(Tm):
+        P = np.eye(4)
+        P[:3, :4] = Ks @ Tm[:3, :4]
+        return swap @ P
+
+    projs = []
+    for _ in range(V):
+        Tm = np.eye(4)
+        Tm[:3, :3] = gc.rot_xyz(0.0, rng.uniform(-2e-5, 2e-5), 0.0)
+        Tm[:3, 3] = [rng.uniform(-3e-5, 3e-5), rng.uniform(-2e-6, 2e-6), rng.uniform(-2e-4, 2e-4)]
+        projs.append(proj(Tm)[None].astype(np.float32))
+    key_inv = np.linalg.inv(proj(np.eye(4)))[None].astype(np.float32)
+    if transposed:
+        feats = [np.ascontiguousarray(f.transpose(0, 1, 3, 2)) for f in feats]
+    depth = np.linspace(0.5, 10.0, D, dtype=np.float32)[None]
+    return feats, projs, key_inv, depth
+
+
+@pytest.mark.parametrize("transposed", [False, True])
+def test_warp_variance_beyond_tile_limit(transposed, dev, monkeypatch):
+    """C = 32 channel-last maps longer than the tile kernel covers (65,532 px) run the gather kernel: a D-slab against the
+    oracle on the folded and the exact grid, NDHWC against NCDHW bit for bit, and, with the experiments library built, the
+    marching kernel that took these maps before, bit for bit"""
+    import os
+    from robustmvd_amd import _lib as L
+    from robustmvd_amd import ops
+    feats, projs, key_inv, depth = beyond_tile_inputs(transposed)
+    args = (T(feats[0], dev), [T(f, dev) for f in feats[1:]], [T(p, dev) for p in projs], T(key_inv, dev), T(depth, dev))
+    sl = [1, 6]
+    small = CO.warp_variance(feats[0], feats[1:], projs, key_inv, depth[:, sl])
+    for exact in (False, True):
+        var = ops.warp_variance(*args, channels_last=True, exact_grid=exact)
+        got = var[0, sl].permute(3, 0, 1, 2).cpu().numpy()
+        if exact:
+            np.testing.assert_allclose(got, small[0], atol=ATOL, rtol=RTOL)
+        else:
+            assert (~np.isclose(got, small[0], atol=ATOL, rtol=RTOL)).mean() < 2e-4
+            np.testing.assert_allclose(got, small[0], atol=2e-3, rtol=2e-3)
+        assert torch.equal(ops.warp_variance(*args, channels_last=False, exact_grid=exact).permute(0, 2, 3, 4, 1), var)
+    if os.path.exists(L.EXP_LIB_PATH):
+        ref = ops.warp_variance(*args, channels_last=True)
+        monkeypatch.setenv("MVD_K3_CFG", "M4,2,4")
+        with L.use_experiments_library():
+            got = ops.warp_variance(*args, channels_last=True)
+        assert torch.equal(got, ref)
+
+
+def test_warp_variance_f16_beyond_tile_limit_is_refused(dev):
+    """mvd_warp_variance_f16 runs only the tile kernel: maps longer than it covers are refused, naming the limit"""
+    from robustmvd_amd import ops
+    feats, projs, key_inv, depth = beyond_tile_inputs(False)
+    bordered = torch.zeros(1, 4 + 3, 65540 + 3, 32, dtype=torch.float16, device=dev)
+    with pytest.raises(RuntimeError, match="h, w <= 65532"):
+        ops.warp_variance_f16(bordered, [bordered, bordered], [T(p, dev) for p in projs], T(key_inv, dev), T(depth, dev))
+
+
 def test_largest_baseline_shape_runs(dev):
     """BASELINE configs[4] (704x1280, 6 source views, 512 planes: a 3.7 GB variance volume, > 2^31 bytes per tensor):
     the whole Path-B hot path runs, stays finite, and a D-slab of K3 matches the oracle (64-bit offsets everywhere)."""

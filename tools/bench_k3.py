@@ -53,7 +53,7 @@ def main():
     import contextlib
     for cfg in args.cfgs:
       # "product" = the shipped library (fixed dispatch); anything else = a variant of the experiments library
-      # "lib:<path>" = an alternate library (knock-out builds of tools/ko_k3.sh)
+      # "lib:<path>" = an alternate library (knock-out builds of tools/ko_k3t.sh)
       alt = cfg[4:] if cfg.startswith("lib:") else None
       with (contextlib.nullcontext() if cfg == "product" else L.use_experiments_library(alt)):
         os.environ["MVD_K3_CFG"] = "" if alt else cfg
