@@ -208,7 +208,9 @@ size_t mvd_conv3d_packed_weight_floats(int Cin, int Cout);
 /* w: Conv3d layout (Cout,Cin,3,3,3), or ConvTranspose3d layout (Cin,Cout,3,3,3) when mode == MVD_DECONV3D_STRIDE2 */
 int mvd_pack_conv3d_weights_f32(const float* w, int Cin, int Cout, int mode, float* packed, mvd_stream_t stream);
 /* x (B,Di,hi,wi,Cin) -> y (B,Do,ho,wo,Cout); Do = Di (stride 1), Di/2 (stride 2; Di,hi,wi even), 2*Di (deconv).
- * scale, shift (Cout); skip NULL or (B,Do,ho,wo,Cout).  Cin in {8,16,32,64}; Cout in {1,8,16,32,64}. */
+ * scale, shift (Cout); skip NULL or (B,Do,ho,wo,Cout).  Cin in {8,16,32,64}; Cout in {1,8,16,32,64}.
+ * Also Cin = 1 with MVD_CONV3D_STRIDE1 and Cout a multiple of 4 up to 64 (the adjoint of `prob` in training, below): a vector
+ * kernel over the one-channel volume. */
 int mvd_conv3d_bn_relu_f32(const float* x, const float* packed_w, const float* scale, const float* shift,
                            const float* skip, float* y, int B, int Di, int hi, int wi, int Cin, int Cout, int mode,
                            int relu, mvd_stream_t stream);
@@ -218,6 +220,23 @@ int mvd_conv3d_bn_relu_f32(const float* x, const float* packed_w, const float* s
 int mvd_conv3d_bn_relu_absmax_f32(const float* x, const float* packed_w, const float* scale, const float* shift,
                                   const float* skip, float* y, float* absmax_out, int B, int Di, int hi, int wi, int Cin,
                                   int Cout, int mode, int relu, mvd_stream_t stream);
+
+/* K4 for training — the backward of one CostRegNet layer, i.e. what autograd runs for
+ *   rmvd/models/blocks/mvsnet_components.py:25-41,69-123 when rmvd/train/multi_view_depth_training.py:231-246 calls backward().
+ * Data gradient: no entry point of its own.  Each layer's adjoint is a layer mvd_conv3d_bn_relu_f32 runs (scale 1, shift 0, no
+ * ReLU): stride-1 conv W -> stride-1 conv with W flipped along the taps and its channel axes swapped; stride-2 conv W ->
+ * MVD_DECONV3D_STRIDE2 with W as it is (in = Cout, out = Cin); transposed conv W -> MVD_CONV3D_STRIDE2 with W as it is.
+ * Weight gradient: mvd_conv3d_weight_grad_f32.  x (B,Di,hi,wi,Cin) the layer's input, gy (B,Do,ho,wo,Cout) the gradient of its
+ * output (sizes as for mvd_conv3d_bn_relu_f32; Di,hi,wi even for MVD_CONV3D_STRIDE2), both channel-last;
+ *   gw (Cout,Cin,3,3,3)[co,ci,k] = sum_{b,o} gy[b,o,co] * xpad[b, s*o + k, ci]          (conv, stride s, xpad = x padded by 1)
+ *   gw (Cin,Cout,3,3,3)[ci,co,k] = sum_{b,i} x[b,i,ci] * gypad[b, 2*i + k, co]          (MVD_DECONV3D_STRIDE2)
+ * i.e. the layer's own torch weight layout.  Cin, Cout in 1..64; any positive sizes.  fp32 MFMA: exact products, fp32 sums.
+ * DETERMINISTIC: no atomics; every workgroup writes one partial gradient to the workspace and a second kernel adds the
+ * partials in a fixed order, so two calls on the same inputs give bit-identical gw.  gw is written, not accumulated.
+ * The measurement hook (mvd_arm_kernel_timing) brackets the two kernels. */
+size_t mvd_conv3d_weight_grad_workspace_bytes(int B, int Di, int hi, int wi, int Cin, int Cout, int mode);
+int mvd_conv3d_weight_grad_f32(const float* x, const float* gy, float* gw, int B, int Di, int hi, int wi, int Cin, int Cout,
+                               int mode, void* workspace, size_t workspace_bytes, mvd_stream_t stream);
 
 /* K4, fp16-input first layer (BASELINE.json configs[3]: "3D-conv regulariser on MFMA, fp16 features"): conv0 of
  * CostRegNet (mvsnet_components.py:78; ConvBnReLU3D 32 -> 8, 3x3x3, stride 1, padding 1, :25-41) on
@@ -366,7 +385,7 @@ int mvd_softmax_regress_backward_f32(const float* cost, const float* depth_value
 int mvd_stream_fill_f32(float* dst, long long n, float value, mvd_stream_t stream);
 
 /* Measurement hook (bench.py): arms a pair of hipEvent_t for THIS thread; the next mvd_warp_variance_f32,
- * mvd_homo_warp_f32 or mvd_sweep_corr_f32 call records `start` on its stream immediately before its main kernel
+ * mvd_homo_warp_f32, mvd_sweep_corr_f32 or mvd_conv3d_weight_grad_f32 call records `start` on its stream immediately before its main kernel
  * (after the small feature re-packing launches) and `stop` immediately after it, then disarms.  Pass NULLs to
  * disarm.  Nothing is synchronised; the caller reads the events after synchronising the stream. */
 int mvd_arm_kernel_timing(void* start_event, void* stop_event);

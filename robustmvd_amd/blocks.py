@@ -449,6 +449,50 @@ class CostRegNet(nn.Module):
         x = conv0 + self.conv11(x)
         return self.prob(x)
 
+    def forward_autograd_engine(self, x):
+        """forward_autograd with the eleven convolutions on the engine in both directions (ops.conv3d_autograd: forward and data
+        gradient on mvd_conv3d_bn_relu_f32, weight gradient on mvd_conv3d_weight_grad_f32): x (B,D,h,w,32) channel-last ->
+        cost (B,D,h,w), with an autograd graph.  BatchNorm (in the module's mode, running statistics and num_batches_tracked
+        included), ReLU, the three skip additions and `prob`'s bias are torch ops on the channel-last tensors."""
+        if x.dim() != 5 or x.shape[1] % 8 or x.shape[2] % 8 or x.shape[3] % 8:
+            raise ValueError(f"CostRegNet needs (B,D,h,w,32) with D,h,w divisible by 8, got {tuple(x.shape)}")
+
+        def layer(name, t):
+            m = getattr(self, name)
+            stride = m.conv.stride[0]
+            y = ops.conv3d_autograd(t, m.conv.weight, L.CONV3D_STRIDE1 if stride == 1 else L.CONV3D_STRIDE2)
+            return F.relu(_batch_norm_channels_last(m.bn, y), inplace=True)
+
+        def up(name, t):
+            m = getattr(self, name)
+            y = ops.conv3d_autograd(t, m[0].weight, L.DECONV3D_STRIDE2)
+            return F.relu(_batch_norm_channels_last(m[1], y), inplace=True)
+
+        conv0 = layer("conv0", x)
+        conv2 = layer("conv2", layer("conv1", conv0))
+        conv4 = layer("conv4", layer("conv3", conv2))
+        x = layer("conv6", layer("conv5", conv4))
+        x = conv4 + up("conv7", x)
+        x = conv2 + up("conv9", x)
+        x = conv0 + up("conv11", x)
+        return (ops.conv3d_autograd(x, self.prob.weight, L.CONV3D_STRIDE1) + self.prob.bias).squeeze(-1)
+
+
+def _batch_norm_channels_last(bn, y):
+    """nn.BatchNorm3d.forward on a channel-last (B,D,h,w,C) tensor: the (N,C) view of it has the same per-channel statistics,
+    so F.batch_norm on that view is the module's arithmetic, running statistics included; the functional call does not count
+    batches, which is done here as the module does it."""
+    factor = 0.0 if bn.momentum is None else bn.momentum
+    if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+        if bn.momentum is None:
+            factor = 1.0 / float(bn.num_batches_tracked)
+    batch_stats = bn.training or (bn.running_mean is None and bn.running_var is None)
+    keep = not bn.training or bn.track_running_stats
+    out = F.batch_norm(y.reshape(-1, y.shape[-1]), bn.running_mean if keep else None, bn.running_var if keep else None,
+                       bn.weight, bn.bias, batch_stats, factor, bn.eps)
+    return out.view(y.shape)
+
 
 # ------------------------------------------------------------------------------------------------
 # DispNet 2-D CNN around the Path-A sweep (plain torch; MIOpen)

@@ -1559,6 +1559,7 @@ static bool cout_ok(int c) { return c == 1 || c == 8 || c == 16 || c == 32 || c 
 extern "C" {
 
 size_t mvd_conv3d_packed_weight_floats(int Cin, int Cout) {
+    if (Cin == 1) return mvd::conv3d_c1_ok(Cout) ? (size_t)27 * Cout : 0;  // the one-input-channel vector kernel: [tap][Cout]
     if (!mvd::cin_ok(Cin) || !mvd::cout_ok(Cout)) return 0;
     // 36 taps when a stride-1 layer with 8 output channels is packed for PAIR mode (the larger of the forms a
     // (Cin, Cout) pair can take: the transposed pair form has 18)
@@ -1567,6 +1568,10 @@ size_t mvd_conv3d_packed_weight_floats(int Cin, int Cout) {
 
 int mvd_pack_conv3d_weights_f32(const float* w, int Cin, int Cout, int mode, float* packed, mvd_stream_t stream) {
     MVD_REQUIRE(w && packed, "pack_conv3d_weights: NULL argument");
+    if (Cin == 1) {
+        MVD_REQUIRE(mvd::conv3d_c1_ok(Cout) && mode == MVD_CONV3D_STRIDE1, "pack_conv3d_weights: Cin=1 needs stride 1 and Cout=%d in 4, 8 .. 64", Cout);
+        return mvd::conv3d_c1_pack(w, Cout, packed, (hipStream_t)stream);
+    }
     MVD_REQUIRE(mvd::cin_ok(Cin) && mvd::cout_ok(Cout), "pack_conv3d_weights: Cin=%d/Cout=%d unsupported", Cin, Cout);
     MVD_REQUIRE(mode >= 0 && mode <= 2, "pack_conv3d_weights: mode=%d unknown", mode);
     const int NT = (Cout + 15) / 16;
@@ -1608,6 +1613,10 @@ static int conv3d_entry(const float* x, const float* packed_w, const float* scal
                         float* absmax_out, int B, int Di, int hi, int wi, int Cin, int Cout, int mode, int relu, mvd_stream_t stream) {
     MVD_REQUIRE(x && packed_w && scale && shift && y, "conv3d: NULL argument");
     MVD_REQUIRE(B > 0 && Di > 0 && hi > 0 && wi > 0, "conv3d: non-positive dimension");
+    if (Cin == 1) {  // the adjoint of `prob` (conv3d_backward.hip)
+        MVD_REQUIRE(mvd::conv3d_c1_ok(Cout) && mode == MVD_CONV3D_STRIDE1 && !absmax_out, "conv3d: Cin=1 needs stride 1 and Cout=%d in 4, 8 .. 64", Cout);
+        return mvd::conv3d_c1_launch(x, packed_w, scale, shift, skip, y, B, Di, hi, wi, Cout, relu, (hipStream_t)stream);
+    }
     MVD_REQUIRE(mvd::cin_ok(Cin) && mvd::cout_ok(Cout), "conv3d: Cin=%d/Cout=%d unsupported", Cin, Cout);
     mvd::ConvParams p{};
     p.x = x; p.wpk = packed_w; p.scale = scale; p.shift = shift; p.skip = skip; p.y = y;

@@ -32,6 +32,12 @@ __device__ __forceinline__ float finite_abs_or_zero(float v) {
     return a <= 3.402823466e38f ? a : 0.f;  // false for inf and NaN
 }
 
+// stride-1 3x3x3 convolution with ONE input channel (conv3d_backward.hip): what mvd_conv3d_bn_relu_f32 runs for Cin == 1
+bool conv3d_c1_ok(int Cout);
+int conv3d_c1_pack(const float* w, int Cout, float* packed, hipStream_t st);
+int conv3d_c1_launch(const float* x, const float* packed_w, const float* scale, const float* shift, const float* skip, float* y, int B,
+                     int D, int h, int w, int Cout, int relu, hipStream_t st);
+
 inline int launch_status(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

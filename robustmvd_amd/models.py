@@ -186,7 +186,7 @@ class RobustMVD(nn.Module):
 
 class MVSNet(nn.Module):
     def __init__(self, sample_in_inv_depth_space=False, num_sampling_steps=192, half_features=False, conv0_split=True,
-                 exact_grid=False):
+                 exact_grid=False, train_regulariser="vendor"):
         """half_features (an extension; the reference has no such switch): BASELINE.json configs[3] — the feature maps
         are rounded to fp16 before the sweep, the variance volume is stored fp16 and the regulariser's first layer runs
         on fp16 MFMA with fp32 accumulation; everything else (positions, blend, variance, layers 2..11, soft argmin)
@@ -197,8 +197,15 @@ class MVSNet(nn.Module):
         Training: in training mode, or with autograd recording and a parameter that requires grad, forward takes the
         differentiable path (_forward_autograd: the reference-form FeatureNet / CostRegNet on the vendor library's convolutions,
         K3 and K5 with their VJP kernels); conv0_split and exact_grid apply to the inference path only, and half_features=True
-        raises there (the fp16 variant is inference-only)."""
+        raises there (the fp16 variant is inference-only).
+        train_regulariser: where the differentiable path runs CostRegNet's convolutions.  "vendor" (default): the vendor library,
+        forward and backward.  "engine": the HIP engine in both directions (CostRegNet.forward_autograd_engine: forward and data
+        gradients on the fp32-MFMA layer kernels, weight gradients on mvd_conv3d_weight_grad_f32, deterministic).  The inference
+        path ignores the switch."""
         super().__init__()
+        if train_regulariser not in ("vendor", "engine"):
+            raise ValueError(f"train_regulariser must be 'vendor' or 'engine', got {train_regulariser!r}")
+        self.train_regulariser = train_regulariser
         self.half_features = bool(half_features)
         if sample_in_inv_depth_space:
             raise NotImplementedError("sample_in_inv_depth_space=True is a dead branch in the reference "
@@ -302,12 +309,15 @@ class MVSNet(nn.Module):
     def _forward_autograd(self, views, projs, depth_samples, n):
         """mvsnet.py:117-168 with an autograd graph: FeatureNet and CostRegNet in the reference's form on the vendor library's
         convolutions (BN in the module's mode), K3 and K5 on the engine with their VJP kernels (ops.warp_variance_autograd,
-        ops.softmax_regress_autograd).  Gradients reach every parameter; the uncertainty carries none (no_grad in the reference)."""
+        ops.softmax_regress_autograd).  train_regulariser="engine": CostRegNet's convolutions on the engine too, channel-last.  Gradients reach every parameter; the uncertainty carries none (no_grad in the reference)."""
         if self.half_features:
             raise ValueError("MVSNet(half_features=True) is inference-only: call .eval() and run under torch.no_grad()")
         feats = list(torch.split(self.feature.forward_autograd(_as_batch(views)), n, 0))                  # (B,32,h,w) per view
         var = ops.warp_variance_autograd(feats[0], feats[1:], projs[1:], projs[0], depth_samples)         # K3 (B,32,D,h,w)
-        cost = self.cost_regularization.forward_autograd(var).squeeze(1)                                  # (B,D,h,w)
+        if self.train_regulariser == "engine":
+            cost = self.cost_regularization.forward_autograd_engine(var.permute(0, 2, 3, 4, 1).contiguous())  # (B,D,h,w)
+        else:
+            cost = self.cost_regularization.forward_autograd(var).squeeze(1)                              # (B,D,h,w)
         depth, conf = ops.softmax_regress_autograd(cost, depth_samples)                                   # K5
         pred = {"depth": depth.unsqueeze(1), "depth_uncertainty": (1 - conf).unsqueeze(1)}
         return pred, {}

@@ -4,6 +4,7 @@ libmvd_hip.so on the tensor's device and torch's current stream.  Inference only
 autograd is recording raises (see inference_only).
 """
 import functools
+import itertools
 
 import torch
 
@@ -308,7 +309,7 @@ def pack_conv3d_weights(weight, mode):
         Cout, Cin = wt.shape[0], wt.shape[1]
     n = lib.mvd_conv3d_packed_weight_floats(Cin, Cout)
     if n == 0:
-        raise ValueError(f"conv3d: Cin={Cin}, Cout={Cout} unsupported (Cin in 8/16/32/64, Cout in 1/8/16/32/64)")
+        raise ValueError(f"conv3d: Cin={Cin}, Cout={Cout} unsupported (Cin in 8/16/32/64, Cout in 1/8/16/32/64; Cin 1 with Cout 4, 8 .. 64)")
     packed = torch.empty(n, dtype=torch.float32, device=wt.device)
     with torch.cuda.device(wt.device):
         rc = lib.mvd_pack_conv3d_weights_f32(L.ptr(wt), Cin, Cout, mode, L.ptr(packed), L.stream_of(wt))
@@ -1074,6 +1075,147 @@ def softmax_regress_autograd(cost, depth_values):
     softmax_regress's.  The gradient flows to the cost volume only (mvd_softmax_regress_backward_f32); the confidence is
     non-differentiable (the reference computes it under no_grad, mvsnet.py:143-160) and the depth samples are constants."""
     return _SoftmaxRegress.apply(cost, depth_values)
+
+
+def conv3d_adjoint(weight, mode):
+    """The layer whose FORWARD is the gradient of a CostRegNet layer w.r.t. its input: (weight, mode) -> (weight', mode').
+    stride-1 conv W (Cout,Cin,3,3,3): a stride-1 conv with the taps flipped and the channel axes swapped, (Cin <- Cout);
+    stride-2 conv W (Cout,Cin,...): a transposed conv whose weight (in = Cout, out = Cin) is W as it stands;
+    transposed conv W (Cin,Cout,...): a stride-2 conv whose weight (out = Cin, in = Cout) is W as it stands.
+    Plain tensor work on any device (include/mvd.h, "K4 for training")."""
+    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3):
+        raise ValueError(f"weight must be (*,*,3,3,3), got {tuple(weight.shape)}")
+    if mode == L.CONV3D_STRIDE1:
+        return weight.flip(2, 3, 4).transpose(0, 1).contiguous(), L.CONV3D_STRIDE1
+    if mode == L.CONV3D_STRIDE2:
+        return weight, L.DECONV3D_STRIDE2
+    if mode == L.DECONV3D_STRIDE2:
+        return weight, L.CONV3D_STRIDE2
+    raise ValueError(f"mode {mode}")
+
+
+def _conv3d_channels(weight, mode):
+    """(Cin, Cout) of a layer from its torch weight."""
+    return (weight.shape[0], weight.shape[1]) if mode == L.DECONV3D_STRIDE2 else (weight.shape[1], weight.shape[0])
+
+
+_IDENTITY_EPILOGUE = {}
+
+
+def _conv3d_plain(x, weight, mode):
+    """One engine layer without epilogue (scale 1, shift 0, no ReLU, no skip); the weights are packed on every call."""
+    packed, Cin, Cout = pack_conv3d_weights(weight, mode)
+    key = (x.device, Cout)
+    if key not in _IDENTITY_EPILOGUE:
+        _IDENTITY_EPILOGUE[key] = (torch.ones(Cout, dtype=torch.float32, device=x.device),
+                                   torch.zeros(Cout, dtype=torch.float32, device=x.device))
+    scale, shift = _IDENTITY_EPILOGUE[key]
+    return conv3d_bn_relu(x, packed, Cin, Cout, scale, shift, mode, relu=False)
+
+
+# The layer kernels add every product of an output voxel into ONE fp32 accumulator, so their rounding error grows like the
+# square root of the chain length.  27 taps x 8 channels is what the full-resolution layers have; longer reductions (the
+# low-resolution layers with 16 .. 64 channels, a few per cent of the voxels) are cut into chains of at most that length.
+_MAX_CHAIN = 27 * 8
+
+
+def _conv3d_blocked(x, weight, mode):
+    """_conv3d_plain with blocked accumulation: the reduction over (taps, Cin) is split along kd, then kh, then kw until no
+    accumulator chain is longer than _MAX_CHAIN products; each part is the same layer with the other taps' weights zeroed
+    (adding an exact zero product leaves the accumulator unchanged) and the parts are added in a fixed order.  Deterministic."""
+    Cin, _ = _conv3d_channels(weight, mode)
+    per_dim = 2 if mode == L.DECONV3D_STRIDE2 else 3  # taps that reach one output voxel, per dimension
+    chain, level = per_dim ** 3 * Cin, 0
+    while chain > _MAX_CHAIN and level < 3:
+        chain //= per_dim
+        level += 1
+    if level == 0:
+        return _conv3d_plain(x, weight, mode)
+    out = None
+    for idx in itertools.product(range(3), repeat=level):
+        sel = (slice(None), slice(None)) + idx
+        part = torch.zeros_like(weight)
+        part[sel] = weight[sel]
+        y = _conv3d_plain(x, part, mode)
+        out = y if out is None else out.add_(y)
+    return out
+
+
+def _strict_f32(t, name):
+    """The differentiable ops do not convert: a silent .float() / .cuda() copy would detach the caller's tensor from its gradient."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise ValueError(f"{name}: tensor is on {t.device}; the HIP engine needs a cuda (ROCm) device tensor")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name}: dtype {t.dtype}, expected torch.float32")
+    return t
+
+
+@inference_only
+def conv3d_weight_grad(x, gy, mode):
+    """mvd_conv3d_weight_grad_f32: x (B,Di,hi,wi,Cin) and gy (B,Do,ho,wo,Cout) channel-last -> the gradient of the layer's
+    3x3x3 weight in its torch layout, (Cout,Cin,3,3,3) or (Cin,Cout,3,3,3) for DECONV3D_STRIDE2.  Deterministic."""
+    lib = L.load()
+    x = L.as_f32(x, "x")
+    if x.dim() != 5:
+        raise ValueError(f"x must be (B,D,h,w,Cin) channel-last, got {tuple(x.shape)}")
+    B, Di, hi, wi, Cin = x.shape
+    if mode == L.CONV3D_STRIDE1:
+        osz = (Di, hi, wi)
+    elif mode == L.CONV3D_STRIDE2:
+        if Di % 2 or hi % 2 or wi % 2:
+            raise ValueError(f"stride-2 conv needs even D,h,w, got {Di},{hi},{wi}")
+        osz = (Di // 2, hi // 2, wi // 2)
+    elif mode == L.DECONV3D_STRIDE2:
+        osz = (Di * 2, hi * 2, wi * 2)
+    else:
+        raise ValueError(f"mode {mode}")
+    gy = L.as_f32(gy, "gy", device=x.device)
+    if gy.dim() != 5 or tuple(gy.shape[:4]) != (B, *osz):
+        raise ValueError(f"gy must be ({B},{osz[0]},{osz[1]},{osz[2]},Cout) channel-last, got {tuple(gy.shape)}")
+    Cout = gy.shape[4]
+    nbytes = lib.mvd_conv3d_weight_grad_workspace_bytes(B, Di, hi, wi, Cin, Cout, mode)
+    if nbytes == 0:
+        raise ValueError(f"conv3d_weight_grad: Cin={Cin}, Cout={Cout} unsupported (1..64)")
+    ws = _workspace(nbytes, x.device)
+    gw = torch.empty((Cin, Cout, 3, 3, 3) if mode == L.DECONV3D_STRIDE2 else (Cout, Cin, 3, 3, 3), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.mvd_conv3d_weight_grad_f32(L.ptr(x), L.ptr(gy), L.ptr(gw), B, Di, hi, wi, Cin, Cout, mode, L.ptr(ws), nbytes,
+                                            L.stream_of(x))
+    L.check(rc, "mvd_conv3d_weight_grad_f32")
+    return gw
+
+
+class _Conv3d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, mode):
+        ctx.save_for_backward(x, weight)
+        ctx.mode = mode
+        return _conv3d_plain(x.detach(), weight.detach(), mode)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight = ctx.saved_tensors
+        gx = gw = None
+        with torch.no_grad():
+            gy = gy.float().contiguous()
+            if ctx.needs_input_grad[0]:
+                gx = _conv3d_blocked(gy, *conv3d_adjoint(weight.detach(), ctx.mode))
+            if ctx.needs_input_grad[1]:
+                gw = conv3d_weight_grad(x.detach(), gy, ctx.mode)
+        return gx, gw, None
+
+
+def conv3d_autograd(x, weight, mode):
+    """Differentiable K4 layer without epilogue: x (B,D,h,w,Cin) channel-last fp32, weight in the layer's torch layout
+    ((Cout,Cin,3,3,3), or (Cin,Cout,3,3,3) for DECONV3D_STRIDE2) -> (B,Do,ho,wo,Cout).  Forward and the gradient w.r.t. x run on
+    mvd_conv3d_bn_relu_f32 (the latter with conv3d_adjoint's weights and blocked accumulation, _conv3d_blocked), the gradient
+    w.r.t. weight on mvd_conv3d_weight_grad_f32."""
+    x, weight = _strict_f32(x, "x"), _strict_f32(weight, "weight")
+    if x.dim() != 5 or weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or x.shape[-1] != _conv3d_channels(weight, mode)[0]:
+        raise ValueError(f"x {tuple(x.shape)} / weight {tuple(weight.shape)}: expected (B,D,h,w,Cin) and a 3x3x3 weight with Cin inputs")
+    return _Conv3d.apply(x.contiguous(), weight.contiguous(), mode)
 
 
 def needs_grad(*objs):

@@ -4,7 +4,11 @@
 FeatureNet fwd / bwd, K3 fwd / VJP, CostRegNet fwd / bwd and K5 fwd / VJP (the stages are cut at detached tensors, so each
 backward runs on its own), next to the unsplit model(**sample) + backward.  Also times K5's VJP kernel against torch autograd of
 softmax + depth_regression on the same cost volume, with its rate against 4*B*D*h*w*2 bytes (one read of the cost, one write
-of its gradient).  GPU box only.  Usage: python tools/time_mvsnet_train.py [--configs 1 2] [--reps 5] [--warmup 2]"""
+of its gradient).  --regulariser engine runs CostRegNet's convolutions on the engine in both directions
+(MVSNet(train_regulariser="engine")) and splits `CostRegNet bwd` into data-gradient, weight-gradient and BN / elementwise time
+(events around the two engine calls inside the backward; the rest is torch's BatchNorm, ReLU and add backward), with the
+weight-gradient kernels' rate against the fp32-matrix peak (157 TFLOP/s) and HBM bandwidth (8 TB/s) for their bytes.
+GPU box only.  Usage: python tools/time_mvsnet_train.py [--configs 1 2] [--reps 5] [--warmup 2] [--regulariser vendor|engine]"""
 import argparse
 import json
 import os
@@ -40,6 +44,60 @@ class Events:
         return {n1: e0.elapsed_time(e1) for (_, e0), (n1, e1) in zip(self.marks, self.marks[1:])}
 
 
+class BackwardSplit:
+    """Events around ops._conv3d_blocked (data gradient) and ops.conv3d_weight_grad inside the regulariser's backward."""
+
+    def __init__(self):
+        self.spans = {"data": [], "weight": []}
+        self.on = False
+        self._blocked, self._wgrad = ops._conv3d_blocked, ops.conv3d_weight_grad
+        ops._conv3d_blocked = self._timed("data", self._blocked)
+        ops.conv3d_weight_grad = self._timed("weight", self._wgrad)
+
+    def _timed(self, kind, fn):
+        def wrapper(*args):
+            if not self.on:
+                return fn(*args)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn(*args)
+            e1.record()
+            self.spans[kind].append((e0, e1))
+            return out
+        return wrapper
+
+    def take(self):
+        torch.cuda.synchronize()
+        out = {k: sum(a.elapsed_time(b) for a, b in v) for k, v in self.spans.items()}
+        self.spans = {"data": [], "weight": []}
+        return out
+
+
+SPLIT = BackwardSplit()
+
+
+def weight_grad_work(model, D, h, w):
+    """(FLOPs, bytes) of the eleven weight-gradient reductions at a (D,h,w) cost volume: 2 * 27 * Cin * Cout per voxel of the
+    smaller of the layer's two tensors; bytes = one read of the layer's input and of its output gradient."""
+    from robustmvd_amd.blocks import CostRegNet
+    flops = nbytes = 0
+    lvl = 1
+    for _, cin, cout, stride in CostRegNet.LAYERS + [("prob", 8, 1, 1)]:
+        vin = (D // lvl) * (h // lvl) * (w // lvl)
+        lvl *= stride
+        vout = (D // lvl) * (h // lvl) * (w // lvl)
+        flops += 2 * 27 * cin * cout * vout
+        nbytes += 4 * (vin * cin + vout * cout)
+    lvl = 8
+    for _, cin, cout in CostRegNet.UPS:
+        vin = (D // lvl) * (h // lvl) * (w // lvl)
+        lvl //= 2
+        vout = (D // lvl) * (h // lvl) * (w // lvl)
+        flops += 2 * 27 * cin * cout * vin
+        nbytes += 4 * (vin * cin + vout * cout)
+    return flops, nbytes
+
+
 def split_step(model, sample):
     """One training step, stage by stage; returns {stage: ms}."""
     model.zero_grad(set_to_none=True)
@@ -57,20 +115,29 @@ def split_step(model, sample):
     v = ops.warp_variance_autograd(feats[0], feats[1:], projs[1:], projs[0], dv)
     ev.mark("K3 fwd")
     vd = v.detach().requires_grad_(True)
-    c = model.cost_regularization.forward_autograd(vd).squeeze(1)
+    if model.train_regulariser == "engine":
+        c = model.cost_regularization.forward_autograd_engine(vd.permute(0, 2, 3, 4, 1).contiguous())
+    else:
+        c = model.cost_regularization.forward_autograd(vd).squeeze(1)
     ev.mark("CostRegNet fwd")
     cd = c.detach().requires_grad_(True)
     d, _ = ops.softmax_regress_autograd(cd, dv)
     ev.mark("K5 fwd")
     d.backward(torch.ones_like(d))
     ev.mark("K5 VJP")
+    SPLIT.on = True
     c.backward(cd.grad)
+    SPLIT.on = False
     ev.mark("CostRegNet bwd")
     v.backward(vd.grad)
     ev.mark("K3 VJP")
     f.backward(fd.grad)
     ev.mark("FeatureNet bwd")
-    return ev.spans()
+    out = ev.spans()
+    if model.train_regulariser == "engine":
+        sp = SPLIT.take()
+        out["bwd data-gradient"], out["bwd weight-gradient"] = sp["data"], sp["weight"]
+    return out
 
 
 def full_step(model, sample):
@@ -126,9 +193,9 @@ def k5_vjp_vs_torch(cost, dv, reps, n=50):
             "torch_softmax_regression_bwd_ms": t_torch, "k5_vjp_bytes": nbytes}
 
 
-def run(cfg, reps, warmup):
+def run(cfg, reps, warmup, regulariser="vendor"):
     H, W, V, D = CONFIGS[cfg]
-    model = R.MVSNet(num_sampling_steps=D).to(dev).train()
+    model = R.MVSNet(num_sampling_steps=D, train_regulariser=regulariser).to(dev).train()
     s = gc.synthetic_sample(cfg, H, W, V)
     im, key, po, intr, dr = add_batch_dim(s["images"], 0, s["poses"], s["intrinsics"], (np.float32(0.5), np.float32(10.0)))
     sample = model.input_adapter(images=im, keyview_idx=key, poses=po, intrinsics=intr, depth_range=dr)
@@ -141,12 +208,19 @@ def run(cfg, reps, warmup):
         fulls.append(full_step(model, sample))
         print(f"  configs[{cfg}] timed step {i + 1}/{reps}: split {sum(runs[-1].values()):.1f} ms, full {fulls[-1]:.1f} ms", flush=True)
     stages = {k: float(np.median([r[k] for r in runs])) for k in runs[0]}
+    split = {k: stages.pop(k) for k in list(stages) if k.startswith("bwd ")}  # parts of CostRegNet bwd, not stages of their own
     full = float(np.median(fulls))
     with torch.no_grad():
         cost = torch.randn(1, D, H // 4, W // 4, device=dev) * 3
     dv = model.depth_samples(sample["depth_range"], 1, dev)
     out = {"config": cfg, "H": H, "W": W, "V": V, "D": D, "stages_ms": stages, "sum_of_stages_ms": sum(stages.values()),
-           "full_step_ms": full, "peak_mem_gb": torch.cuda.max_memory_allocated() / 1e9}
+           "full_step_ms": full, "peak_mem_gb": torch.cuda.max_memory_allocated() / 1e9, "regulariser": regulariser}
+    if split:
+        split["bwd BN / elementwise"] = stages["CostRegNet bwd"] - sum(split.values())
+        flops, nbytes = weight_grad_work(model, D, H // 4, W // 4)
+        t = split["bwd weight-gradient"] * 1e-3
+        out.update({"costregnet_bwd_split_ms": split, "weight_grad_tflops": flops / t / 1e12, "weight_grad_gbs": nbytes / t / 1e9,
+                    "weight_grad_flops": flops, "weight_grad_bytes": nbytes})
     out.update(k5_vjp_vs_torch(cost, dv, reps))
     return out
 
@@ -156,13 +230,20 @@ if __name__ == "__main__":
     ap.add_argument("--configs", type=int, nargs="+", default=[1, 2])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--regulariser", choices=["vendor", "engine"], default="vendor")
     a = ap.parse_args()
     for cfg in a.configs:
-        r = run(cfg, a.reps, a.warmup)
-        print(f"configs[{cfg}] {r['H']}x{r['W']} V{r['V']} D{r['D']}: training step {r['full_step_ms']:.2f} ms "
+        r = run(cfg, a.reps, a.warmup, a.regulariser)
+        print(f"configs[{cfg}] {r['H']}x{r['W']} V{r['V']} D{r['D']} regulariser={a.regulariser}: training step {r['full_step_ms']:.2f} ms "
               f"(stages sum {r['sum_of_stages_ms']:.2f} ms, peak {r['peak_mem_gb']:.1f} GB)")
         for k, v in r["stages_ms"].items():
             print(f"  {k:16s} {v:9.3f} ms  {100 * v / r['sum_of_stages_ms']:5.1f} %")
+        for k, v in r.get("costregnet_bwd_split_ms", {}).items():
+            print(f"    {k:22s} {v:9.3f} ms  {100 * v / r['stages_ms']['CostRegNet bwd']:5.1f} % of CostRegNet bwd")
+        if "weight_grad_tflops" in r:
+            print(f"    weight gradients: {r['weight_grad_flops'] / 1e9:.1f} GFLOP at {r['weight_grad_tflops']:.1f} TFLOP/s = "
+                  f"{100 * r['weight_grad_tflops'] / 157:.1f} % of 157 TFLOP/s; {r['weight_grad_bytes'] / 1e6:.0f} MB at "
+                  f"{r['weight_grad_gbs']:.0f} GB/s = {100 * r['weight_grad_gbs'] / 8000:.1f} % of 8 TB/s")
         print(f"  K5 VJP kernel {r['k5_vjp_kernel_ms'] * 1e3:.1f} us = {r['k5_vjp_kernel_gbs']:.0f} GB/s of {r['k5_vjp_bytes'] / 1e6:.1f} MB; "
               f"through autograd {r['k5_vjp_autograd_ms'] * 1e3:.1f} us; torch softmax + depth_regression backward "
               f"{r['torch_softmax_regression_bwd_ms'] * 1e3:.1f} us")
