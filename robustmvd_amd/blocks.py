@@ -191,6 +191,19 @@ def fold_bn(bn):
     return scale.detach().contiguous(), (bn.bias - bn.running_mean * scale).detach().contiguous()
 
 
+class FeatureNetWeights:
+    """What FeatureNet._prepare packs.  layers: conv0 .. conv6 and `feature` as ops.conv2d_bn_relu's arguments
+    (packed, cin, cout, k, stride, scale, shift, relu), also read as pk[i].  With split_layers, split: conv2 .. `feature` as
+    (SplitConv2dWeights, relu) for ops.conv2d_split, and head: ops.conv2d_head's (w0, scale0, shift0, w1, scale1, shift1)."""
+    __slots__ = ("layers", "split", "head")
+
+    def __init__(self):
+        self.layers, self.split, self.head = [], [], ()
+
+    def __getitem__(self, i):
+        return self.layers[i]
+
+
 class FeatureNet(nn.Module):
     """2-D feature pyramid of MVSNet (mvsnet_components.py:44-66).  Parameters live in ordinary nn.Conv2d /
     nn.BatchNorm2d modules (the reference's checkpoints load); forward folds BN (eval mode) and runs 8 fused HIP
@@ -221,23 +234,22 @@ class FeatureNet(nn.Module):
             return self._packed
         if self.training:
             raise RuntimeError("FeatureNet HIP path folds BatchNorm running statistics: call .eval() first")
-        pk = []
+        pk = FeatureNetWeights()
         for i, (cin, cout, k, stride, _) in enumerate(self.SPEC):
             m = getattr(self, f"conv{i}")
             w, _, _, _ = ops.pack_conv2d_weights(m.conv.weight.detach())
-            pk.append((w, cin, cout, k, stride, *fold_bn(m.bn), True))
+            pk.layers.append((w, cin, cout, k, stride, *fold_bn(m.bn), True))
         w, _, _, _ = ops.pack_conv2d_weights(self.feature.weight.detach())
-        pk.append((w, 32, 32, 3, 1, torch.ones(32, device=w.device), self.feature.bias.detach().contiguous(), False))
+        pk.layers.append((w, 32, 32, 3, 1, torch.ones(32, device=w.device), self.feature.bias.detach().contiguous(), False))
         if self.split_layers:  # layers 2 .. 7 for the split-operand kernel: BN scale folded into the weights, shift as the bias
-            sp = []
             for i in range(2, 8):
                 conv = getattr(self, f"conv{i}").conv if i < 7 else self.feature
-                _, _, _, _, stride, scale, shift, relu = pk[i]
-                sp.append((ops.pack_conv2d_weights_split(conv.weight.detach() * scale.view(-1, 1, 1, 1), shift, stride=stride), relu))
-            pk.append(sp)
+                _, _, _, _, stride, scale, shift, relu = pk.layers[i]
+                pk.split.append((ops.pack_conv2d_weights_split(conv.weight.detach() * scale.view(-1, 1, 1, 1), shift, stride=stride), relu))
             # conv0 -> conv1 in one launch (ops.conv2d_head): weights as [ky][kx][cin][cout]
-            hw = [getattr(self, f"conv{i}").conv.weight.detach().permute(2, 3, 1, 0).contiguous() for i in range(2)]
-            pk.append((hw[0], pk[0][5], pk[0][6], hw[1], pk[1][5], pk[1][6]))
+            for i in range(2):
+                _, _, _, _, _, scale, shift, _ = pk.layers[i]
+                pk.head += (getattr(self, f"conv{i}").conv.weight.detach().permute(2, 3, 1, 0).contiguous(), scale, shift)
         self._packed, self._packed_key = pk, key
         return pk
 
@@ -247,22 +259,21 @@ class FeatureNet(nn.Module):
         over the batch as a one-element device tensor (a by-product of the last layer's store epilogue)."""
         pk = self._prepare()
         if not self.split_layers:
-            for i, (w, cin, cout, k, stride, scale, shift, relu) in enumerate(pk):
+            for i, (w, cin, cout, k, stride, scale, shift, relu) in enumerate(pk.layers):
                 x = ops.conv2d_bn_relu(x, w, cin, cout, k, stride, scale, shift, relu=relu,
-                                       out_layout=out_layout if i == len(pk) - 1 else L.LAYOUT_NHWC)
+                                       out_layout=out_layout if i == len(pk.layers) - 1 else L.LAYOUT_NHWC)
             return (x, ops.absmax(x)) if return_absmax else x
         slots = torch.zeros(8, dtype=torch.float32, device=x.device)  # max-|y| slots of the layers, raised by their producers
         if self.fused_head:  # the 8-channel full-resolution intermediate never leaves the chip; max |conv1| from per-tile maxima
-            x, a_in = ops.conv2d_head(x, *pk[9], return_absmax=True)
+            x, a_in = ops.conv2d_head(x, *pk.head, return_absmax=True)
         else:
-            for i in range(2):
-                w, cin, cout, k, stride, scale, shift, relu = pk[i]
+            for w, cin, cout, k, stride, scale, shift, relu in pk.layers[:2]:
                 x = ops.conv2d_bn_relu(x, w, cin, cout, k, stride, scale, shift, relu=relu)
             # max |conv1| by a pass of its own (29 us for 141 MB): as a by-product of conv1's store epilogue (out_absmax=) it cost 65 us
             # in the frame, where the maximum grows across the image and many of the layer's 69,000 waves reach the atomic
             a_in = ops.absmax(x)
-        for j, (wts, relu) in enumerate(pk[8]):
-            last = j == len(pk[8]) - 1
+        for j, (wts, relu) in enumerate(pk.split):
+            last = j == len(pk.split) - 1
             if not last:
                 x = ops.conv2d_split(x, a_in, wts, act=2 if relu else 0, out_absmax=slots[j:j + 1])
                 a_in = slots[j:j + 1]
@@ -607,9 +618,10 @@ class DispnetDecoder(nn.Module):
             ch = nxt
 
     @staticmethod
-    def _record(pred, preds):
+    def _record(pred, preds, ent=None):
         mean, log_b = pred[:, 0:1], pred[:, 1:2]
-        ent = torch.log(2 * torch.exp(log_b) + 1e-4) + 1
+        if ent is None:
+            ent = torch.log(2 * torch.exp(log_b) + 1e-4) + 1
         preds.setdefault("invdepth_uncertainties_all", []).append(ent)
         preds.setdefault("invdepth_log_bs_all", []).append(log_b)
         preds.setdefault("invdepths_all", []).append(mean)
@@ -620,15 +632,10 @@ class DispnetDecoder(nn.Module):
         (ops.dispnet_head) instead of torch's ~10 elementwise kernels per head; same formulas."""
         blk = getattr(self, f"pred_{lvl}")
         if torch.is_grad_enabled() or not feat.is_cuda or feat.dtype != torch.float32:
-            pred = blk(feat)
-            self._record(pred, preds)
-            return pred
-        pred, ent = ops.dispnet_head(blk[0](feat))
-        mean, log_b = pred[:, 0:1], pred[:, 1:2]
-        preds.setdefault("invdepth_uncertainties_all", []).append(ent)
-        preds.setdefault("invdepth_log_bs_all", []).append(log_b)
-        preds.setdefault("invdepths_all", []).append(mean)
-        preds["invdepth_uncertainty"], preds["invdepth_log_b"], preds["invdepth"] = ent, log_b, mean
+            pred, ent = blk(feat), None
+        else:
+            pred, ent = ops.dispnet_head(blk[0](feat))
+        self._record(pred, preds, ent)
         return pred
 
     def forward(self, enc_fused, all_enc):

@@ -1,7 +1,10 @@
 """Operator-level entry points of the HIP engine on torch (ROCm) tensors.  Each function validates its
-arguments in Python (ValueError), allocates outputs/workspace with torch and calls one C-ABI function of
-libmvd_hip.so on the tensor's device and torch's current stream.  Inference only: an input that requires grad while
-autograd is recording raises (see inference_only).
+arguments in Python (ValueError), allocates outputs/workspace with torch and launches one C-ABI function of
+libmvd_hip.so on the tensor's device and torch's current stream, through call.
+
+The first part holds the inference entry points: an input that requires grad while autograd is recording raises
+(see inference_only).  The second part holds their differentiable forms (*_autograd), torch.autograd.Function wrappers
+whose backward runs the engine's gradient kernels.
 """
 import functools
 import itertools
@@ -45,7 +48,30 @@ def inference_only(fn):
     return wrapper
 
 
-def _views(ts, name, V=None):
+def call(name, dev, *args):
+    """Launches the C entry point `name` (any one that returns a status) on `dev` and torch's current stream of it.  args: the
+    header's arguments in order, without the trailing stream.  Ints and floats go as they are and None as a NULL pointer; a
+    tensor goes as its device address (L.ptr's value); a list or tuple of tensors goes as a void** array, which lives until
+    the call has returned.  A non-zero status raises `name failed (status N): <mvd_last_error>`."""
+    argv, keep = list(args), []
+    for i, a in enumerate(args):
+        t = type(a)
+        # every launch of a frame passes here, most arguments are ints: asking isinstance(a, torch.Tensor) of each of them
+        # first cost 0.08 ms of the 1.1 ms a robust_mvd frame takes to enqueue
+        if t is int or t is float or a is None:
+            continue
+        if t is list or t is tuple:
+            argv[i], arr = L.ptr_array(a)
+            keep.append(arr)
+        elif isinstance(a, torch.Tensor):
+            argv[i] = a.data_ptr()
+    with torch.cuda.device(dev):
+        rc = getattr(L.load(), name)(*argv, L.raw_stream(dev))
+    L.check(rc, name)
+
+
+def views(ts, name, V=None):
+    """The per-view arguments of an op as a list of 1..MVD_MAX_VIEWS entries (of V entries, where V is given)."""
     ts = list(ts)
     if len(ts) == 0 or len(ts) > L.MVD_MAX_VIEWS:
         raise ValueError(f"{name}: {len(ts)} views, supported 1..{L.MVD_MAX_VIEWS}")
@@ -54,7 +80,7 @@ def _views(ts, name, V=None):
     return ts
 
 
-def _workspace(nbytes, device):
+def workspace(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
@@ -67,43 +93,63 @@ def _invdepth_mode(inv, N, h, w):
     raise ValueError(f"sampling_invdepths must be (1 or N, S) or (N, S, h, w), got {tuple(inv.shape)}")
 
 
+def _k1_calibration(K_key, K_sources, T_src2key, invdepths, V, N, h, w, dev):
+    """K1's calibration arguments, validated: relative intrinsics (N,3,3) of the key view and of the V source views, V
+    source-to-key transforms (N,4,4) and the inverse depths -> (Kk, Ks, Ts, inv, the inverse depths' INVDEPTH_* mode)."""
+    Kk = L.as_f32(K_key, "intrinsics_key", (N, 3, 3), dev)
+    Ks = [L.as_f32(k, f"intrinsics_sources[{i}]", (N, 3, 3), dev) for i, k in enumerate(views(K_sources, "intrinsics_sources", V))]
+    Ts = [L.as_f32(t, f"source_to_key_transforms[{i}]", (N, 4, 4), dev) for i, t in enumerate(views(T_src2key, "source_to_key_transforms", V))]
+    inv = L.as_f32(invdepths, "sampling_invdepths", device=dev)
+    return Kk, Ks, Ts, inv, _invdepth_mode(inv, N, h, w)
+
+
+def _corr_scale(corr_scale, C):
+    """The multiplier of K1's dot products: 1/sqrt(C) (normalize="dim") unless the caller gives one."""
+    return float(corr_scale) if corr_scale is not None else 1.0 / float(C) ** 0.5
+
+
+def _k3_depths(depth_values, B, C, dev):
+    """K3's depth samples (B,D), validated together with the channel count C, which must be one the kernels are built for."""
+    dv = L.as_f32(depth_values, "depth_values", device=dev)
+    if dv.dim() != 2 or dv.shape[0] != B:
+        raise ValueError(f"depth_values must be (B,D), got {tuple(dv.shape)}")
+    if C not in (4, 8, 16, 32, 64):
+        raise ValueError(f"feature channels C={C} unsupported (4, 8, 16, 32, 64)")
+    return dv
+
+
+def _k3_calibration(src_projs, key_proj_inv, depth_values, V, B, C, dev):
+    """K3's calibration arguments, validated: V source projections and the inverse key projection (B,4,4), and _k3_depths
+    -> (projs, kpi, dv)."""
+    projs = [L.as_f32(p, f"src_projs[{i}]", (B, 4, 4), dev) for i, p in enumerate(views(src_projs, "src_projs", V))]
+    kpi = L.as_f32(key_proj_inv, "key_proj_inv", (B, 4, 4), dev)
+    return projs, kpi, _k3_depths(depth_values, B, C, dev)
+
+
 @inference_only
 def sweep_corr(feat_key, feat_sources, K_key, K_sources, T_src2key, invdepths, corr_scale=None):
     """K1. feat_key (N,C,h,w); feat_sources V x (N,C,hs,ws); K_* relative intrinsics (N,3,3);
     T_src2key V x (N,4,4); invdepths (1 or N, S) or per key pixel (N,S,h,w); corr_scale: multiplier of the dot products,
     default 1/sqrt(C) (normalize="dim").  Returns (corrs[V], masks[V]) each (N,S,h,w)."""
-    lib = L.load()
     fk = L.as_f32(feat_key, "feat_key")
     if fk.dim() != 4:
         raise ValueError("feat_key must be (N,C,h,w)")
     N, C, h, w = fk.shape
     dev = fk.device
-    srcs = _views(feat_sources, "feat_sources")
+    srcs = views(feat_sources, "feat_sources")
     V = len(srcs)
     hs, ws = srcs[0].shape[-2:]
     srcs = [L.as_f32(s, f"feat_sources[{i}]", (N, C, hs, ws), dev) for i, s in enumerate(srcs)]
-    Kk = L.as_f32(K_key, "intrinsics_key", (N, 3, 3), dev)
-    Ks = [L.as_f32(k, f"intrinsics_sources[{i}]", (N, 3, 3), dev) for i, k in enumerate(_views(K_sources, "intrinsics_sources", V))]
-    Ts = [L.as_f32(t, f"source_to_key_transforms[{i}]", (N, 4, 4), dev) for i, t in enumerate(_views(T_src2key, "source_to_key_transforms", V))]
-    inv = L.as_f32(invdepths, "sampling_invdepths", device=dev)
-    mode = _invdepth_mode(inv, N, h, w)
+    Kk, Ks, Ts, inv, mode = _k1_calibration(K_key, K_sources, T_src2key, invdepths, V, N, h, w, dev)
     S = inv.shape[1]
-    scale = float(corr_scale) if corr_scale is not None else 1.0 / float(C) ** 0.5
+    scale = _corr_scale(corr_scale, C)
     if C % 64 != 0:
         raise ValueError(f"feature channels C={C} must be a multiple of 64")
     corrs = [torch.empty((N, S, h, w), dtype=torch.float32, device=dev) for _ in range(V)]
     masks = [torch.empty((N, S, h, w), dtype=torch.float32, device=dev) for _ in range(V)]
-    wsb = lib.mvd_sweep_corr_workspace_bytes(N, C, h, w, hs, ws, V)
-    wsp = _workspace(wsb, dev)
-    a_src, k1 = L.ptr_array(srcs)
-    a_K, k2 = L.ptr_array(Ks)
-    a_T, k3 = L.ptr_array(Ts)
-    a_c, k4 = L.ptr_array(corrs)
-    a_m, k5 = L.ptr_array(masks)
-    with torch.cuda.device(dev):
-        rc = lib.mvd_sweep_corr_ex_f32(L.ptr(fk), a_src, L.ptr(Kk), a_K, a_T, L.ptr(inv), mode, scale,
-                                       N, C, h, w, hs, ws, S, V, a_c, a_m, L.ptr(wsp), wsb, L.stream_of(fk))
-    L.check(rc, "mvd_sweep_corr_ex_f32")
+    wsb = L.load().mvd_sweep_corr_workspace_bytes(N, C, h, w, hs, ws, V)
+    call("mvd_sweep_corr_ex_f32", dev, fk, srcs, Kk, Ks, Ts, inv, mode, scale, N, C, h, w, hs, ws, S, V, corrs, masks,
+          workspace(wsb, dev), wsb)
     return corrs, masks
 
 
@@ -111,8 +157,7 @@ def sweep_corr(feat_key, feat_sources, K_key, K_sources, T_src2key, invdepths, c
 def sweep_warp(feat_sources, K_key, K_sources, T_src2key, invdepths, key_size, normalize_after=False):
     """WarpOnlyCorr's sweep (planesweep_corr.py:107-140).  feat_sources V x (N,C,hs,ws); key_size (h, w) of the key feature
     map; invdepths as in sweep_corr.  Returns (warped[V] (N,S,C,h,w), masks[V] (N,S,h,w))."""
-    lib = L.load()
-    srcs = _views(feat_sources, "feat_sources")
+    srcs = views(feat_sources, "feat_sources")
     V = len(srcs)
     s0 = L.as_f32(srcs[0], "feat_sources[0]")
     if s0.dim() != 4:
@@ -121,46 +166,28 @@ def sweep_warp(feat_sources, K_key, K_sources, T_src2key, invdepths, key_size, n
     dev = s0.device
     h, w = int(key_size[0]), int(key_size[1])
     srcs = [L.as_f32(s, f"feat_sources[{i}]", (N, C, hs, ws), dev) for i, s in enumerate(srcs)]
-    Kk = L.as_f32(K_key, "intrinsics_key", (N, 3, 3), dev)
-    Ks = [L.as_f32(k, f"intrinsics_sources[{i}]", (N, 3, 3), dev) for i, k in enumerate(_views(K_sources, "intrinsics_sources", V))]
-    Ts = [L.as_f32(t, f"source_to_key_transforms[{i}]", (N, 4, 4), dev) for i, t in enumerate(_views(T_src2key, "source_to_key_transforms", V))]
-    inv = L.as_f32(invdepths, "sampling_invdepths", device=dev)
-    mode = _invdepth_mode(inv, N, h, w)
+    Kk, Ks, Ts, inv, mode = _k1_calibration(K_key, K_sources, T_src2key, invdepths, V, N, h, w, dev)
     S = inv.shape[1]
     outs = [torch.empty((N, S, C, h, w), dtype=torch.float32, device=dev) for _ in range(V)]
     masks = [torch.empty((N, S, h, w), dtype=torch.float32, device=dev) for _ in range(V)]
-    a_src, k1 = L.ptr_array(srcs)
-    a_K, k2 = L.ptr_array(Ks)
-    a_T, k3 = L.ptr_array(Ts)
-    a_o, k4 = L.ptr_array(outs)
-    a_m, k5 = L.ptr_array(masks)
-    with torch.cuda.device(dev):
-        rc = lib.mvd_sweep_warp_f32(a_src, L.ptr(Kk), a_K, a_T, L.ptr(inv), mode, 1 if normalize_after else 0,
-                                    N, C, h, w, hs, ws, S, V, a_o, a_m, L.stream_of(s0))
-    L.check(rc, "mvd_sweep_warp_f32")
+    call("mvd_sweep_warp_f32", dev, srcs, Kk, Ks, Ts, inv, mode, 1 if normalize_after else 0, N, C, h, w, hs, ws, S, V, outs, masks)
     return outs, masks
 
 
 @inference_only
 def fuse_views(corrs, masks, scores):
     """K2. corrs, masks V x (N,S,h,w); scores V x (N,1,h,w) -> fused, fused_mask (N,S,h,w)."""
-    lib = L.load()
-    corrs = _views(corrs, "corrs")
+    corrs = views(corrs, "corrs")
     V = len(corrs)
     c0 = L.as_f32(corrs[0], "corrs[0]")
     N, S, h, w = c0.shape
     dev = c0.device
     corrs = [L.as_f32(c, f"corrs[{i}]", (N, S, h, w), dev) for i, c in enumerate(corrs)]
-    masks = [L.as_f32(m, f"masks[{i}]", (N, S, h, w), dev) for i, m in enumerate(_views(masks, "masks", V))]
-    scores = [L.as_f32(s, f"scores[{i}]", (N, 1, h, w), dev) for i, s in enumerate(_views(scores, "scores", V))]
+    masks = [L.as_f32(m, f"masks[{i}]", (N, S, h, w), dev) for i, m in enumerate(views(masks, "masks", V))]
+    scores = [L.as_f32(s, f"scores[{i}]", (N, 1, h, w), dev) for i, s in enumerate(views(scores, "scores", V))]
     fused = torch.empty_like(c0)
     fmask = torch.empty_like(c0)
-    a_c, k1 = L.ptr_array(corrs)
-    a_m, k2 = L.ptr_array(masks)
-    a_s, k3 = L.ptr_array(scores)
-    with torch.cuda.device(dev):
-        rc = lib.mvd_fuse_views_f32(a_c, a_m, a_s, N, S, h, w, V, L.ptr(fused), L.ptr(fmask), L.stream_of(c0))
-    L.check(rc, "mvd_fuse_views_f32")
+    call("mvd_fuse_views_f32", dev, corrs, masks, scores, N, S, h, w, V, fused, fmask)
     return fused, fmask
 
 
@@ -169,12 +196,11 @@ def warp_variance(key_feat, src_feats, src_projs, key_proj_inv, depth_values, ch
                   staged=False, return_absmax=False):
     """K3. key_feat (B,C,h,w); src_feats V x (B,C,h,w); src_projs V x (B,4,4); key_proj_inv (B,4,4);
     depth_values (B,D).  Returns the variance volume (B,C,D,h,w), or (B,D,h,w,C) if channels_last.
-    return_absmax: also returns max |volume| as a one-element device tensor (mvd_warp_variance_absmax_f32: a by-product of
-    the store epilogue for C = 32 channel-last), which conv3d_bn_relu_split takes as its activation range.
+    return_absmax: also returns max |volume| as a one-element device tensor (a by-product of the store epilogue for
+    C = 32 channel-last), which conv3d_bn_relu_split takes as its activation range.
     exact_grid: sampling positions follow the reference's operation chain rounding for rounding (MVD_GRID_EXACT).
     staged: the feature maps are the zero-bordered channel-last (B,h+3,w+3,C) copies K6 writes
     (conv2d_bn_relu(..., out_layout=LAYOUT_NHWC_BORDER)); the re-packing launches are skipped (MVD_FEAT_NHWC_BORDER)."""
-    lib = L.load()
     kf = L.as_f32(key_feat, "key_feat")
     if kf.dim() != 4:
         raise ValueError("key_feat must be (B,C,h,w)" + (" / (B,h+3,w+3,C) when staged" if staged else ""))
@@ -183,96 +209,61 @@ def warp_variance(key_feat, src_feats, src_projs, key_proj_inv, depth_values, ch
     else:
         B, C, h, w = kf.shape
     dev = kf.device
-    srcs = [L.as_f32(s, f"src_feats[{i}]", tuple(kf.shape), dev) for i, s in enumerate(_views(src_feats, "src_feats"))]
+    srcs = [L.as_f32(s, f"src_feats[{i}]", tuple(kf.shape), dev) for i, s in enumerate(views(src_feats, "src_feats"))]
     V = len(srcs)
-    projs = [L.as_f32(p, f"src_projs[{i}]", (B, 4, 4), dev) for i, p in enumerate(_views(src_projs, "src_projs", V))]
-    kpi = L.as_f32(key_proj_inv, "key_proj_inv", (B, 4, 4), dev)
-    dv = L.as_f32(depth_values, "depth_values", device=dev)
-    if dv.dim() != 2 or dv.shape[0] != B:
-        raise ValueError(f"depth_values must be (B,D), got {tuple(dv.shape)}")
+    projs, kpi, dv = _k3_calibration(src_projs, key_proj_inv, depth_values, V, B, C, dev)
     D = dv.shape[1]
-    if C not in (4, 8, 16, 32, 64):
-        raise ValueError(f"feature channels C={C} unsupported (4, 8, 16, 32, 64)")
-    shape = (B, D, h, w, C) if channels_last else (B, C, D, h, w)
-    out = torch.empty(shape, dtype=torch.float32, device=dev)
-    wsb = lib.mvd_warp_variance_workspace_bytes(B, C, h, w, 0 if staged else V)
-    wsp = _workspace(wsb, dev)
-    a_s, k1 = L.ptr_array(srcs)
-    a_p, k2 = L.ptr_array(projs)
+    out = torch.empty((B, D, h, w, C) if channels_last else (B, C, D, h, w), dtype=torch.float32, device=dev)
+    wsb = L.load().mvd_warp_variance_workspace_bytes(B, C, h, w, 0 if staged else V)
     flags = (L.LAYOUT_NDHWC if channels_last else L.LAYOUT_NCDHW) | (L.GRID_EXACT if exact_grid else 0) | \
         (L.FEAT_NHWC_BORDER if staged else 0)
-    if return_absmax:
-        amax = torch.empty(1, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.mvd_warp_variance_absmax_f32(L.ptr(kf), a_s, a_p, L.ptr(kpi), L.ptr(dv), B, C, D, h, w, V, L.ptr(out),
-                                                  L.ptr(amax), flags, L.ptr(wsp), wsb, L.stream_of(kf))
-        L.check(rc, "mvd_warp_variance_absmax_f32")
-        return out, amax
-    with torch.cuda.device(dev):
-        rc = lib.mvd_warp_variance_f32(L.ptr(kf), a_s, a_p, L.ptr(kpi), L.ptr(dv), B, C, D, h, w, V, L.ptr(out), flags,
-                                       L.ptr(wsp), wsb, L.stream_of(kf))
-    L.check(rc, "mvd_warp_variance_f32")
-    return out
+    name, amax = "mvd_warp_variance_f32", []
+    if return_absmax:  # the twin takes one more pointer, behind the volume
+        name, amax = "mvd_warp_variance_absmax_f32", [torch.empty(1, dtype=torch.float32, device=dev)]
+    call(name, dev, kf, srcs, projs, kpi, dv, B, C, D, h, w, V, out, *amax, flags, workspace(wsb, dev), wsb)
+    return (out, amax[0]) if return_absmax else out
 
 
 @inference_only
 def absmax(x):
-    """max |x| over a float32 device tensor as a one-element device tensor (NaNs ignored; mvd_absmax_f32, a streaming read)."""
-    lib = L.load()
+    """max |x| over a float32 device tensor as a one-element device tensor (NaNs ignored; a streaming read)."""
     x = L.as_f32(x, "x")
     out = torch.empty(1, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.mvd_absmax_f32(L.ptr(x), x.numel(), L.ptr(out), L.stream_of(x))
-    L.check(rc, "mvd_absmax_f32")
+    call("mvd_absmax_f32", x.device, x, x.numel(), out)
     return out
 
 
 @inference_only
 def to_f16(x):
     """fp32 -> fp16 (round to nearest even) through the library's converter; numel must be a multiple of 4."""
-    lib = L.load()
     x = L.as_f32(x, "x")
     y = torch.empty(x.shape, dtype=torch.float16, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.mvd_convert_f32_to_f16(L.ptr(x), L.ptr(y), x.numel(), L.stream_of(x))
-    L.check(rc, "mvd_convert_f32_to_f16")
+    call("mvd_convert_f32_to_f16", x.device, x, y, x.numel())
     return y
 
 
 @inference_only
 def warp_variance_f16(key_feat, src_feats, src_projs, key_proj_inv, depth_values):
-    """K3, fp16-feature variant (mvd_warp_variance_f16).  key_feat, src_feats: fp16 zero-bordered channel-last maps
+    """K3, fp16-feature variant.  key_feat, src_feats: fp16 zero-bordered channel-last maps
     (B,h+3,w+3,32); calibration fp32.  Returns the fp16 channel-last variance volume (B,D,h,w,32)."""
-    lib = L.load()
     kf = L.as_f16(key_feat, "key_feat")
     if kf.dim() != 4 or kf.shape[3] != 32:
         raise ValueError("key_feat must be the fp16 zero-bordered channel-last map (B,h+3,w+3,32)")
     B, h, w = kf.shape[0], kf.shape[1] - 3, kf.shape[2] - 3
     dev = kf.device
-    srcs = [L.as_f16(s, f"src_feats[{i}]", tuple(kf.shape), dev) for i, s in enumerate(_views(src_feats, "src_feats"))]
+    srcs = [L.as_f16(s, f"src_feats[{i}]", tuple(kf.shape), dev) for i, s in enumerate(views(src_feats, "src_feats"))]
     V = len(srcs)
-    projs = [L.as_f32(p, f"src_projs[{i}]", (B, 4, 4), dev) for i, p in enumerate(_views(src_projs, "src_projs", V))]
-    kpi = L.as_f32(key_proj_inv, "key_proj_inv", (B, 4, 4), dev)
-    dv = L.as_f32(depth_values, "depth_values", device=dev)
-    if dv.dim() != 2 or dv.shape[0] != B:
-        raise ValueError(f"depth_values must be (B,D), got {tuple(dv.shape)}")
+    projs, kpi, dv = _k3_calibration(src_projs, key_proj_inv, depth_values, V, B, 32, dev)
     D = dv.shape[1]
     out = torch.empty((B, D, h, w, 32), dtype=torch.float16, device=dev)
-    wsb = lib.mvd_warp_variance_f16_workspace_bytes(B)
-    wsp = _workspace(wsb, dev)
-    a_s, k1 = L.ptr_array(srcs)
-    a_p, k2 = L.ptr_array(projs)
-    with torch.cuda.device(dev):
-        rc = lib.mvd_warp_variance_f16(L.ptr(kf), a_s, a_p, L.ptr(kpi), L.ptr(dv), B, D, h, w, V, L.ptr(out), L.ptr(wsp), wsb,
-                                       L.stream_of(kf))
-    L.check(rc, "mvd_warp_variance_f16")
+    wsb = L.load().mvd_warp_variance_f16_workspace_bytes(B)
+    call("mvd_warp_variance_f16", dev, kf, srcs, projs, kpi, dv, B, D, h, w, V, out, workspace(wsb, dev), wsb)
     return out
 
 
 @inference_only
 def homo_warp(src_feat, src_proj, ref_proj_inv, depth_values):
     """Drop-in for rmvd.models.blocks.utils.homo_warp (blocks/utils.py:222): -> (B,C,D,H,W)."""
-    lib = L.load()
     sf = L.as_f32(src_feat, "src_feat")
     if sf.dim() != 4:
         raise ValueError("src_feat must be (B,C,H,W)")
@@ -280,40 +271,45 @@ def homo_warp(src_feat, src_proj, ref_proj_inv, depth_values):
     dev = sf.device
     sp = L.as_f32(src_proj, "src_proj", (B, 4, 4), dev)
     kpi = L.as_f32(ref_proj_inv, "ref_proj_inv", (B, 4, 4), dev)
-    dv = L.as_f32(depth_values, "depth_values", device=dev)
-    if dv.dim() != 2 or dv.shape[0] != B:
-        raise ValueError(f"depth_values must be (B,D), got {tuple(dv.shape)}")
+    dv = _k3_depths(depth_values, B, C, dev)
     D = dv.shape[1]
-    if C not in (4, 8, 16, 32, 64):
-        raise ValueError(f"feature channels C={C} unsupported (4, 8, 16, 32, 64)")
     out = torch.empty((B, C, D, h, w), dtype=torch.float32, device=dev)
-    wsb = lib.mvd_warp_variance_workspace_bytes(B, C, h, w, 0)
-    wsp = _workspace(wsb, dev)
-    with torch.cuda.device(dev):
-        rc = lib.mvd_homo_warp_f32(L.ptr(sf), L.ptr(sp), L.ptr(kpi), L.ptr(dv), B, C, D, h, w, L.ptr(out), L.ptr(wsp),
-                                   wsb, L.stream_of(sf))
-    L.check(rc, "mvd_homo_warp_f32")
+    wsb = L.load().mvd_warp_variance_workspace_bytes(B, C, h, w, 0)
+    call("mvd_homo_warp_f32", dev, sf, sp, kpi, dv, B, C, D, h, w, out, workspace(wsb, dev), wsb)
     return out
+
+
+def _conv3d_channels(weight, mode):
+    """(Cin, Cout) of a 3x3x3 layer from its torch weight: Conv3d (Cout,Cin,3,3,3), or ConvTranspose3d (Cin,Cout,3,3,3) for mode
+    DECONV3D_STRIDE2."""
+    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3):
+        raise ValueError(f"weight must be (*,*,3,3,3), got {tuple(weight.shape)}")
+    return (weight.shape[0], weight.shape[1]) if mode == L.DECONV3D_STRIDE2 else (weight.shape[1], weight.shape[0])
+
+
+def _conv3d_out_size(mode, Di, hi, wi):
+    """(Do, ho, wo) of a 3x3x3 layer of `mode` on a (Di, hi, wi) volume."""
+    if mode == L.CONV3D_STRIDE1:
+        return Di, hi, wi
+    if mode == L.CONV3D_STRIDE2:
+        if Di % 2 or hi % 2 or wi % 2:
+            raise ValueError(f"stride-2 conv needs even D,h,w, got {Di},{hi},{wi}")
+        return Di // 2, hi // 2, wi // 2
+    if mode == L.DECONV3D_STRIDE2:
+        return Di * 2, hi * 2, wi * 2
+    raise ValueError(f"mode {mode}")
 
 
 @inference_only
 def pack_conv3d_weights(weight, mode):
     """weight: Conv3d (Cout,Cin,3,3,3) or, for mode DECONV3D_STRIDE2, ConvTranspose3d (Cin,Cout,3,3,3)."""
-    lib = L.load()
     wt = L.as_f32(weight, "weight")
-    if wt.dim() != 5 or tuple(wt.shape[2:]) != (3, 3, 3):
-        raise ValueError(f"weight must be (*,*,3,3,3), got {tuple(wt.shape)}")
-    if mode == L.DECONV3D_STRIDE2:
-        Cin, Cout = wt.shape[0], wt.shape[1]
-    else:
-        Cout, Cin = wt.shape[0], wt.shape[1]
-    n = lib.mvd_conv3d_packed_weight_floats(Cin, Cout)
+    Cin, Cout = _conv3d_channels(wt, mode)
+    n = L.load().mvd_conv3d_packed_weight_floats(Cin, Cout)
     if n == 0:
         raise ValueError(f"conv3d: Cin={Cin}, Cout={Cout} unsupported (Cin in 8/16/32/64, Cout in 1/8/16/32/64; Cin 1 with Cout 4, 8 .. 64)")
     packed = torch.empty(n, dtype=torch.float32, device=wt.device)
-    with torch.cuda.device(wt.device):
-        rc = lib.mvd_pack_conv3d_weights_f32(L.ptr(wt), Cin, Cout, mode, L.ptr(packed), L.stream_of(wt))
-    L.check(rc, "mvd_pack_conv3d_weights_f32")
+    call("mvd_pack_conv3d_weights_f32", wt.device, wt, Cin, Cout, mode, packed)
     return packed, Cin, Cout
 
 
@@ -322,59 +318,38 @@ def conv3d_bn_relu(x, packed, Cin, Cout, scale, shift, mode, relu=True, skip=Non
     """K4. x (B,D,h,w,Cin) channel-last -> (B,Do,ho,wo,Cout).  return_absmax: also max |y| over the finite outputs (device,
     one float; what conv3d_bn_relu_split scales a following layer's activations by): a by-product of the store epilogue of
     the stride-2 layers, a pass over y otherwise."""
-    lib = L.load()
     x = L.as_f32(x, "x")
     if x.dim() != 5 or x.shape[-1] != Cin:
         raise ValueError(f"x must be (B,D,h,w,{Cin}) channel-last, got {tuple(x.shape)}")
     B, Di, hi, wi, _ = x.shape
     dev = x.device
-    if mode == L.CONV3D_STRIDE1:
-        oshape = (B, Di, hi, wi, Cout)
-    elif mode == L.CONV3D_STRIDE2:
-        if Di % 2 or hi % 2 or wi % 2:
-            raise ValueError(f"stride-2 conv needs even D,h,w, got {Di},{hi},{wi}")
-        oshape = (B, Di // 2, hi // 2, wi // 2, Cout)
-    elif mode == L.DECONV3D_STRIDE2:
-        oshape = (B, Di * 2, hi * 2, wi * 2, Cout)
-    else:
-        raise ValueError(f"mode {mode}")
+    oshape = (B, *_conv3d_out_size(mode, Di, hi, wi), Cout)
     scale = L.as_f32(scale, "scale", (Cout,), dev)
     shift = L.as_f32(shift, "shift", (Cout,), dev)
     if skip is not None:
         skip = L.as_f32(skip, "skip", oshape, dev)
     y = torch.empty(oshape, dtype=torch.float32, device=dev)
-    if return_absmax:
-        amax = torch.empty(1, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.mvd_conv3d_bn_relu_absmax_f32(L.ptr(x), L.ptr(packed), L.ptr(scale), L.ptr(shift), L.ptr(skip), L.ptr(y),
-                                                   L.ptr(amax), B, Di, hi, wi, Cin, Cout, mode, int(bool(relu)), L.stream_of(x))
-        L.check(rc, "mvd_conv3d_bn_relu_absmax_f32")
-        return y, amax
-    with torch.cuda.device(dev):
-        rc = lib.mvd_conv3d_bn_relu_f32(L.ptr(x), L.ptr(packed), L.ptr(scale), L.ptr(shift), L.ptr(skip), L.ptr(y), B, Di,
-                                        hi, wi, Cin, Cout, mode, int(bool(relu)), L.stream_of(x))
-    L.check(rc, "mvd_conv3d_bn_relu_f32")
-    return y
+    name, amax = "mvd_conv3d_bn_relu_f32", []
+    if return_absmax:  # the twin takes one more pointer, behind y
+        name, amax = "mvd_conv3d_bn_relu_absmax_f32", [torch.empty(1, dtype=torch.float32, device=dev)]
+    call(name, dev, x, packed, scale, shift, skip, y, *amax, B, Di, hi, wi, Cin, Cout, mode, int(bool(relu)))
+    return (y, amax[0]) if return_absmax else y
 
 
 @inference_only
 def pack_conv3d_weights_f16(weight):
     """weight: Conv3d (8,32,3,3,3) fp32 -> fp16 MFMA-fragment-ordered buffer for conv3d_bn_relu_f16in."""
-    lib = L.load()
     wt = L.as_f32(weight, "weight")
     if tuple(wt.shape) != (8, 32, 3, 3, 3):
         raise ValueError(f"conv3d f16: only the 32 -> 8 first layer is built, got weight {tuple(wt.shape)}")
-    packed = torch.empty(lib.mvd_conv3d_f16_packed_weight_bytes(32, 8), dtype=torch.uint8, device=wt.device)
-    with torch.cuda.device(wt.device):
-        rc = lib.mvd_pack_conv3d_weights_f16(L.ptr(wt), 32, 8, L.ptr(packed), L.stream_of(wt))
-    L.check(rc, "mvd_pack_conv3d_weights_f16")
+    packed = torch.empty(L.load().mvd_conv3d_f16_packed_weight_bytes(32, 8), dtype=torch.uint8, device=wt.device)
+    call("mvd_pack_conv3d_weights_f16", wt.device, wt, 32, 8, packed)
     return packed
 
 
 @inference_only
 def conv3d_bn_relu_f16in(x, packed, scale, shift, relu=True):
     """K4 first layer on fp16 MFMA: x (B,D,h,w,32) fp16 channel-last -> (B,D,h,w,8) fp32."""
-    lib = L.load()
     x = L.as_f16(x, "x")
     if x.dim() != 5 or x.shape[-1] != 32:
         raise ValueError(f"x must be (B,D,h,w,32) fp16 channel-last, got {tuple(x.shape)}")
@@ -383,10 +358,7 @@ def conv3d_bn_relu_f16in(x, packed, scale, shift, relu=True):
     scale = L.as_f32(scale, "scale", (8,), dev)
     shift = L.as_f32(shift, "shift", (8,), dev)
     y = torch.empty((B, D, h, w, 8), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.mvd_conv3d_bn_relu_f16in(L.ptr(x), L.ptr(packed), L.ptr(scale), L.ptr(shift), L.ptr(y), B, D, h, w, 32, 8,
-                                          int(bool(relu)), L.stream_of(x))
-    L.check(rc, "mvd_conv3d_bn_relu_f16in")
+    call("mvd_conv3d_bn_relu_f16in", dev, x, packed, scale, shift, y, B, D, h, w, 32, 8, int(bool(relu)))
     return y
 
 
@@ -394,15 +366,12 @@ def conv3d_bn_relu_f16in(x, packed, scale, shift, relu=True):
 def pack_conv3d_weights_split(weight):
     """weight: Conv3d (Cout,Cin,3,3,3) fp32, Cin 16 or 32, Cout in 8, 16, ... 64 -> per block of 8 output channels the
     [w_hi | w_lo] fp16 fragments for conv3d_bn_relu_split, followed by the channels' power-of-two scales."""
-    lib = L.load()
     wt = L.as_f32(weight, "weight")
     cout, cin = (wt.shape[0], wt.shape[1]) if wt.dim() == 5 else (0, 0)
     if wt.dim() != 5 or tuple(wt.shape[2:]) != (3, 3, 3) or cin not in (16, 32) or cout % 8 or not 8 <= cout <= 64:
         raise ValueError(f"conv3d split: 16 or 32 input channels and 8..64 output channels (a multiple of 8) are built, got weight {tuple(wt.shape)}")
-    packed = torch.empty(lib.mvd_conv3d_split_packed_weight_bytes(cin, cout), dtype=torch.uint8, device=wt.device)
-    with torch.cuda.device(wt.device):
-        rc = lib.mvd_pack_conv3d_weights_split(L.ptr(wt), cin, cout, L.ptr(packed), L.stream_of(wt))
-    L.check(rc, "mvd_pack_conv3d_weights_split")
+    packed = torch.empty(L.load().mvd_conv3d_split_packed_weight_bytes(cin, cout), dtype=torch.uint8, device=wt.device)
+    call("mvd_pack_conv3d_weights_split", wt.device, wt, cin, cout, packed)
     return packed
 
 
@@ -410,11 +379,10 @@ def pack_conv3d_weights_split(weight):
 def conv3d_bn_relu_split(x, packed, scale, shift, relu=True, x_absmax=None, return_absmax=False):
     """K4's stride-1 layers with 16 or 32 input channels (conv0: 32 -> 8, conv2: 16 -> 16, conv4: 32 -> 32), split-operand
     form: x (B,D,h,w,Cin) fp32 -> (B,D,h,w,Cout) fp32 (Cout = len(scale)) on fp16 MFMA with two-term operand
-    splitting and power-of-two range scaling (mvd_conv3d_bn_relu_f32_split; fp32-grade results for inputs of any
+    splitting and power-of-two range scaling (fp32-grade results for inputs of any
     magnitude).  x_absmax: one-element device tensor with max |x| (warp_variance(..., return_absmax=True)); computed here
     with a streaming pass over x when omitted.  return_absmax: also max |y| (one-element device tensor), a by-product of the
     store epilogue."""
-    lib = L.load()
     x = L.as_f32(x, "x")
     if x.dim() != 5 or x.shape[-1] not in (16, 32):
         raise ValueError(f"x must be (B,D,h,w,16 or 32) channel-last, got {tuple(x.shape)}")
@@ -422,49 +390,37 @@ def conv3d_bn_relu_split(x, packed, scale, shift, relu=True, x_absmax=None, retu
     dev = x.device
     scale = L.as_f32(scale, "scale", device=dev)
     cout = scale.numel()
-    if packed.numel() != lib.mvd_conv3d_split_packed_weight_bytes(cin, cout):
+    if packed.numel() != L.load().mvd_conv3d_split_packed_weight_bytes(cin, cout):
         raise ValueError(f"packed weights of {packed.numel()} bytes do not belong to a {cin} -> {cout} layer")
     shift = L.as_f32(shift, "shift", (cout,), dev)
     y = torch.empty((B, D, h, w, cout), dtype=torch.float32, device=dev)
     if x_absmax is None:
         x_absmax = absmax(x)
     x_absmax = L.as_f32(x_absmax, "x_absmax", (1,), dev)
-    if return_absmax:
-        yam = torch.empty(1, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.mvd_conv3d_bn_relu_absmax_f32_split(L.ptr(x), L.ptr(x_absmax), L.ptr(packed), L.ptr(scale), L.ptr(shift), L.ptr(y),
-                                                         L.ptr(yam), B, D, h, w, cin, cout, int(bool(relu)), L.stream_of(x))
-        L.check(rc, "mvd_conv3d_bn_relu_absmax_f32_split")
-        return y, yam
-    with torch.cuda.device(dev):
-        rc = lib.mvd_conv3d_bn_relu_f32_split(L.ptr(x), L.ptr(x_absmax), L.ptr(packed), L.ptr(scale), L.ptr(shift), L.ptr(y), B, D, h, w,
-                                              cin, cout, int(bool(relu)), L.stream_of(x))
-    L.check(rc, "mvd_conv3d_bn_relu_f32_split")
-    return y
+    name, yam = "mvd_conv3d_bn_relu_f32_split", []
+    if return_absmax:  # the twin takes one more pointer, behind y
+        name, yam = "mvd_conv3d_bn_relu_absmax_f32_split", [torch.empty(1, dtype=torch.float32, device=dev)]
+    call(name, dev, x, x_absmax, packed, scale, shift, y, *yam, B, D, h, w, cin, cout, int(bool(relu)))
+    return (y, yam[0]) if return_absmax else y
 
 
 @inference_only
 def pack_conv3d_weights_igemm(weight, mode):
     """weight: Conv3d (Cout,Cin,3,3,3), or ConvTranspose3d (Cin,Cout,3,3,3) for mode DECONV3D_STRIDE2 -> packed split-operand
-    fragments for conv3d_bn_relu_igemm (mvd_pack_conv3d_weights_igemm)."""
-    lib = L.load()
+    fragments for conv3d_bn_relu_igemm."""
     wt = L.as_f32(weight, "weight")
-    if wt.dim() != 5 or tuple(wt.shape[2:]) != (3, 3, 3):
-        raise ValueError(f"weight must be (*,*,3,3,3), got {tuple(wt.shape)}")
-    cin, cout = (wt.shape[0], wt.shape[1]) if mode == L.DECONV3D_STRIDE2 else (wt.shape[1], wt.shape[0])
-    n = lib.mvd_conv3d_igemm_packed_weight_bytes(cin, cout, mode)
+    cin, cout = _conv3d_channels(wt, mode)
+    n = L.load().mvd_conv3d_igemm_packed_weight_bytes(cin, cout, mode)
     if n == 0:
         raise ValueError(f"conv3d igemm: {cin} -> {cout} channels, mode {mode} is not built (Cin a multiple of 8 (16 transposed), Cout of 4)")
     packed = torch.empty(n, dtype=torch.uint8, device=wt.device)
-    with torch.cuda.device(wt.device):
-        rc = lib.mvd_pack_conv3d_weights_igemm(L.ptr(wt), cin, cout, mode, L.ptr(packed), L.stream_of(wt))
-    L.check(rc, "mvd_pack_conv3d_weights_igemm")
+    call("mvd_pack_conv3d_weights_igemm", wt.device, wt, cin, cout, mode, packed)
     return packed
 
 
 @inference_only
 def conv3d_bn_relu_igemm(x, x_absmax, packed, Cin, Cout, scale, shift, mode, relu=True, skip=None, return_absmax=False, out_absmax=None):
-    """K4's stride-2 / transposed / wide stride-1 layers on the split-operand implicit-GEMM kernel (mvd_conv3d_bn_relu_igemm_f32).
+    """K4's stride-2 / transposed / wide stride-1 layers on the split-operand implicit-GEMM kernel.
     x (B,D,h,w,Cin) channel-last fp32, x_absmax one-element device tensor with max |x| -> (B,Do,ho,wo,Cout); skip (like the output)
     is added after the activation.  return_absmax: also max |y| (out_absmax: a zeroed one-element device tensor to raise instead of a
     fresh one: several layers' slots can come from one zeroed buffer)."""
@@ -474,16 +430,7 @@ def conv3d_bn_relu_igemm(x, x_absmax, packed, Cin, Cout, scale, shift, mode, rel
         raise ValueError(f"x must be (B,D,h,w,{Cin}) channel-last, got {tuple(x.shape)}")
     B, Di, hi, wi, _ = x.shape
     dev = x.device
-    if mode == L.CONV3D_STRIDE1:
-        oshape = (B, Di, hi, wi, Cout)
-    elif mode == L.CONV3D_STRIDE2:
-        if Di % 2 or hi % 2 or wi % 2:
-            raise ValueError(f"stride-2 conv needs even D,h,w, got {Di},{hi},{wi}")
-        oshape = (B, Di // 2, hi // 2, wi // 2, Cout)
-    elif mode == L.DECONV3D_STRIDE2:
-        oshape = (B, Di * 2, hi * 2, wi * 2, Cout)
-    else:
-        raise ValueError(f"mode {mode}")
+    oshape = (B, *_conv3d_out_size(mode, Di, hi, wi), Cout)
     if packed.numel() != lib.mvd_conv3d_igemm_packed_weight_bytes(Cin, Cout, mode):
         raise ValueError(f"packed weights of {packed.numel()} bytes do not belong to a {Cin} -> {Cout} layer of mode {mode}")
     scale = L.as_f32(scale, "scale", (Cout,), dev)
@@ -496,38 +443,31 @@ def conv3d_bn_relu_igemm(x, x_absmax, packed, Cin, Cout, scale, shift, mode, rel
     if return_absmax:
         yam = torch.zeros(1, dtype=torch.float32, device=dev) if out_absmax is None else L.as_f32(out_absmax, "out_absmax", (1,), dev)
     wsb = lib.mvd_conv3d_igemm_workspace_bytes(B, Di, hi, wi, Cin, Cout, mode)
-    wsp = _workspace(wsb, dev) if wsb else None
-    with torch.cuda.device(dev):
-        rc = lib.mvd_conv3d_bn_relu_igemm_f32(L.ptr(x), L.ptr(xam), L.ptr(packed), L.ptr(scale), L.ptr(shift), L.ptr(skip), L.ptr(y),
-                                              L.ptr(yam), B, Di, hi, wi, Cin, Cout, mode, int(bool(relu)), L.ptr(wsp), wsb, L.stream_of(x))
-    L.check(rc, "mvd_conv3d_bn_relu_igemm_f32")
+    call("mvd_conv3d_bn_relu_igemm_f32", dev, x, xam, packed, scale, shift, skip, y, yam, B, Di, hi, wi, Cin, Cout, mode,
+          int(bool(relu)), workspace(wsb, dev) if wsb else None, wsb)
     return (y, yam) if return_absmax else y
 
 
 @inference_only
 def pack_conv2d_weights(weight):
     """weight: Conv2d (Cout,Cin,k,k), k in (3, 5) -> (packed, Cin, Cout, k)."""
-    lib = L.load()
     wt = L.as_f32(weight, "weight")
     if wt.dim() != 4 or wt.shape[2] != wt.shape[3]:
         raise ValueError(f"weight must be (Cout,Cin,k,k), got {tuple(wt.shape)}")
     Cout, Cin, k = wt.shape[0], wt.shape[1], wt.shape[2]
-    n = lib.mvd_conv2d_packed_weight_floats(Cin, Cout, k)
+    n = L.load().mvd_conv2d_packed_weight_floats(Cin, Cout, k)
     if n == 0:
         raise ValueError(f"conv2d: Cin={Cin}, Cout={Cout}, k={k} unsupported (Cin in 3/8/16/32, Cout in 8/16/32, k in 3/5)")
     packed = torch.empty(n, dtype=torch.float32, device=wt.device)
-    with torch.cuda.device(wt.device):
-        rc = lib.mvd_pack_conv2d_weights_f32(L.ptr(wt), Cin, Cout, k, L.ptr(packed), L.stream_of(wt))
-    L.check(rc, "mvd_pack_conv2d_weights_f32")
+    call("mvd_pack_conv2d_weights_f32", wt.device, wt, Cin, Cout, k, packed)
     return packed, Cin, Cout, k
 
 
 @inference_only
 def conv2d_head(image, w0, scale0, shift0, w1, scale1, shift1, return_absmax=False):
-    """FeatureNet's conv0 -> conv1 in one launch (mvd_conv2d_head_f32).  image (B,3,H,W); w0 (3,3,3,8), w1 (3,3,8,8): the Conv2d
+    """FeatureNet's conv0 -> conv1 in one launch.  image (B,3,H,W); w0 (3,3,3,8), w1 (3,3,8,8): the Conv2d
     weights as [ky][kx][cin][cout]; folded BN scale / shift (8) per layer.  Returns (B,H,W,8) channel-last; with return_absmax also
     max |y| as a one-element device tensor (per-tile maxima from the kernel, reduced by a pass over that small array)."""
-    lib = L.load()
     x = L.as_f32(image, "image")
     if x.dim() != 4 or x.shape[1] != 3:
         raise ValueError(f"image must be (B,3,H,W), got {tuple(x.shape)}")
@@ -537,11 +477,8 @@ def conv2d_head(image, w0, scale0, shift0, w1, scale1, shift1, return_absmax=Fal
     w1 = L.as_f32(w1, "w1", (3, 3, 8, 8), dev)
     vs = [L.as_f32(v, n, (8,), dev) for v, n in ((scale0, "scale0"), (shift0, "shift0"), (scale1, "scale1"), (shift1, "shift1"))]
     y = torch.empty((B, H, W, 8), dtype=torch.float32, device=dev)
-    tiles = torch.empty(lib.mvd_conv2d_head_tile_count(B, H, W), dtype=torch.float32, device=dev) if return_absmax else None
-    with torch.cuda.device(dev):
-        rc = lib.mvd_conv2d_head_f32(L.ptr(x), L.ptr(w0), L.ptr(vs[0]), L.ptr(vs[1]), L.ptr(w1), L.ptr(vs[2]), L.ptr(vs[3]), L.ptr(y),
-                                     L.ptr(tiles), B, H, W, L.stream_of(x))
-    L.check(rc, "mvd_conv2d_head_f32")
+    tiles = torch.empty(L.load().mvd_conv2d_head_tile_count(B, H, W), dtype=torch.float32, device=dev) if return_absmax else None
+    call("mvd_conv2d_head_f32", dev, x, w0, vs[0], vs[1], w1, vs[2], vs[3], y, tiles, B, H, W)
     return (y, absmax(tiles)) if return_absmax else y
 
 
@@ -549,8 +486,7 @@ def conv2d_bn_relu(x, packed, Cin, Cout, ksize, stride, scale, shift, relu=True,
     """K6. x: (B,3,H,W) image when Cin == 3, else channel-last (B,h,w,Cin).  Returns (B,ho,wo,Cout) for LAYOUT_NHWC,
     (B,Cout,ho,wo) for LAYOUT_NCHW, or the zero-bordered (B,ho+3,wo+3,Cout) staging map for LAYOUT_NHWC_BORDER
     (`out` may pass a buffer whose border is already zero; only the interior is written).  out_absmax: a zeroed one-element
-    device tensor that is raised to max |y| (mvd_conv2d_bn_relu_absmax_f32), for a split-operand layer behind this one."""
-    lib = L.load()
+    device tensor that is raised to max |y|, for a split-operand layer behind this one."""
     x = L.as_f32(x, "x")
     if Cin == 3:
         if x.dim() != 4 or x.shape[1] != 3:
@@ -580,24 +516,16 @@ def conv2d_bn_relu(x, packed, Cin, Cout, ksize, stride, scale, shift, relu=True,
         y = torch.zeros(oshape, dtype=torch.float32, device=dev)
     else:
         y = torch.empty(oshape, dtype=torch.float32, device=dev)
-    if out_absmax is not None:
-        yam = L.as_f32(out_absmax, "out_absmax", (1,), dev)
-        with torch.cuda.device(dev):
-            rc = lib.mvd_conv2d_bn_relu_absmax_f32(L.ptr(x), in_layout, L.ptr(packed), L.ptr(scale), L.ptr(shift), L.ptr(y), L.ptr(yam),
-                                                   out_layout, B, hi, wi, Cin, Cout, ksize, stride, int(bool(relu)), L.stream_of(x))
-        L.check(rc, "mvd_conv2d_bn_relu_absmax_f32")
-        return y
-    with torch.cuda.device(dev):
-        rc = lib.mvd_conv2d_bn_relu_f32(L.ptr(x), in_layout, L.ptr(packed), L.ptr(scale), L.ptr(shift), L.ptr(y), out_layout,
-                                        B, hi, wi, Cin, Cout, ksize, stride, int(bool(relu)), L.stream_of(x))
-    L.check(rc, "mvd_conv2d_bn_relu_f32")
+    name, yam = "mvd_conv2d_bn_relu_f32", []
+    if out_absmax is not None:  # the twin takes one more pointer, behind y
+        name, yam = "mvd_conv2d_bn_relu_absmax_f32", [L.as_f32(out_absmax, "out_absmax", (1,), dev)]
+    call(name, dev, x, in_layout, packed, scale, shift, y, *yam, out_layout, B, hi, wi, Cin, Cout, ksize, stride, int(bool(relu)))
     return y
 
 
 @inference_only
 def softmax_regress(cost, depth_values, with_confidence=True):
     """K5. cost (B,D,h,w); depth_values (B,D) -> depth (B,h,w), confidence (B,h,w) or None."""
-    lib = L.load()
     c = L.as_f32(cost, "cost")
     if c.dim() != 4:
         raise ValueError("cost must be (B,D,h,w)")
@@ -605,9 +533,7 @@ def softmax_regress(cost, depth_values, with_confidence=True):
     dv = L.as_f32(depth_values, "depth_values", (B, D), c.device)
     depth = torch.empty((B, h, w), dtype=torch.float32, device=c.device)
     conf = torch.empty((B, h, w), dtype=torch.float32, device=c.device) if with_confidence else None
-    with torch.cuda.device(c.device):
-        rc = lib.mvd_softmax_regress_f32(L.ptr(c), L.ptr(dv), B, D, h, w, L.ptr(depth), L.ptr(conf), L.stream_of(c))
-    L.check(rc, "mvd_softmax_regress_f32")
+    call("mvd_softmax_regress_f32", c.device, c, dv, B, D, h, w, depth, conf)
     return depth, conf
 
 
@@ -625,7 +551,6 @@ def pack_conv2d_weights_split(weight, bias=None, stride=1, mode=L.CONV2D, cin_pa
     """weight: Conv2d (Cout,Cin,k,k) (mode CONV2D / CONV2D_IMAGE) or ConvTranspose2d (Cin,Cout,4,4) (mode DECONV2D), fp32 ->
     SplitConv2dWeights for conv2d_split.  cin_pad: the channel count of the (zero-padded) input slice the layer will read, a
     multiple of 8 (default: Cin rounded up to 8)."""
-    lib = L.load()
     wt = L.as_f32(weight, "weight")
     if wt.dim() != 4:
         raise ValueError(f"weight must be 4-D, got {tuple(wt.shape)}")
@@ -635,13 +560,11 @@ def pack_conv2d_weights_split(weight, bias=None, stride=1, mode=L.CONV2D, cin_pa
         cout, cin = wt.shape[0], wt.shape[1]
     kh, kw = wt.shape[2], wt.shape[3]
     cin_pad = (cin + 7) // 8 * 8 if cin_pad is None else int(cin_pad)
-    nbytes = lib.mvd_conv2d_split_packed_weight_bytes(cin_pad, cout, kh, kw, stride, mode) if cin_pad >= cin else 0
+    nbytes = L.load().mvd_conv2d_split_packed_weight_bytes(cin_pad, cout, kh, kw, stride, mode) if cin_pad >= cin else 0
     if nbytes == 0:
         raise ValueError(f"conv2d split: a {kh}x{kw} stride-{stride} layer (mode {mode}) with {cin} (padded {cin_pad}) -> {cout} channels is not built")
     packed = torch.empty(nbytes, dtype=torch.uint8, device=wt.device)
-    with torch.cuda.device(wt.device):
-        rc = lib.mvd_pack_conv2d_weights_split(L.ptr(wt), cin, cin_pad, cout, kh, kw, stride, mode, L.ptr(packed), L.stream_of(wt))
-    L.check(rc, "mvd_pack_conv2d_weights_split")
+    call("mvd_pack_conv2d_weights_split", wt.device, wt, cin, cin_pad, cout, kh, kw, stride, mode, packed)
     b = None if bias is None else L.as_f32(bias.detach(), "bias", (cout,), wt.device).clone()
     return SplitConv2dWeights(packed, b, cin, cin_pad, cout, kh, kw, stride, mode)
 
@@ -666,12 +589,11 @@ def _nhwc_slice(t, name, channels=None, free_rows=False):
 
 @inference_only
 def conv2d_split(x, x_absmax, wts, act=1, slope=0.2, out=None, out_absmax=None, use_workspace=True, planar_out=False):
-    """One layer of Path A's 2-D CNN on the split-operand kernel (mvd_conv2d_split_f32).  x: (B,Hi,Wi,Cin_pad) NHWC fp32, possibly
+    """One layer of Path A's 2-D CNN on the split-operand kernel.  x: (B,Hi,Wi,Cin_pad) NHWC fp32, possibly
     a channel slice of a wider buffer (mode CONV2D_IMAGE: the planar (B,3,Hi,Wi) image); x_absmax: one-element device tensor with
     max |x|; wts: SplitConv2dWeights.  out: NHWC destination view (B,Ho,Wo,Cout), e.g. a slice of a concat buffer or the interior
     of a zero-bordered map (allocated if None); planar_out: allocate and return (B,Cout,Ho,Wo) instead.  out_absmax: one-element
     device tensor that receives max |out| by atomic maximum (zero it first), or None.  act 0 none / 1 LeakyReLU(slope) / 2 ReLU."""
-    lib = L.load()
     if wts.mode == L.CONV2D_IMAGE:
         xi = L.as_f32(x, "x")
         if xi.dim() != 4 or xi.shape[1] != 3:
@@ -700,51 +622,39 @@ def conv2d_split(x, x_absmax, wts, act=1, slope=0.2, out=None, out_absmax=None, 
             raise ValueError(f"out is {tuple(out.shape)}, the layer writes ({B},{Ho},{Wo},{wts.cout})")
     xam = L.as_f32(x_absmax, "x_absmax", (1,), dev)
     yam = None if out_absmax is None else L.as_f32(out_absmax, "out_absmax", (1,), dev)
-    wsb = lib.mvd_conv2d_split_workspace_bytes(B, Hi, Wi, wts.cin_pad, wts.cout, wts.kh, wts.kw, wts.stride, wts.mode) if use_workspace else 0
-    wsp = _workspace(wsb, dev) if wsb else None
-    with torch.cuda.device(dev):
-        rc = lib.mvd_conv2d_split_f32(L.ptr(x), L.ptr(xam), L.ptr(wts.packed), L.ptr(wts.bias), L.ptr(out), L.ptr(yam), B, Hi, Wi,
-                                      wts.cin_pad, xs, wts.cout, ys, rs, ims, cs, wts.kh, wts.kw, wts.stride, wts.mode, int(act),
-                                      float(slope), L.ptr(wsp), wsb, L.stream_of(x))
-    L.check(rc, "mvd_conv2d_split_f32")
+    wsb = L.load().mvd_conv2d_split_workspace_bytes(B, Hi, Wi, wts.cin_pad, wts.cout, wts.kh, wts.kw, wts.stride, wts.mode) if use_workspace else 0
+    call("mvd_conv2d_split_f32", dev, x, xam, wts.packed, wts.bias, out, yam, B, Hi, Wi, wts.cin_pad, xs, wts.cout, ys, rs, ims, cs,
+          wts.kh, wts.kw, wts.stride, wts.mode, int(act), float(slope), workspace(wsb, dev) if wsb else None, wsb)
     return out
 
 
 @inference_only
 def upsample2x_into(x, out, out_absmax=None):
     """F.interpolate(x, size=(2h,2w), mode="bilinear", align_corners=False) of a planar (B,C,h,w) map written into the channel-last
-    slice out (B,2h,2w,C) (mvd_upsample2x_nhwc_f32: the decoder's up-sampled prediction inside the next level's concat buffer)."""
-    lib = L.load()
+    slice out (B,2h,2w,C) (the decoder's up-sampled prediction inside the next level's concat buffer)."""
     x = L.as_f32(x, "x")
     B, C, h, w = x.shape
     ob, oh, ow, _, ys, _, _ = _nhwc_slice(out, "out", C)
     if (ob, oh, ow) != (B, 2 * h, 2 * w):
         raise ValueError(f"out is {tuple(out.shape)}, expected ({B},{2 * h},{2 * w},{C})")
     yam = None if out_absmax is None else L.as_f32(out_absmax, "out_absmax", (1,), x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.mvd_upsample2x_nhwc_f32(L.ptr(x), L.ptr(out), L.ptr(yam), B, C, h, w, ys, L.stream_of(x))
-    L.check(rc, "mvd_upsample2x_nhwc_f32")
+    call("mvd_upsample2x_nhwc_f32", x.device, x, out, yam, B, C, h, w, ys)
     return out
 
 
 @inference_only
 def sweep_corr_nhwc(feat_key, feat_sources, K_key, K_sources, T_src2key, invdepths, corrs, masks, corr_scale=None, corr_absmax=None):
-    """K1 on its working layouts (mvd_sweep_corr_nhwc_f32): feat_key (N,h,w,C) channel-last; feat_sources V x zero-bordered
+    """K1 on its working layouts: feat_key (N,h,w,C) channel-last; feat_sources V x zero-bordered
     channel-last (N,hs+3,ws+3,C); corrs, masks: V x pixel-major destinations (N,h,w,S) (channel slices allowed), filled in place.
     corr_absmax: one-element device tensor raised to max |corr| over all views (zero it first), or None."""
-    lib = L.load()
     fk = L.as_f32(feat_key, "feat_key")
     N, h, w, C = fk.shape
     dev = fk.device
-    srcs = _views(feat_sources, "feat_sources")
+    srcs = views(feat_sources, "feat_sources")
     V = len(srcs)
     hs, ws = srcs[0].shape[1] - 3, srcs[0].shape[2] - 3
     srcs = [L.as_f32(s, f"feat_sources[{i}]", (N, hs + 3, ws + 3, C), dev) for i, s in enumerate(srcs)]
-    Kk = L.as_f32(K_key, "intrinsics_key", (N, 3, 3), dev)
-    Ks = [L.as_f32(k, f"intrinsics_sources[{i}]", (N, 3, 3), dev) for i, k in enumerate(_views(K_sources, "intrinsics_sources", V))]
-    Ts = [L.as_f32(t, f"source_to_key_transforms[{i}]", (N, 4, 4), dev) for i, t in enumerate(_views(T_src2key, "source_to_key_transforms", V))]
-    inv = L.as_f32(invdepths, "sampling_invdepths", device=dev)
-    mode = _invdepth_mode(inv, N, h, w)
+    Kk, Ks, Ts, inv, mode = _k1_calibration(K_key, K_sources, T_src2key, invdepths, V, N, h, w, dev)
     S = inv.shape[1]
     if C % 64 != 0:
         raise ValueError(f"feature channels C={C} must be a multiple of 64")
@@ -757,17 +667,9 @@ def sweep_corr_nhwc(feat_key, feat_sources, K_key, K_sources, T_src2key, invdept
             if (b_, h_, w_) != (N, h, w) or (ps is not None and p_ != ps):
                 raise ValueError(f"{name}: (N,h,w,S) = ({N},{h},{w},{S}) maps with one common pixel stride are needed")
             ps = p_
-    scale = float(corr_scale) if corr_scale is not None else 1.0 / float(C) ** 0.5
-    a_src, k1 = L.ptr_array(srcs)
-    a_K, k2 = L.ptr_array(Ks)
-    a_T, k3 = L.ptr_array(Ts)
-    a_c, k4 = L.ptr_array(list(corrs))
-    a_m, k5 = L.ptr_array(list(masks))
     cam = None if corr_absmax is None else L.as_f32(corr_absmax, "corr_absmax", (1,), dev)
-    with torch.cuda.device(dev):
-        rc = lib.mvd_sweep_corr_nhwc_f32(L.ptr(fk), a_src, L.ptr(Kk), a_K, a_T, L.ptr(inv), mode, scale, N, C, h, w, hs, ws, S, V,
-                                         a_c, a_m, ps, L.ptr(cam), L.stream_of(fk))
-    L.check(rc, "mvd_sweep_corr_nhwc_f32")
+    call("mvd_sweep_corr_nhwc_f32", dev, fk, srcs, Kk, Ks, Ts, inv, mode, _corr_scale(corr_scale, C), N, C, h, w, hs, ws, S, V,
+          list(corrs), list(masks), ps, cam)
     return corrs, masks
 
 
@@ -775,7 +677,6 @@ def sweep_corr_nhwc(feat_key, feat_sources, K_key, K_sources, T_src2key, invdept
 def fuse_views_nhwc(corrs, masks, scores, out, out_absmax=None):
     """K2 on pixel-major volumes: corrs, masks V x (N,h,w,S); scores V x (N,h,w,1) or (N,1,h,w); out: (N,h,w,S) destination view
     (a channel slice of the cost-volume encoder's input buffer).  Returns out."""
-    lib = L.load()
     V = len(corrs)
     N, h, w, S, ps, _, _ = _nhwc_slice(corrs[0], "corrs[0]")
     dev = corrs[0].device
@@ -783,39 +684,30 @@ def fuse_views_nhwc(corrs, masks, scores, out, out_absmax=None):
         for t in ts:
             if _nhwc_slice(t, name, S)[:5] != (N, h, w, S, ps):
                 raise ValueError(f"{name}: equal (N,h,w,S) maps are needed")
-    scores = [L.as_f32(s_.reshape(N, h * w), f"scores[{i}]", (N, h * w), dev) for i, s_ in enumerate(_views(scores, "scores", V))]
+    scores = [L.as_f32(s_.reshape(N, h * w), f"scores[{i}]", (N, h * w), dev) for i, s_ in enumerate(views(scores, "scores", V))]
     ob, oh, ow, _, ops_, _, _ = _nhwc_slice(out, "out", S)
     if (ob, oh, ow) != (N, h, w):
         raise ValueError(f"out is {tuple(out.shape)}, expected ({N},{h},{w},{S})")
     yam = None if out_absmax is None else L.as_f32(out_absmax, "out_absmax", (1,), dev)
-    a_c, k1 = L.ptr_array(list(corrs))
-    a_m, k2 = L.ptr_array(list(masks))
-    a_s, k3 = L.ptr_array(scores)
-    with torch.cuda.device(dev):
-        rc = lib.mvd_fuse_views_nhwc_f32(a_c, a_m, a_s, N, S, h, w, V, ps, L.ptr(out), None, ops_, L.ptr(yam), L.stream_of(corrs[0]))
-    L.check(rc, "mvd_fuse_views_nhwc_f32")
+    call("mvd_fuse_views_nhwc_f32", dev, list(corrs), list(masks), scores, N, S, h, w, V, ps, out, None, ops_, yam)
     return out
 
 
 @inference_only
 def bias_leaky_relu_(x, bias, slope=0.2):
     """In place: x (N,C,H,W) contiguous <- leaky_relu(x + bias[c], slope).  Returns x."""
-    lib = L.load()
     if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() >= 2):
         raise ValueError("bias_leaky_relu_: x must be a contiguous fp32 device tensor (N,C,...)")
     N, C = x.shape[0], x.shape[1]
     b = L.as_f32(bias, "bias", (C,), x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.mvd_bias_leaky_relu_f32(L.ptr(x), L.ptr(b), N, C, x.numel() // (N * C), float(slope), L.stream_of(x))
-    L.check(rc, "mvd_bias_leaky_relu_f32")
+    call("mvd_bias_leaky_relu_f32", x.device, x, b, N, C, x.numel() // (N * C), float(slope))
     return x
 
 
 @inference_only
 def resize_order1(images, ht, wd):
     """images (..., H, W) fp32 device tensor -> (..., ht, wd): skimage.transform.resize(order=1) for upscaling
-    (rmvd/data/transforms.py:64-66), on the device (mvd_resize_order1_f32)."""
-    lib = L.load()
+    (rmvd/data/transforms.py:64-66), on the device."""
     x = L.as_f32(images, "images")
     if x.dim() < 2:
         raise ValueError("images must be (..., H, W)")
@@ -824,9 +716,7 @@ def resize_order1(images, ht, wd):
         raise ValueError(f"resize_order1: only upscaling is built ({hi}x{wi} -> {ht}x{wd})")
     planes = x.numel() // (hi * wi)
     y = torch.empty(tuple(x.shape[:-2]) + (ht, wd), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.mvd_resize_order1_f32(L.ptr(x), L.ptr(y), planes, hi, wi, ht, wd, L.stream_of(x))
-    L.check(rc, "mvd_resize_order1_f32")
+    call("mvd_resize_order1_f32", x.device, x, y, planes, hi, wi, ht, wd)
     return y
 
 
@@ -834,42 +724,33 @@ def resize_order1(images, ht, wd):
 def dispnet_head(x):
     """x (N,2,h,w) raw output of a pred_k convolution -> (pred (N,2,h,w) = [relu(x0), sigmoid(0.2 x1) * 20 - 10],
     entropy (N,1,h,w) = log(2 exp(pred1) + 1e-4) + 1) in one launch (dispnet_decoder.py:17-22,126-138)."""
-    lib = L.load()
     x = L.as_f32(x, "x")
     if x.dim() != 4 or x.shape[1] != 2:
         raise ValueError(f"x must be (N,2,h,w), got {tuple(x.shape)}")
     N, _, h, w = x.shape
     pred = torch.empty_like(x)
     ent = torch.empty((N, 1, h, w), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.mvd_dispnet_head_f32(L.ptr(x), L.ptr(pred), L.ptr(ent), N, h * w, L.stream_of(x))
-    L.check(rc, "mvd_dispnet_head_f32")
+    call("mvd_dispnet_head_f32", x.device, x, pred, ent, N, h * w)
     return pred, ent
 
 
 @inference_only
 def to_channels_last_3d(x):
     """(B,C,D,h,w) -> (B,D,h,w,C) through the library's tiled transpose."""
-    lib = L.load()
     x = L.as_f32(x, "x")
     B, C, D, h, w = x.shape
     y = torch.empty((B, D, h, w, C), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.mvd_nchw_to_nhwc_f32(L.ptr(x), L.ptr(y), B, C, D * h * w, L.stream_of(x))
-    L.check(rc, "mvd_nchw_to_nhwc_f32")
+    call("mvd_nchw_to_nhwc_f32", x.device, x, y, B, C, D * h * w)
     return y
 
 
 @inference_only
 def from_channels_last_3d(y):
     """(B,D,h,w,C) -> (B,C,D,h,w)."""
-    lib = L.load()
     y = L.as_f32(y, "y")
     B, D, h, w, C = y.shape
     x = torch.empty((B, C, D, h, w), dtype=torch.float32, device=y.device)
-    with torch.cuda.device(y.device):
-        rc = lib.mvd_nhwc_to_nchw_f32(L.ptr(y), L.ptr(x), B, C, D * h * w, L.stream_of(y))
-    L.check(rc, "mvd_nhwc_to_nchw_f32")
+    call("mvd_nhwc_to_nchw_f32", y.device, y, x, B, C, D * h * w)
     return x
 
 
@@ -901,12 +782,10 @@ class _WarpVariance(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gvar):
-        lib = L.load()
         V = ctx.n_views
         kpi, dv, key = ctx.saved_tensors[:3]
         srcs, projs = list(ctx.saved_tensors[3:3 + V]), list(ctx.saved_tensors[3 + V:])
         B, C, h, w = key.shape
-        D = dv.shape[1]
         dev = key.device
         with torch.no_grad():
             kb = _bordered_channels_last(key.float())
@@ -914,25 +793,18 @@ class _WarpVariance(torch.autograd.Function):
             g = gvar.float().permute(0, 2, 3, 4, 1).contiguous()  # (B,D,h,w,C)
             gk = torch.empty_like(kb)
             gs = [torch.empty_like(kb) for _ in range(V)]
-            pr = [L.as_f32(p, "src_proj", (B, 4, 4), dev) for p in projs]
-            wsb = lib.mvd_warp_variance_backward_workspace_bytes(B)
-            wsp = _workspace(wsb, dev)
-            a_s, k1 = L.ptr_array(sb)
-            a_p, k2 = L.ptr_array(pr)
-            a_g, k3 = L.ptr_array(gs)
-            with torch.cuda.device(dev):
-                rc = lib.mvd_warp_variance_backward_f32(L.ptr(kb), a_s, a_p, L.ptr(L.as_f32(kpi, "key_proj_inv", (B, 4, 4), dev)),
-                                                        L.ptr(L.as_f32(dv, "depth_values", (B, D), dev)), L.ptr(g), B, C, D, h, w,
-                                                        V, L.ptr(gk), a_g, L.ptr(wsp), wsb, L.stream_of(kb))
-            L.check(rc, "mvd_warp_variance_backward_f32")
+            projs, kpi, dv = _k3_calibration(projs, kpi, dv, V, B, C, dev)
+            wsb = L.load().mvd_warp_variance_backward_workspace_bytes(B)
+            call("mvd_warp_variance_backward_f32", dev, kb, sb, projs, kpi, dv, g, B, C, dv.shape[1], h, w, V, gk, gs,
+                  workspace(wsb, dev), wsb)
             out = [None, None, None, _interior_nchw(gk, h, w)] + [_interior_nchw(x, h, w) for x in gs] + [None] * V
         return tuple(out)
 
 
 def warp_variance_autograd(key_feat, src_feats, src_projs, key_proj_inv, depth_values):
     """Differentiable K3: like warp_variance (reference layout (B,C,D,h,w)), with gradients to key_feat and src_feats."""
-    srcs = _views(src_feats, "src_feats")
-    return _WarpVariance.apply(key_proj_inv, depth_values, len(srcs), key_feat, *srcs, *_views(src_projs, "src_projs", len(srcs)))
+    srcs = views(src_feats, "src_feats")
+    return _WarpVariance.apply(key_proj_inv, depth_values, len(srcs), key_feat, *srcs, *views(src_projs, "src_projs", len(srcs)))
 
 
 class _SweepCorr(torch.autograd.Function):
@@ -949,7 +821,6 @@ class _SweepCorr(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        lib = L.load()
         V = ctx.n_views
         Kk, inv, fk = ctx.saved_tensors[:3]
         srcs = list(ctx.saved_tensors[3:3 + V])
@@ -964,30 +835,19 @@ class _SweepCorr(torch.autograd.Function):
             gc = [(g if g is not None else torch.zeros((N, S, h, w), device=dev)).float().contiguous() for g in grads[:V]]
             gk = torch.empty_like(key)
             gs = [torch.empty_like(sb[0]) for _ in range(V)]
-            Ksf = [L.as_f32(k, "K_src", (N, 3, 3), dev) for k in Ks]
-            Tsf = [L.as_f32(t, "T", (N, 4, 4), dev) for t in Ts]
-            a_s, k1 = L.ptr_array(sb)
-            a_K, k2 = L.ptr_array(Ksf)
-            a_T, k3 = L.ptr_array(Tsf)
-            a_gc, k4 = L.ptr_array(gc)
-            a_gs, k5 = L.ptr_array(gs)
-            invf = L.as_f32(inv, "invdepths", device=dev)
-            scale = float(ctx.corr_scale) if ctx.corr_scale is not None else 1.0 / float(C) ** 0.5
-            with torch.cuda.device(dev):
-                rc = lib.mvd_sweep_corr_backward_f32(L.ptr(key), a_s, L.ptr(L.as_f32(Kk, "K_key", (N, 3, 3), dev)), a_K, a_T,
-                                                     L.ptr(invf), _invdepth_mode(invf, N, h, w), scale, a_gc, N, C, h, w, hs, ws,
-                                                     S, V, L.ptr(gk), a_gs, L.stream_of(key))
-            L.check(rc, "mvd_sweep_corr_backward_f32")
+            Kk, Ks, Ts, inv, mode = _k1_calibration(Kk, Ks, Ts, inv, V, N, h, w, dev)
+            call("mvd_sweep_corr_backward_f32", dev, key, sb, Kk, Ks, Ts, inv, mode, _corr_scale(ctx.corr_scale, C), gc,
+                  N, C, h, w, hs, ws, S, V, gk, gs)
             out = [None, None, None, None, gk.permute(0, 3, 1, 2).contiguous()] + [_interior_nchw(x, hs, ws) for x in gs] + [None] * (2 * V)
         return tuple(out)
 
 
 def sweep_corr_autograd(feat_key, feat_sources, K_key, K_sources, T_src2key, invdepths, corr_scale=None):
     """Differentiable K1: returns (corrs[V], masks[V]); gradients to feat_key and feat_sources."""
-    srcs = _views(feat_sources, "feat_sources")
+    srcs = views(feat_sources, "feat_sources")
     V = len(srcs)
-    outs = _SweepCorr.apply(K_key, invdepths, V, corr_scale, feat_key, *srcs, *_views(K_sources, "intrinsics_sources", V),
-                            *_views(T_src2key, "source_to_key_transforms", V))
+    outs = _SweepCorr.apply(K_key, invdepths, V, corr_scale, feat_key, *srcs, *views(K_sources, "intrinsics_sources", V),
+                            *views(T_src2key, "source_to_key_transforms", V))
     return list(outs[:V]), list(outs[V:])
 
 
@@ -1004,41 +864,32 @@ class _FuseViews(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gfused, _gmask):
-        lib = L.load()
         V = ctx.n_views
         t = ctx.saved_tensors
         corrs, masks, scores = list(t[:V]), list(t[V:2 * V]), list(t[2 * V:])
         N, S, h, w = corrs[0].shape
         dev = corrs[0].device
         with torch.no_grad():
-            cs = [L.as_f32(c, "corr", (N, S, h, w), dev) for c in corrs]
-            ms = [L.as_f32(m, "mask", (N, S, h, w), dev) for m in masks]
-            ss = [L.as_f32(s, "score", (N, 1, h, w), dev) for s in scores]
+            cs = [L.as_f32(c, f"corrs[{i}]", (N, S, h, w), dev) for i, c in enumerate(corrs)]
+            ms = [L.as_f32(m, f"masks[{i}]", (N, S, h, w), dev) for i, m in enumerate(masks)]
+            ss = [L.as_f32(s, f"scores[{i}]", (N, 1, h, w), dev) for i, s in enumerate(scores)]
             g = gfused.float().contiguous()
             gcs = [torch.empty_like(cs[0]) for _ in range(V)]
             gss = [torch.empty_like(ss[0]) for _ in range(V)]
-            a_c, k1 = L.ptr_array(cs)
-            a_m, k2 = L.ptr_array(ms)
-            a_s, k3 = L.ptr_array(ss)
-            a_gc, k4 = L.ptr_array(gcs)
-            a_gs, k5 = L.ptr_array(gss)
-            with torch.cuda.device(dev):
-                rc = lib.mvd_fuse_views_backward_f32(a_c, a_m, a_s, L.ptr(g), N, S, h, w, V, a_gc, a_gs, L.stream_of(g))
-            L.check(rc, "mvd_fuse_views_backward_f32")
+            call("mvd_fuse_views_backward_f32", dev, cs, ms, ss, g, N, S, h, w, V, gcs, gss)
         return (None,) + tuple(gcs) + (None,) * V + tuple(gss)
 
 
 def fuse_views_autograd(corrs, masks, scores):
     """Differentiable K2: gradients to corrs and scores."""
-    corrs = _views(corrs, "corrs")
+    corrs = views(corrs, "corrs")
     V = len(corrs)
-    return _FuseViews.apply(V, *corrs, *_views(masks, "masks", V), *_views(scores, "scores", V))
+    return _FuseViews.apply(V, *corrs, *views(masks, "masks", V), *views(scores, "scores", V))
 
 
 class _SoftmaxRegress(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cost, depth_values):
-        lib = L.load()
         c = L.as_f32(cost.detach(), "cost")
         if c.dim() != 4:
             raise ValueError("cost must be (B,D,h,w)")
@@ -1047,26 +898,19 @@ class _SoftmaxRegress(torch.autograd.Function):
         depth = torch.empty((B, h, w), dtype=torch.float32, device=c.device)
         conf = torch.empty((B, h, w), dtype=torch.float32, device=c.device)
         stats = torch.empty((B, 2, h, w), dtype=torch.float32, device=c.device)
-        with torch.cuda.device(c.device):
-            rc = lib.mvd_softmax_regress_stats_f32(L.ptr(c), L.ptr(dv), B, D, h, w, L.ptr(depth), L.ptr(conf), L.ptr(stats),
-                                                   L.stream_of(c))
-        L.check(rc, "mvd_softmax_regress_stats_f32")
+        call("mvd_softmax_regress_stats_f32", c.device, c, dv, B, D, h, w, depth, conf, stats)
         ctx.save_for_backward(c, dv, depth, stats)
         ctx.mark_non_differentiable(conf)
         return depth, conf
 
     @staticmethod
     def backward(ctx, g_depth, _g_conf):
-        lib = L.load()
         c, dv, depth, stats = ctx.saved_tensors
         B, D, h, w = c.shape
         with torch.no_grad():
             g = g_depth.float().contiguous() if g_depth is not None else None
             g_cost = torch.empty_like(c)
-            with torch.cuda.device(c.device):
-                rc = lib.mvd_softmax_regress_backward_f32(L.ptr(c), L.ptr(dv), L.ptr(depth), L.ptr(stats), L.ptr(g), B, D, h, w,
-                                                          L.ptr(g_cost), L.stream_of(c))
-            L.check(rc, "mvd_softmax_regress_backward_f32")
+            call("mvd_softmax_regress_backward_f32", c.device, c, dv, depth, stats, g, B, D, h, w, g_cost)
         return g_cost, None
 
 
@@ -1092,11 +936,6 @@ def conv3d_adjoint(weight, mode):
     if mode == L.DECONV3D_STRIDE2:
         return weight, L.CONV3D_STRIDE2
     raise ValueError(f"mode {mode}")
-
-
-def _conv3d_channels(weight, mode):
-    """(Cin, Cout) of a layer from its torch weight."""
-    return (weight.shape[0], weight.shape[1]) if mode == L.DECONV3D_STRIDE2 else (weight.shape[1], weight.shape[0])
 
 
 _IDENTITY_EPILOGUE = {}
@@ -1141,49 +980,25 @@ def _conv3d_blocked(x, weight, mode):
     return out
 
 
-def _strict_f32(t, name):
-    """The differentiable ops do not convert: a silent .float() / .cuda() copy would detach the caller's tensor from its gradient."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
-    if not t.is_cuda:
-        raise ValueError(f"{name}: tensor is on {t.device}; the HIP engine needs a cuda (ROCm) device tensor")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name}: dtype {t.dtype}, expected torch.float32")
-    return t
-
-
 @inference_only
 def conv3d_weight_grad(x, gy, mode):
-    """mvd_conv3d_weight_grad_f32: x (B,Di,hi,wi,Cin) and gy (B,Do,ho,wo,Cout) channel-last -> the gradient of the layer's
+    """x (B,Di,hi,wi,Cin) and gy (B,Do,ho,wo,Cout) channel-last -> the gradient of the layer's
     3x3x3 weight in its torch layout, (Cout,Cin,3,3,3) or (Cin,Cout,3,3,3) for DECONV3D_STRIDE2.  Deterministic."""
-    lib = L.load()
     x = L.as_f32(x, "x")
     if x.dim() != 5:
         raise ValueError(f"x must be (B,D,h,w,Cin) channel-last, got {tuple(x.shape)}")
     B, Di, hi, wi, Cin = x.shape
-    if mode == L.CONV3D_STRIDE1:
-        osz = (Di, hi, wi)
-    elif mode == L.CONV3D_STRIDE2:
-        if Di % 2 or hi % 2 or wi % 2:
-            raise ValueError(f"stride-2 conv needs even D,h,w, got {Di},{hi},{wi}")
-        osz = (Di // 2, hi // 2, wi // 2)
-    elif mode == L.DECONV3D_STRIDE2:
-        osz = (Di * 2, hi * 2, wi * 2)
-    else:
-        raise ValueError(f"mode {mode}")
+    osz = _conv3d_out_size(mode, Di, hi, wi)
     gy = L.as_f32(gy, "gy", device=x.device)
     if gy.dim() != 5 or tuple(gy.shape[:4]) != (B, *osz):
         raise ValueError(f"gy must be ({B},{osz[0]},{osz[1]},{osz[2]},Cout) channel-last, got {tuple(gy.shape)}")
     Cout = gy.shape[4]
-    nbytes = lib.mvd_conv3d_weight_grad_workspace_bytes(B, Di, hi, wi, Cin, Cout, mode)
+    nbytes = L.load().mvd_conv3d_weight_grad_workspace_bytes(B, Di, hi, wi, Cin, Cout, mode)
     if nbytes == 0:
         raise ValueError(f"conv3d_weight_grad: Cin={Cin}, Cout={Cout} unsupported (1..64)")
-    ws = _workspace(nbytes, x.device)
+    ws = workspace(nbytes, x.device)
     gw = torch.empty((Cin, Cout, 3, 3, 3) if mode == L.DECONV3D_STRIDE2 else (Cout, Cin, 3, 3, 3), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.mvd_conv3d_weight_grad_f32(L.ptr(x), L.ptr(gy), L.ptr(gw), B, Di, hi, wi, Cin, Cout, mode, L.ptr(ws), nbytes,
-                                            L.stream_of(x))
-    L.check(rc, "mvd_conv3d_weight_grad_f32")
+    call("mvd_conv3d_weight_grad_f32", x.device, x, gy, gw, B, Di, hi, wi, Cin, Cout, mode, ws, nbytes)
     return gw
 
 
@@ -1211,8 +1026,9 @@ def conv3d_autograd(x, weight, mode):
     """Differentiable K4 layer without epilogue: x (B,D,h,w,Cin) channel-last fp32, weight in the layer's torch layout
     ((Cout,Cin,3,3,3), or (Cin,Cout,3,3,3) for DECONV3D_STRIDE2) -> (B,Do,ho,wo,Cout).  Forward and the gradient w.r.t. x run on
     mvd_conv3d_bn_relu_f32 (the latter with conv3d_adjoint's weights and blocked accumulation, _conv3d_blocked), the gradient
-    w.r.t. weight on mvd_conv3d_weight_grad_f32."""
-    x, weight = _strict_f32(x, "x"), _strict_f32(weight, "weight")
+    w.r.t. weight on mvd_conv3d_weight_grad_f32.  Nothing is converted: a silent .float() / .cuda() copy would detach the
+    caller's tensor from its gradient."""
+    x, weight = L.as_dtype(torch.float32, False, x, "x"), L.as_dtype(torch.float32, False, weight, "weight")
     if x.dim() != 5 or weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or x.shape[-1] != _conv3d_channels(weight, mode)[0]:
         raise ValueError(f"x {tuple(x.shape)} / weight {tuple(weight.shape)}: expected (B,D,h,w,Cin) and a 3x3x3 weight with Cin inputs")
     return _Conv3d.apply(x.contiguous(), weight.contiguous(), mode)

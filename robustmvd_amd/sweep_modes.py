@@ -20,15 +20,14 @@ def sweep_reduce(key_feat, src_feats, Ms, depth, mode, groups=1, pix_offset=0.0,
     stretch=True: homo_warp's convention (index = X/Z * W/(W-1) - 0.5 from integer pixel positions);
     stretch=False with pix_offset=0.5: homography_warping's (index = X/Z - 0.5 from positions x + 0.5).
     Returns (B,C,D,h,w) for the variance modes, a list of V (B,groups,D,h,w) volumes for REDUCE_GROUPCORR."""
-    lib = L.load()
     kf = L.as_f32(key_feat, "key_feat")
     if kf.dim() != 4:
         raise ValueError("key_feat must be (B,C,h,w)")
     B, C, h, w = kf.shape
     dev = kf.device
-    srcs = [L.as_f32(s, f"src_feats[{i}]", (B, C, h, w), dev) for i, s in enumerate(ops._views(src_feats, "src_feats"))]
+    srcs = [L.as_f32(s, f"src_feats[{i}]", (B, C, h, w), dev) for i, s in enumerate(ops.views(src_feats, "src_feats"))]
     V = len(srcs)
-    Ms = [L.as_f32(m, f"Ms[{i}]", (B, 3, 4), dev) for i, m in enumerate(ops._views(Ms, "Ms", V))]
+    Ms = [L.as_f32(m, f"Ms[{i}]", (B, 3, 4), dev) for i, m in enumerate(ops.views(Ms, "Ms", V))]
     dv = L.as_f32(depth, "depth", device=dev)
     if dv.dim() == 2 and dv.shape[0] == B:
         per_pixel, D = 0, dv.shape[1]
@@ -47,15 +46,9 @@ def sweep_reduce(key_feat, src_feats, Ms, depth, mode, groups=1, pix_offset=0.0,
     else:
         raise ValueError(f"mode {mode}")
     sx, sy = (w / (w - 1), h / (h - 1)) if stretch else (1.0, 1.0)
-    wsb = lib.mvd_sweep_reduce_workspace_bytes(B, C, h, w, V)
-    wsp = ops._workspace(wsb, dev)
-    a_s, k1 = L.ptr_array(srcs)
-    a_m, k2 = L.ptr_array(Ms)
-    a_o, k3 = L.ptr_array(outs)
-    with torch.cuda.device(dev):
-        rc = lib.mvd_sweep_reduce_f32(L.ptr(kf), a_s, a_m, L.ptr(dv), per_pixel, float(pix_offset), float(sx), float(sy), -0.5,
-                                      mode, groups, B, C, D, h, w, V, a_o, L.ptr(wsp), wsb, L.stream_of(kf))
-    L.check(rc, "mvd_sweep_reduce_f32")
+    wsb = L.load().mvd_sweep_reduce_workspace_bytes(B, C, h, w, V)
+    ops.call("mvd_sweep_reduce_f32", dev, kf, srcs, Ms, dv, per_pixel, float(pix_offset), float(sx), float(sy), -0.5, mode, groups,
+             B, C, D, h, w, V, outs, ops.workspace(wsb, dev), wsb)
     return outs if mode == L.REDUCE_GROUPCORR else outs[0]
 
 

@@ -38,8 +38,8 @@ def timed(fn, n=20):
     return e0.elapsed_time(e1) / n * 1e3
 
 
-a, b = two(), ops.conv2d_head(img, *pk[9])
+a, b = two(), ops.conv2d_head(img, *pk.head)
 print(f"max |one launch - two launches| = {float((a - b).abs().max()):.3g} (max |y| {float(a.abs().max()):.3g})")
-t2, t1 = timed(two), timed(lambda: ops.conv2d_head(img, *pk[9]))
+t2, t1 = timed(two), timed(lambda: ops.conv2d_head(img, *pk.head))
 mb = (B * 3 * H * W + B * 8 * H * W) * 4 / 1e6
 print(f"two launches {t2:.1f} us, one launch {t1:.1f} us ({mb:.0f} MB algorithmic -> {mb / t1 * 1e3:.0f} GB/s)")
