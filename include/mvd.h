@@ -431,6 +431,22 @@ int mvd_warp_variance_backward_f32(const float* key_feat, const float* const* sr
                                    int D, int h, int w, int V, float* grad_key, float* const* grad_src, void* workspace,
                                    size_t workspace_bytes, mvd_stream_t stream);
 
+/* The same VJP as a gather: no float atomics and a fixed summation order, so two calls on the same inputs return the same bits.
+ * Arguments as mvd_warp_variance_backward_f32 (C in {4,8,16,32,64}; all maps 16-byte aligned), with these differences:
+ *   - grad_src[v] receives its INTERIOR only (written once, not accumulated; no memset needed); its border entries are undefined.
+ *     grad_key is bit-identical to mvd_warp_variance_backward_f32's.
+ *   - every source pixel searches a window of (2 MVD_K3_GATHER_RADIUS + 1)^2 key pixels per plane.  Where a view's mapping minifies
+ *     so much that a contribution falls outside that window, the kernels detect it on the device (exactly, per (b, view)) and that
+ *     view's gradient is produced by the atomic scatter instead: always correct, bit-reproducible for the views that did not fall
+ *     back.  fallback_count: device int, or NULL; the number of (b, view) that fell back is ADDED to it (zero it yourself).
+ *   - the workspace also holds the per-voxel mean volume (B,D,h,w,C).  No host synchronisation. */
+#define MVD_K3_GATHER_RADIUS 3
+size_t mvd_warp_variance_backward_gather_workspace_bytes(int B, int C, int D, int h, int w, int V);
+int mvd_warp_variance_backward_gather_f32(const float* key_feat, const float* const* src_feat, const float* const* src_proj,
+                                          const float* key_proj_inv, const float* depth_values, const float* grad_var, int B, int C,
+                                          int D, int h, int w, int V, float* grad_key, float* const* grad_src, int* fallback_count,
+                                          void* workspace, size_t workspace_bytes, mvd_stream_t stream);
+
 /* VJP of mvd_sweep_corr_f32 (masks are constants).  feat_key, grad_key (N,h,w,C) channel-last; feat_src[v], grad_src[v]
  * (N,hs+3,ws+3,C) zero-bordered channel-last; grad_corr[v] (N,S,h,w).  C in {64,128,192,256}.  invdepth_mode / corr_scale as
  * in mvd_sweep_corr_ex_f32. */

@@ -30,6 +30,7 @@ INVDEPTH_SHARED, INVDEPTH_BATCHED, INVDEPTH_PER_PIXEL = 0, 1, 2
 REDUCE_VARIANCE = 0
 REDUCE_VARIANCE_KEYSQ = 1
 REDUCE_GROUPCORR = 2
+K3_GATHER_RADIUS = 3  # MVD_K3_GATHER_RADIUS: the gather backward's window is (2 * 3 + 1)^2 key pixels per plane
 
 _c_float_p = ctypes.c_void_p
 _pp = ctypes.POINTER(ctypes.c_void_p)
@@ -108,6 +109,9 @@ SIGNATURES = {
     "mvd_warp_variance_backward_workspace_bytes": (_sz, [_i]),
     "mvd_warp_variance_backward_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _c_float_p, _c_float_p] + [_i] * 6
                                        + [_c_float_p, _pp, ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "mvd_warp_variance_backward_gather_workspace_bytes": (_sz, [_i] * 6),
+    "mvd_warp_variance_backward_gather_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _c_float_p, _c_float_p] + [_i] * 6
+                                              + [_c_float_p, _pp, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
     "mvd_sweep_corr_backward_f32": (_i, [_c_float_p, _pp, _c_float_p, _pp, _pp, _c_float_p, _i, ctypes.c_float, _pp] + [_i] * 8
                                     + [_c_float_p, _pp, ctypes.c_void_p]),
     "mvd_fuse_views_backward_f32": (_i, [_pp, _pp, _pp, _c_float_p] + [_i] * 5 + [_pp, _pp, ctypes.c_void_p]),

@@ -5,10 +5,12 @@
 // so that the training loop (rmvd/train/multi_view_depth_training.py:231-246) can back-propagate through the engine.
 // The sampling grids depend on calibration only and carry no gradient: the backward of a bilinear gather is a
 // scatter-add of the incoming gradient times the same weights, done with no-return float atomics
-// (global_atomic_add_f32; MI355X_MICROARCH.md "Global float atomics").  These kernels favour simplicity over speed: the
-// forward kernels are the hot path, training runs at reduced sizes.  Summation order differs from run to run (atomics),
-// results agree with autograd through the reference to ~1e-5 relative (tests/golden/g10_grads.npz).
-#include "mvd_common.h"
+// (global_atomic_add_f32; MI355X_MICROARCH.md "Global float atomics").  Summation order differs from run to run (atomics),
+// results agree with autograd through the reference to ~1e-5 relative (tests/golden/g10_grads.npz).  MVSNet trains through K3's
+// kernel at full size (profiles/mvsnet_train_step.txt), where the scatter runs at the chip's float-atomic rate and is the largest
+// stage of a step; warp_variance_backward_gather.hip is the same VJP as a gather, without atomics and bit-reproducible, and uses
+// this file's kernel (FLAGGED) for the views its window cannot cover.  K1's and K2's kernels favour simplicity over speed.
+#include "warp_variance_backward_common.h"
 
 namespace mvd {
 
@@ -21,17 +23,9 @@ __device__ __forceinline__ void atomic_add4(float* p, float4 v) {
 // samples to form the planes' means, pass 2 gathers again per view (no per-view register array) and scatters
 // 2 g (x_v - mean) / (V+1) times the bilinear weights into that view's gradient map, runs of planes that hit the same source
 // cell summed in registers first.  Sampling positions: the folded form of the forward kernel.
-struct WarpBwdParams {
-    ViewPtrs src;            // V x (B,h+3,w+3,C) zero-bordered channel-last source features
-    ViewOutPtrs gsrc;        // V x (B,h+3,w+3,C) zero-initialised gradient maps (border entries receive the padding's share)
-    const float* key;        // (B,h+3,w+3,C)
-    float* gkey;             // (B,h+3,w+3,C), interior written (not accumulated)
-    const float* M;          // (V,B,12) composed transforms
-    const float* depth;      // (B,D)
-    const float* gvar;       // (B,D,h,w,C) channel-last
-    int B, C, D, h, w, V;
-};
-
+// FLAGGED (the gather path's fallback): only the (b, view) with a non-zero p.flags entry are scattered, a batch element without
+// one leaves at once, and the key gradient (the gather path has written it) is left alone.
+template <bool FLAGGED>
 __global__ void __launch_bounds__(256) warp_variance_backward_kernel(WarpBwdParams p) {
     const int lpp = p.C / 4;
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -43,6 +37,12 @@ __global__ void __launch_bounds__(256) warp_variance_backward_kernel(WarpBwdPara
     const int y = (int)(pix % p.h);
     const int b = (int)(pix / p.h);
     const int h = p.h, w = p.w, C = p.C, D = p.D, V = p.V;
+    if constexpr (FLAGGED) {
+        int n = 0;
+        for (int v = 0; v < V; ++v) n += p.flags[b * V + v] != 0;
+        if (n == 0) return;
+        if (x == 0 && y == 0 && q == 0 && p.fallback_count) atomicAdd(p.fallback_count, n);
+    }
     const int W2 = w + 3;
     const size_t img = (size_t)(h + 3) * W2 * C;
     const float sx = (float)w / (float)(w - 1), sy = (float)h / (float)(h - 1);
@@ -51,31 +51,11 @@ __global__ void __launch_bounds__(256) warp_variance_backward_kernel(WarpBwdPara
     const size_t self = ((size_t)(y + 1) * W2 + (x + 1)) * C + q * 4;
     const float4 k = *reinterpret_cast<const float4*>(p.key + b * img + self);
 
-    struct Loc { size_t o; float w00, w10, w01, w11; };
+    using Loc = BwdLoc;
     auto locate = [&](int v, float depth) {
-        const float* __restrict__ M = p.M + ((size_t)v * p.B + b) * 12;
-        const float ax = fmaf(M[0], fx, fmaf(M[1], fy, M[2])), ay = fmaf(M[4], fx, fmaf(M[5], fy, M[6]));
-        const float az = fmaf(M[8], fx, fmaf(M[9], fy, M[10]));
-        const float X = fmaf(ax, depth, M[3]), Y = fmaf(ay, depth, M[7]), Z = fmaf(az, depth, M[11]);
-        const float rz = __builtin_amdgcn_rcpf(Z);
-        float ix = fmaf(X * rz, sx, -0.5f), iy = fmaf(Y * rz, sy, -0.5f);
-        ix = __builtin_amdgcn_fmed3f(ix, -1.0f, xhi);
-        iy = __builtin_amdgcn_fmed3f(iy, -1.0f, yhi);
-        const float xf = floorf(ix), yf = floorf(iy);
-        const float wx = ix - xf, wy = iy - yf, ux = 1.0f - wx, uy = 1.0f - wy;
-        Loc L;
-        L.o = ((size_t)((int)yf + 1) * W2 + ((int)xf + 1)) * C + q * 4;
-        L.w00 = ux * uy; L.w10 = wx * uy; L.w01 = ux * wy; L.w11 = wx * wy;
-        return L;
+        return bwd_locate(p.M + ((size_t)v * p.B + b) * 12, fx, fy, depth, sx, sy, xhi, yhi, W2, C, q);
     };
-    auto sample = [&](const float* __restrict__ f, const Loc& L) {
-        const float4 a = *reinterpret_cast<const float4*>(f + L.o), bq = *reinterpret_cast<const float4*>(f + L.o + C);
-        const float4 c = *reinterpret_cast<const float4*>(f + L.o + (size_t)W2 * C), d = *reinterpret_cast<const float4*>(f + L.o + (size_t)W2 * C + C);
-        return make_float4(fmaf(d.x, L.w11, fmaf(c.x, L.w01, fmaf(bq.x, L.w10, a.x * L.w00))),
-                           fmaf(d.y, L.w11, fmaf(c.y, L.w01, fmaf(bq.y, L.w10, a.y * L.w00))),
-                           fmaf(d.z, L.w11, fmaf(c.z, L.w01, fmaf(bq.z, L.w10, a.z * L.w00))),
-                           fmaf(d.w, L.w11, fmaf(c.w, L.w01, fmaf(bq.w, L.w10, a.w * L.w00))));
-    };
+    auto sample = [&](const float* __restrict__ f, const Loc& L) { return bwd_sample(f, L, W2, C); };
 
     // Planes in chunks of BWD_DZ: the chunk's means stay in registers, then each view walks the chunk with ONE pending 2 x 2 cell of
     // tap gradients in registers: consecutive planes of a pixel mostly sample the same source cell (the forward kernel's tap
@@ -104,6 +84,9 @@ __global__ void __launch_bounds__(256) warp_variance_backward_kernel(WarpBwdPara
             gk.z += gs[dd].z * (k.z - mean[dd].z); gk.w += gs[dd].w * (k.w - mean[dd].w);
         }
         for (int v = 0; v < V; ++v) {
+            if constexpr (FLAGGED) {
+                if (p.flags[b * V + v] == 0) continue;
+            }
             const float* __restrict__ f = p.src.p[v] + b * img;
             float* __restrict__ gv = p.gsrc.p[v] + b * img;
             constexpr size_t NONE = ~(size_t)0;
@@ -141,7 +124,7 @@ __global__ void __launch_bounds__(256) warp_variance_backward_kernel(WarpBwdPara
             if (pend != NONE) flush();
         }
     }
-    *reinterpret_cast<float4*>(p.gkey + b * img + self) = gk;
+    if constexpr (!FLAGGED) *reinterpret_cast<float4*>(p.gkey + b * img + self) = gk;
 }
 
 __global__ void compose_transforms_bwd_kernel(ViewPtrs proj, const float* __restrict__ key_proj_inv, int B, int V, float* __restrict__ M) {
@@ -344,6 +327,16 @@ __global__ void __launch_bounds__(256) fuse_views_backward_kernel(FuseBwdParams 
         for (int v = 0; v < V; ++v) p.gscore.p[v][n * hw + pix] = pr[v] * (dp[v] - dot);
 }
 
+void launch_compose_transforms_bwd(const ViewPtrs& proj, const float* key_proj_inv, int B, int V, float* M, hipStream_t st) {
+    hipLaunchKernelGGL(compose_transforms_bwd_kernel, dim3((unsigned)((V * B * 12 + 255) / 256)), dim3(256), 0, st, proj, key_proj_inv,
+                       B, V, M);
+}
+
+void launch_warp_variance_backward_flagged(const WarpBwdParams& p, hipStream_t st) {
+    const long long nthr = (long long)p.B * p.h * p.w * (p.C / 4);
+    hipLaunchKernelGGL(warp_variance_backward_kernel<true>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, p);
+}
+
 }  // namespace mvd
 
 extern "C" {
@@ -385,7 +378,7 @@ int mvd_warp_variance_backward_f32(const float* key_feat, const float* const* sr
     p.B = B; p.C = C; p.D = D; p.h = h; p.w = w; p.V = V;
     const long long nthr = (long long)B * h * w * (C / 4), nblk = (nthr + 255) / 256;
     MVD_REQUIRE(nblk <= 0x7fffffffLL, "warp_variance_backward: grid too large");
-    hipLaunchKernelGGL(warp_variance_backward_kernel, dim3((unsigned)nblk), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(warp_variance_backward_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, st, p);
     return launch_status("warp_variance_backward");
 }
 

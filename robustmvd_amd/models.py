@@ -186,7 +186,7 @@ class RobustMVD(nn.Module):
 
 class MVSNet(nn.Module):
     def __init__(self, sample_in_inv_depth_space=False, num_sampling_steps=192, half_features=False, conv0_split=True,
-                 exact_grid=False, train_regulariser="vendor"):
+                 exact_grid=False, train_regulariser="vendor", sweep_backward="atomic"):
         """half_features (an extension; the reference has no such switch): BASELINE.json configs[3] — the feature maps
         are rounded to fp16 before the sweep, the variance volume is stored fp16 and the regulariser's first layer runs
         on fp16 MFMA with fp32 accumulation; everything else (positions, blend, variance, layers 2..11, soft argmin)
@@ -201,11 +201,23 @@ class MVSNet(nn.Module):
         train_regulariser: where the differentiable path runs CostRegNet's convolutions.  "vendor" (default): the vendor library,
         forward and backward.  "engine": the HIP engine in both directions (CostRegNet.forward_autograd_engine: forward and data
         gradients on the fp32-MFMA layer kernels, weight gradients on mvd_conv3d_weight_grad_f32, deterministic).  The inference
+        path ignores the switch.
+        sweep_backward: K3's vector-Jacobian product in the differentiable path.  "atomic" (default): a scatter with float atomics,
+        whose sums differ in the last bits from run to run.  "gather": a fixed-order gather without atomics
+        (ops.warp_variance_autograd(backward="gather")); together with train_regulariser="engine" every gradient the engine computes
+        is then bit-reproducible.  The model owns a device int32 counter, sweep_backward_fallbacks, that the kernel raises by the
+        number of (batch element, view) whose mapping minified beyond the gather's window: those views took the atomic path (still
+        correct, not reproducible).  Read it with .item() when you choose; it is never read on the training path.  The inference
         path ignores the switch."""
         super().__init__()
         if train_regulariser not in ("vendor", "engine"):
             raise ValueError(f"train_regulariser must be 'vendor' or 'engine', got {train_regulariser!r}")
         self.train_regulariser = train_regulariser
+        if sweep_backward not in ops.K3_BACKWARDS:
+            raise ValueError(f"sweep_backward must be 'atomic' or 'gather', got {sweep_backward!r}")
+        self.sweep_backward = sweep_backward
+        if sweep_backward == "gather":
+            self.register_buffer("sweep_backward_fallbacks", torch.zeros(1, dtype=torch.int32), persistent=False)
         self.half_features = bool(half_features)
         if sample_in_inv_depth_space:
             raise NotImplementedError("sample_in_inv_depth_space=True is a dead branch in the reference "
@@ -313,7 +325,11 @@ class MVSNet(nn.Module):
         if self.half_features:
             raise ValueError("MVSNet(half_features=True) is inference-only: call .eval() and run under torch.no_grad()")
         feats = list(torch.split(self.feature.forward_autograd(_as_batch(views)), n, 0))                  # (B,32,h,w) per view
-        var = ops.warp_variance_autograd(feats[0], feats[1:], projs[1:], projs[0], depth_samples)         # K3 (B,32,D,h,w)
+        if self.sweep_backward == "gather":
+            var = ops.warp_variance_autograd(feats[0], feats[1:], projs[1:], projs[0], depth_samples, backward="gather",
+                                             fallback_count=self.sweep_backward_fallbacks)                # K3 (B,32,D,h,w)
+        else:
+            var = ops.warp_variance_autograd(feats[0], feats[1:], projs[1:], projs[0], depth_samples)     # K3 (B,32,D,h,w)
         if self.train_regulariser == "engine":
             cost = self.cost_regularization.forward_autograd_engine(var.permute(0, 2, 3, 4, 1).contiguous())  # (B,D,h,w)
         else:

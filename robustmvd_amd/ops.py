@@ -774,10 +774,10 @@ def _interior_nchw(g, h, w):
 
 class _WarpVariance(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, key_proj_inv, depth_values, n_views, key_feat, *rest):
+    def forward(ctx, key_proj_inv, depth_values, n_views, backward, fallback_count, key_feat, *rest):
         srcs, projs = list(rest[:n_views]), list(rest[n_views:])
         ctx.save_for_backward(key_proj_inv, depth_values, key_feat, *srcs, *projs)
-        ctx.n_views = n_views
+        ctx.n_views, ctx.mode, ctx.fallback_count = n_views, backward, fallback_count
         return warp_variance(key_feat.detach(), [s.detach() for s in srcs], projs, key_proj_inv, depth_values)
 
     @staticmethod
@@ -794,17 +794,39 @@ class _WarpVariance(torch.autograd.Function):
             gk = torch.empty_like(kb)
             gs = [torch.empty_like(kb) for _ in range(V)]
             projs, kpi, dv = _k3_calibration(projs, kpi, dv, V, B, C, dev)
-            wsb = L.load().mvd_warp_variance_backward_workspace_bytes(B)
-            call("mvd_warp_variance_backward_f32", dev, kb, sb, projs, kpi, dv, g, B, C, dv.shape[1], h, w, V, gk, gs,
-                  workspace(wsb, dev), wsb)
-            out = [None, None, None, _interior_nchw(gk, h, w)] + [_interior_nchw(x, h, w) for x in gs] + [None] * V
+            if ctx.mode == "gather":
+                wsb = L.load().mvd_warp_variance_backward_gather_workspace_bytes(B, C, dv.shape[1], h, w, V)
+                call("mvd_warp_variance_backward_gather_f32", dev, kb, sb, projs, kpi, dv, g, B, C, dv.shape[1], h, w, V, gk, gs,
+                      ctx.fallback_count, workspace(wsb, dev), wsb)
+            else:
+                wsb = L.load().mvd_warp_variance_backward_workspace_bytes(B)
+                call("mvd_warp_variance_backward_f32", dev, kb, sb, projs, kpi, dv, g, B, C, dv.shape[1], h, w, V, gk, gs,
+                      workspace(wsb, dev), wsb)
+            out = [None] * 5 + [_interior_nchw(gk, h, w)] + [_interior_nchw(x, h, w) for x in gs] + [None] * V
         return tuple(out)
 
 
-def warp_variance_autograd(key_feat, src_feats, src_projs, key_proj_inv, depth_values):
-    """Differentiable K3: like warp_variance (reference layout (B,C,D,h,w)), with gradients to key_feat and src_feats."""
+K3_BACKWARDS = ("atomic", "gather")
+
+
+def warp_variance_autograd(key_feat, src_feats, src_projs, key_proj_inv, depth_values, backward="atomic", fallback_count=None):
+    """Differentiable K3: like warp_variance (reference layout (B,C,D,h,w)), with gradients to key_feat and src_feats.
+    backward: "atomic" (default) scatters the source gradients with float atomics, so their last bits vary from run to run;
+    "gather" collects them per source pixel in a fixed order (mvd_warp_variance_backward_gather_f32): two calls on the same inputs
+    give the same bits.  A view whose mapping minifies beyond the gather's window (more than L.K3_GATHER_RADIUS key pixels from a
+    source pixel's centre) is detected on the device and takes the atomic path; fallback_count, an int32 device tensor of one
+    element, is then raised by the number of such (batch element, view) (no host synchronisation: read it when you choose)."""
+    if backward not in K3_BACKWARDS:
+        raise ValueError(f"backward must be 'atomic' or 'gather', got {backward!r}")
+    if fallback_count is not None:
+        if backward != "gather":
+            raise ValueError("fallback_count belongs to backward='gather'")
+        if not (isinstance(fallback_count, torch.Tensor) and fallback_count.is_cuda and fallback_count.dtype == torch.int32
+                and fallback_count.numel() == 1):
+            raise ValueError("fallback_count must be a one-element int32 device tensor")
     srcs = views(src_feats, "src_feats")
-    return _WarpVariance.apply(key_proj_inv, depth_values, len(srcs), key_feat, *srcs, *views(src_projs, "src_projs", len(srcs)))
+    return _WarpVariance.apply(key_proj_inv, depth_values, len(srcs), backward, fallback_count, key_feat, *srcs,
+                               *views(src_projs, "src_projs", len(srcs)))
 
 
 class _SweepCorr(torch.autograd.Function):

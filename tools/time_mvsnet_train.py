@@ -8,7 +8,11 @@ of its gradient).  --regulariser engine runs CostRegNet's convolutions on the en
 (MVSNet(train_regulariser="engine")) and splits `CostRegNet bwd` into data-gradient, weight-gradient and BN / elementwise time
 (events around the two engine calls inside the backward; the rest is torch's BatchNorm, ReLU and add backward), with the
 weight-gradient kernels' rate against the fp32-matrix peak (157 TFLOP/s) and HBM bandwidth (8 TB/s) for their bytes.
-GPU box only.  Usage: python tools/time_mvsnet_train.py [--configs 1 2] [--reps 5] [--warmup 2] [--regulariser vendor|engine]"""
+--sweep-backward gather runs K3's VJP as the fixed-order gather (MVSNet(sweep_backward="gather")) and splits `K3 VJP` into its
+stage A (means, key gradient, window check), stage B (the gather) and fallback (scatter of flagged views) kernels, timed by
+torch.profiler over one more K3 backward after the timed steps; it also prints the model's fallback counter.
+GPU box only.  Usage: python tools/time_mvsnet_train.py [--configs 1 2] [--reps 5] [--warmup 2] [--regulariser vendor|engine]
+[--sweep-backward atomic|gather]"""
 import argparse
 import json
 import os
@@ -98,6 +102,43 @@ def weight_grad_work(model, D, h, w):
     return flops, nbytes
 
 
+def k3_forward(model, feats, projs, dv):
+    if model.sweep_backward == "gather":
+        return ops.warp_variance_autograd(feats[0], feats[1:], projs[1:], projs[0], dv, backward="gather",
+                                          fallback_count=model.sweep_backward_fallbacks)
+    return ops.warp_variance_autograd(feats[0], feats[1:], projs[1:], projs[0], dv)
+
+
+K3_GATHER_KERNELS = {"stage A": "gather_stage_a", "stage B": "gather_stage_b", "fallback": "warp_variance_backward_kernel",
+                     "plane inverses": "plane_inverse"}
+
+
+def k3_vjp_split(model, sample):
+    """Device time of the gather VJP's kernels over one K3 backward, by kernel name, from torch.profiler -> {part: ms}."""
+    from torch.profiler import ProfilerActivity, profile
+    n = sample["images"][0].shape[0]
+    dv = model.depth_samples(sample["depth_range"], n, dev)
+    proj = model.projection_matrices(sample["intrinsics"], sample["poses"], [0] * n, dev)
+    with torch.no_grad():
+        f = model.feature.forward_autograd(_as_batch(list(sample["images"])))
+    feats = list(torch.split(f.detach().requires_grad_(True), n, 0))
+    v = k3_forward(model, feats, list(proj), dv)
+    g = torch.randn_like(v)
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        v.backward(g)
+        torch.cuda.synchronize()
+    out = {k: 0.0 for k in K3_GATHER_KERNELS}
+    for e in prof.key_averages():
+        t = getattr(e, "device_time_total", None)
+        if t is None:
+            t = getattr(e, "cuda_time_total", 0.0)
+        for part, pat in K3_GATHER_KERNELS.items():
+            if pat in e.key:
+                out[part] += t / 1e3
+    return out
+
+
 def split_step(model, sample):
     """One training step, stage by stage; returns {stage: ms}."""
     model.zero_grad(set_to_none=True)
@@ -112,7 +153,7 @@ def split_step(model, sample):
     ev.mark("FeatureNet fwd")
     fd = f.detach().requires_grad_(True)
     feats = list(torch.split(fd, n, 0))
-    v = ops.warp_variance_autograd(feats[0], feats[1:], projs[1:], projs[0], dv)
+    v = k3_forward(model, feats, projs, dv)
     ev.mark("K3 fwd")
     vd = v.detach().requires_grad_(True)
     if model.train_regulariser == "engine":
@@ -193,9 +234,9 @@ def k5_vjp_vs_torch(cost, dv, reps, n=50):
             "torch_softmax_regression_bwd_ms": t_torch, "k5_vjp_bytes": nbytes}
 
 
-def run(cfg, reps, warmup, regulariser="vendor"):
+def run(cfg, reps, warmup, regulariser="vendor", sweep_backward="atomic"):
     H, W, V, D = CONFIGS[cfg]
-    model = R.MVSNet(num_sampling_steps=D, train_regulariser=regulariser).to(dev).train()
+    model = R.MVSNet(num_sampling_steps=D, train_regulariser=regulariser, sweep_backward=sweep_backward).to(dev).train()
     s = gc.synthetic_sample(cfg, H, W, V)
     im, key, po, intr, dr = add_batch_dim(s["images"], 0, s["poses"], s["intrinsics"], (np.float32(0.5), np.float32(10.0)))
     sample = model.input_adapter(images=im, keyview_idx=key, poses=po, intrinsics=intr, depth_range=dr)
@@ -214,7 +255,14 @@ def run(cfg, reps, warmup, regulariser="vendor"):
         cost = torch.randn(1, D, H // 4, W // 4, device=dev) * 3
     dv = model.depth_samples(sample["depth_range"], 1, dev)
     out = {"config": cfg, "H": H, "W": W, "V": V, "D": D, "stages_ms": stages, "sum_of_stages_ms": sum(stages.values()),
-           "full_step_ms": full, "peak_mem_gb": torch.cuda.max_memory_allocated() / 1e9, "regulariser": regulariser}
+           "full_step_ms": full, "peak_mem_gb": torch.cuda.max_memory_allocated() / 1e9, "regulariser": regulariser,
+           "sweep_backward": sweep_backward}
+    if sweep_backward == "gather":
+        try:
+            out["k3_vjp_split_ms"] = k3_vjp_split(model, sample)
+        except Exception as e:  # no profiler in this build of torch: the stage total above still stands
+            print(f"  K3 VJP split unavailable: {type(e).__name__}: {e}", flush=True)
+        out["sweep_backward_fallbacks"] = int(model.sweep_backward_fallbacks.item())
     if split:
         split["bwd BN / elementwise"] = stages["CostRegNet bwd"] - sum(split.values())
         flops, nbytes = weight_grad_work(model, D, H // 4, W // 4)
@@ -231,13 +279,18 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--regulariser", choices=["vendor", "engine"], default="vendor")
+    ap.add_argument("--sweep-backward", choices=["atomic", "gather"], default="atomic")
     a = ap.parse_args()
     for cfg in a.configs:
-        r = run(cfg, a.reps, a.warmup, a.regulariser)
-        print(f"configs[{cfg}] {r['H']}x{r['W']} V{r['V']} D{r['D']} regulariser={a.regulariser}: training step {r['full_step_ms']:.2f} ms "
+        r = run(cfg, a.reps, a.warmup, a.regulariser, a.sweep_backward)
+        print(f"configs[{cfg}] {r['H']}x{r['W']} V{r['V']} D{r['D']} regulariser={a.regulariser} sweep_backward={a.sweep_backward}: training step {r['full_step_ms']:.2f} ms "
               f"(stages sum {r['sum_of_stages_ms']:.2f} ms, peak {r['peak_mem_gb']:.1f} GB)")
         for k, v in r["stages_ms"].items():
             print(f"  {k:16s} {v:9.3f} ms  {100 * v / r['sum_of_stages_ms']:5.1f} %")
+        for k, v in r.get("k3_vjp_split_ms", {}).items():
+            print(f"    K3 VJP {k:15s} {v:9.3f} ms (kernel time, one backward under the profiler)")
+        if "sweep_backward_fallbacks" in r:
+            print(f"    K3 VJP views that fell back to the atomic scatter, all steps: {r['sweep_backward_fallbacks']}")
         for k, v in r.get("costregnet_bwd_split_ms", {}).items():
             print(f"    {k:22s} {v:9.3f} ms  {100 * v / r['stages_ms']['CostRegNet bwd']:5.1f} % of CostRegNet bwd")
         if "weight_grad_tflops" in r:
