@@ -24,6 +24,10 @@
 // 4-tap kernel W'[j][t] = W[t-j] (zero outside 0..2): 4/3 of the taps but twice the useful rows, 1.5x
 // fewer MFMAs for the same result (each product that is kept is bit-identical; the extra ones multiply by 0).
 // Cout = 1 (the final `prob` layer) would use 1 row of 16: it has its own vector-ALU kernel below.
+//
+// Shared pieces: decode_tile (all six kernels), load_frag (every weight and activation fragment that is read from
+// memory: the five matrix-core kernels; conv0_ksplit_kernel keeps its weights in registers and conv3d_c8_to_1_kernel
+// has no fragments) and, on the host, launch_tiles (all six launchers: grid limit, LDS attribute, launch, status).
 #include "mvd_common.h"
 #include <stdlib.h>
 
@@ -75,6 +79,33 @@ __host__ __device__ constexpr size_t packed_floats(int nt, int taps = 27) {
     return (size_t)taps * KGroup<CIN>::NKG * nt * 64 * KGroup<CIN>::R;
 }
 constexpr int MVD_CONV3D_S1_PAIR = 3;  // internal mode: stride-1 conv with Cout == 8 (see header)
+
+// ---- shared device pieces -----------------------------------------------------------------------------------------
+// A first step: these two compile to the parent's code in every kernel.  Still written out per kernel: the slab share
+// with its plane prefetch / ring store, the two-plane staging of the transposed-conv kernels, the per-lane affine, the
+// epilogue values, and read_step / mfma_step next to read_group / mfma_group.  As functions they changed the code of the
+// kernels tried (measured once: the per-lane affine took deconv3d_all_kernel<16,1,2> from 128 to 132 registers, 4 -> 3
+// waves per SIMD); sharing them needs a per-kernel resource comparison and timings, which has not been done.
+
+// R consecutive floats (one lane's share of a k-group) as one 16-B or 8-B load: weight and activation fragments
+template <int R>
+__device__ __forceinline__ void load_frag(const float* src, float (&dst)[R]) {
+    static_assert(R == 4 || R == 2, "k-groups of 16 or 8 channels");
+    if constexpr (R == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(src);
+        dst[0] = t.x; dst[1] = t.y; dst[2] = t.z; dst[3] = t.w;
+    } else {
+        const float2 t = *reinterpret_cast<const float2*>(src);
+        dst[0] = t.x; dst[1] = t.y;
+    }
+}
+
+// tile index -> (column tile, row tile); returns what is left: depth plane or chunk, parity class, batch element
+__device__ __forceinline__ int decode_tile(const ConvParams& p, int bx, int& tw, int& th) {
+    tw = bx % p.tiles_w; bx /= p.tiles_w;
+    th = bx % p.tiles_h;
+    return bx / p.tiles_h;
+}
 
 template <int CIN>
 __global__ void pack_weights_kernel(const float* __restrict__ w, float* __restrict__ packed, int Cout, int NT,
@@ -141,9 +172,8 @@ __global__ void __launch_bounds__(256) conv3d_kernel(ConvParams p) {
     const int vox = lane & 15, q = lane >> 4;
 
     // ---- which tile ---------------------------------------------------------------------------
-    int bx = blockIdx.x;
-    const int tw = bx % p.tiles_w; bx /= p.tiles_w;
-    const int th = bx % p.tiles_h; bx /= p.tiles_h;
+    int tw, th;
+    int bx = decode_tile(p, blockIdx.x, tw, th);
     int pd = 0, ph = 0;  // output (d, h) parity class (deconv only)
     if constexpr (DECONV) { pd = (bx >> 1) & 1; ph = bx & 1; bx >>= 2; }
     // grid z-extent: output depth planes (conv) or input depth planes (deconv, one per parity class)
@@ -238,16 +268,8 @@ __global__ void __launch_bounds__(256) conv3d_kernel(ConvParams p) {
 #pragma unroll
                 for (int g = 0; g < G::NKG; ++g)
 #pragma unroll
-                    for (int n = 0; n < NT; ++n) {
-                        const float* wp = p.wpk + ((((size_t)tap * G::NKG + g) * NT + n) * 64 + lane) * G::R;
-                        if constexpr (G::R == 4) {
-                            const float4 t = *reinterpret_cast<const float4*>(wp);
-                            dst[g][n][0] = t.x; dst[g][n][1] = t.y; dst[g][n][2] = t.z; dst[g][n][3] = t.w;
-                        } else {
-                            const float2 t = *reinterpret_cast<const float2*>(wp);
-                            dst[g][n][0] = t.x; dst[g][n][1] = t.y;
-                        }
-                    }
+                    for (int n = 0; n < NT; ++n)
+                        load_frag(p.wpk + ((((size_t)tap * G::NKG + g) * NT + n) * 64 + lane) * G::R, dst[g][n]);
             };
             if constexpr (ABATCH) {
 #pragma unroll
@@ -265,16 +287,7 @@ __global__ void __launch_bounds__(256) conv3d_kernel(ConvParams p) {
                 for (int g = 0; g < G::NKG; ++g) {
                     float bf[MT][G::R];
 #pragma unroll
-                    for (int m = 0; m < MT; ++m) {
-                        const float* bp = srow_p + ((m * 16 + vox) * SX) * PSTR + g * G::KG;
-                        if constexpr (G::R == 4) {
-                            const float4 t = *reinterpret_cast<const float4*>(bp);
-                            bf[m][0] = t.x; bf[m][1] = t.y; bf[m][2] = t.z; bf[m][3] = t.w;
-                        } else {
-                            const float2 t = *reinterpret_cast<const float2*>(bp);
-                            bf[m][0] = t.x; bf[m][1] = t.y;
-                        }
-                    }
+                    for (int m = 0; m < MT; ++m) load_frag(srow_p + ((m * 16 + vox) * SX) * PSTR + g * G::KG, bf[m]);
 #pragma unroll
                     for (int j = 0; j < G::R; ++j)
 #pragma unroll
@@ -386,9 +399,8 @@ __global__ void __launch_bounds__(256) conv3d_march_kernel(ConvParams p) {
     const int lane = tid & 63, wave = tid >> 6;
     const int vox = lane & 15, q = lane >> 4;
 
-    int bx = blockIdx.x;
-    const int tw = bx % p.tiles_w; bx /= p.tiles_w;
-    const int th = bx % p.tiles_h; bx /= p.tiles_h;
+    int tw, th;
+    const int bx = decode_tile(p, blockIdx.x, tw, th);
     const int nzc = (p.Do + DZ - 1) / DZ;
     const int zc = bx % nzc;
     const int b = bx / nzc;
@@ -503,29 +515,13 @@ __global__ void __launch_bounds__(256) conv3d_march_kernel(ConvParams p) {
 #pragma unroll
                 for (int g = 0; g < G::NKG; ++g) {
 #pragma unroll
-                    for (int n = 0; n < NT; ++n) {
-                        const float* wp = wsrc + (((tap * G::NKG + g) * NT + n) * 64 + lane) * G::R;
-                        if constexpr (G::R == 4) {
-                            const float4 t = *reinterpret_cast<const float4*>(wp);
-                            A[iw * G::NKG + g][n][0] = t.x; A[iw * G::NKG + g][n][1] = t.y;
-                            A[iw * G::NKG + g][n][2] = t.z; A[iw * G::NKG + g][n][3] = t.w;
-                        } else {
-                            const float2 t = *reinterpret_cast<const float2*>(wp);
-                            A[iw * G::NKG + g][n][0] = t.x; A[iw * G::NKG + g][n][1] = t.y;
-                        }
-                    }
+                    for (int n = 0; n < NT; ++n)
+                        load_frag(wsrc + (((tap * G::NKG + g) * NT + n) * 64 + lane) * G::R, A[iw * G::NKG + g][n]);
 #pragma unroll
                     for (int m = 0; m < MT; ++m) {
                         const float* bp = srow_p + ((m * 16 + vox) * SX) * PSTR + g * G::KG;
                         if constexpr (SWZ) bp += (((g * 4 + q) ^ ((m * 16 + vox + (iw >> 1)) & (C4 - 1))) - g * 4) * 4;
-                        if constexpr (G::R == 4) {
-                            const float4 t = *reinterpret_cast<const float4*>(bp);
-                            B[iw * G::NKG + g][m][0] = t.x; B[iw * G::NKG + g][m][1] = t.y;
-                            B[iw * G::NKG + g][m][2] = t.z; B[iw * G::NKG + g][m][3] = t.w;
-                        } else {
-                            const float2 t = *reinterpret_cast<const float2*>(bp);
-                            B[iw * G::NKG + g][m][0] = t.x; B[iw * G::NKG + g][m][1] = t.y;
-                        }
+                        load_frag(bp, B[iw * G::NKG + g][m]);
                     }
                 }
             }
@@ -562,16 +558,12 @@ __global__ void __launch_bounds__(256) conv3d_march_kernel(ConvParams p) {
                 const int tap = PAIR ? step * 4 + iw : step * 3 + iw;
                 const float* __restrict__ srow_p = slab + ((wave + kh) * COLS + iw) * PSTR + (SWZ ? 0 : G::R * q);
 #pragma unroll
-                for (int n = 0; n < NT; ++n) {
-                    const float4 t = *reinterpret_cast<const float4*>(wsrc + (((tap * G::NKG + g) * NT + n) * 64 + lane) * G::R);
-                    A[grp][n][0] = t.x; A[grp][n][1] = t.y; A[grp][n][2] = t.z; A[grp][n][3] = t.w;
-                }
+                for (int n = 0; n < NT; ++n) load_frag(wsrc + (((tap * G::NKG + g) * NT + n) * 64 + lane) * G::R, A[grp][n]);
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
                     const float* bp = srow_p + ((m * 16 + vox) * SX) * PSTR + g * G::KG;
                     if constexpr (SWZ) bp += (((g * 4 + q) ^ ((m * 16 + vox + (iw >> 1)) & (C4 - 1))) - g * 4) * 4;
-                    const float4 t = *reinterpret_cast<const float4*>(bp);
-                    B[grp][m][0] = t.x; B[grp][m][1] = t.y; B[grp][m][2] = t.z; B[grp][m][3] = t.w;
+                    load_frag(bp, B[grp][m]);
                 }
             };
             auto mfma_group = [&](int grp, float (&A)[NGRP][NT][G::R], float (&B)[NGRP][MT][G::R]) {
@@ -664,6 +656,21 @@ __global__ void __launch_bounds__(256) conv3d_march_kernel(ConvParams p) {
 }
 
 
+// Launch of a tile kernel: one workgroup per tile (and depth chunk / plane, batch element)
+template <typename K>
+static int launch_tiles(K kernel, long long nblk, int threads, size_t lds_bytes, const char* name, const ConvParams& p,
+                        hipStream_t st) {
+    if (nblk > 0x7fffffffLL) {
+        set_error("conv3d: %lld workgroups exceed the grid limit", nblk);
+        return MVD_ERR_INVALID_ARG;
+    }
+    if (lds_bytes > 64 * 1024 &&
+        hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
+        return launch_status("conv3d: LDS attribute");
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(threads), lds_bytes, st, p);
+    return launch_status(name);
+}
+
 static long long march_min_blocks() {
     const char* e = exp_env("MVD_K4_MARCH_MIN");
     return e ? atoll(e) : 1024;
@@ -683,21 +690,12 @@ static int launch_march(const ConvParams& p0, hipStream_t st) {
     p.tiles_h = (p.ho + CONV_TH - 1) / CONV_TH;
     p.tiles_w = (gw + TW - 1) / TW;
     const long long nblk = (long long)p.tiles_w * p.tiles_h * ((p.Do + MARCH_DZ - 1) / MARCH_DZ) * p.B;
-    if (nblk > 0x7fffffffLL) {
-        set_error("conv3d: %lld workgroups exceed the grid limit", nblk);
-        return MVD_ERR_INVALID_ARG;
-    }
     // too few depth-marching workgroups to fill 256 CUs: shorter plane chunks, then the plane-at-a-time kernel
     if (nblk < march_min_blocks()) {
         if constexpr (MARCH_DZ > 8) return launch_march<CIN, NT, MT, PAIR, 8>(p0, st);
         return -1;
     }
-    auto kern = conv3d_march_kernel<CIN, NT, MT, PAIR, MARCH_DZ>;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return launch_status("conv3d: LDS attribute");
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), lds, st, p);
-    return launch_status("conv3d_march");
+    return launch_tiles(conv3d_march_kernel<CIN, NT, MT, PAIR, MARCH_DZ>, nblk, 256, lds, "conv3d_march", p, st);
 }
 
 // conv0 (32 -> 8, PAIR mode) with the reduction dimension split over TWO waves per output row: a workgroup is 8 waves —
@@ -722,9 +720,8 @@ __global__ void __launch_bounds__(512) conv0_ksplit_kernel(ConvParams p) {
     const int row = wave & 3, kh_ = wave >> 2;  // output row of the tile, channel half
     const int vox = lane & 15, q = lane >> 4;
 
-    int bx = blockIdx.x;
-    const int tw = bx % p.tiles_w; bx /= p.tiles_w;
-    const int th = bx % p.tiles_h; bx /= p.tiles_h;
+    int tw, th;
+    const int bx = decode_tile(p, blockIdx.x, tw, th);
     const int nzc = (p.Do + DZ - 1) / DZ;
     const int zc = bx % nzc;
     const int b = bx / nzc;
@@ -830,10 +827,8 @@ __global__ void __launch_bounds__(512) conv0_ksplit_kernel(ConvParams p) {
             const int tap = step * 4 + iw;
             const float4 ta = wreg[tap];
             A[iw][0] = ta.x; A[iw][1] = ta.y; A[iw][2] = ta.z; A[iw][3] = ta.w;
-            const float* bp = slab + ((row + kh) * COLS + iw) * PSTR + (vox * SX) * PSTR +
-                              (((kh_ * 4 + q) ^ ((vox + (iw >> 1)) & (C4 - 1)))) * 4;
-            const float4 tb = *reinterpret_cast<const float4*>(bp);
-            B[iw][0] = tb.x; B[iw][1] = tb.y; B[iw][2] = tb.z; B[iw][3] = tb.w;
+            load_frag(slab + ((row + kh) * COLS + iw) * PSTR + (vox * SX) * PSTR +
+                          (((kh_ * 4 + q) ^ ((vox + (iw >> 1)) & (C4 - 1)))) * 4, B[iw]);
         };
         auto mfma_group = [&](int iw, float (&A)[NWT][4], float (&B)[NWT][4]) {
 #pragma unroll
@@ -884,24 +879,16 @@ static int launch_conv0_ksplit(const ConvParams& p0, hipStream_t st) {
     ConvParams p = p0;
     constexpr int ROWS = CONV_TH + 2, COLS = 34, SLAB = ROWS * COLS * 32;
     constexpr size_t lds = (size_t)(4 * SLAB + 4 + 2 * 4 * 64 * 4) * sizeof(float);
-    static_assert(lds <= 160 * 1024, "conv0 k-split: LDS");
+    static_assert(lds > 64 * 1024 && lds <= 160 * 1024, "conv0 k-split: LDS");
     p.tiles_h = (p.ho + CONV_TH - 1) / CONV_TH;
     p.tiles_w = ((p.wo + 1) / 2 + 15) / 16;
     const long long nblk = (long long)p.tiles_w * p.tiles_h * ((p.Do + DZ - 1) / DZ) * p.B;
-    if (nblk > 0x7fffffffLL) {
-        set_error("conv3d: %lld workgroups exceed the grid limit", nblk);
-        return MVD_ERR_INVALID_ARG;
-    }
     if (nblk < march_min_blocks()) {  // too few workgroups to fill 256 CUs: shorter chunks, then the other kernels
         if constexpr (DZ > 16) return launch_conv0_ksplit<16>(p0, st);
         else if constexpr (DZ > 8) return launch_conv0_ksplit<8>(p0, st);
         return -1;
     }
-    auto kern = conv0_ksplit_kernel<DZ>;
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return launch_status("conv3d: LDS attribute");
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(512), lds, st, p);
-    return launch_status("conv0_ksplit");
+    return launch_tiles(conv0_ksplit_kernel<DZ>, nblk, 512, lds, "conv0_ksplit", p, st);
 }
 
 // ConvTranspose3d (k3 s2 p1 op1) with ALL 8 output parity classes in one workgroup: out[2a+p] along each axis
@@ -919,9 +906,8 @@ __global__ void __launch_bounds__(256) deconv3d_all_kernel(ConvParams p) {
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int vox = lane & 15, q = lane >> 4;
-    int bx = blockIdx.x;
-    const int tw = bx % p.tiles_w; bx /= p.tiles_w;
-    const int th = bx % p.tiles_h; bx /= p.tiles_h;
+    int tw, th;
+    const int bx = decode_tile(p, blockIdx.x, tw, th);
     const int zd = bx % p.Di;
     const int b = bx / p.Di;
     const int r0 = th * CONV_TH, c0 = tw * TW;
@@ -947,14 +933,7 @@ __global__ void __launch_bounds__(256) deconv3d_all_kernel(ConvParams p) {
 #pragma unroll
                 for (int n = 0; n < NT; ++n) {
                     const int tap = step * 3 + kw;
-                    const float* wp = p.wpk + ((((size_t)tap * G::NKG + g) * NT + n) * 64 + lane) * G::R;
-                    if constexpr (G::R == 4) {
-                        const float4 t = *reinterpret_cast<const float4*>(wp);
-                        dst[kw][g][n][0] = t.x; dst[kw][g][n][1] = t.y; dst[kw][g][n][2] = t.z; dst[kw][g][n][3] = t.w;
-                    } else {
-                        const float2 t = *reinterpret_cast<const float2*>(wp);
-                        dst[kw][g][n][0] = t.x; dst[kw][g][n][1] = t.y;
-                    }
+                    load_frag(p.wpk + ((((size_t)tap * G::NKG + g) * NT + n) * 64 + lane) * G::R, dst[kw][g][n]);
                 }
     };
     constexpr bool AHEAD = 2 * 3 * G::NKG * NT * G::R <= 96;  // both batches fit the register file
@@ -1012,16 +991,7 @@ __global__ void __launch_bounds__(256) deconv3d_all_kernel(ConvParams p) {
             for (int g = 0; g < G::NKG; ++g) {
                 float bf[MT][G::R];
 #pragma unroll
-                for (int m = 0; m < MT; ++m) {
-                    const float* bp = srow_p + (m * 16 + vox) * PSTR + g * G::KG;
-                    if constexpr (G::R == 4) {
-                        const float4 t = *reinterpret_cast<const float4*>(bp);
-                        bf[m][0] = t.x; bf[m][1] = t.y; bf[m][2] = t.z; bf[m][3] = t.w;
-                    } else {
-                        const float2 t = *reinterpret_cast<const float2*>(bp);
-                        bf[m][0] = t.x; bf[m][1] = t.y;
-                    }
-                }
+                for (int m = 0; m < MT; ++m) load_frag(srow_p + (m * 16 + vox) * PSTR + g * G::KG, bf[m]);
 #pragma unroll
                 for (int j = 0; j < G::R; ++j)
 #pragma unroll
@@ -1090,9 +1060,8 @@ __global__ void __launch_bounds__(256, 4) deconv3d_pair_kernel(ConvParams p) {
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int vox = lane & 15, q = lane >> 4;
-    int bx = tile_index(p);
-    const int tw = bx % p.tiles_w; bx /= p.tiles_w;
-    const int th = bx % p.tiles_h; bx /= p.tiles_h;
+    int tw, th;
+    const int bx = decode_tile(p, tile_index(p), tw, th);
     const int zd = bx % p.Di;
     const int b = bx / p.Di;
     const int r0 = th * CONV_TH, c0 = tw * TW;
@@ -1109,16 +1078,8 @@ __global__ void __launch_bounds__(256, 4) deconv3d_pair_kernel(ConvParams p) {
 #pragma unroll
         for (int st = 0; st < 2; ++st)
 #pragma unroll
-            for (int g = 0; g < G::NKG; ++g) {
-                const float* wp = p.wpk + (((size_t)(kdh * 2 + st) * G::NKG + g) * 64 + lane) * G::R;
-                if constexpr (G::R == 4) {
-                    const float4 t = *reinterpret_cast<const float4*>(wp);
-                    dst[st][g][0] = t.x; dst[st][g][1] = t.y; dst[st][g][2] = t.z; dst[st][g][3] = t.w;
-                } else {
-                    const float2 t = *reinterpret_cast<const float2*>(wp);
-                    dst[st][g][0] = t.x; dst[st][g][1] = t.y;
-                }
-            }
+            for (int g = 0; g < G::NKG; ++g)
+                load_frag(p.wpk + (((size_t)(kdh * 2 + st) * G::NKG + g) * 64 + lane) * G::R, dst[st][g]);
     };
     float af[2][G::NKG][G::R];
     load_a(0, af);
@@ -1168,16 +1129,7 @@ __global__ void __launch_bounds__(256, 4) deconv3d_pair_kernel(ConvParams p) {
             for (int g = 0; g < G::NKG; ++g) {
                 float bf[MT][G::R];
 #pragma unroll
-                for (int m = 0; m < MT; ++m) {
-                    const float* bp = srow_p + (m * 16 + vox) * PSTR + g * G::KG;
-                    if constexpr (G::R == 4) {
-                        const float4 t = *reinterpret_cast<const float4*>(bp);
-                        bf[m][0] = t.x; bf[m][1] = t.y; bf[m][2] = t.z; bf[m][3] = t.w;
-                    } else {
-                        const float2 t = *reinterpret_cast<const float2*>(bp);
-                        bf[m][0] = t.x; bf[m][1] = t.y;
-                    }
-                }
+                for (int m = 0; m < MT; ++m) load_frag(srow_p + (m * 16 + vox) * PSTR + g * G::KG, bf[m]);
 #pragma unroll
                 for (int j = 0; j < G::R; ++j)
 #pragma unroll
@@ -1249,17 +1201,8 @@ static int launch_deconv_pair(const ConvParams& p0, hipStream_t st) {
     p.tiles_h = (p.hi + CONV_TH - 1) / CONV_TH;
     p.tiles_w = (p.wi + 16 * MT - 1) / (16 * MT);
     const long long nblk = (long long)p.tiles_w * p.tiles_h * p.Di * p.B;
-    if (nblk > 0x7fffffffLL) {
-        set_error("conv3d: %lld workgroups exceed the grid limit", nblk);
-        return MVD_ERR_INVALID_ARG;
-    }
     p.per_xcd = xcd_run(nblk, 1);
-    auto kern = deconv3d_pair_kernel<CIN, MT>;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return launch_status("conv3d: LDS attribute");
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), lds, st, p);
-    return launch_status("deconv3d_pair");
+    return launch_tiles(deconv3d_pair_kernel<CIN, MT>, nblk, 256, lds, "deconv3d_pair", p, st);
 }
 
 template <int CIN, int NT, int MT>
@@ -1270,16 +1213,7 @@ static int launch_deconv_all(const ConvParams& p0, hipStream_t st) {
     p.tiles_h = (p.hi + CONV_TH - 1) / CONV_TH;
     p.tiles_w = (p.wi + 16 * MT - 1) / (16 * MT);
     const long long nblk = (long long)p.tiles_w * p.tiles_h * p.Di * p.B;
-    if (nblk > 0x7fffffffLL) {
-        set_error("conv3d: %lld workgroups exceed the grid limit", nblk);
-        return MVD_ERR_INVALID_ARG;
-    }
-    auto kern = deconv3d_all_kernel<CIN, NT, MT>;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return launch_status("conv3d: LDS attribute");
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), lds, st, p);
-    return launch_status("deconv3d_all");
+    return launch_tiles(deconv3d_all_kernel<CIN, NT, MT>, nblk, 256, lds, "deconv3d_all", p, st);
 }
 
 // `prob`: 3x3x3, 8 -> 1 channels, stride 1 (mvsnet_components.py:109).  One GEMM row of 16 would be used on
@@ -1302,9 +1236,8 @@ __global__ void __launch_bounds__(256, 4) conv3d_c8_to_1_kernel(ConvParams p) {
     constexpr int NEL = ROWS * COLS * 2, NPF = (NEL + 255) / 256, DZ = C8_DZ;
     __shared__ __attribute__((aligned(16))) float ring[3 * SLAB + 4];  // 37 KB + dummy slot
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int bx = tile_index(p);
-    const int tw = bx % p.tiles_w; bx /= p.tiles_w;
-    const int th = bx % p.tiles_h; bx /= p.tiles_h;
+    int tw, th;
+    const int bx = decode_tile(p, tile_index(p), tw, th);
     const int nzc = (p.Do + DZ - 1) / DZ;
     const int zc = bx % nzc;
     const int b = bx / nzc;
@@ -1415,16 +1348,7 @@ static int launch_conv(const ConvParams& p0, hipStream_t st) {
     p.tiles_w = (gw + T::TW - 1) / T::TW;
     const long long nz = T::DECONV ? (long long)p.Di * 4 : p.Do;
     const long long nblk = (long long)p.tiles_w * p.tiles_h * nz * p.B;
-    if (nblk > 0x7fffffffLL) {
-        set_error("conv3d: %lld workgroups exceed the grid limit", nblk);
-        return MVD_ERR_INVALID_ARG;
-    }
-    auto kern = conv3d_kernel<CIN, NT, MT, MODE>;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return launch_status("conv3d: LDS attribute");
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), lds, st, p);
-    return launch_status("conv3d");
+    return launch_tiles(conv3d_kernel<CIN, NT, MT, MODE>, nblk, 256, lds, "conv3d", p, st);
 }
 
 static int launch_c8_to_1(const ConvParams& p0, hipStream_t st) {
@@ -1432,13 +1356,8 @@ static int launch_c8_to_1(const ConvParams& p0, hipStream_t st) {
     p.tiles_h = (p.ho + CONV_TH - 1) / CONV_TH;
     p.tiles_w = (p.wo + C8_TW - 1) / C8_TW;
     const long long nblk = (long long)p.tiles_w * p.tiles_h * ((p.Do + C8_DZ - 1) / C8_DZ) * p.B;
-    if (nblk > 0x7fffffffLL) {
-        set_error("conv3d: %lld workgroups exceed the grid limit", nblk);
-        return MVD_ERR_INVALID_ARG;
-    }
     p.per_xcd = xcd_run(nblk, 0);
-    hipLaunchKernelGGL(conv3d_c8_to_1_kernel, dim3((unsigned)nblk), dim3(256), 0, st, p);
-    return launch_status("conv3d_c8_to_1");
+    return launch_tiles(conv3d_c8_to_1_kernel, nblk, 256, 0, "conv3d_c8_to_1", p, st);
 }
 
 // 16-column tiles per wave row, lo..hi: the choice that pads a row of `cols` GEMM columns least (ties: the widest)
@@ -1487,10 +1406,13 @@ static int dispatch_cout(const ConvParams& p, hipStream_t st) {
             if constexpr (CIN == 32)
                 if (!old && !p.skip && !exp_env("MVD_K4_NOKSPLIT")) {  // conv0: two waves per row, split over the input channels
                     int rc = -1;
-                    const char* dz = exp_env("MVD_K4_CONV0_DZ");  // experiments library: planes per workgroup march
+#ifdef MVD_EXPERIMENTS
+                    const char* dz = exp_env("MVD_K4_CONV0_DZ");  // planes per workgroup march
                     if (dz && atoi(dz) == 32) rc = launch_conv0_ksplit<32>(p, st);
                     else if (dz && atoi(dz) == 64) rc = launch_conv0_ksplit<64>(p, st);
-                    else rc = launch_conv0_ksplit<16>(p, st);
+                    else
+#endif
+                        rc = launch_conv0_ksplit<16>(p, st);
                     if (rc >= 0) return rc;
                 }
             if constexpr (CIN <= 32)
@@ -1501,16 +1423,17 @@ static int dispatch_cout(const ConvParams& p, hipStream_t st) {
             return launch_conv<CIN, 1, (CIN >= 64 ? 1 : 2), MVD_CONV3D_S1_PAIR>(p, st);
         }
         if (p.Cout == 1 && CIN == 8) return launch_c8_to_1(p, st);
-        if (!old && CIN >= 16) {
-            constexpr int MM = CIN == 16 ? 4 : CIN == 32 ? 2 : 1;
-            int rc = -1;
-            switch ((p.Cout + 15) / 16) {
-                case 1: rc = launch_march_best<CIN, 1, MM>(p, st); break;
-                case 2: rc = launch_march_best<CIN, 2, MM>(p, st); break;
-                case 4: rc = launch_march_best<CIN, 4, MM>(p, st); break;
+        if constexpr (CIN >= 16)
+            if (!old) {
+                constexpr int MM = CIN == 16 ? 4 : CIN == 32 ? 2 : 1;
+                int rc = -1;
+                switch ((p.Cout + 15) / 16) {
+                    case 1: rc = launch_march_best<CIN, 1, MM>(p, st); break;
+                    case 2: rc = launch_march_best<CIN, 2, MM>(p, st); break;
+                    case 4: rc = launch_march_best<CIN, 4, MM>(p, st); break;
+                }
+                if (rc >= 0) return rc;
             }
-            if (rc >= 0) return rc;
-        }
     }
     const int nt = (p.Cout + 15) / 16;
     if constexpr (MODE == MVD_DECONV3D_STRIDE2) {

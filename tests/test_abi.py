@@ -69,7 +69,8 @@ def test_product_library_never_reads_the_environment():
     und = subprocess.run(["nm", "-D", "--undefined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
     assert "getenv" not in und
     blob = open(_lib.LIB_PATH, "rb").read()
-    for name in (b"MVD_K3_CFG", b"MVD_K4_NOMARCH", b"MVD_K4_NOKSPLIT", b"MVD_K4_DECONV_CLASSES", b"MVD_K4_MARCH_MIN"):
+    for name in (b"MVD_K3_CFG", b"MVD_K4_NOMARCH", b"MVD_K4_NOKSPLIT", b"MVD_K4_DECONV_CLASSES", b"MVD_K4_MARCH_MIN",
+                 b"MVD_K4_XCD", b"MVD_K4_CONV0_DZ", b"MVD_K4_MARCH_MT"):
         assert name not in blob, f"{name.decode()} is compiled into the product library"
     for f in os.listdir(os.path.join(ROOT, "robustmvd_amd", "csrc")):
         if f.endswith((".hip", ".h")) and f != "mvd_api.hip":

@@ -192,6 +192,61 @@ def test_conv0_marching_large_grid_vs_oracle(dev):
     np.testing.assert_allclose(yp[..., 0].cpu().numpy(), refp[:, 0], atol=ATOL, rtol=RTOL)
 
 
+MARCH_CASES = [  # (Cin, Cout, w, skip): the conv3d_march_kernel<CIN, NT, MT, PAIR> each reaches, GEMM columns per tile
+    (64, 64, 19, False),  # <64, 4, 1, false>, 16
+    (64, 16, 19, False),  # <64, 1, 1, false>, 16: one accumulator tile, split in two
+    (32, 32, 35, True),   # <32, 2, 2, false>, 32
+    (32, 64, 35, False),  # <32, 4, 2, false>, 32
+    (16, 32, 90, False),  # <16, 2, 3, false>, 48: 96 - 90 = 6 padded columns against 128 - 90 = 38 with 64-wide tiles
+    (8, 8, 67, False),    # <8, 1, 2, true>, 32 pairs: 8-channel k-groups, the loop that is not software-pipelined
+    (16, 8, 67, False),   # <16, 1, 2, true>, 32 pairs
+    (32, 8, 35, True),    # <32, 1, 1, true>, 16 pairs, swizzled pixels: the skip keeps conv0's k-split kernel out
+]
+@pytest.fixture(scope="module")
+def march_cases():
+    """per MARCH_CASES layer, built on first use and shared by both batch sizes: three distinct elements on the device,
+    channel-last, with their C-oracle references; released with the module"""
+    cache = {}
+
+    def get(case, dev):
+        if case not in cache:
+            Cin, Cout, w, skip = MARCH_CASES[case]
+            D, h = 17, 9
+            rng = np.random.default_rng(700 + case)
+            wgt = (rng.standard_normal((Cout, Cin, 3, 3, 3)) * np.sqrt(2.0 / (27 * Cin))).astype(np.float32)
+            scale = rng.uniform(0.5, 1.5, Cout).astype(np.float32)
+            shift = (rng.standard_normal(Cout) * 0.1).astype(np.float32)
+            x = rng.standard_normal((3, Cin, D, h, w)).astype(np.float32)
+            sk = rng.standard_normal((3, Cout, D, h, w)).astype(np.float32) if skip else None
+            ref = np.stack([CO.conv3d(x[e], wgt, scale, shift, relu=True, skip=sk[e] if skip else None) for e in range(3)])
+            cl = lambda a: T(a, dev).permute(0, 2, 3, 4, 1).contiguous()
+            cache[case] = (T(wgt, dev), T(scale, dev), T(shift, dev), cl(x), cl(sk) if skip else None, cl(ref))
+        return cache[case]
+
+    yield get
+    cache.clear()
+
+
+@pytest.mark.parametrize("B", [57, 86])
+@pytest.mark.parametrize("case", range(len(MARCH_CASES)))
+def test_conv3d_marching_instantiations_vs_oracle(case, B, dev, march_cases):
+    """The depth-marching instantiations that the small grids above never reach (they need >= 1024 workgroups and
+    fall through to conv3d_kernel), at both chunk lengths, against the C oracle.  The workgroups come from the
+    batch, so the reference stays tiny: an element is D=17 x h=9 x w, i.e. 3 row tiles (the last with one row),
+    2 column tiles (the second ragged: w = 19 / 35 / 90 columns on 16 / 32 / 48-wide tiles, (w+1)/2 = 34 / 18 pairs on
+    32 / 16-pair tiles) and depth chunks 16+1 or 8+8+1.  B=57: 6 x 2 x 57 = 684 workgroups of 16 planes (< 1024) and
+    6 x 3 x 57 = 1026 of 8 (56 would give 1008), so the 8-plane kernel runs; B=86: 6 x 2 x 86 = 1032 of 16 planes
+    (85 would give 1020), so the 16-plane kernel runs.  Batch element b is element b % 3 of three distinct ones, so
+    a wrong batch offset shows."""
+    from robustmvd_amd import ops
+    Cin, Cout, w, skip = MARCH_CASES[case]
+    wgt, scale, shift, x, sk, ref = march_cases(case, dev)
+    idx = torch.arange(B, device=dev) % 3
+    packed, _, _ = ops.pack_conv3d_weights(wgt, 0)
+    y = ops.conv3d_bn_relu(x[idx], packed, Cin, Cout, scale, shift, 0, relu=True, skip=sk[idx] if skip else None)
+    torch.testing.assert_close(y, ref[idx], atol=ATOL, rtol=RTOL)
+
+
 @pytest.mark.parametrize("Cin,Cout,k,stride,B,h,w,relu,layout", [
     (3, 8, 3, 1, 2, 37, 70, True, "nhwc"), (3, 16, 5, 2, 1, 33, 45, True, "nchw"), (3, 32, 3, 1, 1, 9, 130, False, "nhwc"),
     (8, 8, 3, 1, 1, 40, 64, True, "nhwc"), (8, 16, 5, 2, 2, 38, 66, True, "nhwc"), (8, 32, 5, 2, 1, 21, 35, True, "border"),
