@@ -455,6 +455,30 @@ int mvd_sweep_corr_backward_f32(const float* feat_key, const float* const* feat_
                                 int invdepth_mode, float corr_scale, const float* const* grad_corr, int N, int C, int h, int w,
                                 int hs, int ws, int S, int V, float* grad_key, float* const* grad_src, mvd_stream_t stream);
 
+/* VJP of mvd_sweep_warp_f32 (normalize_after = 0) w.r.t. the source features: what autograd computes through WarpOnlyCorr's
+ * grid_sample (rmvd/models/blocks/planesweep_corr.py:107-140; grids under no_grad, :436,464,489).  The op is linear in the
+ * features, so no feature map is passed: grad_warped[v] (N,S,C,h,w) is the cotangent of warped_out[v]; grad_src[v]
+ * (N,hs+3,ws+3,C) zero-bordered channel-last (border = the zero padding's share; discard it).  The sampling mask is a constant
+ * and a masked sample contributes nothing.  C in 1..256.  normalize_after has no kernel here: differentiate x / (|x|_2 + 1e-9)
+ * outside (ops.sweep_warp_autograd does it in torch). */
+int mvd_sweep_warp_backward_f32(const float* K_key, const float* const* K_src, const float* const* T_src2key, const float* invdepths,
+                                int invdepth_mode, const float* const* grad_warped, int N, int C, int h, int w, int hs, int ws, int S,
+                                int V, float* const* grad_src, mvd_stream_t stream);
+
+/* VJP of mvd_sweep_reduce_f32 w.r.t. the feature maps: what autograd computes through grid_sample in CVP-MVSNet's proj_cost
+ * (rmvd/models/blocks/cvp_mvsnet_components.py:375-456, grid detached :397) and in Vis-MVSNet's homography_warping +
+ * groupwise_correlation (rmvd/models/blocks/utils.py:71-89,154-186, grids without gradient :97,164,181; the depths are detached,
+ * rmvd/models/vis_mvsnet.py:124,150).  Forward arguments as in mvd_sweep_reduce_f32, in the reference's layouts:
+ *   key_feat, src_feat[v], grad_key, grad_src[v] (B,C,h,w); grad_out: the cotangent of `out`, grad_out[0] (B,C,D,h,w) for the
+ *   variance modes, grad_out[v] (B,groups,D,h,w) for MVD_REDUCE_GROUPCORR.
+ * Depths and M are constants.  grad_key is a plain sum (bit-reproducible); grad_src is scatter-added with float atomics into
+ * zero-bordered maps in the workspace and copied out without the border. */
+size_t mvd_sweep_reduce_backward_workspace_bytes(int B, int C, int h, int w, int V);
+int mvd_sweep_reduce_backward_f32(const float* key_feat, const float* const* src_feat, const float* const* M, const float* depth,
+                                  int depth_per_pixel, float pix_offset, float scale_x, float scale_y, float bias, int mode,
+                                  int groups, const float* const* grad_out, int B, int C, int D, int h, int w, int V, float* grad_key,
+                                  float* const* grad_src, void* workspace, size_t workspace_bytes, mvd_stream_t stream);
+
 /* VJP of mvd_fuse_views_f32 w.r.t. corr[v] (N,S,h,w) and score[v] (N,1,h,w); masks and the fused mask are constants. */
 int mvd_fuse_views_backward_f32(const float* const* corr, const float* const* mask, const float* const* score,
                                 const float* grad_fused, int N, int S, int h, int w, int V, float* const* grad_corr,

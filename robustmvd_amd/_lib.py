@@ -118,18 +118,27 @@ SIGNATURES = {
     "mvd_sweep_reduce_workspace_bytes": (_sz, [_i] * 5),
     "mvd_sweep_reduce_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _i] + [ctypes.c_float] * 4 + [_i] * 8
                              + [_pp, ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "mvd_sweep_reduce_backward_workspace_bytes": (_sz, [_i] * 5),
+    "mvd_sweep_reduce_backward_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _i] + [ctypes.c_float] * 4 + [_i, _i, _pp] + [_i] * 6
+                                      + [_c_float_p, _pp, ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "mvd_sweep_warp_backward_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _i, _pp] + [_i] * 8 + [_pp, ctypes.c_void_p]),
     "mvd_resize_order1_f32": (_i, [_c_float_p, _c_float_p, ctypes.c_longlong, _i, _i, _i, _i, ctypes.c_void_p]),
     "mvd_nchw_to_nhwc_f32": (_i, [_c_float_p, _c_float_p, _i, _i, ctypes.c_longlong, ctypes.c_void_p]),
     "mvd_nhwc_to_nchw_f32": (_i, [_c_float_p, _c_float_p, _i, _i, ctypes.c_longlong, ctypes.c_void_p]),
 }
 
+# built into the product library only (csrc/Makefile PRODSRCS): the experiments library has no variants of these
+PRODUCT_ONLY = ("mvd_sweep_reduce_backward_workspace_bytes", "mvd_sweep_reduce_backward_f32")
+
 _lib = None
 _override = None  # set by use_experiments_library()
 
 
-def _bind(path):
+def _bind(path, skip=()):
     lib = ctypes.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
+        if name in skip:
+            continue
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -163,7 +172,7 @@ class use_experiments_library:
         if not os.path.exists(self.path):
             raise RuntimeError(f"{self.path} not found: run `make -C robustmvd_amd/csrc exp`")
         self._prev = _override
-        _override = _bind(self.path)
+        _override = _bind(self.path, skip=PRODUCT_ONLY)
         return _override
 
     def __exit__(self, *exc):

@@ -43,14 +43,17 @@ class PlanesweepCorrelation(nn.Module):
     """Same call signature and return value as the reference block; no parameters.
     Stateless across calls (the reference keeps per-call state on self and is not re-entrant)."""
 
-    def __init__(self, warp_only=False, normalize="dim"):
+    def __init__(self, warp_only=False, normalize="dim", differentiable=False):
         """normalize (TorchCorr, planesweep_corr.py:142-189): "dim" divides the dot products by sqrt(C) (what robust_mvd
         uses); True / "before" L2-normalises both feature maps along C first (x / (|x| + 1e-9), :8-10); False leaves
         the raw dot products.  warp_only=True (WarpOnlyCorr, :106-139) returns the warped source FEATURES (N,S,C,h,w) and
         the sampling mask instead of correlations; there "before" normalises the source features first, True / "after" the
-        warped ones along C, "dim" / False nothing (:128-136).  Inference only."""
+        warped ones along C, "dim" / False nothing (:128-136).  The warp-only sweep refuses source features that require grad
+        unless differentiable=True: then it goes through ops.sweep_warp_autograd (mvd_sweep_warp_backward_f32) and gradients
+        reach feat_sources in every normalisation mode, like the reference's.  (The correlation sweep needs no switch.)"""
         super().__init__()
         self.warp_only = bool(warp_only)
+        self.differentiable = bool(differentiable)
         allowed = ("dim", "before", "after", True, False) if warp_only else ("dim", "before", True, False)
         if normalize not in allowed:
             raise ValueError(f"normalize={normalize!r}: expected one of {allowed}")
@@ -76,9 +79,12 @@ class PlanesweepCorrelation(nn.Module):
                 min_depth, max_depth, sampling_invdepths, sampling_type)
         if self.warp_only:
             if ops.needs_grad(feat_sources):
-                raise ValueError("PlanesweepCorrelation(warp_only=True) has no backward in this engine: detach the features")
+                if not self.differentiable:
+                    raise ValueError("PlanesweepCorrelation(warp_only=True): a source feature map requires grad; construct the "
+                                     "block with differentiable=True for the engine's backward, or detach the features")
+                return self._forward(ops.sweep_warp_autograd, *args)
             with torch.no_grad():
-                return self._forward(None, *args)
+                return self._forward(ops.sweep_warp, *args)
         if ops.needs_grad(feat_key, feat_sources):
             return self._forward(ops.sweep_corr_autograd, *args)
         with torch.no_grad():
@@ -123,7 +129,7 @@ class PlanesweepCorrelation(nn.Module):
             for i, f in enumerate(srcs):
                 groups.setdefault(tuple(f.shape[-2:]), []).append(i)
             for idxs in groups.values():
-                wv, mv = ops.sweep_warp([srcs[i] for i in idxs], intrinsics_key, [intrinsics_sources[i] for i in idxs],
+                wv, mv = sweep([srcs[i] for i in idxs], intrinsics_key, [intrinsics_sources[i] for i in idxs],
                                         [source_to_key_transforms[i] for i in idxs], inv, feat_key.shape[-2:], after)
                 for i, wi, mi in zip(idxs, wv, mv):
                     warped[i], masks[i] = wi, mi

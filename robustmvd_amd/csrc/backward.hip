@@ -2,6 +2,7 @@
 //   K3  homo_warp + variance          rmvd/models/blocks/utils.py:222-268, rmvd/models/mvsnet.py:124-135
 //   K1  PlanesweepCorrelation          rmvd/models/blocks/planesweep_corr.py:152-195 (grids under no_grad: :436,464,489)
 //   K2  LearnedFusion view weighting   rmvd/models/blocks/learned_fusion.py:32-48
+//   WarpOnlyCorr (warp-only sweep)     rmvd/models/blocks/planesweep_corr.py:107-140
 // so that the training loop (rmvd/train/multi_view_depth_training.py:231-246) can back-propagate through the engine.
 // The sampling grids depend on calibration only and carry no gradient: the backward of a bilinear gather is a
 // scatter-add of the incoming gradient times the same weights, done with no-return float atomics
@@ -13,10 +14,6 @@
 #include "warp_variance_backward_common.h"
 
 namespace mvd {
-
-__device__ __forceinline__ void atomic_add4(float* p, float4 v) {
-    unsafeAtomicAdd(p + 0, v.x); unsafeAtomicAdd(p + 1, v.y); unsafeAtomicAdd(p + 2, v.z); unsafeAtomicAdd(p + 3, v.w);
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // K3 backward.  Thread = (pixel, channel quad); loops over the D planes in chunks of 8.  Per chunk: pass 1 gathers every view's
@@ -172,6 +169,35 @@ __device__ __forceinline__ float fix_nonfinite(float v) {
     return v;
 }
 
+// What a key pixel's ray needs per source view, and per plane the sampled 2x2 cell: the forward's operation chain, shared by the
+// K1 backward and the warp-only backward (the callers form their own 0/1 mask from `t.inb` and `visible`).
+struct SweepRay { Epi E; float u_inf, v_inf, k_inf, z_pole; };
+__device__ __forceinline__ SweepRay sweep_bwd_ray(const float* __restrict__ Kk, const float* __restrict__ Ks, const float* __restrict__ T,
+                                                  int h, int w, int hs, int ws, float xc, float yc) {
+    SweepRay R;
+    R.E = epipolar_b(Kk, Ks, T, h, w, hs, ws);
+    R.u_inf = (R.E.a * xc + R.E.b * yc) + R.E.c; R.v_inf = (R.E.f * xc + R.E.g * yc) + R.E.h; R.k_inf = (R.E.j * xc + R.E.k * yc) + R.E.l;
+    R.z_pole = -(R.E.m / R.k_inf);
+    return R;
+}
+struct SweepCell { Taps t; int cell; bool visible; };  // cell: index of the top-left tap in the zero-bordered map, W2 = ws + 3 wide
+__device__ __forceinline__ SweepCell sweep_bwd_cell(const SweepRay& R, float ds, int hs, int ws, int W2) {
+    const Epi& E = R.E;
+    const float fws = (float)ws, fhs = (float)hs;
+    const float den = R.k_inf + E.m * ds;
+    const float us = fix_nonfinite((R.u_inf + E.e * ds) / den), vs = fix_nonfinite((R.v_inf + E.i * ds) / den);
+    const float zs = 1.0f / ds;
+    SweepCell G;
+    G.visible = (zs > 0.f) && (((R.k_inf > 0.f) && (zs > R.z_pole)) || ((R.k_inf < 0.f) && (zs < R.z_pole)) ||
+                               ((R.k_inf == 0.f) && (E.m > 0.f)));
+    const float ix = unnormalize_coord(2.0f * us / fws - 1.0f, fws), iy = unnormalize_coord(2.0f * vs / fhs - 1.0f, fhs);
+    G.t = bilinear_taps(ix, iy, hs, ws);
+    const int cx = (int)fminf(fmaxf(floorf(ix), -1.0f), (float)(ws - 1)) + 1;
+    const int cy = (int)fminf(fmaxf(floorf(iy), -1.0f), (float)(hs - 1)) + 1;
+    G.cell = cy * W2 + cx;
+    return G;
+}
+
 struct SweepBwdParams {
     ViewPtrs src;        // V x (N,hs+3,ws+3,C) zero-bordered channel-last source features
     ViewPtrs K_src, T;   // V x (N,3,3), V x (N,4,4)
@@ -196,7 +222,7 @@ __global__ void __launch_bounds__(256) sweep_corr_backward_kernel(SweepBwdParams
     const int x = (int)(wid % p.w), y = (int)((wid / p.w) % p.h), n = (int)(wid / ((long long)p.w * p.h));
     const int h = p.h, w = p.w, hs = p.hs, ws = p.ws, S = p.S, W2 = ws + 3;
     const float inv_sqrt_c = p.corr_scale;
-    const float fws = (float)ws, fhs = (float)hs, xc = (float)x + 0.5f, yc = (float)y + 0.5f;
+    const float xc = (float)x + 0.5f, yc = (float)y + 0.5f;
     const float* __restrict__ invd = p.invd + (size_t)n * p.invd_stride;
     float kf[NJ], gk[NJ];
     const size_t koff = (((size_t)n * h + y) * w + x) * C + lane * NJ;
@@ -204,9 +230,7 @@ __global__ void __launch_bounds__(256) sweep_corr_backward_kernel(SweepBwdParams
     for (int j = 0; j < NJ; ++j) { kf[j] = p.key[koff + j]; gk[j] = 0.f; }
 
     for (int v = 0; v < p.V; ++v) {
-        const Epi E = epipolar_b(p.K_key + n * 9, p.K_src.p[v] + n * 9, p.T.p[v] + n * 16, h, w, hs, ws);
-        const float u_inf = (E.a * xc + E.b * yc) + E.c, v_inf = (E.f * xc + E.g * yc) + E.h, k_inf = (E.j * xc + E.k * yc) + E.l;
-        const float z_pole = -(E.m / k_inf);
+        const SweepRay R = sweep_bwd_ray(p.K_key + n * 9, p.K_src.p[v] + n * 9, p.T.p[v] + n * 16, h, w, hs, ws, xc, yc);
         const size_t simg = (size_t)n * (hs + 3) * W2 * C;
         const float* __restrict__ src = p.src.p[v] + simg + lane * NJ;
         float* __restrict__ gsrc = p.gsrc.p[v] + simg + lane * NJ;
@@ -227,17 +251,10 @@ __global__ void __launch_bounds__(256) sweep_corr_backward_kernel(SweepBwdParams
             const bool live = s < S;
             const int sc = live ? s : S - 1;
             const float ds = p.invd_per_pixel ? p.invd[(((size_t)n * S + sc) * h + y) * w + x] : invd[sc];
-            const float den = k_inf + E.m * ds;
-            const float us = fix_nonfinite((u_inf + E.e * ds) / den), vs = fix_nonfinite((v_inf + E.i * ds) / den);
-            const float zs = 1.0f / ds;
-            const bool visible = (zs > 0.f) && (((k_inf > 0.f) && (zs > z_pole)) || ((k_inf < 0.f) && (zs < z_pole)) ||
-                                               ((k_inf == 0.f) && (E.m > 0.f)));
-            const float ix = unnormalize_coord(2.0f * us / fws - 1.0f, fws), iy = unnormalize_coord(2.0f * vs / fhs - 1.0f, fhs);
-            const Taps t = bilinear_taps(ix, iy, hs, ws);
-            const float mk = (t.inb < 0.9999f || !visible) ? 0.f : 1.f;
-            const int cx = (int)fminf(fmaxf(floorf(ix), -1.0f), (float)(ws - 1)) + 1;
-            const int cy = (int)fminf(fmaxf(floorf(iy), -1.0f), (float)(hs - 1)) + 1;
-            const int cell = cy * W2 + cx;
+            const SweepCell G = sweep_bwd_cell(R, ds, hs, ws, W2);
+            const Taps& t = G.t;
+            const float mk = (t.inb < 0.9999f || !G.visible) ? 0.f : 1.f;
+            const int cell = G.cell;
             const float gcoef = live ? gc[(size_t)s * h * w] * mk * inv_sqrt_c : 0.f;
             const int npl = min(64, S - s0);
             for (int i = 0; i < npl; ++i) {  // wave-uniform
@@ -272,6 +289,86 @@ __global__ void __launch_bounds__(256) sweep_corr_backward_kernel(SweepBwdParams
     }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) p.gkey[koff + j] = gk[j];
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Warp-only backward: VJP of sweep_warp_kernel (sweep_corr.hip, WarpOnlyCorr planesweep_corr.py:107-140) w.r.t. the source
+// features, normalize_after = 0: warped = sample * mask is linear in the features, so the gradient of a source pixel is the sum of
+// the cotangents of the samples that touched it times their tap weights; no feature map is read.  K1 backward's shape: one
+// wave per key pixel, lane = channel (c = j * 64 + lane), geometry by lane = plane in passes of 64 and broadcast with readlane,
+// runs of planes in one 2x2 cell summed in registers.  The mask is the SAMPLING mask alone, as in the forward (WarpOnlyCorr
+// does not take the visibility mask).
+struct WarpOnlyBwdParams {
+    ViewPtrs K_src, T;   // V x (N,3,3), V x (N,4,4)
+    ViewPtrs gwarp;      // V x (N,S,C,h,w)
+    ViewOutPtrs gsrc;    // V x (N,hs+3,ws+3,C), zero-initialised
+    const float* K_key;  // (N,3,3)
+    const float* invd;
+    int invd_stride, invd_per_pixel;
+    int N, C, h, w, hs, ws, S, V;
+};
+
+template <int NJ>
+__global__ void __launch_bounds__(256) sweep_warp_backward_kernel(WarpOnlyBwdParams p) {
+    const int lane = threadIdx.x & 63;
+    const long long wid = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (wid >= (long long)p.N * p.h * p.w) return;  // wave-uniform
+    const int x = (int)(wid % p.w), y = (int)((wid / p.w) % p.h), n = (int)(wid / ((long long)p.w * p.h));
+    const int h = p.h, w = p.w, hs = p.hs, ws = p.ws, S = p.S, C = p.C, W2 = ws + 3;
+    const size_t hw = (size_t)h * w;
+    const float xc = (float)x + 0.5f, yc = (float)y + 0.5f;
+    const float* __restrict__ invd = p.invd + (size_t)n * p.invd_stride;
+
+    for (int v = 0; v < p.V; ++v) {
+        const SweepRay R = sweep_bwd_ray(p.K_key + n * 9, p.K_src.p[v] + n * 9, p.T.p[v] + n * 16, h, w, hs, ws, xc, yc);
+        float* __restrict__ gsrc = p.gsrc.p[v] + (size_t)n * (hs + 3) * W2 * C;
+        const float* __restrict__ gw = p.gwarp.p[v] + (size_t)n * S * C * hw + (size_t)y * w + x;
+        int cur = -1;
+        float gt[4][NJ];
+        auto flush = [&]() {
+            if (cur < 0) return;
+            float* g0 = gsrc + (size_t)cur * C;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int c = j * 64 + lane;
+                if (c < C) {
+                    unsafeAtomicAdd(g0 + c, gt[0][j]); unsafeAtomicAdd(g0 + C + c, gt[1][j]);
+                    unsafeAtomicAdd(g0 + (size_t)W2 * C + c, gt[2][j]); unsafeAtomicAdd(g0 + (size_t)W2 * C + C + c, gt[3][j]);
+                }
+            }
+        };
+        for (int s0 = 0; s0 < S; s0 += 64) {
+            const int s = s0 + lane;
+            const bool live = s < S;
+            const int sc = live ? s : S - 1;
+            const float ds = p.invd_per_pixel ? p.invd[(((size_t)n * S + sc) * h + y) * w + x] : invd[sc];
+            const SweepCell G = sweep_bwd_cell(R, ds, hs, ws, W2);
+            const float mk = (live && !(G.t.inb < 0.9999f)) ? 1.f : 0.f;
+            const int npl = min(64, S - s0);
+            for (int i = 0; i < npl; ++i) {  // wave-uniform
+                const float mki = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mk), i));
+                if (mki == 0.f) continue;
+                const int ci = __builtin_amdgcn_readlane(G.cell, i);
+                if (ci != cur) {
+                    flush();
+                    cur = ci;
+#pragma unroll
+                    for (int j = 0; j < NJ; ++j) gt[0][j] = gt[1][j] = gt[2][j] = gt[3][j] = 0.f;
+                }
+                float wk[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) wk[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(G.t.w[k]), i));
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) {
+                    const int c = j * 64 + lane;
+                    const float g = c < C ? gw[((size_t)(s0 + i) * C + c) * hw] : 0.f;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) gt[k][j] = fmaf(g, wk[k], gt[k][j]);
+                }
+            }
+        }
+        flush();
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -415,6 +512,39 @@ int mvd_sweep_corr_backward_f32(const float* feat_key, const float* const* feat_
         default: hipLaunchKernelGGL(sweep_corr_backward_kernel<4>, dim3((unsigned)nblk), dim3(256), 0, st, p); break;
     }
     return launch_status("sweep_corr_backward");
+}
+
+int mvd_sweep_warp_backward_f32(const float* K_key, const float* const* K_src, const float* const* T_src2key, const float* invdepths,
+                                int invdepth_mode, const float* const* grad_warped, int N, int C, int h, int w, int hs, int ws, int S,
+                                int V, float* const* grad_src, mvd_stream_t stream) {
+    using namespace mvd;
+    MVD_REQUIRE(invdepth_mode >= MVD_INVDEPTH_SHARED && invdepth_mode <= MVD_INVDEPTH_PER_PIXEL, "sweep_warp_backward: invdepth_mode %d", invdepth_mode);
+    MVD_REQUIRE(K_key && K_src && T_src2key && invdepths && grad_warped && grad_src, "sweep_warp_backward: NULL argument");
+    MVD_REQUIRE(N > 0 && h > 0 && w > 0 && hs > 0 && ws > 0 && S > 0 && V >= 1 && V <= MVD_MAX_VIEWS, "sweep_warp_backward: bad dimensions");
+    MVD_REQUIRE(C >= 1 && C <= 256, "sweep_warp_backward: C=%d unsupported (1..256)", C);
+    MVD_REQUIRE((long long)(hs + 3) * (ws + 3) < 0x7fffffffLL, "sweep_warp_backward: source map %dx%d too large", hs, ws);
+    hipStream_t st = (hipStream_t)stream;
+    WarpOnlyBwdParams p{};
+    const size_t slot = (size_t)N * (hs + 3) * (ws + 3) * C * sizeof(float);
+    for (int v = 0; v < V; ++v)
+        MVD_REQUIRE(K_src[v] && T_src2key[v] && grad_warped[v] && grad_src[v], "sweep_warp_backward: NULL view %d", v);
+    const long long nwave = (long long)N * h * w, nblk = (nwave + 3) / 4;
+    MVD_REQUIRE(nblk <= 0x7fffffffLL, "sweep_warp_backward: grid too large");
+    for (int v = 0; v < V; ++v) {
+        p.K_src.p[v] = K_src[v]; p.T.p[v] = T_src2key[v]; p.gwarp.p[v] = grad_warped[v]; p.gsrc.p[v] = grad_src[v];
+        if (hipMemsetAsync(grad_src[v], 0, slot, st) != hipSuccess) return launch_status("sweep_warp_backward: memset");
+    }
+    p.K_key = K_key; p.invd = invdepths;
+    p.invd_stride = invdepth_mode == MVD_INVDEPTH_BATCHED ? S : 0;
+    p.invd_per_pixel = invdepth_mode == MVD_INVDEPTH_PER_PIXEL;
+    p.N = N; p.C = C; p.h = h; p.w = w; p.hs = hs; p.ws = ws; p.S = S; p.V = V;
+    switch ((C + 63) / 64) {
+        case 1: hipLaunchKernelGGL(sweep_warp_backward_kernel<1>, dim3((unsigned)nblk), dim3(256), 0, st, p); break;
+        case 2: hipLaunchKernelGGL(sweep_warp_backward_kernel<2>, dim3((unsigned)nblk), dim3(256), 0, st, p); break;
+        case 3: hipLaunchKernelGGL(sweep_warp_backward_kernel<3>, dim3((unsigned)nblk), dim3(256), 0, st, p); break;
+        default: hipLaunchKernelGGL(sweep_warp_backward_kernel<4>, dim3((unsigned)nblk), dim3(256), 0, st, p); break;
+    }
+    return launch_status("sweep_warp_backward");
 }
 
 int mvd_fuse_views_backward_f32(const float* const* corr, const float* const* mask, const float* const* score,

@@ -14,7 +14,7 @@
 // Generic and simple by design (the tuned K3 tile kernel is the hot path): thread = (pixel, unit), unit = channel quad
 // (variance modes) or channel group (group correlation); pixels are the fast index so that stores into the
 // reference's (B,C,D,h,w) layout are coalesced.  Gathers come from zero-bordered channel-last copies like K3's.
-#include "mvd_common.h"
+#include "sweep_modes_common.h"
 
 namespace mvd {
 int repack_padded_launch(const float* src, float* dst, int B, int C, int h, int w, hipStream_t st);
@@ -37,13 +37,8 @@ __device__ __forceinline__ float4 reduce_sample(const ReduceParams& p, int v, in
                                                 size_t img) {
     const float xhi = (float)p.w, yhi = (float)p.h;
     const int C = p.C;
-    const float* __restrict__ M = p.M.p[v] + (size_t)b * 12;
-    const float ax = fmaf(M[0], fx, fmaf(M[1], fy, M[2])), ay = fmaf(M[4], fx, fmaf(M[5], fy, M[6]));
-    const float az = fmaf(M[8], fx, fmaf(M[9], fy, M[10]));
-    const float X = fmaf(ax, depth, M[3]), Y = fmaf(ay, depth, M[7]), Z = fmaf(az, depth, M[11]);
-    float ix = fmaf(X / Z, p.scale_x, p.bias), iy = fmaf(Y / Z, p.scale_y, p.bias);
-    ix = __builtin_amdgcn_fmed3f(ix, -1.0f, xhi);  // NaN -> -1: all taps in the zero border
-    iy = __builtin_amdgcn_fmed3f(iy, -1.0f, yhi);
+    const ReducePos P = reduce_position(p.M.p[v] + (size_t)b * 12, fx, fy, depth, p.scale_x, p.scale_y, p.bias, xhi, yhi);
+    const float ix = P.ix, iy = P.iy;
     const float xf = floorf(ix), yf = floorf(iy);
     const float wx = ix - xf, wy = iy - yf, ux = 1.0f - wx, uy = 1.0f - wy;
     const float* __restrict__ f = p.src.p[v] + b * img + ((size_t)((int)yf + 1) * W2 + ((int)xf + 1)) * C + c0;
@@ -172,13 +167,8 @@ __global__ void __launch_bounds__(256) sweep_reduce_kernel(ReduceParams p) {
                 s2 = make_float4(k.x * k.x, k.y * k.y, k.z * k.z, k.w * k.w);
             }
             for (int v = 0; v < V; ++v) {
-                const float* __restrict__ M = p.M.p[v] + (size_t)b * 12;
-                const float ax = fmaf(M[0], fx, fmaf(M[1], fy, M[2])), ay = fmaf(M[4], fx, fmaf(M[5], fy, M[6]));
-                const float az = fmaf(M[8], fx, fmaf(M[9], fy, M[10]));
-                const float X = fmaf(ax, depth, M[3]), Y = fmaf(ay, depth, M[7]), Z = fmaf(az, depth, M[11]);
-                float ix = fmaf(X / Z, p.scale_x, p.bias), iy = fmaf(Y / Z, p.scale_y, p.bias);
-                ix = __builtin_amdgcn_fmed3f(ix, -1.0f, xhi);  // NaN -> -1: all taps in the zero border
-                iy = __builtin_amdgcn_fmed3f(iy, -1.0f, yhi);
+                const ReducePos P = reduce_position(p.M.p[v] + (size_t)b * 12, fx, fy, depth, p.scale_x, p.scale_y, p.bias, xhi, yhi);
+                const float ix = P.ix, iy = P.iy;
                 const float xf = floorf(ix), yf = floorf(iy);
                 const float wx = ix - xf, wy = iy - yf, ux = 1.0f - wx, uy = 1.0f - wy;
                 const float* __restrict__ f = p.src.p[v] + b * img + ((size_t)((int)yf + 1) * W2 + ((int)xf + 1)) * C + c0;

@@ -66,4 +66,9 @@ __device__ __forceinline__ float4 bwd_sample(const float* __restrict__ f, const 
                        fmaf(d.w, L.w11, fmaf(c.w, L.w01, fmaf(bq.w, L.w10, a.w * L.w00))));
 }
 
+// four no-return float atomics (global_atomic_add_f32) on consecutive addresses: the scatter kernels' flush
+__device__ __forceinline__ void atomic_add4(float* p, float4 v) {
+    unsafeAtomicAdd(p + 0, v.x); unsafeAtomicAdd(p + 1, v.y); unsafeAtomicAdd(p + 2, v.z); unsafeAtomicAdd(p + 3, v.w);
+}
+
 }  // namespace mvd

@@ -873,6 +873,102 @@ def sweep_corr_autograd(feat_key, feat_sources, K_key, K_sources, T_src2key, inv
     return list(outs[:V]), list(outs[V:])
 
 
+class _SweepWarp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, K_key, invdepths, key_size, n_views, *rest):
+        V = n_views
+        srcs, Ks, Ts = list(rest[:V]), list(rest[V:2 * V]), list(rest[2 * V:])
+        outs, masks = sweep_warp([s.detach() for s in srcs], K_key, Ks, Ts, invdepths, key_size, False)
+        ctx.save_for_backward(K_key, invdepths, *Ks, *Ts)  # the op is linear in the features: the VJP needs their shape only
+        ctx.n_views, ctx.key_size, ctx.src_shape = V, (int(key_size[0]), int(key_size[1])), tuple(srcs[0].shape)
+        ctx.mark_non_differentiable(*masks)
+        return tuple(outs) + tuple(masks)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        V = ctx.n_views
+        Kk, inv = ctx.saved_tensors[:2]
+        Ks, Ts = list(ctx.saved_tensors[2:2 + V]), list(ctx.saved_tensors[2 + V:])
+        N, C, hs, ws = ctx.src_shape
+        h, w = ctx.key_size
+        dev = Kk.device
+        with torch.no_grad():
+            Kk, Ks, Ts, inv, mode = _k1_calibration(Kk, Ks, Ts, inv, V, N, h, w, dev)
+            S = inv.shape[1]
+            gw = [L.as_f32(g, f"grad_warped[{i}]", (N, S, C, h, w), dev) for i, g in enumerate(grads[:V])]
+            gs = [torch.empty((N, hs + 3, ws + 3, C), dtype=torch.float32, device=dev) for _ in range(V)]
+            call("mvd_sweep_warp_backward_f32", dev, Kk, Ks, Ts, inv, mode, gw, N, C, h, w, hs, ws, S, V, gs)
+            gsrc = [_interior_nchw(g, hs, ws) if need else None for g, need in zip(gs, ctx.needs_input_grad[4:4 + V])]
+        return (None,) * 4 + tuple(gsrc) + (None,) * (2 * V)
+
+
+class _ForwardValue(torch.autograd.Function):
+    """y with the value of `value` (same shape): the gradient goes to y unchanged."""
+    @staticmethod
+    def forward(ctx, y, value):
+        return value.view_as(y)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
+def sweep_warp_autograd(feat_sources, K_key, K_sources, T_src2key, invdepths, key_size, normalize_after=False):
+    """Differentiable sweep_warp: returns (warped[V] (N,S,C,h,w), masks[V] (N,S,h,w)) with the same bits; gradients to
+    feat_sources (mvd_sweep_warp_backward_f32), calibration, inverse depths and masks are constants.  The VJP kernel is the
+    un-normalised warp's.  normalize_after: x / (|x|_2 + 1e-9) along C is applied to the un-normalised warp in torch and
+    differentiated by autograd (a masked sample is 0 before and after it); the VALUE handed back is the fused inference kernel's
+    own, so that training and inference see one forward."""
+    srcs = views(feat_sources, "feat_sources")
+    V = len(srcs)
+    Ks, Ts = views(K_sources, "intrinsics_sources", V), views(T_src2key, "source_to_key_transforms", V)
+    outs = _SweepWarp.apply(K_key, invdepths, tuple(key_size), V, *srcs, *Ks, *Ts)
+    warped, masks = list(outs[:V]), list(outs[V:])
+    if normalize_after:
+        exact, _ = sweep_warp([s.detach() for s in srcs], K_key, Ks, Ts, invdepths, key_size, True)
+        warped = [_ForwardValue.apply(u / (torch.linalg.norm(u, dim=2, keepdim=True) + 1e-9), e) for u, e in zip(warped, exact)]
+    return warped, masks
+
+
+class _SweepReduce(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, mode, groups, pix_offset, stretch, n_views, key_feat, *rest):
+        from . import sweep_modes
+        V = n_views
+        srcs, Ms = list(rest[:V]), list(rest[V:])
+        ctx.save_for_backward(depth, key_feat, *srcs, *Ms)
+        ctx.cfg = (mode, groups, pix_offset, stretch, V)
+        out = sweep_modes.sweep_reduce_inference(key_feat.detach(), [s.detach() for s in srcs], Ms, depth, mode, groups, pix_offset, stretch)
+        return tuple(out) if mode == L.REDUCE_GROUPCORR else out
+
+    @staticmethod
+    def backward(ctx, *grads):
+        from . import sweep_modes
+        mode, groups, pix_offset, stretch, V = ctx.cfg
+        depth, key = ctx.saved_tensors[:2]
+        srcs, Ms = list(ctx.saved_tensors[2:2 + V]), list(ctx.saved_tensors[2 + V:])
+        with torch.no_grad():
+            kf, srcs, Ms, dv, per_pixel, (B, C, D, h, w, _), (sx, sy) = sweep_modes._reduce_args(key, srcs, Ms, depth, mode, groups, stretch)
+            dev = kf.device
+            oshape = (B, groups, D, h, w) if mode == L.REDUCE_GROUPCORR else (B, C, D, h, w)
+            gout = [L.as_f32(g, f"grad_out[{i}]", oshape, dev) for i, g in enumerate(grads)]
+            gk = torch.empty_like(kf)
+            gs = [torch.empty_like(kf) for _ in range(V)]
+            wsb = L.load().mvd_sweep_reduce_backward_workspace_bytes(B, C, h, w, V)
+            call("mvd_sweep_reduce_backward_f32", dev, kf, srcs, Ms, dv, per_pixel, float(pix_offset), float(sx), float(sy), -0.5, mode,
+                 groups, gout, B, C, D, h, w, V, gk, gs, workspace(wsb, dev), wsb)
+        need = ctx.needs_input_grad
+        return (None,) * 6 + (gk if need[6] else None,) + tuple(g if n else None for g, n in zip(gs, need[7:7 + V])) + (None,) * V
+
+
+def sweep_reduce_autograd(key_feat, src_feats, Ms, depth, mode, groups=1, pix_offset=0.0, stretch=True):
+    """Differentiable sweep_modes.sweep_reduce (same arguments, same forward bits): gradients to key_feat and src_feats through
+    mvd_sweep_reduce_backward_f32; Ms and depth are constants.  Group correlation returns a list of V volumes."""
+    srcs = views(src_feats, "src_feats")
+    out = _SweepReduce.apply(depth, mode, groups, pix_offset, stretch, len(srcs), key_feat, *srcs, *views(Ms, "Ms", len(srcs)))
+    return list(out) if mode == L.REDUCE_GROUPCORR else out
+
+
 class _FuseViews(torch.autograd.Function):
     @staticmethod
     def forward(ctx, n_views, *rest):

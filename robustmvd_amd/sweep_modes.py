@@ -7,6 +7,7 @@
                            rmvd/models/blocks/vis_mvsnet_singlestage.py:86-122,242 and blocks/utils.py:71-152
 
 Both are CUDA-only in the reference (hard `.cuda()` calls); the arithmetic is the same bilinear sweep as Path B.
+Both are differentiable w.r.t. the feature maps (sweep_reduce routes to the engine's VJP kernel when a feature requires grad).
 """
 import torch
 
@@ -14,12 +15,8 @@ from . import _lib as L
 from . import ops
 
 
-@ops.inference_only
-def sweep_reduce(key_feat, src_feats, Ms, depth, mode, groups=1, pix_offset=0.0, stretch=True):
-    """key_feat (B,C,h,w); src_feats V x (B,C,h,w); Ms V x (B,3,4) [R|t]; depth (B,D) or (B,D,h,w).
-    stretch=True: homo_warp's convention (index = X/Z * W/(W-1) - 0.5 from integer pixel positions);
-    stretch=False with pix_offset=0.5: homography_warping's (index = X/Z - 0.5 from positions x + 0.5).
-    Returns (B,C,D,h,w) for the variance modes, a list of V (B,groups,D,h,w) volumes for REDUCE_GROUPCORR."""
+def _reduce_args(key_feat, src_feats, Ms, depth, mode, groups, stretch):
+    """sweep_reduce's arguments, validated -> (kf, srcs, Ms, dv, per_pixel, (B, C, D, h, w, V), (scale_x, scale_y))."""
     kf = L.as_f32(key_feat, "key_feat")
     if kf.dim() != 4:
         raise ValueError("key_feat must be (B,C,h,w)")
@@ -38,18 +35,44 @@ def sweep_reduce(key_feat, src_feats, Ms, depth, mode, groups=1, pix_offset=0.0,
     if mode == L.REDUCE_GROUPCORR:
         if C % groups or (C // groups) % 4:
             raise ValueError(f"group correlation needs C/groups a multiple of 4, got {C}/{groups}")
-        outs = [torch.empty((B, groups, D, h, w), dtype=torch.float32, device=dev) for _ in range(V)]
     elif mode in (L.REDUCE_VARIANCE, L.REDUCE_VARIANCE_KEYSQ):
         if C % 4:
             raise ValueError(f"C={C} must be a multiple of 4")
-        outs = [torch.empty((B, C, D, h, w), dtype=torch.float32, device=dev)]
     else:
         raise ValueError(f"mode {mode}")
-    sx, sy = (w / (w - 1), h / (h - 1)) if stretch else (1.0, 1.0)
+    scale = (w / (w - 1), h / (h - 1)) if stretch else (1.0, 1.0)
+    return kf, srcs, Ms, dv, per_pixel, (B, C, D, h, w, V), scale
+
+
+@ops.inference_only
+def sweep_reduce_inference(key_feat, src_feats, Ms, depth, mode, groups=1, pix_offset=0.0, stretch=True):
+    """sweep_reduce's inference entry (mvd_sweep_reduce_f32): same arguments and result, no autograd graph; an input that
+    requires grad while autograd is recording raises (ops.inference_only)."""
+    kf, srcs, Ms, dv, per_pixel, (B, C, D, h, w, V), (sx, sy) = _reduce_args(key_feat, src_feats, Ms, depth, mode, groups, stretch)
+    dev = kf.device
+    if mode == L.REDUCE_GROUPCORR:
+        outs = [torch.empty((B, groups, D, h, w), dtype=torch.float32, device=dev) for _ in range(V)]
+    else:
+        outs = [torch.empty((B, C, D, h, w), dtype=torch.float32, device=dev)]
     wsb = L.load().mvd_sweep_reduce_workspace_bytes(B, C, h, w, V)
     ops.call("mvd_sweep_reduce_f32", dev, kf, srcs, Ms, dv, per_pixel, float(pix_offset), float(sx), float(sy), -0.5, mode, groups,
              B, C, D, h, w, V, outs, ops.workspace(wsb, dev), wsb)
     return outs if mode == L.REDUCE_GROUPCORR else outs[0]
+
+
+def sweep_reduce(key_feat, src_feats, Ms, depth, mode, groups=1, pix_offset=0.0, stretch=True):
+    """key_feat (B,C,h,w); src_feats V x (B,C,h,w); Ms V x (B,3,4) [R|t]; depth (B,D) or (B,D,h,w).
+    stretch=True: homo_warp's convention (index = X/Z * W/(W-1) - 0.5 from integer pixel positions);
+    stretch=False with pix_offset=0.5: homography_warping's (index = X/Z - 0.5 from positions x + 0.5).
+    Returns (B,C,D,h,w) for the variance modes, a list of V (B,groups,D,h,w) volumes for REDUCE_GROUPCORR.
+    Differentiable w.r.t. key_feat and src_feats like the reference's grid_sample chains: when autograd is recording and a
+    feature map requires grad the call goes through ops.sweep_reduce_autograd (the engine's VJP kernel,
+    mvd_sweep_reduce_backward_f32), otherwise through sweep_reduce_inference; the forward values are the same bits.  Ms and
+    depth are constants in both (the reference detaches its grids and depths, blocks/utils.py:97,164,181,
+    cvp_mvsnet_components.py:397, vis_mvsnet.py:124,150)."""
+    if ops.needs_grad(key_feat, src_feats):
+        return ops.sweep_reduce_autograd(key_feat, src_feats, Ms, depth, mode, groups, pix_offset, stretch)
+    return sweep_reduce_inference(key_feat, src_feats, Ms, depth, mode, groups, pix_offset, stretch)
 
 
 def _cvp_transform(ref_in, src_in, ref_ex, src_ex):
@@ -65,7 +88,8 @@ def cvp_proj_cost(ref_feature, src_features, ref_in, src_in, ref_ex, src_ex, dep
     src_feature[src][level]: pass the level's maps); ref_in (B,3,3), src_in (B,V,3,3), ref_ex (B,4,4), src_ex (B,V,4,4);
     depth_hypos (B,D) (coarse level, cvp_mvsnet.py:116-160) or (B,D,h,w) (proj_cost, refinement levels).
     reproduce_alias_bug=True gives what the reference computes (its running sum starts from the SQUARED key volume,
-    cvp_mvsnet.py:129-130 / cvp_mvsnet_components.py:393-394); False gives the variance it meant."""
+    cvp_mvsnet.py:129-130 / cvp_mvsnet_components.py:393-394); False gives the variance it meant.
+    Differentiable w.r.t. ref_feature and src_features (see sweep_reduce); the gradient follows the chosen arithmetic."""
     Ms = [_cvp_transform(ref_in, src_in[:, v], ref_ex, src_ex[:, v]) for v in range(len(src_features))]
     mode = L.REDUCE_VARIANCE_KEYSQ if reproduce_alias_bug else L.REDUCE_VARIANCE
     return sweep_reduce(ref_feature, src_features, Ms, depth_hypos, mode)
@@ -89,7 +113,8 @@ def vis_cost_volumes(ref_feat, ref_cam, srcs_feat, srcs_cam, depth_num, depth_st
     key features with the source features warped by the fronto-parallel plane homographies at
     depth_start + depth_interval * k, k = 0..depth_num-1 (cameras already scaled to the feature resolution).
     ref_cam / srcs_cam[v]: (B,2,4,4) [extrinsic; intrinsic]; depth_start, depth_interval: (B,1,1,1) or (B,1,h,w).
-    Returns a list of V volumes (B,groups,depth_num,h,w)."""
+    Returns a list of V volumes (B,groups,depth_num,h,w).  Differentiable w.r.t. ref_feat and srcs_feat (see sweep_reduce);
+    the depths are constants (vis_mvsnet.py:124,150 detach them)."""
     B, C, h, w = ref_feat.shape
     k = torch.arange(depth_num, dtype=torch.float32, device=ref_feat.device).view(1, depth_num, 1, 1)
     depth = depth_start.float() + depth_interval.float() * k  # (B,D,1,1) or (B,D,h,w)
