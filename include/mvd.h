@@ -415,6 +415,27 @@ int mvd_sweep_reduce_f32(const float* key_feat, const float* const* src_feat, co
                          int B, int C, int D, int h, int w, int V, float* const* out, void* workspace, size_t workspace_bytes,
                          mvd_stream_t stream);
 
+/* The variance modes of mvd_sweep_reduce_f32 on the layouts the engine uses between its own kernels, for CVP-MVSNet as a model
+ * (rmvd/models/cvp_mvsnet.py:125-160 coarse level, blocks/cvp_mvsnet_components.py:375-456 proj_cost):
+ *   key_feat (B,h,w,C) channel-last; src_feat[v] (B,h+3,w+3,C) channel-last, zero-bordered with the map at (1,1) (what
+ *   mvd_conv2d_split_f32 writes through its row / image strides); out (B,D,h,w,C) channel-last, what the 3-D convolutions read.
+ *   depth, M, pix_offset, scale, bias: as in mvd_sweep_reduce_f32.  mode MVD_REDUCE_VARIANCE or MVD_REDUCE_VARIANCE_KEYSQ
+ *   (MVD_REDUCE_GROUPCORR: MVD_ERR_INVALID_ARG).  C a multiple of 4 up to 64; all maps 16-byte aligned.
+ * No workspace, no repacking launches.  The arithmetic per output element is mvd_sweep_reduce_f32's operation for operation: the
+ * result is bit-identical to that entry's on the same values, permuted. */
+int mvd_sweep_reduce_nhwc_f32(const float* key_feat, const float* const* src_feat, const float* const* M, const float* depth,
+                              int depth_per_pixel, float pix_offset, float scale_x, float scale_y, float bias, int mode, int B, int C,
+                              int D, int h, int w, int V, float* out, mvd_stream_t stream);
+
+/* K5 with per-pixel hypotheses — replaces F.softmax + depth_regression_refine + the 4-bin confidence of CVPMVSNet.forward
+ *   rmvd/models/cvp_mvsnet.py:210-236, rmvd/models/blocks/cvp_mvsnet_components.py:138-141.
+ *   cost (B,D,h,w) raw regulariser output; depth_hypos (B,D,h,w);
+ *   depth_out (B,h,w) = sum_d softmax(cost)_d * depth_hypos_d
+ *   conf_out  (B,h,w) = sum_{j=idx-1..idx+2, 0<=j<D} softmax(cost)_j, idx = trunc(sum_d p_d * d)   (mvd_softmax_regress_f32's
+ * conventions).  conf_out may be NULL.  Any D >= 1; D <= 8 keeps a pixel's planes in registers (one pass over both volumes). */
+int mvd_softmax_regress_pp_f32(const float* cost, const float* depth_hypos, int B, int D, int h, int w, float* depth_out,
+                               float* conf_out, mvd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Backward of the sweep operators w.r.t. the feature maps, for the training loop
  * (rmvd/train/multi_view_depth_training.py:231-246).  The sampling grids carry no gradient (planesweep_corr.py:436,464,489;

@@ -118,6 +118,9 @@ SIGNATURES = {
     "mvd_sweep_reduce_workspace_bytes": (_sz, [_i] * 5),
     "mvd_sweep_reduce_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _i] + [ctypes.c_float] * 4 + [_i] * 8
                              + [_pp, ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "mvd_sweep_reduce_nhwc_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _i] + [ctypes.c_float] * 4 + [_i] * 7
+                                  + [_c_float_p, ctypes.c_void_p]),
+    "mvd_softmax_regress_pp_f32": (_i, [_c_float_p, _c_float_p, _i, _i, _i, _i, _c_float_p, _c_float_p, ctypes.c_void_p]),
     "mvd_sweep_reduce_backward_workspace_bytes": (_sz, [_i] * 5),
     "mvd_sweep_reduce_backward_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _i] + [ctypes.c_float] * 4 + [_i, _i, _pp] + [_i] * 6
                                       + [_c_float_p, _pp, ctypes.c_void_p, _sz, ctypes.c_void_p]),

@@ -131,7 +131,87 @@ __global__ void __launch_bounds__(256) softmax_regress_backward_kernel(const flo
     }
 }
 
+// K5 with PER-PIXEL hypotheses (CVP-MVSNet's refinement levels: F.softmax + depth_regression_refine + the 4-bin confidence,
+// rmvd/models/cvp_mvsnet.py:210-236, blocks/cvp_mvsnet_components.py:138-141): cost and depth_hypos both (B,D,h,w).
+// One lane per pixel over all D planes, lanes along the pixels (every plane row a coalesced 256-B segment per wave): D is 8 there, a
+// lane issues its 16 loads at once and the map has far more pixels than the device has lanes, so K5's split of D over four waves
+// (made for D = 128 .. 256 on few pixels) has nothing to hide here.  SMALL (D <= 8): the pixel's planes stay in registers and the
+// confidence window is taken from them, one pass over both volumes; otherwise K5's chunked online softmax, same operations and
+// conventions, and the four window planes are read again.
+template <bool SMALL>
+__global__ void __launch_bounds__(256) softmax_regress_pp_kernel(const float* __restrict__ cost, const float* __restrict__ hypos, int D,
+                                                                 long long hw, float* __restrict__ depth_out,
+                                                                 float* __restrict__ conf_out) {
+    const int b = blockIdx.y;
+    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (pix >= hw) return;
+    const float* c = cost + (long long)b * D * hw + pix;
+    const float* dh = hypos + (long long)b * D * hw + pix;
+    constexpr int CH = 8;
+    float m = -INFINITY, se = 0.f, sd = 0.f, si = 0.f;
+    float v[CH], e[CH];
+    for (int d0 = 0; d0 < D; d0 += CH) {
+        float q[CH];
+#pragma unroll
+        for (int k = 0; k < CH; ++k) {
+            const bool in = d0 + k < D;
+            v[k] = in ? c[(long long)(d0 + k) * hw] : -INFINITY;
+            q[k] = in ? dh[(long long)(d0 + k) * hw] : 0.f;
+        }
+        float cm = v[0];
+#pragma unroll
+        for (int k = 1; k < CH; ++k) cm = fmaxf(cm, v[k]);
+        if (cm > m) {
+            const float r = expf(m - cm);  // exp(-inf) = 0 on the first chunk
+            se *= r; sd *= r; si *= r;
+            m = cm;
+        }
+#pragma unroll
+        for (int k = 0; k < CH; ++k) {
+            e[k] = 0.f;
+            if (d0 + k < D) {
+                e[k] = expf(v[k] - m);
+                se += e[k];
+                sd = fmaf(e[k], q[k], sd);
+                si = fmaf(e[k], (float)(d0 + k), si);
+            }
+        }
+    }
+    depth_out[(long long)b * hw + pix] = sd / se;
+    if (!conf_out) return;
+    const int idx = (int)(si / se);  // .long(): truncation (cvp_mvsnet.py:228-233)
+    float conf = 0.f;
+    if (SMALL) {  // one chunk: e[k] = exp(c_k - M) is still in registers
+#pragma unroll
+        for (int k = 0; k < CH; ++k)
+            if (k >= idx - 1 && k <= idx + 2) conf += e[k] / se;  // planes k >= D carry e = 0
+    } else {
+#pragma unroll
+        for (int j = -1; j <= 2; ++j) {
+            const int dd = idx + j;
+            if (dd >= 0 && dd < D) conf += expf(c[(long long)dd * hw] - m) / se;
+        }
+    }
+    conf_out[(long long)b * hw + pix] = conf;
+}
+
 }  // namespace mvd
+
+extern "C" int mvd_softmax_regress_pp_f32(const float* cost, const float* depth_hypos, int B, int D, int h, int w, float* depth_out,
+                                          float* conf_out, mvd_stream_t stream) {
+    MVD_REQUIRE(cost && depth_hypos && depth_out, "softmax_regress_pp: NULL argument");
+    MVD_REQUIRE(B > 0 && D > 0 && h > 0 && w > 0 && B <= 65535, "softmax_regress_pp: bad dimension");
+    const long long hw = (long long)h * w;
+    MVD_REQUIRE((hw + 255) / 256 <= 0x7fffffffLL, "softmax_regress_pp: h*w too large");
+    dim3 grid((unsigned)((hw + 255) / 256), (unsigned)B);
+    if (D <= 8)
+        hipLaunchKernelGGL(mvd::softmax_regress_pp_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, cost, depth_hypos, D, hw, depth_out,
+                           conf_out);
+    else
+        hipLaunchKernelGGL(mvd::softmax_regress_pp_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, cost, depth_hypos, D, hw, depth_out,
+                           conf_out);
+    return mvd::launch_status("softmax_regress_pp");
+}
 
 extern "C" int mvd_softmax_regress_f32(const float* cost, const float* depth_values, int B, int D, int h, int w,
                                        float* depth_out, float* conf_out, mvd_stream_t stream) {

@@ -202,9 +202,82 @@ __global__ void __launch_bounds__(256) sweep_reduce_kernel(ReduceParams p) {
     }
 }
 
+// The variance modes on the layouts the engine uses between its own kernels (mvd_sweep_reduce_nhwc_f32): the key map dense
+// channel-last (B,h,w,C) in p.key, the source maps zero-bordered channel-last as above (a 2-D layer wrote them: no repack), the
+// volume channel-last (B,D,h,w,C) in p.out.p[0], what the 3-D convolutions read.
+// Thread = (pixel, channel quad), quad fastest, units = C / 4 quads per pixel, ppw = 256 / units pixels per workgroup (threads beyond
+// ppw * units idle when units does not divide 256).  A pixel's lanes read one tap's C floats as one run (64 B at C = 16) and thread t of
+// a workgroup stores the float4 at plane + pix0 * C + 4 t: a plane's stores of consecutive pixels leave as whole lines, without a
+// turn through LDS.  grid (ceil(h w / ppw), planes / NHWC_DPB rounded up, B): the coarse level (48 planes on a small map) fills the
+// device through the plane chunks, a refinement level (8 planes) reads its key quad once.  Arithmetic per element: the kernels' above.
+constexpr int NHWC_DPB = 8;
+
+__global__ void __launch_bounds__(256) sweep_reduce_nhwc_kernel(ReduceParams p, int units) {
+    const int h = p.h, w = p.w, C = p.C, D = p.D, V = p.V;
+    const int ppw = 256 / units;
+    const int tid = threadIdx.x, unit = tid % units, lp = tid / units;
+    const int b = blockIdx.z;
+    const long long npix = (long long)h * w, pix = (long long)blockIdx.x * ppw + lp;
+    if (lp >= ppw || pix >= npix) return;
+    const int x = (int)(pix % w), y = (int)(pix / w);
+    const int W2 = w + 3;
+    const size_t img = (size_t)(h + 3) * W2 * C;
+    const float fx = (float)x + p.pix_offset, fy = (float)y + p.pix_offset;
+    const float inv_nv = 1.0f / (float)(V + 1);
+    const int c0 = unit * 4;
+    const float4 k = *reinterpret_cast<const float4*>(p.key + ((size_t)b * npix + pix) * C + c0);
+    const int d0 = blockIdx.y * NHWC_DPB, d1 = min(D, d0 + NHWC_DPB);
+    for (int d = d0; d < d1; ++d) {
+        const float depth = p.depth_per_pixel ? p.depth[((size_t)b * D + d) * npix + pix] : p.depth[(size_t)b * D + d];
+        float4 s1, s2;
+        s2 = make_float4(k.x * k.x, k.y * k.y, k.z * k.z, k.w * k.w);
+        s1 = p.mode == MVD_REDUCE_VARIANCE_KEYSQ ? s2 : k;  // the reference's aliasing: both sums start from key^2
+        for (int v = 0; v < V; ++v) {
+            const float4 sv = reduce_sample(p, v, b, fx, fy, depth, c0, W2, img);
+            s1.x += sv.x; s1.y += sv.y; s1.z += sv.z; s1.w += sv.w;
+            s2.x = fmaf(sv.x, sv.x, s2.x); s2.y = fmaf(sv.y, sv.y, s2.y);
+            s2.z = fmaf(sv.z, sv.z, s2.z); s2.w = fmaf(sv.w, sv.w, s2.w);
+        }
+        const float mx = s1.x * inv_nv, my = s1.y * inv_nv, mz = s1.z * inv_nv, mw = s1.w * inv_nv;
+        const float4 r = make_float4(fmaf(s2.x, inv_nv, -mx * mx), fmaf(s2.y, inv_nv, -my * my), fmaf(s2.z, inv_nv, -mz * mz),
+                                     fmaf(s2.w, inv_nv, -mw * mw));
+        *reinterpret_cast<float4*>(p.out.p[0] + (((size_t)b * D + d) * npix + pix) * C + c0) = r;
+    }
+}
+
 }  // namespace mvd
 
 extern "C" {
+
+int mvd_sweep_reduce_nhwc_f32(const float* key_feat, const float* const* src_feat, const float* const* M, const float* depth,
+                              int depth_per_pixel, float pix_offset, float scale_x, float scale_y, float bias, int mode, int B, int C,
+                              int D, int h, int w, int V, float* out, mvd_stream_t stream) {
+    using namespace mvd;
+    MVD_REQUIRE(key_feat && src_feat && M && depth && out, "sweep_reduce_nhwc: NULL argument");
+    MVD_REQUIRE(B > 0 && B <= 65535 && D > 0 && h > 1 && w > 1 && V >= 1 && V <= MVD_MAX_VIEWS, "sweep_reduce_nhwc: bad dimensions");
+    MVD_REQUIRE(C >= 4 && C <= 64 && C % 4 == 0, "sweep_reduce_nhwc: C=%d must be a multiple of 4 up to 64", C);
+    MVD_REQUIRE(mode == MVD_REDUCE_VARIANCE || mode == MVD_REDUCE_VARIANCE_KEYSQ, "sweep_reduce_nhwc: mode %d (the variance modes only)", mode);
+    MVD_REQUIRE((((uintptr_t)key_feat | (uintptr_t)out) & 15) == 0, "sweep_reduce_nhwc: key_feat and out must be 16-byte aligned");
+    ReduceParams p{};
+    for (int v = 0; v < V; ++v) {
+        MVD_REQUIRE(src_feat[v] && M[v], "sweep_reduce_nhwc: NULL view %d", v);
+        MVD_REQUIRE(((uintptr_t)src_feat[v] & 15) == 0, "sweep_reduce_nhwc: src_feat[%d] must be 16-byte aligned", v);
+        p.src.p[v] = src_feat[v];
+        p.M.p[v] = M[v];
+    }
+    p.key = key_feat;
+    p.out.p[0] = out;
+    p.depth = depth; p.depth_per_pixel = depth_per_pixel;
+    p.pix_offset = pix_offset; p.scale_x = scale_x; p.scale_y = scale_y; p.bias = bias;
+    p.mode = mode; p.groups = 1;
+    p.B = B; p.C = C; p.D = D; p.h = h; p.w = w; p.V = V;
+    const int units = C / 4, ppw = 256 / units;
+    const long long nbx = ((long long)h * w + ppw - 1) / ppw;
+    const int nby = (D + NHWC_DPB - 1) / NHWC_DPB;
+    MVD_REQUIRE(nbx <= 0x7fffffffLL && nby <= 65535, "sweep_reduce_nhwc: grid too large");
+    hipLaunchKernelGGL(sweep_reduce_nhwc_kernel, dim3((unsigned)nbx, (unsigned)nby, (unsigned)B), dim3(256), 0, (hipStream_t)stream, p, units);
+    return launch_status("sweep_reduce_nhwc");
+}
 
 size_t mvd_sweep_reduce_workspace_bytes(int B, int C, int h, int w, int V) {
     if (B <= 0 || C <= 0 || h <= 0 || w <= 0 || V < 0) return 0;

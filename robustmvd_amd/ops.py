@@ -537,6 +537,51 @@ def softmax_regress(cost, depth_values, with_confidence=True):
     return depth, conf
 
 
+@inference_only
+def softmax_regress_pp(cost, depth_hypos, with_confidence=True):
+    """K5 with per-pixel hypotheses (CVP-MVSNet's refinement levels). cost (B,D,h,w); depth_hypos (B,D,h,w) -> depth (B,h,w),
+    confidence (B,h,w) or None; softmax_regress's conventions."""
+    c = L.as_f32(cost, "cost")
+    if c.dim() != 4:
+        raise ValueError("cost must be (B,D,h,w)")
+    B, D, h, w = c.shape
+    dh = L.as_f32(depth_hypos, "depth_hypos", (B, D, h, w), c.device)
+    depth = torch.empty((B, h, w), dtype=torch.float32, device=c.device)
+    conf = torch.empty((B, h, w), dtype=torch.float32, device=c.device) if with_confidence else None
+    call("mvd_softmax_regress_pp_f32", c.device, c, dh, B, D, h, w, depth, conf)
+    return depth, conf
+
+
+@inference_only
+def sweep_reduce_nhwc(key_feat, src_feats, Ms, depth, mode, pix_offset=0.0, stretch=True):
+    """The variance modes of sweep_modes.sweep_reduce on the engine's own layouts, without repacking: key_feat (B,h,w,C) channel-last;
+    src_feats V x (B,h+3,w+3,C) channel-last, zero-bordered with the map at (1,1) (what conv2d_split writes with
+    out=buf[:, 1:h+1, 1:w+1, :]); Ms V x (B,3,4) [R|t]; depth (B,D) or (B,D,h,w); mode REDUCE_VARIANCE or REDUCE_VARIANCE_KEYSQ.
+    Returns the volume (B,D,h,w,C) channel-last, bit-identical to sweep_reduce's (B,C,D,h,w) permuted."""
+    if mode not in (L.REDUCE_VARIANCE, L.REDUCE_VARIANCE_KEYSQ):
+        raise ValueError(f"sweep_reduce_nhwc: mode {mode} (the variance modes only)")
+    kf = L.as_f32(key_feat, "key_feat")
+    if kf.dim() != 4 or kf.shape[3] % 4 or kf.shape[3] > 64:
+        raise ValueError(f"key_feat must be (B,h,w,C) channel-last with C a multiple of 4 up to 64, got {tuple(kf.shape)}")
+    B, h, w, C = kf.shape
+    dev = kf.device
+    srcs = [L.as_f32(s, f"src_feats[{i}]", (B, h + 3, w + 3, C), dev) for i, s in enumerate(views(src_feats, "src_feats"))]
+    V = len(srcs)
+    Ms = [L.as_f32(m, f"Ms[{i}]", (B, 3, 4), dev) for i, m in enumerate(views(Ms, "Ms", V))]
+    dv = L.as_f32(depth, "depth", device=dev)
+    if dv.dim() == 2 and dv.shape[0] == B:
+        per_pixel, D = 0, dv.shape[1]
+    elif dv.dim() == 4 and dv.shape[0] == B and tuple(dv.shape[2:]) == (h, w):
+        per_pixel, D = 1, dv.shape[1]
+    else:
+        raise ValueError(f"depth must be (B,D) or (B,D,h,w), got {tuple(dv.shape)}")
+    sx, sy = (w / (w - 1), h / (h - 1)) if stretch else (1.0, 1.0)
+    out = torch.empty((B, D, h, w, C), dtype=torch.float32, device=dev)
+    call("mvd_sweep_reduce_nhwc_f32", dev, kf, srcs, Ms, dv, per_pixel, float(pix_offset), float(sx), float(sy), -0.5, mode,
+         B, C, D, h, w, V, out)
+    return out
+
+
 class SplitConv2dWeights:
     """Packed split-operand weights of one 2-D layer (pack_conv2d_weights_split) with what conv2d_split needs to call it."""
     __slots__ = ("packed", "bias", "cin", "cin_pad", "cout", "kh", "kw", "stride", "mode")

@@ -75,12 +75,14 @@ def sweep_reduce(key_feat, src_feats, Ms, depth, mode, groups=1, pix_offset=0.0,
     return sweep_reduce_inference(key_feat, src_feats, Ms, depth, mode, groups, pix_offset, stretch)
 
 
-def _cvp_transform(ref_in, src_in, ref_ex, src_ex):
-    """cvp_mvsnet_components.py:201-210: proj = [K_s E_s[:3]; 0 0 0 1] @ inverse([K_r E_r[:3]; 0 0 0 1]) -> (B,3,4)."""
+def _cvp_transform(ref_in, src_in, ref_ex, src_ex, check_errors=True):
+    """cvp_mvsnet_components.py:201-210: proj = [K_s E_s[:3]; 0 0 0 1] @ inverse([K_r E_r[:3]; 0 0 0 1]) -> (B,3,4).
+    check_errors=False: the inverse without its singularity check, which synchronises with the host (the cvp_mvsnet model's forward)."""
     last = torch.tensor([[[0.0, 0.0, 0.0, 1.0]]], dtype=torch.float32, device=ref_in.device).repeat(ref_in.shape[0], 1, 1)
     src_proj = torch.cat((torch.matmul(src_in.float(), src_ex.float()[:, 0:3, :]), last), 1)
     ref_proj = torch.cat((torch.matmul(ref_in.float(), ref_ex.float()[:, 0:3, :]), last), 1)
-    return torch.matmul(src_proj, torch.inverse(ref_proj))[:, :3, :4].contiguous()
+    inv = torch.inverse(ref_proj) if check_errors else torch.linalg.inv_ex(ref_proj, check_errors=False).inverse
+    return torch.matmul(src_proj, inv)[:, :3, :4].contiguous()
 
 
 def cvp_proj_cost(ref_feature, src_features, ref_in, src_in, ref_ex, src_ex, depth_hypos, reproduce_alias_bug=True):
