@@ -11,6 +11,7 @@
 // kernel at full size (profiles/mvsnet_train_step.txt), where the scatter runs at the chip's float-atomic rate and is the largest
 // stage of a step; warp_variance_backward_gather.hip is the same VJP as a gather, without atomics and bit-reproducible, and uses
 // this file's kernel (FLAGGED) for the views its window cannot cover.  K1's and K2's kernels favour simplicity over speed.
+#include "sweep_epipolar.h"
 #include "warp_variance_backward_common.h"
 
 namespace mvd {
@@ -48,16 +49,12 @@ __global__ void __launch_bounds__(256) warp_variance_backward_kernel(WarpBwdPara
     const size_t self = ((size_t)(y + 1) * W2 + (x + 1)) * C + q * 4;
     const float4 k = *reinterpret_cast<const float4*>(p.key + b * img + self);
 
-    using Loc = BwdLoc;
     auto locate = [&](int v, float depth) {
-        return bwd_locate(p.M + ((size_t)v * p.B + b) * 12, fx, fy, depth, sx, sy, xhi, yhi, W2, C, q);
+        return sample_cell(sample_position_rcp(p.M + ((size_t)v * p.B + b) * 12, fx, fy, depth, sx, sy, xhi, yhi), W2, C, q * 4);
     };
-    auto sample = [&](const float* __restrict__ f, const Loc& L) { return bwd_sample(f, L, W2, C); };
 
-    // Planes in chunks of BWD_DZ: the chunk's means stay in registers, then each view walks the chunk with ONE pending 2 x 2 cell of
-    // tap gradients in registers: consecutive planes of a pixel mostly sample the same source cell (the forward kernel's tap
-    // reuse), so the four taps' shares are summed in registers and go out as atomics only when the cell changes (and at the end
-    // of the chunk) — about 2.5x fewer atomics at the headline poses.
+    // Planes in chunks of DZ: the chunk's means stay in registers, then each view walks the chunk with one PendingCell of tap
+    // gradients in registers.
     constexpr int DZ = 8;
     const float c2 = 2.0f * inv_nv;
     float4 gk = make_float4(0, 0, 0, 0);
@@ -72,7 +69,7 @@ __global__ void __launch_bounds__(256) warp_variance_backward_kernel(WarpBwdPara
             const float4 g = *reinterpret_cast<const float4*>(p.gvar + ((((size_t)b * D + d) * h + y) * w + x) * C + q * 4);
             float4 sum = k;
             for (int v = 0; v < V; ++v) {
-                const float4 xv = sample(p.src.p[v] + b * img, locate(v, depth));
+                const float4 xv = sample_blend(p.src.p[v] + b * img, locate(v, depth), W2, C);
                 sum.x += xv.x; sum.y += xv.y; sum.z += xv.z; sum.w += xv.w;
             }
             mean[dd] = make_float4(sum.x * inv_nv, sum.y * inv_nv, sum.z * inv_nv, sum.w * inv_nv);
@@ -86,118 +83,27 @@ __global__ void __launch_bounds__(256) warp_variance_backward_kernel(WarpBwdPara
             }
             const float* __restrict__ f = p.src.p[v] + b * img;
             float* __restrict__ gv = p.gsrc.p[v] + b * img;
-            constexpr size_t NONE = ~(size_t)0;
-            size_t pend = NONE;
-            float4 t00 = make_float4(0, 0, 0, 0), t10 = t00, t01 = t00, t11 = t00;
-            auto flush = [&]() {
-                float* go = gv + pend;
-                atomic_add4(go, t00);
-                atomic_add4(go + C, t10);
-                atomic_add4(go + (size_t)W2 * C, t01);
-                atomic_add4(go + (size_t)W2 * C + C, t11);
-            };
+            PendingCell pend(W2, C);
 #pragma unroll
             for (int dd = 0; dd < DZ; ++dd) {
                 const int d = d0 + dd;
                 if (d >= D) continue;
-                const Loc L = locate(v, p.depth[(size_t)b * D + d]);
-                const float4 xv = sample(f, L);
-                const float4 gx = make_float4(gs[dd].x * (xv.x - mean[dd].x), gs[dd].y * (xv.y - mean[dd].y),
-                                              gs[dd].z * (xv.z - mean[dd].z), gs[dd].w * (xv.w - mean[dd].w));
-                if (L.o != pend) {
-                    if (pend != NONE) flush();
-                    pend = L.o;
-                    t00 = make_float4(gx.x * L.w00, gx.y * L.w00, gx.z * L.w00, gx.w * L.w00);
-                    t10 = make_float4(gx.x * L.w10, gx.y * L.w10, gx.z * L.w10, gx.w * L.w10);
-                    t01 = make_float4(gx.x * L.w01, gx.y * L.w01, gx.z * L.w01, gx.w * L.w01);
-                    t11 = make_float4(gx.x * L.w11, gx.y * L.w11, gx.z * L.w11, gx.w * L.w11);
-                } else {
-                    t00.x = fmaf(gx.x, L.w00, t00.x); t00.y = fmaf(gx.y, L.w00, t00.y); t00.z = fmaf(gx.z, L.w00, t00.z); t00.w = fmaf(gx.w, L.w00, t00.w);
-                    t10.x = fmaf(gx.x, L.w10, t10.x); t10.y = fmaf(gx.y, L.w10, t10.y); t10.z = fmaf(gx.z, L.w10, t10.z); t10.w = fmaf(gx.w, L.w10, t10.w);
-                    t01.x = fmaf(gx.x, L.w01, t01.x); t01.y = fmaf(gx.y, L.w01, t01.y); t01.z = fmaf(gx.z, L.w01, t01.z); t01.w = fmaf(gx.w, L.w01, t01.w);
-                    t11.x = fmaf(gx.x, L.w11, t11.x); t11.y = fmaf(gx.y, L.w11, t11.y); t11.z = fmaf(gx.z, L.w11, t11.z); t11.w = fmaf(gx.w, L.w11, t11.w);
-                }
+                const SampleCell L = locate(v, p.depth[(size_t)b * D + d]);
+                const float4 xv = sample_blend(f, L, W2, C);
+                pend.add(gv, L, make_float4(gs[dd].x * (xv.x - mean[dd].x), gs[dd].y * (xv.y - mean[dd].y),
+                                            gs[dd].z * (xv.z - mean[dd].z), gs[dd].w * (xv.w - mean[dd].w)));
             }
-            if (pend != NONE) flush();
+            pend.flush(gv);
         }
     }
     if constexpr (!FLAGGED) *reinterpret_cast<float4*>(p.gkey + b * img + self) = gk;
 }
 
-__global__ void compose_transforms_bwd_kernel(ViewPtrs proj, const float* __restrict__ key_proj_inv, int B, int V, float* __restrict__ M) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= V * B * 12) return;
-    const int j = e % 4, i = (e / 4) % 3, b = (e / 12) % B, v = e / (12 * B);
-    const float* P = proj.p[v] + b * 16;
-    const float* Q = key_proj_inv + b * 16;
-    float acc = P[i * 4 + 0] * Q[0 * 4 + j];  // the same fmaf chain as the forward's compose_transforms_kernel
-    acc = fmaf(P[i * 4 + 1], Q[1 * 4 + j], acc);
-    acc = fmaf(P[i * 4 + 2], Q[2 * 4 + j], acc);
-    acc = fmaf(P[i * 4 + 3], Q[3 * 4 + j], acc);
-    M[e] = acc;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // K1 backward.  One wave per key pixel, lane = channel slice (C = 64 NJ), loops over views and planes; geometry (the
-// forward's own operation chain: it decides the 0/1 mask) is evaluated by lane = plane in passes of 64 and broadcast
+// forward's own functions, sweep_epipolar.h: they decide the 0/1 mask) is evaluated by lane = plane in passes of 64 and broadcast
 // with readlane.  Consecutive planes that share a 2x2 source cell accumulate their tap gradients in registers and
 // flush them with atomics when the cell changes (~4x fewer atomics).
-struct Epi { float a, b, c, e, f, g, h, i, j, k, l, m; };
-__device__ __forceinline__ Epi epipolar_b(const float* __restrict__ Kk, const float* __restrict__ Ks, const float* __restrict__ T,
-                                          int h, int w, int hs, int ws) {
-    const float fx = Kk[0] * (float)w, fy = Kk[4] * (float)h, cx = Kk[2] * (float)w, cy = Kk[5] * (float)h;
-    const float fxo = Ks[0] * (float)ws, fyo = Ks[4] * (float)hs, cxo = Ks[2] * (float)ws, cyo = Ks[5] * (float)hs;
-    const float r11 = T[0], r12 = T[1], r13 = T[2], t1 = T[3], r21 = T[4], r22 = T[5], r23 = T[6], t2 = T[7];
-    const float r31 = T[8], r32 = T[9], r33 = T[10], t3 = T[11];
-    Epi E;
-    const float A = fxo * r11 + cxo * r31, Bq = fxo * r12 + cxo * r32;
-    E.a = A / fx; E.b = Bq / fy;
-    E.c = -(cx * A / fx) - (cy * Bq / fy) + (fxo * r13 + cxo * r33);
-    E.e = fxo * t1 + cxo * t3;
-    const float F = fyo * r21 + cyo * r31, G = fyo * r22 + cyo * r32;
-    E.f = F / fx; E.g = G / fy;
-    E.h = -(cx * F / fx) - (cy * G / fy) + (fyo * r23 + cyo * r33);
-    E.i = fyo * t2 + cyo * t3;
-    E.j = r31 / fx; E.k = r32 / fy;
-    E.l = -cx * r31 / fx - cy * r32 / fy + r33;
-    E.m = t3;
-    return E;
-}
-__device__ __forceinline__ float fix_nonfinite(float v) {
-    if (isinf(v)) return v > 0.f ? 1e9f : -1e9f;
-    if (isnan(v)) return 1e9f;
-    return v;
-}
-
-// What a key pixel's ray needs per source view, and per plane the sampled 2x2 cell: the forward's operation chain, shared by the
-// K1 backward and the warp-only backward (the callers form their own 0/1 mask from `t.inb` and `visible`).
-struct SweepRay { Epi E; float u_inf, v_inf, k_inf, z_pole; };
-__device__ __forceinline__ SweepRay sweep_bwd_ray(const float* __restrict__ Kk, const float* __restrict__ Ks, const float* __restrict__ T,
-                                                  int h, int w, int hs, int ws, float xc, float yc) {
-    SweepRay R;
-    R.E = epipolar_b(Kk, Ks, T, h, w, hs, ws);
-    R.u_inf = (R.E.a * xc + R.E.b * yc) + R.E.c; R.v_inf = (R.E.f * xc + R.E.g * yc) + R.E.h; R.k_inf = (R.E.j * xc + R.E.k * yc) + R.E.l;
-    R.z_pole = -(R.E.m / R.k_inf);
-    return R;
-}
-struct SweepCell { Taps t; int cell; bool visible; };  // cell: index of the top-left tap in the zero-bordered map, W2 = ws + 3 wide
-__device__ __forceinline__ SweepCell sweep_bwd_cell(const SweepRay& R, float ds, int hs, int ws, int W2) {
-    const Epi& E = R.E;
-    const float fws = (float)ws, fhs = (float)hs;
-    const float den = R.k_inf + E.m * ds;
-    const float us = fix_nonfinite((R.u_inf + E.e * ds) / den), vs = fix_nonfinite((R.v_inf + E.i * ds) / den);
-    const float zs = 1.0f / ds;
-    SweepCell G;
-    G.visible = (zs > 0.f) && (((R.k_inf > 0.f) && (zs > R.z_pole)) || ((R.k_inf < 0.f) && (zs < R.z_pole)) ||
-                               ((R.k_inf == 0.f) && (E.m > 0.f)));
-    const float ix = unnormalize_coord(2.0f * us / fws - 1.0f, fws), iy = unnormalize_coord(2.0f * vs / fhs - 1.0f, fhs);
-    G.t = bilinear_taps(ix, iy, hs, ws);
-    const int cx = (int)fminf(fmaxf(floorf(ix), -1.0f), (float)(ws - 1)) + 1;
-    const int cy = (int)fminf(fmaxf(floorf(iy), -1.0f), (float)(hs - 1)) + 1;
-    G.cell = cy * W2 + cx;
-    return G;
-}
-
 struct SweepBwdParams {
     ViewPtrs src;        // V x (N,hs+3,ws+3,C) zero-bordered channel-last source features
     ViewPtrs K_src, T;   // V x (N,3,3), V x (N,4,4)
@@ -230,7 +136,8 @@ __global__ void __launch_bounds__(256) sweep_corr_backward_kernel(SweepBwdParams
     for (int j = 0; j < NJ; ++j) { kf[j] = p.key[koff + j]; gk[j] = 0.f; }
 
     for (int v = 0; v < p.V; ++v) {
-        const SweepRay R = sweep_bwd_ray(p.K_key + n * 9, p.K_src.p[v] + n * 9, p.T.p[v] + n * 16, h, w, hs, ws, xc, yc);
+        const Epi E = epipolar(p.K_key + n * 9, p.K_src.p[v] + n * 9, p.T.p[v] + n * 16, h, w, hs, ws);
+        const SweepRay R = sweep_ray(E, xc, yc);
         const size_t simg = (size_t)n * (hs + 3) * W2 * C;
         const float* __restrict__ src = p.src.p[v] + simg + lane * NJ;
         float* __restrict__ gsrc = p.gsrc.p[v] + simg + lane * NJ;
@@ -251,9 +158,9 @@ __global__ void __launch_bounds__(256) sweep_corr_backward_kernel(SweepBwdParams
             const bool live = s < S;
             const int sc = live ? s : S - 1;
             const float ds = p.invd_per_pixel ? p.invd[(((size_t)n * S + sc) * h + y) * w + x] : invd[sc];
-            const SweepCell G = sweep_bwd_cell(R, ds, hs, ws, W2);
+            const SweepSample G = sweep_sample(E, R, ds, hs, ws, W2);
             const Taps& t = G.t;
-            const float mk = (t.inb < 0.9999f || !G.visible) ? 0.f : 1.f;
+            const float mk = sweep_corr_mask(G);
             const int cell = G.cell;
             const float gcoef = live ? gc[(size_t)s * h * w] * mk * inv_sqrt_c : 0.f;
             const int npl = min(64, S - s0);
@@ -320,7 +227,8 @@ __global__ void __launch_bounds__(256) sweep_warp_backward_kernel(WarpOnlyBwdPar
     const float* __restrict__ invd = p.invd + (size_t)n * p.invd_stride;
 
     for (int v = 0; v < p.V; ++v) {
-        const SweepRay R = sweep_bwd_ray(p.K_key + n * 9, p.K_src.p[v] + n * 9, p.T.p[v] + n * 16, h, w, hs, ws, xc, yc);
+        const Epi E = epipolar(p.K_key + n * 9, p.K_src.p[v] + n * 9, p.T.p[v] + n * 16, h, w, hs, ws);
+        const SweepRay R = sweep_ray(E, xc, yc);
         float* __restrict__ gsrc = p.gsrc.p[v] + (size_t)n * (hs + 3) * W2 * C;
         const float* __restrict__ gw = p.gwarp.p[v] + (size_t)n * S * C * hw + (size_t)y * w + x;
         int cur = -1;
@@ -342,8 +250,8 @@ __global__ void __launch_bounds__(256) sweep_warp_backward_kernel(WarpOnlyBwdPar
             const bool live = s < S;
             const int sc = live ? s : S - 1;
             const float ds = p.invd_per_pixel ? p.invd[(((size_t)n * S + sc) * h + y) * w + x] : invd[sc];
-            const SweepCell G = sweep_bwd_cell(R, ds, hs, ws, W2);
-            const float mk = (live && !(G.t.inb < 0.9999f)) ? 1.f : 0.f;
+            const SweepSample G = sweep_sample(E, R, ds, hs, ws, W2);
+            const float mk = live ? sweep_warp_mask(G) : 0.f;
             const int npl = min(64, S - s0);
             for (int i = 0; i < npl; ++i) {  // wave-uniform
                 const float mki = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mk), i));
@@ -424,11 +332,6 @@ __global__ void __launch_bounds__(256) fuse_views_backward_kernel(FuseBwdParams 
         for (int v = 0; v < V; ++v) p.gscore.p[v][n * hw + pix] = pr[v] * (dp[v] - dot);
 }
 
-void launch_compose_transforms_bwd(const ViewPtrs& proj, const float* key_proj_inv, int B, int V, float* M, hipStream_t st) {
-    hipLaunchKernelGGL(compose_transforms_bwd_kernel, dim3((unsigned)((V * B * 12 + 255) / 256)), dim3(256), 0, st, proj, key_proj_inv,
-                       B, V, M);
-}
-
 void launch_warp_variance_backward_flagged(const WarpBwdParams& p, hipStream_t st) {
     const long long nthr = (long long)p.B * p.h * p.w * (p.C / 4);
     hipLaunchKernelGGL(warp_variance_backward_kernel<true>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, p);
@@ -469,8 +372,7 @@ int mvd_warp_variance_backward_f32(const float* key_feat, const float* const* sr
     }
     if (hipMemsetAsync(grad_key, 0, slot, st) != hipSuccess) return launch_status("warp_variance_backward: memset");
     p.M = (float*)workspace;
-    hipLaunchKernelGGL(compose_transforms_bwd_kernel, dim3((unsigned)((V * B * 12 + 255) / 256)), dim3(256), 0, st, proj,
-                       key_proj_inv, B, V, (float*)workspace);
+    launch_compose_transforms(proj, key_proj_inv, B, V, (float*)workspace, st);
     p.key = key_feat; p.gkey = grad_key; p.depth = depth_values; p.gvar = grad_var;
     p.B = B; p.C = C; p.D = D; p.h = h; p.w = w; p.V = V;
     const long long nthr = (long long)B * h * w * (C / 4), nblk = (nthr + 255) / 256;

@@ -65,6 +65,10 @@ struct ViewOutPtrs {
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// M[v][b] = rows 0..2 of src_proj[v][b] @ key_proj_inv[b] into M (V,B,12): the one compose kernel (warp_variance.hip) of K3's
+// forward and both of its backward forms
+void launch_compose_transforms(const ViewPtrs& proj, const float* key_proj_inv, int B, int V, float* M, hipStream_t st);
+
 // Kernel-variant selectors for experiments.  The PRODUCT library (default build) has fixed dispatch and never reads
 // the process environment (include/mvd.h: no global mutable state): exp_env() is a constant nullptr there and every
 // `if (exp_env(...))` branch folds away.  Only the -DMVD_EXPERIMENTS build (`make exp` -> robustmvd_amd/lib_exp/

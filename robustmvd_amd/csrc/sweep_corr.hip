@@ -17,7 +17,7 @@
 // per distinct cell (~60 per pixel and view at 96x144x256 planes) instead of per plane (256).
 // HBM traffic is the feature maps in and 2*V*S*h*w floats out; the kernel is bound by L1 gather bandwidth and
 // vector ALU, not HBM.  Results are staged in LDS and written as 64-B row segments.
-#include "mvd_common.h"
+#include "sweep_epipolar.h"
 
 namespace mvd {
 
@@ -40,43 +40,6 @@ struct SweepParams {
 };
 
 constexpr int SWEEP_PX = 16;  // key pixels per workgroup
-
-// EpipolarCoeffs.from_calib (planesweep_corr.py:262-291): 12 scalars per (view, batch element)
-struct Epi {
-    float a, b, c, e, f, g, h, i, j, k, l, m;
-};
-
-__device__ __forceinline__ Epi epipolar(const float* __restrict__ Kk, const float* __restrict__ Ks,
-                                        const float* __restrict__ T, int h, int w, int hs, int ws) {
-    const float fx = Kk[0] * (float)w, fy = Kk[4] * (float)h, cx = Kk[2] * (float)w, cy = Kk[5] * (float)h;
-    const float fxo = Ks[0] * (float)ws, fyo = Ks[4] * (float)hs, cxo = Ks[2] * (float)ws, cyo = Ks[5] * (float)hs;
-    const float r11 = T[0], r12 = T[1], r13 = T[2], t1 = T[3];
-    const float r21 = T[4], r22 = T[5], r23 = T[6], t2 = T[7];
-    const float r31 = T[8], r32 = T[9], r33 = T[10], t3 = T[11];
-    Epi E;
-    const float A = fxo * r11 + cxo * r31, B = fxo * r12 + cxo * r32;
-    E.a = A / fx;
-    E.b = B / fy;
-    E.c = -(cx * A / fx) - (cy * B / fy) + (fxo * r13 + cxo * r33);
-    E.e = fxo * t1 + cxo * t3;
-    const float F = fyo * r21 + cyo * r31, G = fyo * r22 + cyo * r32;
-    E.f = F / fx;
-    E.g = G / fy;
-    E.h = -(cx * F / fx) - (cy * G / fy) + (fyo * r23 + cyo * r33);
-    E.i = fyo * t2 + cyo * t3;
-    E.j = r31 / fx;
-    E.k = r32 / fy;
-    E.l = -cx * r31 / fx - cy * r32 / fy + r33;
-    E.m = t3;
-    return E;
-}
-
-__device__ __forceinline__ float replace_nonfinite(float v) {
-    // us[isinf] = 1e9*sign(us); us[isnan] = 1e9 (planesweep_corr.py:336-338)
-    if (isinf(v)) return v > 0.f ? 1e9f : -1e9f;
-    if (isnan(v)) return 1e9f;
-    return v;
-}
 
 // sum of 4 values over the 64 lanes with 7 shuffles: after two select+exchange steps lane l holds a partial of value
 // (l & 3), four butterfly steps finish it; value k is read back from lane k.
@@ -148,18 +111,12 @@ __global__ void __launch_bounds__(256) sweep_corr_kernel(SweepParams p) {
     const float* __restrict__ src = p.src.p[v] + (size_t)n * (hs + 3) * W2 * C + lane * NJ;
     const float* __restrict__ invd = p.invd + (size_t)n * p.invd_stride;
     const float inv_sqrt_c = p.corr_scale;
-    const float fws = (float)ws, fhs = (float)hs;
     const float yc = (float)y + 0.5f;
 
     for (int pi = wave; pi < SWEEP_PX; pi += 4) {
         const int x = x0 + pi;
         if (x >= w) break;  // wave-uniform
-        const float xc = (float)x + 0.5f;
-        // u_infs_h = a*x + b*y + c etc. (planesweep_corr.py:277-290), one rounding per operation
-        const float u_inf = (E.a * xc + E.b * yc) + E.c;
-        const float v_inf = (E.f * xc + E.g * yc) + E.h;
-        const float k_inf = (E.j * xc + E.k * yc) + E.l;
-        const float z_pole = -(E.m / k_inf);  // :330
+        const SweepRay R = sweep_ray(E, (float)x + 0.5f, yc);
 
         float kf[NJ];
         const float* kp = p.key + (((size_t)n * h + y) * w + x) * C + lane * NJ;
@@ -172,23 +129,10 @@ __global__ void __launch_bounds__(256) sweep_corr_kernel(SweepParams p) {
             const bool live = s < S;
             const int sc = live ? s : S - 1;
             const float ds = p.invd_per_pixel ? p.invd[(((size_t)n * S + sc) * h + y) * w + x] : invd[sc];
-            const float den = k_inf + E.m * ds;
-            const float us = replace_nonfinite((u_inf + E.e * ds) / den);  // :334
-            const float vs = replace_nonfinite((v_inf + E.i * ds) / den);  // :343
-            const float zs = 1.0f / ds;                                      // :492
-            const bool visible = (zs > 0.f) && (((k_inf > 0.f) && (zs > z_pole)) || ((k_inf < 0.f) && (zs < z_pole)) ||
-                                               ((k_inf == 0.f) && (E.m > 0.f)));  // :499-506
-            // warp(): grid = 2*u/w_x - 1 (:87-88), then grid_sample's unnormalisation
-            const float ix = unnormalize_coord(2.0f * us / fws - 1.0f, fws);
-            const float iy = unnormalize_coord(2.0f * vs / fhs - 1.0f, fhs);
-            const Taps t = bilinear_taps(ix, iy, hs, ws);  // weights are 0 on out-of-image taps
-            // mask[mask < 0.9999] = 0; mask[mask > 0] = 1 (:101-102), times the visibility mask (:191-193)
-            const float mk = (t.inb < 0.9999f || !visible) ? 0.f : 1.f;
-            // 2x2 cell in the zero-bordered copy; a cell entirely outside the image has all-zero weights, so which
-            // (valid) cell stands in for it does not matter
-            const int cx = (int)fminf(fmaxf(floorf(ix), -1.0f), (float)(ws - 1)) + 1;
-            const int cy = (int)fminf(fmaxf(floorf(iy), -1.0f), (float)(hs - 1)) + 1;
-            const int cell = live ? cy * W2 + cx : -1;
+            const SweepSample G = sweep_sample(E, R, ds, hs, ws, W2);
+            const Taps& t = G.t;
+            const float mk = sweep_corr_mask(G);
+            const int cell = live ? G.cell : -1;
 
             // ---- distinct cells of this pass ----
             const int prev = __shfl_up(cell, 1);
@@ -280,7 +224,7 @@ __global__ void __launch_bounds__(256) sweep_corr_kernel(SweepParams p) {
 // The kernel above takes the 2 x 2 cell of every distinct sampling position on its own: neighbouring cells along the epipolar line
 // share two of their four pixels, so nearly half of its gathers and dot products are repeats (profiles/k1_pmc.json: texture
 // addresser 65 % busy, 13.6 GB through the L1 for 184 MB of algorithmic input).  Here, per key pixel (one wave) and 64 planes:
-//   1. lanes = planes: sampling position, bilinear weights, mask, cell (as above; same arithmetic, same values);
+//   1. lanes = planes: sampling position, bilinear weights, mask, cell (sweep_epipolar.h, as above);
 //   2. the distinct cells, in ray order, are compacted (ballot + prefix count) so that lanes = cells;
 //   3. every cell decides in closed form which of its 4 pixels the one or two cells before it already hold (a pixel lies in at most
 //      three consecutive cells of a monotone path; a longer chain just loads it again) and the new pixels get consecutive places
@@ -328,18 +272,13 @@ __global__ void __launch_bounds__(256) sweep_corr_px_kernel(SweepParams p) {
     const float* __restrict__ src = p.src.p[v] + (size_t)n * (hs + 3) * W2 * C + cg * 4;
     const float* __restrict__ invd = p.invd + (size_t)n * p.invd_stride;
     const float inv_sqrt_c = p.corr_scale;
-    const float fws = (float)ws, fhs = (float)hs;
     const float yc = (float)y + 0.5f;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
 
     for (int pi = wave; pi < SWEEP_PX; pi += 4) {
         const int x = x0 + pi;
         if (x >= w) break;  // wave-uniform
-        const float xc = (float)x + 0.5f;
-        const float u_inf = (E.a * xc + E.b * yc) + E.c;
-        const float v_inf = (E.f * xc + E.g * yc) + E.h;
-        const float k_inf = (E.j * xc + E.k * yc) + E.l;
-        const float z_pole = -(E.m / k_inf);
+        const SweepRay R = sweep_ray(E, (float)x + 0.5f, yc);
 
         float kf[NCH];
         const float* kp = p.key + (((size_t)n * h + y) * w + x) * C + cg * 4;
@@ -350,24 +289,15 @@ __global__ void __launch_bounds__(256) sweep_corr_px_kernel(SweepParams p) {
         }
 
         for (int s0 = 0; s0 < S; s0 += 64) {
-            // ---- 1. geometry of plane s0 + lane (the arithmetic of sweep_corr_kernel) ----
+            // ---- 1. geometry of plane s0 + lane ----
             const int s = s0 + lane;
             const bool live = s < S;
             const int sc = live ? s : S - 1;
             const float ds = p.invd_per_pixel ? p.invd[(((size_t)n * S + sc) * h + y) * w + x] : invd[sc];
-            const float den = k_inf + E.m * ds;
-            const float us = replace_nonfinite((u_inf + E.e * ds) / den);
-            const float vs = replace_nonfinite((v_inf + E.i * ds) / den);
-            const float zs = 1.0f / ds;
-            const bool visible = (zs > 0.f) && (((k_inf > 0.f) && (zs > z_pole)) || ((k_inf < 0.f) && (zs < z_pole)) ||
-                                               ((k_inf == 0.f) && (E.m > 0.f)));
-            const float ix = unnormalize_coord(2.0f * us / fws - 1.0f, fws);
-            const float iy = unnormalize_coord(2.0f * vs / fhs - 1.0f, fhs);
-            const Taps t = bilinear_taps(ix, iy, hs, ws);
-            const float mk = (t.inb < 0.9999f || !visible) ? 0.f : 1.f;
-            const int cx = (int)fminf(fmaxf(floorf(ix), -1.0f), (float)(ws - 1)) + 1;
-            const int cy = (int)fminf(fmaxf(floorf(iy), -1.0f), (float)(hs - 1)) + 1;
-            const int cell = live ? cy * W2 + cx : -1;
+            const SweepSample G = sweep_sample(E, R, ds, hs, ws, W2);
+            const Taps& t = G.t;
+            const float mk = sweep_corr_mask(G);
+            const int cell = live ? G.cell : -1;
 
             // ---- 2. distinct cells in ray order -> lanes ----
             const int prev = __shfl_up(cell, 1);
@@ -502,7 +432,7 @@ __global__ void __launch_bounds__(256) sweep_corr_px_kernel(SweepParams p) {
 }
 
 // WarpOnlyCorr (planesweep_corr.py:107-140): the plane sweep without the correlation — the source features sampled at the
-// S positions of every key pixel, times the sampling mask.  Same grids and mask as sweep_corr_kernel; source features in the
+// S positions of every key pixel, times the sampling mask.  The grids of sweep_corr_kernel (sweep_epipolar.h); source features in the
 // caller's own (N,C,hs,ws) layout (one thread per (plane, key pixel) walks the channels, so neighbouring threads read
 // neighbouring source pixels of one channel plane and write neighbouring outputs).  norm_after: normalize(warped, dim=C)
 // = x / (|x|_2 + 1e-9) (:8-10,135-136) before the mask is applied.  Output (N,S,C,h,w), mask (N,S,h,w).
@@ -526,26 +456,11 @@ __global__ void __launch_bounds__(256) sweep_warp_kernel(WarpOnlyParams p) {
     if (pix >= (long long)h * w) return;
     const int y = (int)(pix / w), x = (int)(pix - (long long)y * w);
     const Epi E = epipolar(p.K_key + n * 9, p.K_src.p[v] + n * 9, p.T.p[v] + n * 16, h, w, hs, ws);
-    const float xc = (float)x + 0.5f, yc = (float)y + 0.5f;
-    const float u_inf = (E.a * xc + E.b * yc) + E.c;
-    const float v_inf = (E.f * xc + E.g * yc) + E.h;
-    const float k_inf = (E.j * xc + E.k * yc) + E.l;
-    const float z_pole = -(E.m / k_inf);
+    const SweepRay R = sweep_ray(E, (float)x + 0.5f, (float)y + 0.5f);
     const float ds = p.invd_per_pixel ? p.invd[(((size_t)n * S + s) * h + y) * w + x] : p.invd[(size_t)n * p.invd_stride + s];
-    const float den = k_inf + E.m * ds;
-    const float us = replace_nonfinite((u_inf + E.e * ds) / den);
-    const float vs = replace_nonfinite((v_inf + E.i * ds) / den);
-    const float zs = 1.0f / ds;
-    const bool visible = (zs > 0.f) && (((k_inf > 0.f) && (zs > z_pole)) || ((k_inf < 0.f) && (zs < z_pole)) ||
-                                       ((k_inf == 0.f) && (E.m > 0.f)));
-    const float fws = (float)ws, fhs = (float)hs;
-    const float ix = unnormalize_coord(2.0f * us / fws - 1.0f, fws);
-    const float iy = unnormalize_coord(2.0f * vs / fhs - 1.0f, fhs);
-    const Taps t = bilinear_taps(ix, iy, hs, ws);
-    // WarpOnlyCorr does not take the visibility mask (its forward is called with grids only, :131-133, the `mask`
-    // argument is unused): the returned mask is the sampling mask alone
-    (void)visible;
-    const float mk = t.inb < 0.9999f ? 0.f : 1.f;
+    const SweepSample G = sweep_sample(E, R, ds, hs, ws, ws + 3);  // the cell and the visibility are not used here
+    const Taps& t = G.t;
+    const float mk = sweep_warp_mask(G);
     const size_t plane = (size_t)hs * ws;
     const float* __restrict__ sp = p.src.p[v] + (size_t)n * C * plane;
     float scale = mk;

@@ -14,7 +14,7 @@
 // Generic and simple by design (the tuned K3 tile kernel is the hot path): thread = (pixel, unit), unit = channel quad
 // (variance modes) or channel group (group correlation); pixels are the fast index so that stores into the
 // reference's (B,C,D,h,w) layout are coalesced.  Gathers come from zero-bordered channel-last copies like K3's.
-#include "sweep_modes_common.h"
+#include "sweep_homography.h"
 
 namespace mvd {
 int repack_padded_launch(const float* src, float* dst, int B, int C, int h, int w, hipStream_t st);
@@ -32,30 +32,17 @@ struct ReduceParams {
     int B, C, D, h, w, V;
 };
 
-// One bilinear sample of 4 channels of source view v at the position plane `depth` puts key pixel (fx, fy) at.
+// One bilinear sample of 4 channels (c0 .. c0+3) of source view v at the position plane `depth` puts key pixel (fx, fy) at.
 __device__ __forceinline__ float4 reduce_sample(const ReduceParams& p, int v, int b, float fx, float fy, float depth, int c0, int W2,
                                                 size_t img) {
-    const float xhi = (float)p.w, yhi = (float)p.h;
-    const int C = p.C;
-    const ReducePos P = reduce_position(p.M.p[v] + (size_t)b * 12, fx, fy, depth, p.scale_x, p.scale_y, p.bias, xhi, yhi);
-    const float ix = P.ix, iy = P.iy;
-    const float xf = floorf(ix), yf = floorf(iy);
-    const float wx = ix - xf, wy = iy - yf, ux = 1.0f - wx, uy = 1.0f - wy;
-    const float* __restrict__ f = p.src.p[v] + b * img + ((size_t)((int)yf + 1) * W2 + ((int)xf + 1)) * C + c0;
-    const float4 a = *reinterpret_cast<const float4*>(f), bq = *reinterpret_cast<const float4*>(f + C);
-    const float4 c = *reinterpret_cast<const float4*>(f + (size_t)W2 * C);
-    const float4 e = *reinterpret_cast<const float4*>(f + (size_t)W2 * C + C);
-    const float w00 = ux * uy, w10 = wx * uy, w01 = ux * wy, w11 = wx * wy;
-    return make_float4(fmaf(e.x, w11, fmaf(c.x, w01, fmaf(bq.x, w10, a.x * w00))),
-                       fmaf(e.y, w11, fmaf(c.y, w01, fmaf(bq.y, w10, a.y * w00))),
-                       fmaf(e.z, w11, fmaf(c.z, w01, fmaf(bq.z, w10, a.z * w00))),
-                       fmaf(e.w, w11, fmaf(c.w, w01, fmaf(bq.w, w10, a.w * w00))));
+    const SamplePos P = sample_position_div(p.M.p[v] + (size_t)b * 12, fx, fy, depth, p.scale_x, p.scale_y, p.bias, (float)p.w, (float)p.h);
+    return sample_blend(p.src.p[v] + b * img, sample_cell(P, W2, p.C, c0), W2, p.C);
 }
 
 // The same reduction with the lanes of a pixel side by side (unit fastest: a pixel's units read whole 128-byte lines of a tap,
 // the plain kernel's lanes = pixels read 16 bytes of each) and the results of a plane turned through LDS, so that a channel's
 // 256 / units consecutive pixels leave as one run.  units = a power of two <= 64 (C / 4, or the number of groups).
-// grid (ceil(h w / ppw), B), ppw = 256 / units pixels per workgroup.  Same arithmetic as sweep_reduce_kernel, bit for bit.
+// grid (ceil(h w / ppw), B), ppw = 256 / units pixels per workgroup.
 __global__ void __launch_bounds__(256) sweep_reduce_tile_kernel(ReduceParams p, int units) {
     __shared__ __attribute__((aligned(16))) float tile[2][1024];
     const int h = p.h, w = p.w, C = p.C, D = p.D, V = p.V;
@@ -80,21 +67,11 @@ __global__ void __launch_bounds__(256) sweep_reduce_tile_kernel(ReduceParams p, 
         if (!corr) {
             const int c0 = unit * 4;
             const float4 k = *reinterpret_cast<const float4*>(p.key + b * img + ((size_t)(y + 1) * W2 + (x + 1)) * C + c0);
-            float4 s1, s2;
-            s2 = make_float4(k.x * k.x, k.y * k.y, k.z * k.z, k.w * k.w);
-            s1 = p.mode == MVD_REDUCE_VARIANCE_KEYSQ ? s2 : k;  // the reference's aliasing: both sums start from key^2
-            for (int v = 0; v < V; ++v) {
-                const float4 sv = reduce_sample(p, v, b, fx, fy, depth, c0, W2, img);
-                s1.x += sv.x; s1.y += sv.y; s1.z += sv.z; s1.w += sv.w;
-                s2.x = fmaf(sv.x, sv.x, s2.x); s2.y = fmaf(sv.y, sv.y, s2.y);
-                s2.z = fmaf(sv.z, sv.z, s2.z); s2.w = fmaf(sv.w, sv.w, s2.w);
-            }
-            const float mx = s1.x * inv_nv, my = s1.y * inv_nv, mz = s1.z * inv_nv, mw = s1.w * inv_nv;
+            VarianceSums sums(k, p.mode == MVD_REDUCE_VARIANCE_KEYSQ);
+            for (int v = 0; v < V; ++v) sums.add(reduce_sample(p, v, b, fx, fy, depth, c0, W2, img));
+            const float4 r = sums.finish(inv_nv);
             float* t = tile[buf] + (c0 * ppw + lp);  // [channel][pixel]
-            t[0] = fmaf(s2.x, inv_nv, -mx * mx);
-            t[ppw] = fmaf(s2.y, inv_nv, -my * my);
-            t[2 * ppw] = fmaf(s2.z, inv_nv, -mz * mz);
-            t[3 * ppw] = fmaf(s2.w, inv_nv, -mw * mw);
+            t[0] = r.x; t[ppw] = r.y; t[2 * ppw] = r.z; t[3 * ppw] = r.w;
             __syncthreads();
             // 1024 results = C channels x ppw pixels: thread -> 4 consecutive pixels of one channel
             if (vec4) {
@@ -149,7 +126,6 @@ __global__ void __launch_bounds__(256) sweep_reduce_kernel(ReduceParams p) {
     const int W2 = w + 3;
     const size_t img = (size_t)(h + 3) * W2 * C;
     const float fx = (float)x + p.pix_offset, fy = (float)y + p.pix_offset;
-    const float xhi = (float)w, yhi = (float)h;
     const float inv_nv = 1.0f / (float)(V + 1);
     const size_t dplane = (size_t)h * w;
 
@@ -158,45 +134,24 @@ __global__ void __launch_bounds__(256) sweep_reduce_kernel(ReduceParams p) {
         for (int qq = 0; qq < qpu; ++qq) {
             const int c0 = (unit * qpu + qq) * 4;
             const float4 k = *reinterpret_cast<const float4*>(p.key + b * img + ((size_t)(y + 1) * W2 + (x + 1)) * C + c0);
-            float4 s1, s2;
-            if (p.mode == MVD_REDUCE_VARIANCE_KEYSQ) {  // the reference's aliasing: sum and sum of squares both start from key^2
-                s2 = make_float4(k.x * k.x, k.y * k.y, k.z * k.z, k.w * k.w);
-                s1 = s2;
-            } else {
-                s1 = k;
-                s2 = make_float4(k.x * k.x, k.y * k.y, k.z * k.z, k.w * k.w);
-            }
+            VarianceSums sums(k, p.mode == MVD_REDUCE_VARIANCE_KEYSQ);
             for (int v = 0; v < V; ++v) {
-                const ReducePos P = reduce_position(p.M.p[v] + (size_t)b * 12, fx, fy, depth, p.scale_x, p.scale_y, p.bias, xhi, yhi);
-                const float ix = P.ix, iy = P.iy;
-                const float xf = floorf(ix), yf = floorf(iy);
-                const float wx = ix - xf, wy = iy - yf, ux = 1.0f - wx, uy = 1.0f - wy;
-                const float* __restrict__ f = p.src.p[v] + b * img + ((size_t)((int)yf + 1) * W2 + ((int)xf + 1)) * C + c0;
-                const float4 a = *reinterpret_cast<const float4*>(f), bq = *reinterpret_cast<const float4*>(f + C);
-                const float4 c = *reinterpret_cast<const float4*>(f + (size_t)W2 * C);
-                const float4 e = *reinterpret_cast<const float4*>(f + (size_t)W2 * C + C);
-                const float w00 = ux * uy, w10 = wx * uy, w01 = ux * wy, w11 = wx * wy;
-                const float4 sv = make_float4(fmaf(e.x, w11, fmaf(c.x, w01, fmaf(bq.x, w10, a.x * w00))),
-                                              fmaf(e.y, w11, fmaf(c.y, w01, fmaf(bq.y, w10, a.y * w00))),
-                                              fmaf(e.z, w11, fmaf(c.z, w01, fmaf(bq.z, w10, a.z * w00))),
-                                              fmaf(e.w, w11, fmaf(c.w, w01, fmaf(bq.w, w10, a.w * w00))));
+                const float4 sv = reduce_sample(p, v, b, fx, fy, depth, c0, W2, img);
                 if (corr) {
                     const float dot = fmaf(k.w, sv.w, fmaf(k.z, sv.z, fmaf(k.y, sv.y, k.x * sv.x)));
                     float* o = p.out.p[v] + (((size_t)b * p.groups + unit) * D + d) * dplane + pix;
                     *o = (qq == 0 ? 0.0f : *o) + dot;
                 } else {
-                    s1.x += sv.x; s1.y += sv.y; s1.z += sv.z; s1.w += sv.w;
-                    s2.x = fmaf(sv.x, sv.x, s2.x); s2.y = fmaf(sv.y, sv.y, s2.y);
-                    s2.z = fmaf(sv.z, sv.z, s2.z); s2.w = fmaf(sv.w, sv.w, s2.w);
+                    sums.add(sv);
                 }
             }
             if (!corr) {
-                const float mx = s1.x * inv_nv, my = s1.y * inv_nv, mz = s1.z * inv_nv, mw = s1.w * inv_nv;
+                const float4 r = sums.finish(inv_nv);
                 float* o = p.out.p[0] + (((size_t)b * C + c0) * D + d) * dplane + pix;
-                o[0] = fmaf(s2.x, inv_nv, -mx * mx);
-                o[(size_t)D * dplane] = fmaf(s2.y, inv_nv, -my * my);
-                o[2 * (size_t)D * dplane] = fmaf(s2.z, inv_nv, -mz * mz);
-                o[3 * (size_t)D * dplane] = fmaf(s2.w, inv_nv, -mw * mw);
+                o[0] = r.x;
+                o[(size_t)D * dplane] = r.y;
+                o[2 * (size_t)D * dplane] = r.z;
+                o[3 * (size_t)D * dplane] = r.w;
             }
         }
     }
@@ -209,7 +164,7 @@ __global__ void __launch_bounds__(256) sweep_reduce_kernel(ReduceParams p) {
 // ppw * units idle when units does not divide 256).  A pixel's lanes read one tap's C floats as one run (64 B at C = 16) and thread t of
 // a workgroup stores the float4 at plane + pix0 * C + 4 t: a plane's stores of consecutive pixels leave as whole lines, without a
 // turn through LDS.  grid (ceil(h w / ppw), planes / NHWC_DPB rounded up, B): the coarse level (48 planes on a small map) fills the
-// device through the plane chunks, a refinement level (8 planes) reads its key quad once.  Arithmetic per element: the kernels' above.
+// device through the plane chunks, a refinement level (8 planes) reads its key quad once.
 constexpr int NHWC_DPB = 8;
 
 __global__ void __launch_bounds__(256) sweep_reduce_nhwc_kernel(ReduceParams p, int units) {
@@ -229,19 +184,9 @@ __global__ void __launch_bounds__(256) sweep_reduce_nhwc_kernel(ReduceParams p, 
     const int d0 = blockIdx.y * NHWC_DPB, d1 = min(D, d0 + NHWC_DPB);
     for (int d = d0; d < d1; ++d) {
         const float depth = p.depth_per_pixel ? p.depth[((size_t)b * D + d) * npix + pix] : p.depth[(size_t)b * D + d];
-        float4 s1, s2;
-        s2 = make_float4(k.x * k.x, k.y * k.y, k.z * k.z, k.w * k.w);
-        s1 = p.mode == MVD_REDUCE_VARIANCE_KEYSQ ? s2 : k;  // the reference's aliasing: both sums start from key^2
-        for (int v = 0; v < V; ++v) {
-            const float4 sv = reduce_sample(p, v, b, fx, fy, depth, c0, W2, img);
-            s1.x += sv.x; s1.y += sv.y; s1.z += sv.z; s1.w += sv.w;
-            s2.x = fmaf(sv.x, sv.x, s2.x); s2.y = fmaf(sv.y, sv.y, s2.y);
-            s2.z = fmaf(sv.z, sv.z, s2.z); s2.w = fmaf(sv.w, sv.w, s2.w);
-        }
-        const float mx = s1.x * inv_nv, my = s1.y * inv_nv, mz = s1.z * inv_nv, mw = s1.w * inv_nv;
-        const float4 r = make_float4(fmaf(s2.x, inv_nv, -mx * mx), fmaf(s2.y, inv_nv, -my * my), fmaf(s2.z, inv_nv, -mz * mz),
-                                     fmaf(s2.w, inv_nv, -mw * mw));
-        *reinterpret_cast<float4*>(p.out.p[0] + (((size_t)b * D + d) * npix + pix) * C + c0) = r;
+        VarianceSums sums(k, p.mode == MVD_REDUCE_VARIANCE_KEYSQ);
+        for (int v = 0; v < V; ++v) sums.add(reduce_sample(p, v, b, fx, fy, depth, c0, W2, img));
+        *reinterpret_cast<float4*>(p.out.p[0] + (((size_t)b * D + d) * npix + pix) * C + c0) = sums.finish(inv_nv);
     }
 }
 

@@ -10,11 +10,10 @@
 //   GROUPCORR       out_v[grp,d] = sum_{c in grp} k_c sv_c:                     d/dsv_c = g_v[grp,d] k_c, d/dk_c = sum_v sum_d g_v[grp,d] sv_c
 // The source gradient is the transpose of the bilinear gather: the per-sample gradient times the four tap weights, scatter-added
 // with no-return float atomics into a zero-bordered channel-last gradient map (the border takes the share of the taps that fell
-// on the zero padding and is dropped by the un-padding copy).  Sampling positions: reduce_position, the forward's own.
+// on the zero padding and is dropped by the un-padding copy).  Sampling: sweep_homography.h, the forward's own functions.
 // A first VJP in the shape of warp_variance_backward_kernel (backward.hip): simple, not tuned; summation order varies from run to
 // run for the source gradients, the key gradient is a plain sum per thread (bit-reproducible).
-#include "sweep_modes_common.h"
-#include "warp_variance_backward_common.h"
+#include "sweep_homography.h"
 
 namespace mvd {
 int repack_padded_launch(const float* src, float* dst, int B, int C, int h, int w, hipStream_t st);
@@ -59,8 +58,7 @@ __global__ void __launch_bounds__(256) sweep_reduce_backward_kernel(ReduceBwdPar
     const float4 k = *reinterpret_cast<const float4*>(p.key + b * img + ((size_t)(y + 1) * W2 + (x + 1)) * C + c0);
 
     auto locate = [&](int v, float depth) {
-        const ReducePos P = reduce_position(p.M.p[v] + (size_t)b * 12, fx, fy, depth, p.scale_x, p.scale_y, p.bias, xhi, yhi);
-        return bwd_cell(BwdPos{P.ix, P.iy}, W2, C, q);  // floorf, the four weights and the tap offset: the forward's own
+        return sample_cell(sample_position_div(p.M.p[v] + (size_t)b * 12, fx, fy, depth, p.scale_x, p.scale_y, p.bias, xhi, yhi), W2, C, c0);
     };
     constexpr int DZ = 8;
     float4 gk = make_float4(0, 0, 0, 0);
@@ -79,7 +77,7 @@ __global__ void __launch_bounds__(256) sweep_reduce_backward_kernel(ReduceBwdPar
                 const float4 g = make_float4(go[0], go[(size_t)D * dplane], go[2 * (size_t)D * dplane], go[3 * (size_t)D * dplane]);
                 float4 s1 = keysq ? make_float4(k.x * k.x, k.y * k.y, k.z * k.z, k.w * k.w) : k;
                 for (int v = 0; v < V; ++v) {
-                    const float4 sv = bwd_sample(p.src.p[v] + b * img, locate(v, dep[dd]), W2, C);
+                    const float4 sv = sample_blend(p.src.p[v] + b * img, locate(v, dep[dd]), W2, C);
                     s1.x += sv.x; s1.y += sv.y; s1.z += sv.z; s1.w += sv.w;
                 }
                 const float4 m = make_float4(s1.x * inv_nv, s1.y * inv_nv, s1.z * inv_nv, s1.w * inv_nv);
@@ -97,22 +95,13 @@ __global__ void __launch_bounds__(256) sweep_reduce_backward_kernel(ReduceBwdPar
         for (int v = 0; v < V; ++v) {
             const float* __restrict__ f = p.src.p[v] + b * img;
             float* __restrict__ gv = p.gsrc.p[v] + b * img;
-            constexpr size_t NONE = ~(size_t)0;
-            size_t pend = NONE;
-            float4 t00 = make_float4(0, 0, 0, 0), t10 = t00, t01 = t00, t11 = t00;
-            auto flush = [&]() {
-                float* go = gv + pend;
-                atomic_add4(go, t00);
-                atomic_add4(go + C, t10);
-                atomic_add4(go + (size_t)W2 * C, t01);
-                atomic_add4(go + (size_t)W2 * C + C, t11);
-            };
+            PendingCell pend(W2, C);
 #pragma unroll
             for (int dd = 0; dd < DZ; ++dd) {
                 const int d = d0 + dd;
                 if (d >= D) continue;
-                const BwdLoc L = locate(v, dep[dd]);
-                const float4 xv = bwd_sample(f, L, W2, C);
+                const SampleCell L = locate(v, dep[dd]);
+                const float4 xv = sample_blend(f, L, W2, C);
                 float4 gx;
                 if constexpr (CORR) {
                     const float g = p.gout.p[v][(((size_t)b * p.groups + grp) * D + d) * dplane + pin];
@@ -122,21 +111,9 @@ __global__ void __launch_bounds__(256) sweep_reduce_backward_kernel(ReduceBwdPar
                     gx = make_float4(gs[dd].x * (xv.x - mean[dd].x), gs[dd].y * (xv.y - mean[dd].y),
                                      gs[dd].z * (xv.z - mean[dd].z), gs[dd].w * (xv.w - mean[dd].w));
                 }
-                if (L.o != pend) {
-                    if (pend != NONE) flush();
-                    pend = L.o;
-                    t00 = make_float4(gx.x * L.w00, gx.y * L.w00, gx.z * L.w00, gx.w * L.w00);
-                    t10 = make_float4(gx.x * L.w10, gx.y * L.w10, gx.z * L.w10, gx.w * L.w10);
-                    t01 = make_float4(gx.x * L.w01, gx.y * L.w01, gx.z * L.w01, gx.w * L.w01);
-                    t11 = make_float4(gx.x * L.w11, gx.y * L.w11, gx.z * L.w11, gx.w * L.w11);
-                } else {
-                    t00.x = fmaf(gx.x, L.w00, t00.x); t00.y = fmaf(gx.y, L.w00, t00.y); t00.z = fmaf(gx.z, L.w00, t00.z); t00.w = fmaf(gx.w, L.w00, t00.w);
-                    t10.x = fmaf(gx.x, L.w10, t10.x); t10.y = fmaf(gx.y, L.w10, t10.y); t10.z = fmaf(gx.z, L.w10, t10.z); t10.w = fmaf(gx.w, L.w10, t10.w);
-                    t01.x = fmaf(gx.x, L.w01, t01.x); t01.y = fmaf(gx.y, L.w01, t01.y); t01.z = fmaf(gx.z, L.w01, t01.z); t01.w = fmaf(gx.w, L.w01, t01.w);
-                    t11.x = fmaf(gx.x, L.w11, t11.x); t11.y = fmaf(gx.y, L.w11, t11.y); t11.z = fmaf(gx.z, L.w11, t11.z); t11.w = fmaf(gx.w, L.w11, t11.w);
-                }
+                pend.add(gv, L, gx);
             }
-            if (pend != NONE) flush();
+            pend.flush(gv);
         }
     }
     float* gko = p.gkey + ((size_t)b * C + c0) * dplane + pin;  // written once per (pixel, channel): no atomics

@@ -36,6 +36,10 @@ __global__ void compose_transforms_kernel(ViewPtrs proj, const float* __restrict
     acc = fmaf(P[i * 4 + 3], Q[3 * 4 + j], acc);
     M[e] = acc;
 }
+void launch_compose_transforms(const ViewPtrs& proj, const float* key_proj_inv, int B, int V, float* M, hipStream_t st) {
+    hipLaunchKernelGGL(compose_transforms_kernel, dim3((unsigned)((V * B * 12 + 255) / 256)), dim3(256), 0, st, proj, key_proj_inv,
+                       B, V, M);
+}
 
 // (N, C, h, w) -> channel-last with a zero border: (N, h+3, w+3, C), pixel (y, x) at padded (y+1, x+1).
 // Rows/cols -1, w and w+1 (h, h+1) stay zero (the buffer is cleared first), so a bilinear sample whose
@@ -610,8 +614,7 @@ static int run_warp(const float* key_feat, const float* const* src_feat, const f
         }
         p.proj.p[v] = src_proj[v];
     }
-    hipLaunchKernelGGL(compose_transforms_kernel, dim3((unsigned)((V * B * 12 + 255) / 256)), dim3(256), 0, st, p.proj,
-                       key_proj_inv, B, V, const_cast<float*>(p.M));
+    launch_compose_transforms(p.proj, key_proj_inv, B, V, const_cast<float*>(p.M), st);
     rc = launch_status("compose_transforms");
     if (rc) return rc;
     p.key_proj_inv = key_proj_inv;
@@ -653,8 +656,7 @@ static int run_warp_f16(const void* key_feat, const void* const* src_feat, const
     p.layout = MVD_LAYOUT_NDHWC;
     MVD_REQUIRE(warp_tile_supported(p, true), "%s: maps of %dx%d are outside the fp16 kernel's range (h, w <= 65532 and h*w*64 < 2^31)",
                 who, h, w);
-    hipLaunchKernelGGL(compose_transforms_kernel, dim3((unsigned)((V * B * 12 + 255) / 256)), dim3(256), 0, st, p.proj,
-                       key_proj_inv, B, V, const_cast<float*>(p.M));
+    launch_compose_transforms(p.proj, key_proj_inv, B, V, const_cast<float*>(p.M), st);
     const int rc = launch_status("compose_transforms");
     if (rc) return rc;
     return launch_k3(p, 32, false, true, st);

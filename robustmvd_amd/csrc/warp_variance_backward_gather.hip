@@ -94,9 +94,9 @@ __global__ void __launch_bounds__(256) warp_variance_gather_stage_a_kernel(Gathe
         const float4 g = *reinterpret_cast<const float4*>(p.gvar + vox);
         float4 sum = k;
         for (int v = 0; v < V; ++v) {
-            const BwdPos P = bwd_position(p.M + ((size_t)v * p.B + b) * 12, fx, fy, depth, sx, sy, xhi, yhi);
-            const BwdLoc L = bwd_cell(P, W2, C, q);
-            const float4 xv = bwd_sample(p.src.p[v] + b * img, L, W2, C);
+            const SamplePos P = sample_position_rcp(p.M + ((size_t)v * p.B + b) * 12, fx, fy, depth, sx, sy, xhi, yhi);
+            const SampleCell L = sample_cell(P, W2, C, q * 4);
+            const float4 xv = sample_blend(p.src.p[v] + b * img, L, W2, C);
             sum.x += xv.x; sum.y += xv.y; sum.z += xv.z; sum.w += xv.w;
             // the pixel's channel quads share its four taps between them
             const float* __restrict__ G = gp.G + (((size_t)v * p.B + b) * D + d) * 9;
@@ -163,7 +163,7 @@ __global__ void __launch_bounds__(256) warp_variance_gather_stage_b_kernel(Gathe
             const int px = cx - GR + i % GW, py = cy - GR + i / GW;
             bool hit = false;
             if (i < GW * GW && px >= 0 && px < w && py >= 0 && py < h) {
-                const BwdPos P = bwd_position(M, (float)px, (float)py, depth, sx, sy, xhi, yhi);
+                const SamplePos P = sample_position_rcp(M, (float)px, (float)py, depth, sx, sy, xhi, yhi);
                 const unsigned dx = (unsigned)(qx - (int)floorf(P.ix)), dy = (unsigned)(qy - (int)floorf(P.iy));
                 hit = dx < 2u && dy < 2u;
             }
@@ -175,11 +175,11 @@ __global__ void __launch_bounds__(256) warp_variance_gather_stage_b_kernel(Gathe
             const int i = __builtin_ctzll(hits);
             hits &= hits - 1;
             const int px = cx - GR + i % GW, py = cy - GR + i / GW;
-            const BwdPos P = bwd_position(M, (float)px, (float)py, depth, sx, sy, xhi, yhi);
-            const BwdLoc L = bwd_cell(P, W2, C, sub);
+            const SamplePos P = sample_position_rcp(M, (float)px, (float)py, depth, sx, sy, xhi, yhi);
+            const SampleCell L = sample_cell(P, W2, C, sub * 4);
             const bool right = qx != (int)floorf(P.ix), low = qy != (int)floorf(P.iy);
             const float wt = right ? (low ? L.w11 : L.w10) : (low ? L.w01 : L.w00);
-            const float4 xv = bwd_sample(f, L, W2, C);
+            const float4 xv = sample_blend(f, L, W2, C);
             const size_t vox = ((plane + py) * w + px) * C + sub * 4;
             const float4 g = *reinterpret_cast<const float4*>(p.gvar + vox);
             const float4 mean = *reinterpret_cast<const float4*>(gp.mean + vox);
@@ -250,7 +250,7 @@ int mvd_warp_variance_backward_gather_f32(const float* key_feat, const float* co
         timing_end(st);
         return launch_status("warp_variance_backward_gather: memset");
     }
-    launch_compose_transforms_bwd(proj, key_proj_inv, B, V, M, st);
+    launch_compose_transforms(proj, key_proj_inv, B, V, M, st);
     hipLaunchKernelGGL(plane_inverse_kernel, dim3((unsigned)((V * B * D + 255) / 256)), dim3(256), 0, st, M, depth_values, B, D, V, h, w, G);
     hipLaunchKernelGGL(warp_variance_gather_stage_a_kernel, dim3((unsigned)nblk), dim3(256), 0, st, gp);
     const int lpp = C / 4, ty = 256 / lpp / 8;

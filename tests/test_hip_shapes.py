@@ -70,7 +70,9 @@ def test_warp_variance_wide_baseline_vs_oracle(dev):
 
 @pytest.mark.parametrize("N,C,h,w,hs,ws,S,V,batched", [(2, 64, 13, 21, 11, 19, 7, 3, True), (1, 128, 5, 40, 5, 40, 9, 1, False),
                                                        (1, 256, 17, 16, 17, 16, 33, 2, False),
-                                                       (1, 64, 9, 14, 9, 14, 5, 20, False), (2, 64, 6, 9, 7, 8, 4, 32, True)])
+                                                       (1, 64, 9, 14, 9, 14, 5, 20, False), (2, 64, 6, 9, 7, 8, 4, 32, True),
+                                                       # C above 256: the cells form (sweep_corr_kernel)
+                                                       (1, 320, 7, 12, 7, 12, 6, 2, False)])
 def test_sweep_corr_vs_oracle(N, C, h, w, hs, ws, S, V, batched, dev):
     from robustmvd_amd import ops
     rng = np.random.default_rng(N * 100 + C)

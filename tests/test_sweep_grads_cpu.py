@@ -26,7 +26,7 @@ def _fma(a, b, c):
 
 
 def reduce_positions(M, depth, h, w, pix_offset, stretch):
-    """sweep_modes_common.h reduce_position in float32: M (B,3,4), depth (B,D) or (B,D,h,w) -> ix, iy (B,D,h,w), clamped."""
+    """sweep_homography.h sample_position_div in float32: M (B,3,4), depth (B,D) or (B,D,h,w) -> ix, iy (B,D,h,w), clamped."""
     M = np.asarray(M, f32).reshape(-1, 12)
     B = M.shape[0]
     depth = np.asarray(depth, f32)
@@ -79,7 +79,7 @@ def sweep_reduce_restated(key, srcs, Ms, depth, mode, groups=1, pix_offset=0.0, 
 
 
 def warp_cells(K_key, K_src, T, invd, h, w, hs, ws):
-    """sweep_corr.hip's grid chain in float32, one rounding per operation: K_* (N,3,3) relative intrinsics, T (N,4,4),
+    """sweep_epipolar.h's grid chain in float32, one rounding per operation: K_* (N,3,3) relative intrinsics, T (N,4,4),
     invd (1 or N, S) -> cell_y, cell_x (N,S,h,w), four tap weights (zero where out of bounds) and the 0/1 sampling mask."""
     Kk, Ks, T = np.asarray(K_key, f32), np.asarray(K_src, f32), np.asarray(T, f32)
     N = Kk.shape[0]
