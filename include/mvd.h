@@ -436,6 +436,40 @@ int mvd_sweep_reduce_nhwc_f32(const float* key_feat, const float* const* src_fea
 int mvd_softmax_regress_pp_f32(const float* cost, const float* depth_hypos, int B, int D, int h, int w, float* depth_out,
                                float* conf_out, mvd_stream_t stream);
 
+/* Vis-MVSNet's group-wise correlation (MVD_REDUCE_GROUPCORR of mvd_sweep_reduce_f32) on the layouts the engine uses between its own
+ * kernels, for Vis-MVSNet as a model — replaces SingleStage.build_cost_volume + groupwise_correlation,
+ *   rmvd/models/blocks/vis_mvsnet_singlestage.py:86-122,242, rmvd/models/blocks/utils.py:71-89,95-186.
+ *   key_feat (B,h,w,C) channel-last; src_feat[v] (B,h+3,w+3,C) channel-last, zero-bordered with the map at (1,1);
+ *   out[v] (B,D,h,w,groups) channel-last, what the 3-D convolutions read (V pointers: they may be consecutive slices of one
+ *   (V B,D,h,w,groups) buffer); depth, M, pix_offset, scale, bias: as in mvd_sweep_reduce_f32.
+ *   grid_clamp > 0: the reference's interpolate clamps its NORMALISED sampling grid to +-grid_clamp (1.1, blocks/utils.py:168) before
+ *   grid_sample, i.e. the sample index to [((1 - c) w - 1) / 2, ((1 + c) w - 1) / 2]: on maps narrower than 10 pixels a sample far
+ *   outside the map then still takes a part of the rim pixel (at w = 8 the index stops at 7.9).  The kernel clamps the index to that
+ *   interval (within its own [-1, w]); on wider maps it changes nothing.  grid_clamp <= 0: no such clamp (mvd_sweep_reduce_f32's values).
+ *   C a multiple of 4 up to 64, C / groups a multiple of 4; all maps 16-byte aligned (MVD_ERR_INVALID_ARG otherwise).
+ * No workspace, no repacking launches; without grid_clamp bit-identical to mvd_sweep_reduce_f32's group correlation on the same
+ * values, permuted. */
+int mvd_sweep_groupcorr_nhwc_f32(const float* key_feat, const float* const* src_feat, const float* const* M, const float* depth,
+                                 int depth_per_pixel, float pix_offset, float scale_x, float scale_y, float bias, float grid_clamp,
+                                 int groups, int B, int C, int D, int h, int w, int V, float* const* out, mvd_stream_t stream);
+
+/* Vis-MVSNet's soft argmin, entropy and windowed probability in one kernel — replaces soft_argmin and entropy,
+ *   rmvd/models/blocks/utils.py:51-68, as called from rmvd/models/blocks/vis_mvsnet_singlestage.py:254-258,330-333.
+ *   score (B,D,h,w); depth_start (B), or (B,h,w) when start_per_pixel; depth_interval (B); with p = softmax_D(score):
+ *   depth_out    (B,h,w) = (sum_i i p_i) * depth_interval + depth_start
+ *   entropy_out  (B,h,w) = sum_i -p_i log(clamp(p_i, 1e-9, 1))          (may be NULL)
+ *   prob_map_out (B,h,w) = sum_i p_i [|i - sum_j j p_j| <= window]      (may be NULL; window is read only when it is given)
+ * Any D >= 1. */
+int mvd_soft_argmin_f32(const float* score, const float* depth_start, int start_per_pixel, const float* depth_interval, float window,
+                        int B, int D, int h, int w, float* depth_out, float* entropy_out, float* prob_map_out, mvd_stream_t stream);
+
+/* Vis-MVSNet's "soft" fusion of the pair-wise regularised volumes — replaces the weight / weight_sum / fused_interm chain of
+ *   rmvd/models/blocks/vis_mvsnet_singlestage.py:263-266,302-303.
+ *   x[v] (B,D,h,w,C) channel-last, C a multiple of 4, 16-byte aligned; u[v] (B,h,w);
+ *   out (B,D,h,w,C) = (sum_v x_v exp(-u_v)) / (sum_v exp(-u_v)), both sums in view order starting from 0, then one division. */
+int mvd_vis_fuse_f32(const float* const* x, const float* const* u, int B, int D, int h, int w, int C, int V, float* out,
+                     mvd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Backward of the sweep operators w.r.t. the feature maps, for the training loop
  * (rmvd/train/multi_view_depth_training.py:231-246).  The sampling grids carry no gradient (planesweep_corr.py:436,464,489;

@@ -14,5 +14,7 @@ from .blocks import (PlanesweepCorrelation, LearnedFusion, CostRegNet, homo_warp
                      compute_sampling_invdepths)
 from .models import RobustMVD, MVSNet  # noqa: F401
 from .cvp_mvsnet import CVPMVSNet  # noqa: F401  (registers cvp_mvsnet)
+from .vis_mvsnet import VisMvsnet  # noqa: F401  (registers vis_mvsnet)
+from .ops import sweep_groupcorr_nhwc, soft_argmin, vis_fuse  # noqa: F401
 from .serving import FramePipeline, PinnedUploader  # noqa: F401
 from .sweep_modes import cvp_proj_cost, vis_cost_volumes, sweep_reduce  # noqa: F401

@@ -121,6 +121,9 @@ SIGNATURES = {
     "mvd_sweep_reduce_nhwc_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _i] + [ctypes.c_float] * 4 + [_i] * 7
                                   + [_c_float_p, ctypes.c_void_p]),
     "mvd_softmax_regress_pp_f32": (_i, [_c_float_p, _c_float_p, _i, _i, _i, _i, _c_float_p, _c_float_p, ctypes.c_void_p]),
+    "mvd_sweep_groupcorr_nhwc_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _i] + [ctypes.c_float] * 5 + [_i] * 7 + [_pp, ctypes.c_void_p]),
+    "mvd_soft_argmin_f32": (_i, [_c_float_p, _c_float_p, _i, _c_float_p, ctypes.c_float] + [_i] * 4 + [_c_float_p] * 3 + [ctypes.c_void_p]),
+    "mvd_vis_fuse_f32": (_i, [_pp, _pp] + [_i] * 6 + [_c_float_p, ctypes.c_void_p]),
     "mvd_sweep_reduce_backward_workspace_bytes": (_sz, [_i] * 5),
     "mvd_sweep_reduce_backward_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _i] + [ctypes.c_float] * 4 + [_i, _i, _pp] + [_i] * 6
                                       + [_c_float_p, _pp, ctypes.c_void_p, _sz, ctypes.c_void_p]),

@@ -28,6 +28,7 @@ struct ReduceParams {
     const float* depth;  // (B,D) or (B,D,h,w)
     int depth_per_pixel;
     float pix_offset, scale_x, scale_y, bias;
+    float xlo, xhi, ylo, yhi;  // sweep_groupcorr_nhwc_kernel only: the reference's own clamp of the sample index, within [-1, w] x [-1, h]
     int mode, groups;
     int B, C, D, h, w, V;
 };
@@ -190,9 +191,104 @@ __global__ void __launch_bounds__(256) sweep_reduce_nhwc_kernel(ReduceParams p, 
     }
 }
 
+// Group correlation on the same layouts (mvd_sweep_groupcorr_nhwc_f32): the key map dense channel-last in p.key, the source maps
+// zero-bordered channel-last, one volume per source view channel-last (B,D,h,w,G) in p.out.p[v], what Vis-MVSNet's pair regulariser reads.
+// Thread = (pixel, group), group fastest, ppw = 256 / G pixels per workgroup (threads beyond ppw * G idle when G does not divide 256):
+// thread t of a workgroup stores the float at plane + pix0 * G + t, so a wave's 64 lanes store 256 consecutive bytes of a plane.
+// The sample position is reduce_sample's (sample_position_div, clamped to [-1, w] x [-1, h]) clamped once more to [xlo, xhi] x [ylo, yhi]:
+// the reference clamps its normalised grid to +-1.1 before grid_sample (blocks/utils.py:168), i.e. the index to
+// [-0.05 w - 0.5, 1.05 w - 0.5], which on a map narrower than 10 pixels lies INSIDE [-1, w]: a sample far outside such a map still
+// takes a tenth of the rim pixel.  On wider maps, and without the clamp, the bounds are -1 and w and the second clamp is the identity.
+// QPU = C / G / 4 key quads stay in registers across the planes of a chunk (QPU = 0: any count, the quads are read again per
+// plane).  The dot products are the tile kernel's: the fmaf chain w, z, y, x per quad, quads added in order from 0.0f.
+// grid as the variance kernel's: (ceil(h w / ppw), planes / NHWC_DPB rounded up, B): stage 1 (64 planes on a small map) fills the device.
+template <int QPU>
+__global__ void __launch_bounds__(256) sweep_groupcorr_nhwc_kernel(ReduceParams p) {
+    const int h = p.h, w = p.w, C = p.C, D = p.D, V = p.V, G = p.groups;
+    const int qpu = QPU ? QPU : C / G / 4;
+    const int ppw = 256 / G;
+    const int tid = threadIdx.x, g = tid % G, lp = tid / G;
+    const int b = blockIdx.z;
+    const long long npix = (long long)h * w, pix = (long long)blockIdx.x * ppw + lp;
+    if (lp >= ppw || pix >= npix) return;
+    const int x = (int)(pix % w), y = (int)(pix / w);
+    const int W2 = w + 3;
+    const size_t img = (size_t)(h + 3) * W2 * C;
+    const float fx = (float)x + p.pix_offset, fy = (float)y + p.pix_offset;
+    const int cg = g * qpu * 4;  // the group's first channel
+    const float* kp = p.key + ((size_t)b * npix + pix) * C + cg;
+    float4 k[QPU ? QPU : 1];
+#pragma unroll
+    for (int qq = 0; qq < QPU; ++qq) k[qq] = *reinterpret_cast<const float4*>(kp + 4 * qq);
+    const int d0 = blockIdx.y * NHWC_DPB, d1 = min(D, d0 + NHWC_DPB);
+    for (int d = d0; d < d1; ++d) {
+        const float depth = p.depth_per_pixel ? p.depth[((size_t)b * D + d) * npix + pix] : p.depth[(size_t)b * D + d];
+        for (int v = 0; v < V; ++v) {
+            float acc = 0.0f;
+#pragma unroll
+            for (int qq = 0; qq < qpu; ++qq) {
+                float4 kq;
+                if constexpr (QPU > 0) kq = k[qq];
+                else kq = *reinterpret_cast<const float4*>(kp + 4 * qq);
+                SamplePos P = sample_position_div(p.M.p[v] + (size_t)b * 12, fx, fy, depth, p.scale_x, p.scale_y, p.bias, (float)w, (float)h);
+                P.ix = __builtin_amdgcn_fmed3f(P.ix, p.xlo, p.xhi);
+                P.iy = __builtin_amdgcn_fmed3f(P.iy, p.ylo, p.yhi);
+                const float4 sv = sample_blend(p.src.p[v] + b * img, sample_cell(P, W2, C, cg + 4 * qq), W2, C);
+                const float dot = fmaf(kq.w, sv.w, fmaf(kq.z, sv.z, fmaf(kq.y, sv.y, kq.x * sv.x)));
+                acc = (qq == 0 ? 0.0f : acc) + dot;
+            }
+            p.out.p[v][(((size_t)b * D + d) * npix + pix) * G + g] = acc;
+        }
+    }
+}
+
 }  // namespace mvd
 
 extern "C" {
+
+int mvd_sweep_groupcorr_nhwc_f32(const float* key_feat, const float* const* src_feat, const float* const* M, const float* depth,
+                                 int depth_per_pixel, float pix_offset, float scale_x, float scale_y, float bias, float grid_clamp,
+                                 int groups, int B, int C, int D, int h, int w, int V, float* const* out, mvd_stream_t stream) {
+    using namespace mvd;
+    MVD_REQUIRE(key_feat && src_feat && M && depth && out, "sweep_groupcorr_nhwc: NULL argument");
+    MVD_REQUIRE(B > 0 && B <= 65535 && D > 0 && h > 1 && w > 1 && V >= 1 && V <= MVD_MAX_VIEWS, "sweep_groupcorr_nhwc: bad dimensions");
+    MVD_REQUIRE(C >= 4 && C <= 64 && C % 4 == 0, "sweep_groupcorr_nhwc: C=%d must be a multiple of 4 up to 64", C);
+    MVD_REQUIRE(groups > 0 && C % groups == 0 && (C / groups) % 4 == 0, "sweep_groupcorr_nhwc: C/groups = %d/%d must be a multiple of 4", C, groups);
+    MVD_REQUIRE(((uintptr_t)key_feat & 15) == 0, "sweep_groupcorr_nhwc: key_feat must be 16-byte aligned");
+    ReduceParams p{};
+    for (int v = 0; v < V; ++v) {
+        MVD_REQUIRE(src_feat[v] && M[v] && out[v], "sweep_groupcorr_nhwc: NULL view %d", v);
+        MVD_REQUIRE((((uintptr_t)src_feat[v] | (uintptr_t)out[v]) & 15) == 0, "sweep_groupcorr_nhwc: src_feat[%d] and out[%d] must be 16-byte aligned", v, v);
+        p.src.p[v] = src_feat[v];
+        p.M.p[v] = M[v];
+        p.out.p[v] = out[v];
+    }
+    p.key = key_feat;
+    p.depth = depth; p.depth_per_pixel = depth_per_pixel;
+    p.pix_offset = pix_offset; p.scale_x = scale_x; p.scale_y = scale_y; p.bias = bias;
+    p.mode = MVD_REDUCE_GROUPCORR; p.groups = groups;
+    p.xlo = -1.0f; p.xhi = (float)w; p.ylo = -1.0f; p.yhi = (float)h;
+    if (grid_clamp > 0.0f) {  // grid_sample's un-normalisation ((g + 1) size - 1) / 2 of g = -+grid_clamp, in float32 like the reference's
+        p.xlo = fmaxf(p.xlo, ((1.0f - grid_clamp) * (float)w - 1.0f) / 2.0f);
+        p.xhi = fminf(p.xhi, ((1.0f + grid_clamp) * (float)w - 1.0f) / 2.0f);
+        p.ylo = fmaxf(p.ylo, ((1.0f - grid_clamp) * (float)h - 1.0f) / 2.0f);
+        p.yhi = fminf(p.yhi, ((1.0f + grid_clamp) * (float)h - 1.0f) / 2.0f);
+        MVD_REQUIRE(p.xlo <= p.xhi && p.ylo <= p.yhi, "sweep_groupcorr_nhwc: grid_clamp=%f leaves no map", (double)grid_clamp);
+    }
+    p.B = B; p.C = C; p.D = D; p.h = h; p.w = w; p.V = V;
+    const int ppw = 256 / groups;  // groups <= C / 4 <= 16
+    const long long nbx = ((long long)h * w + ppw - 1) / ppw;
+    const int nby = (D + NHWC_DPB - 1) / NHWC_DPB;
+    MVD_REQUIRE(nbx <= 0x7fffffffLL && nby <= 65535, "sweep_groupcorr_nhwc: grid too large");
+    const dim3 grid((unsigned)nbx, (unsigned)nby, (unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+    switch (C / groups / 4) {
+        case 1: hipLaunchKernelGGL(sweep_groupcorr_nhwc_kernel<1>, grid, dim3(256), 0, st, p); break;
+        case 2: hipLaunchKernelGGL(sweep_groupcorr_nhwc_kernel<2>, grid, dim3(256), 0, st, p); break;
+        default: hipLaunchKernelGGL(sweep_groupcorr_nhwc_kernel<0>, grid, dim3(256), 0, st, p); break;
+    }
+    return launch_status("sweep_groupcorr_nhwc");
+}
 
 int mvd_sweep_reduce_nhwc_f32(const float* key_feat, const float* const* src_feat, const float* const* M, const float* depth,
                               int depth_per_pixel, float pix_offset, float scale_x, float scale_y, float bias, int mode, int B, int C,

@@ -582,6 +582,90 @@ def sweep_reduce_nhwc(key_feat, src_feats, Ms, depth, mode, pix_offset=0.0, stre
     return out
 
 
+@inference_only
+def sweep_groupcorr_nhwc(key_feat, src_feats, Ms, depth, groups, pix_offset=0.0, stretch=True, grid_clamp=0.0, out=None):
+    """sweep_modes.sweep_reduce's REDUCE_GROUPCORR on the engine's own layouts, without repacking (Vis-MVSNet's pair-wise cost
+    volumes): key_feat (B,h,w,C) channel-last; src_feats V x (B,h+3,w+3,C) channel-last, zero-bordered with the map at (1,1);
+    Ms V x (B,3,4) [R|t]; depth (B,D) or (B,D,h,w); C / groups a multiple of 4, C up to 64.  Returns V volumes (B,D,h,w,groups)
+    channel-last, consecutive slices of ONE (V B,D,h,w,groups) buffer (`out`, where given), each bit-identical to sweep_reduce's
+    (B,groups,D,h,w) permuted.  grid_clamp=1.1 adds the clamp of the reference's interpolate (blocks/utils.py:168: the normalised grid
+    to +-1.1 before grid_sample), which changes the values on maps narrower than 10 pixels only (include/mvd.h)."""
+    kf = L.as_f32(key_feat, "key_feat")
+    if kf.dim() != 4 or kf.shape[3] % 4 or kf.shape[3] > 64:
+        raise ValueError(f"key_feat must be (B,h,w,C) channel-last with C a multiple of 4 up to 64, got {tuple(kf.shape)}")
+    B, h, w, C = kf.shape
+    groups = int(groups)
+    if groups < 1 or C % groups or (C // groups) % 4:
+        raise ValueError(f"group correlation needs C/groups a multiple of 4, got {C}/{groups}")
+    dev = kf.device
+    srcs = [L.as_f32(s, f"src_feats[{i}]", (B, h + 3, w + 3, C), dev) for i, s in enumerate(views(src_feats, "src_feats"))]
+    V = len(srcs)
+    Ms = [L.as_f32(m, f"Ms[{i}]", (B, 3, 4), dev) for i, m in enumerate(views(Ms, "Ms", V))]
+    dv = L.as_f32(depth, "depth", device=dev)
+    if dv.dim() == 2 and dv.shape[0] == B:
+        per_pixel, D = 0, dv.shape[1]
+    elif dv.dim() == 4 and dv.shape[0] == B and tuple(dv.shape[2:]) == (h, w):
+        per_pixel, D = 1, dv.shape[1]
+    else:
+        raise ValueError(f"depth must be (B,D) or (B,D,h,w), got {tuple(dv.shape)}")
+    sx, sy = (w / (w - 1), h / (h - 1)) if stretch else (1.0, 1.0)
+    if out is None:
+        out = torch.empty((V * B, D, h, w, groups), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (V * B, D, h, w, groups) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 ({V * B},{D},{h},{w},{groups}) tensor on {dev}")
+    outs = [out[v * B:(v + 1) * B] for v in range(V)]
+    call("mvd_sweep_groupcorr_nhwc_f32", dev, kf, srcs, Ms, dv, per_pixel, float(pix_offset), float(sx), float(sy), -0.5, float(grid_clamp),
+         groups, B, C, D, h, w, V, outs)
+    return outs
+
+
+@inference_only
+def soft_argmin(score, depth_start, depth_interval, with_entropy=False, window=None):
+    """Vis-MVSNet's soft argmin (blocks/utils.py:51-68) in one kernel.  score (B,D,h,w); depth_start (B) or (B,h,w) (any shape with
+    B or B h w elements, e.g. the reference's n111 / n1hw); depth_interval (B) (or n111).
+    Returns (depth, entropy, prob_map), each (B,h,w): depth = (sum_i i p_i) * interval + start with p = softmax_D(score);
+    entropy = sum_i -p_i log(clamp(p_i, 1e-9, 1)) or None; prob_map = sum_i p_i [|i - index| <= window] or None (window=None)."""
+    c = L.as_f32(score, "score")
+    if c.dim() != 4:
+        raise ValueError("score must be (B,D,h,w)")
+    B, D, h, w = c.shape
+    dev = c.device
+    start = L.as_f32(depth_start, "depth_start", device=dev)
+    if start.numel() == B:
+        per_pixel, start = 0, start.reshape(B)
+    elif start.numel() == B * h * w:
+        per_pixel, start = 1, start.reshape(B, h, w)
+    else:
+        raise ValueError(f"depth_start must have {B} or {B}x{h}x{w} elements, got {tuple(start.shape)}")
+    interval = L.as_f32(depth_interval, "depth_interval", device=dev)
+    if interval.numel() != B:
+        raise ValueError(f"depth_interval must have {B} elements, got {tuple(interval.shape)}")
+    new = lambda: torch.empty((B, h, w), dtype=torch.float32, device=dev)
+    depth, ent, prob = new(), new() if with_entropy else None, new() if window is not None else None
+    call("mvd_soft_argmin_f32", dev, c, start, per_pixel, interval.reshape(B), float(window or 0.0), B, D, h, w, depth, ent, prob)
+    return depth, ent, prob
+
+
+@inference_only
+def vis_fuse(xs, us, out=None):
+    """Vis-MVSNet's "soft" fusion (vis_mvsnet_singlestage.py:263-266,302-303): xs V x (B,D,h,w,C) channel-last, C a multiple of 4;
+    us V x (B,h,w) (or (B,1,h,w)) -> (sum_v x_v exp(-u_v)) / (sum_v exp(-u_v)), (B,D,h,w,C)."""
+    xs = [L.as_f32(x, f"xs[{i}]") for i, x in enumerate(views(xs, "xs"))]
+    if xs[0].dim() != 5 or xs[0].shape[4] % 4 or any(x.shape != xs[0].shape or x.device != xs[0].device for x in xs):
+        raise ValueError(f"xs must be equal (B,D,h,w,C) channel-last volumes with C a multiple of 4, got {[tuple(x.shape) for x in xs]}")
+    B, D, h, w, C = xs[0].shape
+    dev = xs[0].device
+    us = [L.as_f32(u, f"us[{i}]", device=dev) for i, u in enumerate(views(us, "us", len(xs)))]
+    if any(u.numel() != B * h * w for u in us):
+        raise ValueError(f"us must be (B,h,w) = ({B},{h},{w}) maps, got {[tuple(u.shape) for u in us]}")
+    if out is None:
+        out = torch.empty_like(xs[0])
+    elif out.dtype != torch.float32 or out.device != dev or out.shape != xs[0].shape or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 {tuple(xs[0].shape)} tensor on {dev}")
+    call("mvd_vis_fuse_f32", dev, xs, us, B, D, h, w, C, len(xs), out)
+    return out
+
+
 class SplitConv2dWeights:
     """Packed split-operand weights of one 2-D layer (pack_conv2d_weights_split) with what conv2d_split needs to call it."""
     __slots__ = ("packed", "bias", "cin", "cin_pad", "cout", "kh", "kw", "stride", "mode")

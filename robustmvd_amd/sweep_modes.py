@@ -97,15 +97,17 @@ def cvp_proj_cost(ref_feature, src_features, ref_in, src_in, ref_ex, src_ex, dep
     return sweep_reduce(ref_feature, src_features, Ms, depth_hypos, mode)
 
 
-def _vis_transform(ref_cam, src_cam):
+def _vis_transform(ref_cam, src_cam, check_errors=True):
     """get_homographies (blocks/utils.py:95-152) in projective form: H(d) x = A x + b / d with
     A = K_r R_r R_l^T K_l^-1 and b = -K_r R_r (c_r - c_l) (the fronto-parallel normal n = R_l[2] gives n^T R_l^T K_l^-1 x = 1
-    for homogeneous pixel coordinates), i.e. d H(d) x = A x d + b: the [R | t] form of the sweep kernel."""
+    for homogeneous pixel coordinates), i.e. d H(d) x = A x d + b: the [R | t] form of the sweep kernel.
+    check_errors=False: the inverse without its singularity check, which synchronises with the host (the vis_mvsnet model's forward)."""
     Rl, Rr = ref_cam[:, 0, :3, :3].float(), src_cam[:, 0, :3, :3].float()
     tl, tr = ref_cam[:, 0, :3, 3:4].float(), src_cam[:, 0, :3, 3:4].float()
     Kl, Kr = ref_cam[:, 1, :3, :3].float(), src_cam[:, 1, :3, :3].float()
     c_rel = (-Rr.transpose(-2, -1) @ tr) - (-Rl.transpose(-2, -1) @ tl)
-    A = Kr @ Rr @ Rl.transpose(-2, -1) @ torch.inverse(Kl)
+    Kl_inv = torch.inverse(Kl) if check_errors else torch.linalg.inv_ex(Kl, check_errors=False).inverse
+    A = Kr @ Rr @ Rl.transpose(-2, -1) @ Kl_inv
     b = -(Kr @ Rr @ c_rel)
     return torch.cat((A, b), 2).contiguous()
 

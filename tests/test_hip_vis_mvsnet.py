@@ -1,0 +1,339 @@
+"""vis_mvsnet on the GPU: the three kernels it adds (mvd_sweep_groupcorr_nhwc_f32, mvd_soft_argmin_f32, mvd_vis_fuse_f32), its
+regulariser alone and the whole model against the reference's own VisMvsnet (tests/golden/g17_vis_mvsnet*.npz, made by
+tests/golden/make_golden_vis.py)."""
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_golden
+import gen_common as gc
+from test_vis_mvsnet_cpu import (CASES, FUSE_SHAPES, SA_SHAPES, fuse_inputs, fuse_reference, golden_state_dict, groupcorr_reference, sa_inputs,
+                                 sa_reference)
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available()
+    return torch.device("cuda:0")
+
+
+def T(x, dev):
+    return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+
+
+# ------------------------------------------------------------------------------------------------------- sweep_groupcorr_nhwc
+def nhwc(x):
+    return x.permute(0, 2, 3, 1).contiguous()
+
+
+def bordered(x):
+    """(B,C,h,w) -> zero-bordered channel-last (B,h+3,w+3,C) with the map at (1,1)"""
+    B, C, h, w = x.shape
+    buf = torch.zeros((B, h + 3, w + 3, C), dtype=torch.float32, device=x.device)
+    buf[:, 1:h + 1, 1:w + 1, :] = x.permute(0, 2, 3, 1)
+    return buf
+
+
+def sweep_inputs(B, C, h, w, D, V, seed, dev):
+    """features, [R|t] per view, and hypotheses that push samples across every border and behind the camera: planes from a negative
+    depth over depths close to the camera (large parallax) to far ones, where the source camera's 3 x longer focal length pushes the
+    map's rim out through all four borders; per pixel spread by +-50 %."""
+    rng = np.random.default_rng(seed)
+    feats = [T(rng.standard_normal((B, C, h, w)).astype(np.float32), dev) for _ in range(V + 1)]
+    K = gc.synthetic_intrinsics(h, w).astype(np.float64)
+    Ksrc = K.copy()
+    Ksrc[0, 0] *= 3.0
+    Ksrc[1, 1] *= 3.0
+    Ms = []
+    for v in range(V):
+        m = []
+        for b in range(B):
+            P = gc.synthetic_pose(rng, 0.1, 0.3).astype(np.float64)
+            P[:3, 3] *= np.array([1, -1, 1]) * (-1) ** (v + b)
+            m.append((Ksrc @ P[:3, :4] @ np.linalg.inv(np.vstack([np.hstack([K, np.zeros((3, 1))]), [0, 0, 0, 1]])))[:3, :4])
+        Ms.append(T(np.stack(m).astype(np.float32), dev))
+    planes = np.concatenate(([-0.7], np.geomspace(1.5, 20.0, D - 1))) if D > 1 else np.array([1.0])
+    shared = T(np.stack([planes * (1 + 0.1 * b) for b in range(B)]).astype(np.float32), dev)
+    per_pixel = (shared[:, :, None, None] * (0.5 + torch.from_numpy(rng.random((B, D, h, w)).astype(np.float32)).to(dev))).contiguous()
+    return feats, Ms, shared, per_pixel
+
+
+def border_crossings(Ms, shared, h, w):
+    """what the shared planes do under Vis-MVSNet's pixel convention (positions x + 0.5, index X / Z - 0.5), accumulated over views,
+    batch, planes and pixels: a sample in front of the camera leaves the map through each border, one stays inside, one lies behind"""
+    dev = shared.device
+    B = shared.shape[0]
+    ys, xs = torch.meshgrid(torch.arange(h, device=dev, dtype=torch.float32), torch.arange(w, device=dev, dtype=torch.float32), indexing="ij")
+    pix = torch.stack((xs + 0.5, ys + 0.5, torch.ones_like(xs)), 0).reshape(1, 3, -1)
+    seen = dict(left=False, right=False, top=False, bottom=False, inside=False, behind=False)
+    for M in Ms:
+        p = (M[:, :, :3] @ pix)[:, :, None, :] * shared[:, None, :, None] + M[:, :, 3].reshape(B, 3, 1, 1)
+        z = p[:, 2]
+        x, y = p[:, 0] / z - 0.5, p[:, 1] / z - 0.5
+        front = z > 0
+        for name, cond in (("left", x < -1), ("right", x > w), ("top", y < -1), ("bottom", y > h),
+                           ("inside", (x >= 0) & (x <= w - 1) & (y >= 0) & (y <= h - 1))):
+            seen[name] |= bool((cond & front).any())
+        seen["behind"] |= bool((z < 0).any())
+    return seen
+
+
+# (B, C, D, h, w, V, G): two batch elements and plane chunks with a remainder (20 = 8 + 8 + 4); an odd map with a partial last
+# workgroup; two quads per group; four groups (64 pixels per workgroup) with 19 planes; and one group of 12 quads (the kernel's
+# form for any quad count, one pixel per lane)
+GC_SHAPES = [(2, 32, 20, 8, 12, 2, 8), (1, 32, 3, 9, 13, 1, 8), (1, 64, 5, 8, 8, 3, 8), (1, 16, 19, 9, 13, 2, 4), (1, 48, 4, 6, 7, 1, 1)]
+
+
+@pytest.mark.parametrize("shape", GC_SHAPES)
+def test_sweep_groupcorr_nhwc_is_sweep_reduce_permuted(shape, dev):
+    """bit for bit, shared and per-pixel depth, Vis-MVSNet's pixel convention and the stretched one"""
+    from robustmvd_amd import _lib as L, ops, sweep_modes as SM
+    B, C, D, h, w, V, G = shape
+    feats, Ms, shared, per_pixel = sweep_inputs(B, C, h, w, D, V, 7, dev)
+    key, srcs = nhwc(feats[0]), [bordered(f) for f in feats[1:]]
+    for kw in (dict(pix_offset=0.5, stretch=False), dict(pix_offset=0.0, stretch=True)):
+        for depth in (shared, per_pixel):
+            want = SM.sweep_reduce_inference(feats[0], feats[1:], Ms, depth, L.REDUCE_GROUPCORR, groups=G, **kw)
+            got = ops.sweep_groupcorr_nhwc(key, srcs, Ms, depth, G, **kw)
+            assert len(got) == V
+            for gv, wv in zip(got, want):
+                assert tuple(gv.shape) == (B, D, h, w, G)
+                assert torch.equal(gv, wv.permute(0, 2, 3, 4, 1))
+                assert torch.isfinite(gv).all()
+            # the V volumes are consecutive slices of one (V B, D, h, w, G) buffer
+            assert all(gv.data_ptr() == got[0].data_ptr() + v * gv.numel() * 4 for v, gv in enumerate(got))
+    assert all(border_crossings(Ms, shared, h, w).values())
+
+
+@pytest.mark.parametrize("name", ["s", "p"])
+def test_sweep_groupcorr_nhwc_vis_golden(name, dev):
+    """g11's vis fixtures (the reference's own build_cost_volume + groupwise_correlation) at the project's atol = rtol = 1e-4"""
+    from robustmvd_amd import ops, sweep_modes as SM
+    g = load_golden("g11_sweep_modes")
+    ref, srcs = T(g["vis_ref"], dev), [T(g["vis_src0"], dev), T(g["vis_src1"], dev)]
+    ref_cam, src_cams = T(g["vis_ref_cam"], dev), [T(g["vis_src_cam0"], dev), T(g["vis_src_cam1"], dev)]
+    D = g[f"vis_{name}_cost0"].shape[2]
+    start, interval = T(g[f"vis_ds_{name}"], dev), T(g[f"vis_di_{name}"], dev)  # s: (B,1,1,1) shared, p: (B,1,h,w) per pixel
+    B, C, h, w = ref.shape
+    k = torch.arange(D, dtype=torch.float32, device=dev).view(1, D, 1, 1)
+    depth = start + interval * k
+    depth = depth.reshape(B, D) if depth.shape[2:] == (1, 1) else depth.expand(B, D, h, w).contiguous()
+    Ms = [SM._vis_transform(ref_cam, sc) for sc in src_cams]
+    got = ops.sweep_groupcorr_nhwc(nhwc(ref), [bordered(s) for s in srcs], Ms, depth, 8, pix_offset=0.5, stretch=False)
+    for v in range(2):
+        np.testing.assert_allclose(got[v].permute(0, 4, 1, 2, 3).cpu().numpy(), g[f"vis_{name}_cost{v}"], atol=1e-4, rtol=1e-4)
+
+
+@pytest.mark.parametrize("shape", [(2, 32, 6, 8, 12, 2, 8), (1, 32, 6, 8, 8, 2, 8), (1, 16, 6, 9, 13, 1, 4)])
+def test_sweep_groupcorr_nhwc_grid_clamp_vs_float64(shape, dev):
+    """grid_clamp = 1.1 against the reference's formulas in float64 torch (test_vis_mvsnet_cpu.groupcorr_reference, which the
+    reference's own homography_warping + groupwise_correlation reproduce to 6e-8) at the project's atol = rtol = 1e-4 for this
+    operator, on maps with a side below 10 pixels, where the clamp lets far samples take a tenth of the rim pixel; planes in front
+    of the cameras, samples leaving through every border.  Without the clamp the result differs there, and on a map with both
+    sides of at least 10 pixels the clamp changes no bit."""
+    from robustmvd_amd import ops
+    B, C, D, h, w, V, G = shape
+    feats, Ms, shared, _ = sweep_inputs(B, C, h, w, D + 1, V, 7, dev)
+    shared = shared[:, 1:].contiguous()  # without the plane behind the camera
+    key, srcs = nhwc(feats[0]), [bordered(f) for f in feats[1:]]
+    got = ops.sweep_groupcorr_nhwc(key, srcs, Ms, shared, G, pix_offset=0.5, stretch=False, grid_clamp=1.1)
+    plain = ops.sweep_groupcorr_nhwc(key, srcs, Ms, shared, G, pix_offset=0.5, stretch=False)
+    want = groupcorr_reference([f.cpu() for f in feats], [m.cpu() for m in Ms], shared.cpu(), G, 1.1)
+    for v in range(V):
+        np.testing.assert_allclose(got[v].cpu().numpy(), want[v].numpy(), atol=1e-4, rtol=1e-4)
+    if min(h, w) < 10:
+        assert max(float((g - q).abs().max()) for g, q in zip(got, plain)) > 1e-2  # the clamp is what makes them agree
+    else:
+        assert all(torch.equal(g, q) for g, q in zip(got, plain))
+
+
+def test_sweep_groupcorr_nhwc_rejects_invalid_arguments(dev):
+    from robustmvd_amd import ops
+    B, C, D, h, w, V, G = 1, 32, 3, 9, 13, 1, 8
+    feats, Ms, shared, _ = sweep_inputs(B, C, h, w, D, V, 7, dev)
+    key, src = nhwc(feats[0]), bordered(feats[1])
+    out = torch.empty((B, D, h, w, G), device=dev)
+
+    def status_1(key, src, C, G, out):
+        with pytest.raises(RuntimeError, match=r"status 1"):  # MVD_ERR_INVALID_ARG
+            ops.call("mvd_sweep_groupcorr_nhwc_f32", dev, key, [src], Ms, shared, 0, 0.5, 1.0, 1.0, -0.5, 0.0, G, B, C, D, h, w, V, [out])
+
+    status_1(key, src, C, 16, out)      # C / G = 2: not a multiple of 4
+    status_1(key, src, C, 3, out)       # G does not divide C
+    status_1(key, src, 128, 8, out)     # C > 64
+    status_1(key.reshape(-1)[1:], src, C, G, out)   # misaligned key
+    status_1(key, src.reshape(-1)[1:], C, G, out)   # misaligned source
+    status_1(key, src, C, G, torch.empty(out.numel() + 1, device=dev)[1:])  # misaligned output
+    with pytest.raises(ValueError):
+        ops.sweep_groupcorr_nhwc(key, [src], Ms, shared, 16)
+
+
+# ------------------------------------------------------------------------------------------------------- soft_argmin
+@pytest.mark.parametrize("shape", SA_SHAPES)
+def test_soft_argmin_vs_float64(shape, dev):
+    from robustmvd_amd import ops
+    B, D, h, w = shape
+    score, start, start_pp, interval = sa_inputs(B, D, h, w)
+    for st in (start, start_pp):
+        want_d, want_e, want_p, keep = sa_reference(score, st, interval, 2.0)
+        depth, ent, prob = ops.soft_argmin(T(score, dev), T(st, dev), T(interval, dev), with_entropy=True, window=2.0)
+        d, e, p = depth.cpu().numpy(), ent.cpu().numpy(), prob.cpu().numpy()
+        print(f"{shape}: max |depth err| {np.abs(d - want_d).max():.2e}, max |entropy err| {np.abs(e - want_e).max():.2e}, "
+              f"max |prob err| kept {np.abs(p - want_p)[keep].max():.2e}, kept {keep.mean():.4f}")
+        assert keep.mean() >= 0.99
+        np.testing.assert_allclose(d, want_d, atol=1e-5, rtol=1e-5)
+        np.testing.assert_allclose(e, want_e, atol=1e-5, rtol=1e-5)
+        np.testing.assert_allclose(p[keep], want_p[keep], atol=1e-5, rtol=0)
+        # NULL optional outputs leave the others bit-identical
+        d1, e1, p1 = ops.soft_argmin(T(score, dev), T(st, dev), T(interval, dev))
+        assert e1 is None and p1 is None and torch.equal(d1, depth)
+        d2, e2, p2 = ops.soft_argmin(T(score, dev), T(st, dev), T(interval, dev), with_entropy=True)
+        assert p2 is None and torch.equal(d2, depth) and torch.equal(e2, ent)
+        d3, e3, p3 = ops.soft_argmin(T(score, dev), T(st, dev), T(interval, dev), window=2.0)
+        assert e3 is None and torch.equal(d3, depth) and torch.equal(p3, prob)
+
+
+# ------------------------------------------------------------------------------------------------------- vis_fuse
+@pytest.mark.parametrize("shape", FUSE_SHAPES)
+def test_vis_fuse_vs_float64(shape, dev):
+    from robustmvd_amd import ops
+    B, D, h, w, C, V = shape
+    xs, us = fuse_inputs(B, D, h, w, C, V)
+    got = ops.vis_fuse([T(x, dev) for x in xs], [T(u, dev) for u in us]).cpu().numpy()
+    want = fuse_reference(xs, us)
+    # rtol 1e-5 of the terms: the sum of V signed terms can cancel, so the absolute part is 1e-5 of the largest |x|
+    np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-5 * max(np.abs(x).max() for x in xs))
+    if V == 1:
+        np.testing.assert_allclose(got, xs[0], rtol=1e-6, atol=0)
+
+
+# ------------------------------------------------------------------------------------------------------- the model
+def fresh_model(dev):
+    import robustmvd_amd as R
+    m = R.VisMvsnet().eval()
+    m.load_state_dict(golden_state_dict(load_golden(CASES["a"]), m), strict=True)
+    return m.to(dev)
+
+
+@pytest.fixture(scope="module")
+def model(dev):
+    import robustmvd_amd as R
+    return R.add_run_function(fresh_model(dev))
+
+
+def golden_inputs(g, dev):
+    from robustmvd_amd.vis_mvsnet import normalise_image
+    images = [normalise_image(T(im, dev)) for im in g["images"]]
+    return dict(images=images, poses=[T(p, dev) for p in g["poses"]], intrinsics=[T(k, dev) for k in g["intrinsics"]], keyview_idx=0,
+                depth_range=(g["depth_range"][0], g["depth_range"][1]))
+
+
+REG_ATOL, REG_RTOL = 2e-4, 1e-3  # the project's gate for the same kind of stack (g5, g16)
+
+
+@pytest.mark.parametrize("case,stage", [("a", 1), ("c", 3)])
+def test_regulariser_alone(case, stage, model, dev):
+    """the reference's own cost volumes (pair 0) through Reg -> reg_pair and through RegFuse: stage 1 of case a (64 planes on 8 x 8) and
+    stage 3 of case c (16 planes on 16 x 16)"""
+    from robustmvd_amd import ops
+    g = load_golden(CASES[case])
+    st = getattr(model, f"stage{stage}")
+    x = ops.to_channels_last_3d(T(g[f"cost_{stage}"], dev))
+    with torch.no_grad():
+        _, pair = st.pair_scores(x)
+        fuse = st.fused_score(x)
+    for got, name in ((pair, "reg_pair"), (fuse, "reg_fuse")):
+        want = g[f"{name}_{stage}"][:, 0]
+        print(f"{name} stage {stage}: max |err| {np.abs(got.cpu().numpy() - want).max():.2e} of max |ref| {np.abs(want).max():.2e}")
+        np.testing.assert_allclose(got.cpu().numpy(), want, atol=REG_ATOL, rtol=REG_RTOL, err_msg=name)
+
+
+@pytest.mark.parametrize("case", ["a", "b"])
+def test_whole_model_vs_reference(case, model, dev):
+    g = load_golden(CASES[case])
+    with torch.no_grad():
+        pred, aux = model(**golden_inputs(g, dev))
+    n, _, H, W = g["images"].shape[1:]
+    V = g["images"].shape[0] - 1
+    assert tuple(pred["depth"].shape) == (n, 1, H // 2, W // 2) and tuple(pred["depth_uncertainty"].shape) == (n, 1, H // 2, W // 2)
+    assert [tuple(p.shape) for p in aux["prob_maps"]] == [(n, 1, H // 2, W // 2)] * 3 and tuple(aux["ref_cam"].shape) == (n, 2, 4, 4)
+    assert len(aux["outputs"]) == 3 and all(len(o[1]) == V and len(o[1][0][1]) == 2 for o in aux["outputs"])
+    depths = [aux["outputs"][s][0][:, 0].cpu().numpy() for s in range(3)]
+    rels = [float(np.max(np.abs(depths[s] - g[f"depth_{s + 1}"]) / np.abs(g[f"depth_{s + 1}"]))) for s in range(3)]
+    unc = pred["depth_uncertainty"][:, 0].cpu().numpy()
+    keep = ~np.unpackbits(g["jump_3"])[:unc.size].reshape(unc.shape).astype(bool)
+    pairs = aux["outputs"][2][1]
+    pair_depth = np.stack([p[0][:, 0].cpu().numpy() for p in pairs])
+    heads = np.stack([np.stack([hd[:, 0].cpu().numpy() for hd in p[1]]) for p in pairs])
+    print(f"case {case}: max relative depth error per stage (coarse first) {rels}; max uncertainty error "
+          f"{np.max(np.abs(unc - g['uncertainty'])[keep]):.3e}; excluded {1 - keep.mean():.4f}; pair depth rel "
+          f"{np.max(np.abs(pair_depth - g['pair_depth_3']) / np.abs(g['pair_depth_3'])):.3e}; heads max err "
+          f"{np.max(np.abs(heads - g['pair_heads_3'])):.3e}; reference f32 vs f64 {float(g['ref_f32_vs_f64_rel']):.2e}")
+    assert keep.mean() >= 0.99
+    for s in range(3):  # coarse first: the first stage that is off is the one to look at
+        np.testing.assert_allclose(depths[s], g[f"depth_{s + 1}"], rtol=1e-3, atol=0, err_msg=f"stage {s + 1}")
+    assert torch.equal(pred["depth"], aux["outputs"][2][0])
+    np.testing.assert_allclose(unc[keep], g["uncertainty"][keep], atol=2e-3, rtol=0)
+    np.testing.assert_allclose(pair_depth, g["pair_depth_3"], rtol=1e-3, atol=0)
+    np.testing.assert_allclose(heads, g["pair_heads_3"], atol=2e-3, rtol=0)
+
+
+@pytest.mark.parametrize("case", ["a", "b"])
+def test_stage3_entropies_vs_reference(case, model, dev, monkeypatch):
+    """the stage-3 pair entropies (UncertNet's input) of the whole forward"""
+    g = load_golden(CASES[case])
+    seen, net = [], model.stage3.uncert_net.forward
+    monkeypatch.setattr(model.stage3.uncert_net, "forward", lambda x: seen.append(x) or net(x))
+    with torch.no_grad():
+        model(**golden_inputs(g, dev))
+    V, n = g["pair_entropy_3"].shape[:2]
+    ent = seen[0][:, 0].reshape(V, n, *seen[0].shape[2:]).cpu().numpy()  # the pairs are batched view-major
+    print(f"case {case}: max entropy error {np.abs(ent - g['pair_entropy_3']).max():.3e}")
+    np.testing.assert_allclose(ent, g["pair_entropy_3"], atol=2e-3, rtol=0)
+
+
+# ------------------------------------------------------------------------------------------------------- protocol
+def test_run_numpy_unbatched(model, dev):
+    """batch element 0 of case b (64 x 128: the adapter leaves a multiple of 64 as it is) as raw 0 .. 255 images through run()"""
+    g = load_golden(CASES["b"])
+    pred, aux = model.run(images=[im[0].astype(np.float32) for im in g["images"]], keyview_idx=0, poses=[p[0] for p in g["poses"]],
+                          intrinsics=[k[0] for k in g["intrinsics"]], depth_range=(np.float32(2.0), np.float32(10.0)))
+    assert isinstance(pred["depth"], np.ndarray) and pred["depth"].shape == (1, 32, 64) and pred["depth_uncertainty"].shape == (1, 32, 64)
+    assert [p.shape for p in aux["prob_maps"]] == [(1, 32, 64)] * 3 and aux["ref_cam"].shape == (2, 4, 4)
+    np.testing.assert_allclose(pred["depth"][0], g["depth_3"][0], rtol=1e-3, atol=0)
+
+
+def test_adapter_upscales_to_a_multiple_of_64(model, dev):
+    """70 x 100 -> 128 x 128, default depth range; the depth is stage 3's, at half resolution"""
+    s = gc.synthetic_sample(3, 70, 100, 2)
+    pred, _ = model.run(images=s["images"], keyview_idx=0, poses=s["poses"], intrinsics=s["intrinsics"])
+    assert pred["depth"].shape == (1, 64, 64) and pred["depth_uncertainty"].shape == (1, 64, 64)
+    assert np.isfinite(pred["depth"]).all() and np.isfinite(pred["depth_uncertainty"]).all()
+    assert pred["depth"][0].shape == (64, 64)
+
+
+def test_buffer_cache_is_keyed_by_shape_and_views(dev):
+    """two forwards with different (n, H, W, V) in one model, then the first again: each the same bits as a fresh model's"""
+    ga, gb = load_golden(CASES["a"]), load_golden(CASES["b"])
+    ia, ib = golden_inputs(ga, dev), golden_inputs(gb, dev)
+    for k in ("images", "poses", "intrinsics"):  # case b with ONE source view: (2, 64, 128, 1) against (1, 64, 64, 2)
+        ib[k] = ib[k][:2]
+    with torch.no_grad():
+        want_a, want_b = fresh_model(dev)(**ia)[0], fresh_model(dev)(**ib)[0]
+        shared = fresh_model(dev)
+        got_a, got_b, again_a = shared(**ia)[0], shared(**ib)[0], shared(**ia)[0]
+    assert len(shared._bufs) == 2
+    for got, want in ((got_a, want_a), (got_b, want_b), (again_a, want_a)):
+        assert torch.equal(got["depth"], want["depth"]) and torch.equal(got["depth_uncertainty"], want["depth_uncertainty"])
+    assert torch.isfinite(want_b["depth"]).all()
+
+
+def test_key_view_other_than_0_is_the_views_reordered(model, dev):
+    g = load_golden(CASES["a"])
+    base = golden_inputs(g, dev)
+    swapped = dict(base, keyview_idx=1, **{k: [base[k][1], base[k][0], base[k][2]] for k in ("images", "poses", "intrinsics")})
+    with torch.no_grad():
+        want, got = model(**base)[0], model(**swapped)[0]
+    assert torch.equal(got["depth"], want["depth"]) and torch.equal(got["depth_uncertainty"], want["depth_uncertainty"])
