@@ -552,6 +552,47 @@ int mvd_resize_order1_f32(const float* src, float* dst, long long planes, int hi
  * pred (N,2,HW): channel 0 = relu(x0), channel 1 = sigmoid(x1 * 0.2) * 20 - 10; ent (N,1,HW) = log(2 exp(pred1) + 1e-4) + 1. */
 int mvd_dispnet_head_f32(const float* x, float* pred, float* ent, int N, long long HW, mvd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Scoring of the multi-view depth evaluation on the device — replaces the numpy post-processing and metrics of
+ *   rmvd/eval/multi_view_depth_evaluation.py:469-547,583-610 and rmvd/eval/metrics.py:32-220.
+ * gt (H,W); pred and the optional uncertainty (h,w), any size relation.  The nearest resize to (H,W) is a gather through two
+ * int32 tables: output row y reads input row row[y] in [0,h), output column x reads col[x] in [0,w); the rule of
+ * skimage.transform.resize(order=0) is floor((o + 0.5) * (n_in / n_out)) in float64, clamped.  The tables are trusted.
+ * mask = gt > 0, and pred != 0 when sparse_pred.  All cross-workgroup float reductions are partials summed in a fixed order (two
+ * calls give the same bits); workspace: mvd_depth_eval_workspace_bytes(H, W), shared by the three entries that take one. */
+#define MVD_ALIGN_NONE 0
+#define MVD_ALIGN_MEDIAN 1 /* ratio = median(gt[mask]) / median(pred[mask]), np.median on float32, exact radix select */
+#define MVD_ALIGN_LSQ 2    /* least-squares scale and shift on nan_to_num(1 / x), five float64 sums */
+size_t mvd_depth_eval_workspace_bytes(int H, int W);
+
+/* params (8 floats, device): [0] ratio (median; NaN = leave the prediction unscaled) or scale (least squares; NaN when the mask is
+ *   empty or det <= 0), [1] shift, [2] median(gt[mask]), [3] median(pred[mask]), [4] 1 when the mask is not empty (median) or
+ *   det > 0 (least squares), [5] min of the resized uncertainty over ALL (H,W) pixels (NaN without one, or when one is NaN).
+ * sums (5 doubles, device, may be NULL; least squares only): sum p^2, sum p, n, sum g p, sum g. */
+int mvd_depth_align_stats_f32(const float* gt, const float* pred, const float* uncertainty, const int* row, const int* col, int H,
+                              int W, int h, int w, int mode, int sparse_pred, float* params, double* sums, void* workspace,
+                              size_t workspace_bytes, mvd_stream_t stream);
+
+/* One run's alignment (params[0..1] read from DEVICE memory: mvd_depth_align_stats_f32's or the caller's own; may be NULL for
+ * MVD_ALIGN_NONE), clip to [clip_lo, clip_hi] times the prediction mask when clip, invdepth = nan_to_num(1 / pred), rel_ae =
+ * nan_to_num(|pred - gt| / gt) * mask and the inlier test 0 < max(nan_to_num(gt / pred -> thresh_plus_one), nan_to_num(pred / gt))
+ * < thresh.  result (40 bytes, device, 8-byte aligned): double sum of rel_ae; int64 count of the mask, of the inliers in it, of the
+ * evaluated pixels (pred_aligned != 0 when sparse_pred, else all); float min of rel_ae over all pixels; 4 bytes of scratch.
+ * The four (H,W) maps are written where their pointer is not NULL. */
+int mvd_depth_score_f32(const float* gt, const float* pred, const float* uncertainty, const int* row, const int* col, int H, int W,
+                        int h, int w, int mode, int sparse_pred, int clip, float clip_lo, float clip_hi, float thresh,
+                        float thresh_plus_one, const float* params, void* result, float* pred_out, float* invdepth_out,
+                        float* rel_ae_out, float* uncertainty_out, void* workspace, size_t workspace_bytes, mvd_stream_t stream);
+
+/* keys[p] = ((u[p] - u_min[0]) + 1) * mask[p] in float32 (metrics.py:169); u, gt, pred_aligned, keys: n floats; u_min on the device. */
+int mvd_rank_keys_f32(const float* u, const float* u_min, const float* gt, const float* pred_aligned, int sparse_pred, long long n,
+                      float* keys, mvd_stream_t stream);
+
+/* ranked: n errors in ranked order (the valid pixels first); count[0] (device int64, clamped to n): the number of valid ones.
+ * step_sums[i], i < 100 = float64 sum of ranked[int((count / 100) * i) .. count), the steps formed on the device in float64. */
+int mvd_ranked_step_sums_f64(const float* ranked, long long n, const long long* count, double* step_sums, void* workspace,
+                             size_t workspace_bytes, mvd_stream_t stream);
+
 /* layout helpers used at the operator-level boundary (reference tensors are NCHW / NCDHW) */
 int mvd_nchw_to_nhwc_f32(const float* src, float* dst, int N, int C, long long HW, mvd_stream_t stream);
 int mvd_nhwc_to_nchw_f32(const float* src, float* dst, int N, int C, long long HW, mvd_stream_t stream);

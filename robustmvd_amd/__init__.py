@@ -18,3 +18,5 @@ from .vis_mvsnet import VisMvsnet  # noqa: F401  (registers vis_mvsnet)
 from .ops import sweep_groupcorr_nhwc, soft_argmin, vis_fuse  # noqa: F401
 from .serving import FramePipeline, PinnedUploader  # noqa: F401
 from .sweep_modes import cvp_proj_cost, vis_cost_volumes, sweep_reduce  # noqa: F401
+from . import eval  # noqa: F401,E402
+from .eval import create_evaluation, list_evaluations, MultiViewDepthEvaluation  # noqa: F401,E402

@@ -30,6 +30,7 @@ INVDEPTH_SHARED, INVDEPTH_BATCHED, INVDEPTH_PER_PIXEL = 0, 1, 2
 REDUCE_VARIANCE = 0
 REDUCE_VARIANCE_KEYSQ = 1
 REDUCE_GROUPCORR = 2
+ALIGN_NONE, ALIGN_MEDIAN, ALIGN_LSQ = 0, 1, 2  # MVD_ALIGN_*
 K3_GATHER_RADIUS = 3  # MVD_K3_GATHER_RADIUS: the gather backward's window is (2 * 3 + 1)^2 key pixels per plane
 
 _c_float_p = ctypes.c_void_p
@@ -131,6 +132,14 @@ SIGNATURES = {
     "mvd_resize_order1_f32": (_i, [_c_float_p, _c_float_p, ctypes.c_longlong, _i, _i, _i, _i, ctypes.c_void_p]),
     "mvd_nchw_to_nhwc_f32": (_i, [_c_float_p, _c_float_p, _i, _i, ctypes.c_longlong, ctypes.c_void_p]),
     "mvd_nhwc_to_nchw_f32": (_i, [_c_float_p, _c_float_p, _i, _i, ctypes.c_longlong, ctypes.c_void_p]),
+    "mvd_depth_eval_workspace_bytes": (_sz, [_i, _i]),
+    "mvd_depth_align_stats_f32": (_i, [_c_float_p] * 3 + [ctypes.c_void_p] * 2 + [_i] * 6 + [_c_float_p, ctypes.c_void_p,
+                                                                                            ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "mvd_depth_score_f32": (_i, [_c_float_p] * 3 + [ctypes.c_void_p] * 2 + [_i] * 7 + [ctypes.c_float] * 4
+                            + [_c_float_p, ctypes.c_void_p] + [_c_float_p] * 4 + [ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "mvd_rank_keys_f32": (_i, [_c_float_p] * 4 + [_i, ctypes.c_longlong, _c_float_p, ctypes.c_void_p]),
+    "mvd_ranked_step_sums_f64": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _sz,
+                                      ctypes.c_void_p]),
 }
 
 # built into the product library only (csrc/Makefile PRODSRCS): the experiments library has no variants of these

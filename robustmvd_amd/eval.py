@@ -1,0 +1,389 @@
+"""The robust multi-view depth benchmark's evaluation (rmvd/eval/): create_evaluation("mvd") and MultiViewDepthEvaluation.
+
+    from robustmvd_amd import create_model, create_evaluation
+    evaluation = create_evaluation("mvd", out_dir=None, inputs=["poses", "intrinsics"], alignment=None)
+    results = evaluation(dataset=samples, model=create_model("robust_mvd", pretrained=False))
+
+Constructor and call arguments, control flow (_evaluate, multi_view_depth_evaluation.py:269-357), metric names and the returned
+frame are the reference's: the source views are ordered ("quasi-optimal": one model run per source view, ranked by absrel; or
+"nearest"), the model is run with every prefix of that order from min_source_views to max_source_views, each run is logged under
+the column level num_views, the run with the lowest finite absrel is logged as "best", and the AUSE is computed on that run.
+
+Differences from the reference:
+
+* Dataset.  `dataset` is any sequence (len() and [i]) of the reference's unbatched numpy sample dicts (rmvd/data/README.md:153-206:
+  images, poses, intrinsics, keyview_idx, depth, invdepth, depth_range).  Samples are batched with this package's numpy_collate;
+  dataset.get_loader(batch_size=1, indices=, num_workers=0, collate_fn=) is used when the object has one; dataset.name is optional.
+* Where scoring runs.  When the model's output is on the GPU, the raw output of model(**model.input_adapter(...)) is scored on
+  the device by the kernels of csrc/depth_eval.hip (depth_score.DeviceScorer): the ground truth is uploaded once per sample and
+  reused by all of that sample's runs, and a run costs one 72-byte device-to-host read.  model.output_adapter is still called,
+  inside the runtime_model_and_io window, so that column means what it does in the reference; its numpy result is not used for
+  scoring.  The host is synchronised before start_model and before end_model, otherwise runtime_model would time a kernel launch
+  and not the model.
+* Host path.  When the output is on the CPU, or with device_scoring=False, depth_score.score_numpy does the same work in numpy.
+  It restates the reference's formulas; sums are float64 where the reference's are float32, and the sparsification is the
+  vectorised closed form (suffix means at the step positions, then np.interp) instead of the loop over every valid pixel.  It runs
+  on NumPy 2, where the reference's valid_mean raises (nan_to_num(copy=False) on a scalar).
+* Memory columns.  gpu_mem_alloc_in_mib is the allocated peak and a separate gpu_mem_reserved_in_mib the reserved one (the
+  reference writes both under the first key, so its column holds the reserved peak).  Both are NaN without a GPU.
+* Output files.  With out_dir the reference's result files are written: results.{csv,pickle}, num_source_view_results.{csv,pickle}
+  and sparsification_curves.{csv,pickle}, each per sample (per_sample/) and averaged, .results_df.pickle (a later call that finds
+  it returns it without running the model), log.txt and the qualitative .npy maps (pointwise_absrel, pred_depth, pred_invdepth,
+  pred_depth_uncertainty).  The curves are averaged with groupby(level=1).mean(); mean(level=) no longer exists in pandas 2.
+  Not written: PNG renderings, the dataset layout / update pickles and dataset.cfg, tensorboard scalars.
+* A sample without any finite absrel (no valid ground-truth pixel) is logged with its first run as "best" and NaN uncertainty
+  metrics, and a model without a depth_uncertainty output gets no uncertainty metrics; the reference raises in both cases.
+* robust_mvd_benchmark.py, the loop over the five benchmark datasets, is not part of this package.
+"""
+import os
+import os.path as osp
+import time
+from copy import deepcopy
+
+import numpy as np
+import torch
+
+from . import depth_score as DS
+from .utils import numpy_collate, select_by_index
+
+CURVES = ("oracle", "pred", "error")
+
+
+def filter_views_in_sample(sample, indices_to_keep):
+    """A copy of the batched sample with only the views `indices_to_keep` (which must hold the key view)."""
+    sample = deepcopy(sample)
+    key = _as_int(sample["keyview_idx"])
+    if key not in indices_to_keep:
+        raise ValueError("the key view must be kept")
+    for name in ("images", "poses", "intrinsics"):
+        if name in sample:
+            sample[name] = [select_by_index(sample[name], i) for i in indices_to_keep]
+    sample["keyview_idx"] = np.array([indices_to_keep.index(key)])
+    return sample
+
+
+def _as_int(x):
+    """keyview_idx of a batch of one: an int, or an array with one entry"""
+    return int(np.asarray(x).reshape(-1)[0])
+
+
+def _first_map(x):
+    """(1,1,h,w) / (1,h,w) / (h,w) -> (h,w)"""
+    return x.reshape(x.shape[-2], x.shape[-1])
+
+
+class _Run:
+    """One model run: its Score, and what is needed to score it again with the per-pixel maps."""
+
+    def __init__(self, score, depth, uncertainty, on_device):
+        self.score, self.depth, self.uncertainty, self.on_device = score, depth, uncertainty, on_device
+
+    def keep(self):
+        if self.on_device:  # a model may hand out the same buffers again on its next run
+            self.depth = self.depth.clone()
+            self.uncertainty = self.uncertainty.clone() if self.uncertainty is not None else None
+        return self
+
+
+class MultiViewDepthEvaluation:
+    """Multi-view depth evaluation of a model on a dataset; see the module docstring.
+
+    out_dir: where results are written; None writes nothing.
+    inputs: modalities given to the model besides "images": "intrinsics", "poses", "depth_range".
+    alignment: None, "median" (scale by the ratio of medians) or "least_squares_scale_shift" (in inverse depth).
+    max_source_views / min_source_views: range of the number of source views; None = all available.
+    view_ordering: "quasi-optimal", "nearest" or None.
+    eval_uncertainty: also compute the sparsification curves and the AUSE of pred["depth_uncertainty"].
+    clip_pred_depth: True = clip predictions to [0.1, 100], a (lo, hi) tuple, or False.
+    sparse_pred: zeros in the prediction mark invalid pixels, which are left out.
+    device_scoring: score GPU outputs on the GPU (default); False always uses the numpy path.
+    """
+
+    def __init__(self, out_dir=None, inputs=None, alignment=None, max_source_views=None, min_source_views=1,
+                 view_ordering="quasi-optimal", eval_uncertainty=True, clip_pred_depth=True, sparse_pred=False, verbose=True,
+                 device_scoring=True, **_):
+        if alignment not in DS.ALIGNMENTS:
+            raise ValueError(f"alignment {alignment!r}: expected one of {DS.ALIGNMENTS}")
+        if view_ordering not in ("quasi-optimal", "nearest", None):
+            raise ValueError(f"view_ordering {view_ordering!r}: expected 'quasi-optimal', 'nearest' or None")
+        self.verbose = verbose
+        self.out_dir = out_dir
+        self.sample_results_dir = self.qualitatives_dir = self.results_file = self.log_file_path = None
+        if out_dir is not None:
+            self.sample_results_dir = osp.join(out_dir, "per_sample")
+            self.qualitatives_dir = osp.join(out_dir, "qualitative")
+            self.results_file = osp.join(out_dir, ".results_df.pickle")
+            self.log_file_path = osp.join(out_dir, "log.txt")
+            for d in (out_dir, self.sample_results_dir, self.qualitatives_dir):
+                os.makedirs(d, exist_ok=True)
+        self.inputs = list(set(list(inputs) + ["images"])) if inputs is not None else ["images"]
+        self.alignment = alignment
+        self.max_source_views = max_source_views
+        self.min_source_views = min_source_views if max_source_views is None else min(min_source_views, max_source_views)
+        self.view_ordering = view_ordering if max_source_views is None or max_source_views > 0 else None
+        self.eval_uncertainty = eval_uncertainty
+        self.clip_pred_depth = clip_pred_depth
+        self.sparse_pred = sparse_pred
+        self.device_scoring = device_scoring
+        self._clip = DS.normalize_clip(clip_pred_depth)
+        self._reset()
+        self._log(str(self))
+
+    @property
+    def name(self):
+        return type(self).__name__
+
+    def __str__(self):
+        rows = [("Inputs", self.inputs), ("Alignment", self.alignment), ("Min source views", self.min_source_views),
+                ("Max source views", "All" if self.max_source_views is None else self.max_source_views),
+                ("View ordering", self.view_ordering), ("Evaluate uncertainty", self.eval_uncertainty),
+                ("Clip predicted depth", self.clip_pred_depth), ("Predicted depth is sparse", self.sparse_pred),
+                ("Score on the device", self.device_scoring),
+                ("Output directory", self.out_dir if self.out_dir is not None else "None. Results will not be written to disk!")]
+        return f"{self.name} with settings:" + "".join(f"\n\t{k}: {v}" for k, v in rows)
+
+    def _log(self, msg=""):
+        if self.verbose:
+            print(msg)
+        if self.log_file_path is not None:
+            with open(self.log_file_path, "a") as f:
+                f.write(str(msg) + "\n")
+
+    def _reset(self):
+        self.dataset = self.model = self.eval_name = self.finished_iterations = None
+        self.sample_indices = self.qualitative_indices = self.burn_in_samples = None
+        self.cur_sample_num = self.cur_sample_idx = 0
+        self.results = self.sparsification_curves = None
+        self._scorer = None
+
+    @torch.no_grad()
+    def __call__(self, dataset, model, samples=None, qualitatives=10, burn_in_samples=3, eval_name=None, finished_iterations=None,
+                 **_):
+        """Evaluates `model` on `dataset` and returns the results frame: one row per sample, columns (num_views, metric) with
+        num_views 1..n and "best".
+
+        samples: number of (evenly spaced) samples, a list of indices, or None for all.
+        qualitatives: number of samples, a list of indices, or -1 for all, whose per-pixel maps are written to out_dir.
+        burn_in_samples: samples at the start whose runtime and memory columns are NaN.
+        """
+        import pandas as pd
+        if self.results_file is not None and osp.exists(self.results_file):
+            self._log(f"Skipping evaluation {self.name} because it is already finished.")
+            return pd.read_pickle(self.results_file)
+        self.dataset, self.model = dataset, model
+        self.eval_name, self.finished_iterations, self.burn_in_samples = eval_name, finished_iterations, burn_in_samples
+        self._init_indices(samples, qualitatives)
+        self._init_results()
+        for num, (idx, sample) in enumerate(zip(self.sample_indices, self._loader())):
+            self.cur_sample_num, self.cur_sample_idx = num, idx
+            self._evaluate_sample(sample)
+        results = self.results
+        self._output_results()
+        self._reset()
+        return results
+
+    # ---- set-up ----
+    def _init_indices(self, samples, qualitatives):
+        n = len(self.dataset)
+        if isinstance(samples, list):
+            self.sample_indices = samples
+        elif isinstance(samples, int) and samples > 0:
+            self.sample_indices = [int(i * (n / samples)) for i in range(samples)]
+        else:
+            self.sample_indices = list(range(n))
+        if qualitatives is None:
+            self.qualitative_indices = []
+        elif isinstance(qualitatives, list):
+            self.qualitative_indices = qualitatives
+        elif qualitatives < 0:
+            self.qualitative_indices = self.sample_indices
+        else:
+            step = len(self.sample_indices) / qualitatives if qualitatives else 0
+            self.qualitative_indices = list({self.sample_indices[int(i * step)] for i in range(qualitatives)})
+
+    def _init_results(self):
+        import pandas as pd
+        frame = pd.DataFrame()
+        frame.index.name = "sample_idx"
+        frame.columns.name = "metric"
+        self.results = pd.concat({1: frame}, axis=1, names=["num_views"])
+        if self.eval_uncertainty:
+            columns = pd.Index(np.linspace(0, 0.99, DS.NUM_STEPS), name="frac_removed")
+            index = pd.MultiIndex.from_tuples([], names=("sample_idx", "curve"))
+            self.sparsification_curves = pd.DataFrame(columns=columns, index=index)
+
+    def _loader(self):
+        if hasattr(self.dataset, "get_loader"):  # batch_size=1 keeps the runtimes comparable
+            return self.dataset.get_loader(batch_size=1, indices=self.sample_indices, num_workers=0, collate_fn=numpy_collate)
+        return (numpy_collate([self.dataset[i]]) for i in self.sample_indices)
+
+    # ---- one sample ----
+    def _evaluate_sample(self, sample):
+        self._log(f"Processing sample {self.cur_sample_num + 1} / {len(self.sample_indices)} (index: {self.cur_sample_idx}):")
+        self._scorer = None  # the next GPU output uploads this sample's ground truth
+        keyview_idx = _as_int(sample["keyview_idx"])
+        is_input = lambda key: key in self.inputs or key == "keyview_idx"
+        inputs = {k: v for k, v in sample.items() if is_input(k)}
+        gt = {k: v for k, v in sample.items() if not is_input(k)}
+        gt_depth = np.ascontiguousarray(_first_map(gt["depth"]), dtype=np.float32)
+
+        order = self._source_view_ordering(inputs, gt_depth)
+        most = len(order) if self.max_source_views is None else min(len(order), self.max_source_views)
+        best = best_metrics = first = None
+        for num_source_views in range(self.min_source_views, most + 1):
+            sources = order[:num_source_views]
+            self._log(f"\tEvaluating with {num_source_views} / {most} source views:\n\t\tSource view indices: {sources}.")
+            self._reset_memory_stats()
+            run, runtimes, gpu_mem = self._run_and_score(filter_views_in_sample(inputs, sorted([keyview_idx] + sources)), gt_depth)
+            metrics = DS.metrics(run.score)
+            metrics.update(runtimes)
+            metrics.update(gpu_mem)
+            self._log_metrics(metrics, num_source_views)
+            self._log(f"\t\tAbsrel={metrics['absrel']}.")
+            if first is None:
+                first = (dict(metrics, num_views=num_source_views), run.keep())
+            if np.isfinite(metrics["absrel"]) and (best_metrics is None or metrics["absrel"] < best_metrics["absrel"]):
+                best_metrics, best = metrics, run.keep()
+                best_metrics["num_views"] = num_source_views
+        if first is None:
+            raise ValueError(f"sample {self.cur_sample_idx}: no run (min_source_views {self.min_source_views} > {most} source views)")
+        scored = best is not None
+        if not scored:
+            best_metrics, best = first
+
+        should_qualitative = self.cur_sample_idx in self.qualitative_indices and self.out_dir is not None
+        need_maps = should_qualitative or (self.eval_uncertainty and scored and best.uncertainty is not None)
+        full = self._score(best.depth, best.uncertainty, gt_depth, maps=True) if need_maps else None
+        if self.eval_uncertainty and scored and best.uncertainty is not None:
+            self._log("\tComputing uncertainty metrics:")
+            best_metrics.update(self._uncertainty_metrics(full, gt_depth))
+        elif self.eval_uncertainty:
+            best_metrics["ause"] = np.nan
+        self._log_metrics(best_metrics, "best")
+        if should_qualitative:
+            self._write_qualitatives(full)
+        self._log(f"Sample with index {self.cur_sample_idx} has AbsRel={best_metrics['absrel']} with {best_metrics['num_views']} "
+                  "source views.\n")
+
+    def _source_view_ordering(self, inputs, gt_depth):
+        key = _as_int(inputs["keyview_idx"])
+        sources = [i for i in range(len(inputs["images"])) if i != key]
+        if self.view_ordering != "quasi-optimal":
+            return sorted(sources, key=lambda i: abs(i - key))
+        absrel = {}
+        for i in sources:  # one run per (key view, source view) pair
+            run, _, _ = self._run_and_score(filter_views_in_sample(inputs, [key, i]), gt_depth)
+            absrel[i] = DS.metrics(run.score)["absrel"]
+        return sorted(absrel, key=absrel.get)
+
+    def _reset_memory_stats(self):
+        if torch.cuda.is_available():
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            torch.cuda.reset_accumulated_memory_stats()
+
+    def _run_and_score(self, sample_inputs, gt_depth):
+        sync = torch.cuda.synchronize if torch.cuda.is_available() else (lambda: None)
+        start_io = time.time()
+        if hasattr(self.model, "input_adapter"):
+            sample_inputs = self.model.input_adapter(**sample_inputs)
+        sync()
+        start_model = time.time()
+        raw = self.model(**sample_inputs)
+        sync()
+        end_model = time.time()
+        adapted = self.model.output_adapter(raw)[0] if hasattr(self.model, "output_adapter") else None
+        end_io = time.time()
+
+        valid = self.cur_sample_num >= self.burn_in_samples
+        t_model = end_model - start_model if valid else np.nan
+        t_io = end_io - start_io if valid else np.nan
+        runtimes = {"runtime_model_in_sec": t_model, "runtime_model_in_msec": 1000 * t_model,
+                    "runtime_model_and_io_in_sec": t_io, "runtime_model_and_io_in_msec": 1000 * t_io}
+        mib = lambda b: int(b / 1024 / 1024)
+        have = valid and torch.cuda.is_available()
+        gpu_mem = {"gpu_mem_alloc_in_mib": mib(torch.cuda.max_memory_allocated()) if have else np.nan,
+                   "gpu_mem_reserved_in_mib": mib(torch.cuda.max_memory_reserved()) if have else np.nan}
+
+        pred = raw[0] if isinstance(raw, (tuple, list)) else raw
+        depth = pred["depth"]
+        on_device = self.device_scoring and isinstance(depth, torch.Tensor) and depth.is_cuda
+        if not on_device and adapted is not None:
+            pred, depth = adapted, adapted["depth"]
+        unc = pred.get("depth_uncertainty")
+        if not on_device:
+            to_np = lambda x: None if x is None else (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x))
+            depth, unc = to_np(depth), to_np(unc)
+        depth, unc = _first_map(depth), (_first_map(unc) if unc is not None else None)
+        run = _Run(self._score(depth, unc, gt_depth, maps=False), depth, unc, on_device)
+        return run, runtimes, gpu_mem
+
+    def _score(self, depth, unc, gt_depth, maps):
+        if isinstance(depth, torch.Tensor):
+            if self._scorer is None or self._scorer.device != depth.device:
+                self._scorer = DS.DeviceScorer(gt_depth, depth.device, self.alignment, self.sparse_pred, self._clip)
+            return self._scorer.score(depth, unc, maps=maps)
+        return DS.score_numpy(gt_depth, depth, unc, self.alignment, self.sparse_pred, self._clip, maps=maps)
+
+    def _uncertainty_metrics(self, full, gt_depth):
+        if isinstance(full.rel_ae, torch.Tensor):
+            oracle, pred = self._scorer.uncertainty_curves(full)
+        else:
+            oracle, pred = DS.uncertainty_curves_numpy(gt_depth, full, self.sparse_pred)
+        error, ause = DS.ause(oracle, pred)
+        for name, curve in zip(CURVES, (oracle, pred, error)):
+            self.sparsification_curves.loc[(self.cur_sample_idx, name), :] = curve
+        self._log(f"\t\t\tAUSE={ause}.")
+        return {"ause": ause}
+
+    def _log_metrics(self, metrics, num_views):
+        for metric, val in metrics.items():
+            self.results.loc[self.cur_sample_idx, (num_views, metric)] = val
+
+    def _write_qualitatives(self, full):
+        host = lambda x: x.cpu().numpy() if isinstance(x, torch.Tensor) else x
+        maps = {"pointwise_absrel": full.rel_ae, "pred_depth": full.pred_depth, "pred_invdepth": full.pred_invdepth}
+        if full.uncertainty is not None:
+            maps["pred_depth_uncertainty"] = full.uncertainty
+        for name, m in maps.items():
+            np.save(osp.join(self.qualitatives_dir, f"{self.cur_sample_idx:07d}-{name}.npy"), host(m)[None])
+
+    # ---- output ----
+    def _output_results(self):
+        per_sample = self.results["best"]
+        mean = per_sample.mean()
+        views_per_sample = self.results.drop("best", axis=1, level=0)
+        views_mean = views_per_sample.mean()
+        self._log("\nResults:")
+        self._log(mean)
+        if self.out_dir is None:
+            return
+        self._log(f"Writing results to {self.out_dir}.")
+
+        def write(obj, directory, stem):
+            obj.to_pickle(osp.join(directory, stem + ".pickle"))
+            obj.to_csv(osp.join(directory, stem + ".csv"))
+
+        write(per_sample, self.sample_results_dir, "results")
+        write(mean, self.out_dir, "results")
+        write(views_per_sample, self.sample_results_dir, "num_source_view_results")
+        write(views_mean, self.out_dir, "num_source_view_results")
+        if self.eval_uncertainty:
+            write(self.sparsification_curves.astype(np.float64).groupby(level=1).mean(), self.out_dir, "sparsification_curves")
+            write(self.sparsification_curves, self.sample_results_dir, "sparsification_curves")
+        self.results.to_pickle(self.results_file)
+
+
+_EVALUATIONS = {"mvd": MultiViewDepthEvaluation}
+
+
+def list_evaluations():
+    """Names that create_evaluation accepts."""
+    return sorted(_EVALUATIONS)
+
+
+def create_evaluation(evaluation_type, **kwargs):
+    """create_evaluation("mvd", out_dir=..., inputs=..., alignment=..., ...) -> MultiViewDepthEvaluation."""
+    if evaluation_type not in _EVALUATIONS:
+        raise ValueError(f"unknown evaluation {evaluation_type!r}; available: {list_evaluations()}")
+    return _EVALUATIONS[evaluation_type](**kwargs)
