@@ -593,6 +593,34 @@ int mvd_rank_keys_f32(const float* u, const float* u_min, const float* gt, const
 int mvd_ranked_step_sums_f64(const float* ranked, long long n, const long long* count, double* step_sums, void* workspace,
                              size_t workspace_bytes, mvd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Multi-view depth fusion: geometric consistency of per-view depth maps and their point cloud.  The reference has NO counterpart
+ * (it stops at the per-view depth map): the definition is robustmvd_amd/depth_fusion.py's fuse_numpy and DESIGN.md.
+ * key_depth and every src_depth[s]: (H,W), H and W >= 2, no alignment requirement.  matrices (V,24) on the device, composed by the
+ * host in float64: per source  A = Ks R Kk^-1 (9, row-major), b = Ks t (3) with [R|t] = Ts Tk^-1, then A' = Kk R' Ks^-1 (9) and
+ * b' = Kk t' (3) with [R'|t'] = Tk Ts^-1.  For key pixel (x,y) with depth d:  Q = d A (x,y,1) + b, (u,v) = Q.xy / Q.z, valid when d
+ * is finite and > 0, Q.z > 0 and 0 <= u <= W-1, 0 <= v <= H-1;  ds = the bilinear blend of src_depth[s] in the cell x0 = min(floor(u),
+ * W-2), y0 = min(floor(v), H-2), invalid when one of its four taps is not finite or <= 0;  Q' = ds A' (u,v,1) + b', d' = Q'.z,
+ * err = hypot(Q'.x / d' - x, Q'.y / d' - y), rel = |d' - d| / d;  consistent = valid and err < max_reproj_error and
+ * rel < max_rel_depth_diff.  (The kernel forms (u,v) from Q / d = A (x,y,1) + b / d, which is (x,y) itself for A = I, b = 0.)
+ * view_bits (H,W) uint32: bit s = source s is consistent;  fused (H,W) = (d + sum of the consistent d') / (count + 1), 0 where d is
+ * invalid;  mask (H,W) uint8 = count >= min_consistent_views, and uncertainty <= max_uncertainty (false for a NaN) when uncertainty
+ * is not NULL;  num_consistent (H,W) uint8, may be NULL = popcount(view_bits), for callers that would otherwise count the bits again.
+ * No atomics and a fixed summation order: two calls give the same bits. */
+int mvd_geo_consistency_f32(const float* key_depth, const float* const* src_depth, const float* matrices, const float* uncertainty,
+                            int V, int H, int W, float max_reproj_error, float max_rel_depth_diff, int min_consistent_views,
+                            float max_uncertainty, unsigned* view_bits, float* fused, unsigned char* mask,
+                            unsigned char* num_consistent, mvd_stream_t stream);
+
+/* The masked pixels in row-major order as 3-D points: a deterministic stream compaction (per-chunk counts from wave ballots, an exclusive scan
+ * by one workgroup, a scatter to chunk offset + rank in the ballot; no atomic decides a position).
+ * backproject (12 floats, device): B = Rk^T Kk^-1 (9, row-major) and c = -Rk^T tk (3) of the key's world-to-view pose [Rk|tk]:
+ * xyz[m] = depth * B (x,y,1) + c.  image: NULL or planar (3,H,W), gathered into rgb (M,3).  xyz and rgb hold H*W points; count (device,
+ * 8-byte aligned) receives M.  workspace: mvd_compact_points_workspace_bytes(H, W). */
+size_t mvd_compact_points_workspace_bytes(int H, int W);
+int mvd_compact_points_f32(const unsigned char* mask, const float* depth, const float* image, const float* backproject, int H, int W,
+                           float* xyz, float* rgb, long long* count, void* workspace, size_t workspace_bytes, mvd_stream_t stream);
+
 /* layout helpers used at the operator-level boundary (reference tensors are NCHW / NCDHW) */
 int mvd_nchw_to_nhwc_f32(const float* src, float* dst, int N, int C, long long HW, mvd_stream_t stream);
 int mvd_nhwc_to_nchw_f32(const float* src, float* dst, int N, int C, long long HW, mvd_stream_t stream);

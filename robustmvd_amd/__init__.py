@@ -20,3 +20,5 @@ from .serving import FramePipeline, PinnedUploader  # noqa: F401
 from .sweep_modes import cvp_proj_cost, vis_cost_volumes, sweep_reduce  # noqa: F401
 from . import eval  # noqa: F401,E402
 from .eval import create_evaluation, list_evaluations, MultiViewDepthEvaluation  # noqa: F401,E402
+from . import depth_fusion  # noqa: F401,E402
+from .depth_fusion import DepthFusion, fuse_numpy, write_ply  # noqa: F401,E402

@@ -140,6 +140,11 @@ SIGNATURES = {
     "mvd_rank_keys_f32": (_i, [_c_float_p] * 4 + [_i, ctypes.c_longlong, _c_float_p, ctypes.c_void_p]),
     "mvd_ranked_step_sums_f64": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _sz,
                                       ctypes.c_void_p]),
+    "mvd_geo_consistency_f32": (_i, [_c_float_p, _pp, _c_float_p, _c_float_p, _i, _i, _i, ctypes.c_float, ctypes.c_float, _i,
+                                     ctypes.c_float] + [ctypes.c_void_p] * 5),
+    "mvd_compact_points_workspace_bytes": (_sz, [_i, _i]),
+    "mvd_compact_points_f32": (_i, [ctypes.c_void_p] + [_c_float_p] * 3 + [_i, _i, _c_float_p, _c_float_p, ctypes.c_void_p,
+                                                                          ctypes.c_void_p, _sz, ctypes.c_void_p]),
 }
 
 # built into the product library only (csrc/Makefile PRODSRCS): the experiments library has no variants of these

@@ -666,6 +666,71 @@ def vis_fuse(xs, us, out=None):
     return out
 
 
+@inference_only
+def geo_consistency(key_depth, src_depths, matrices, uncertainty=None, min_consistent_views=None, max_reproj_error=1.0,
+                    max_rel_depth_diff=0.01, max_uncertainty=None):
+    """The geometric consistency of one key depth map (H,W) against V <= 32 source maps of the same size (include/mvd.h:
+    mvd_geo_consistency_f32; the reference has no counterpart).  matrices (V,24): per source A (9), b (3), A' (9), b' (3), as
+    depth_fusion.compose_matrices forms them.  min_consistent_views defaults to min(3, V); the uncertainty filter applies when both
+    `uncertainty` (H,W) and `max_uncertainty` are given.
+    Returns (view_bits uint32, fused float32, mask uint8, num_consistent uint8), each (H,W)."""
+    d = L.as_f32(key_depth, "key_depth")
+    if d.dim() != 2 or d.shape[0] < 2 or d.shape[1] < 2:
+        raise ValueError(f"key_depth must be (H,W) with H, W >= 2, got {tuple(d.shape)}")
+    H, W = d.shape
+    dev = d.device
+    srcs = [L.as_f32(s, f"src_depths[{i}]", (H, W), dev) for i, s in enumerate(views(src_depths, "src_depths"))]
+    V = len(srcs)
+    mats = L.as_f32(matrices, "matrices", (V, 24), dev)
+    unc = None
+    if uncertainty is not None and max_uncertainty is not None:
+        unc = L.as_f32(uncertainty, "uncertainty", (H, W), dev)
+    min_views = min(3, V) if min_consistent_views is None else int(min_consistent_views)
+    bits = torch.empty((H, W), dtype=torch.uint32, device=dev)
+    fused = torch.empty((H, W), dtype=torch.float32, device=dev)
+    mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    count = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    call("mvd_geo_consistency_f32", dev, d, srcs, mats, unc, V, H, W, float(max_reproj_error), float(max_rel_depth_diff), min_views,
+         float(max_uncertainty) if unc is not None else 0.0, bits, fused, mask, count)
+    return bits, fused, mask, count
+
+
+@inference_only
+def compact_points(mask, depth, backproject, image=None, count=None, out=None):
+    """The set pixels of mask (H,W) uint8 in row-major order as world points (include/mvd.h: mvd_compact_points_f32): xyz =
+    depth * B (x,y,1) + c with backproject = (B (9), c (3)) on the device; image: planar (3,H,W), gathered into rgb.
+    Returns (xyz (H*W,3), rgb (H*W,3) or None, count): the first count[0] rows are the points; count is a device int64 tensor of
+    one element (the caller's own, where given), left on the device so that the caller decides when to read it.  out: the
+    (xyz, rgb) of an earlier call on maps of this size, written again instead of two new buffers."""
+    m = L.as_dtype(torch.uint8, False, mask, "mask")
+    if m.dim() != 2:
+        raise ValueError(f"mask must be (H,W), got {tuple(m.shape)}")
+    H, W = m.shape
+    dev = m.device
+    d = L.as_f32(depth, "depth", (H, W), dev)
+    bp = L.as_f32(backproject, "backproject", device=dev)
+    if bp.numel() != 12:
+        raise ValueError(f"backproject must hold 12 floats, got {tuple(bp.shape)}")
+    img = L.as_f32(image, "image", (3, H, W), dev) if image is not None else None
+    if count is None:
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+    elif count.dtype != torch.int64 or count.device != dev or count.numel() != 1:
+        raise ValueError("count must be one int64 on the mask's device")
+    if out is None:
+        xyz = torch.empty((H * W, 3), dtype=torch.float32, device=dev)
+        rgb = torch.empty((H * W, 3), dtype=torch.float32, device=dev) if img is not None else None
+    else:
+        xyz, rgb = out
+        for t, want in ((xyz, True), (rgb, img is not None)):
+            if (t is not None) != want or (want and (t.dtype != torch.float32 or t.device != dev or t.shape != (H * W, 3)
+                                                     or not t.is_contiguous())):
+                raise ValueError(f"out must be (xyz, rgb) contiguous float32 ({H * W},3) tensors on {dev}, rgb None without an image")
+    nbytes = L.load().mvd_compact_points_workspace_bytes(H, W)
+    ws = workspace(nbytes, dev)
+    call("mvd_compact_points_f32", dev, m, d, img, bp, H, W, xyz, rgb, count, ws, int(nbytes))
+    return xyz, rgb, count
+
+
 class SplitConv2dWeights:
     """Packed split-operand weights of one 2-D layer (pack_conv2d_weights_split) with what conv2d_split needs to call it."""
     __slots__ = ("packed", "bias", "cin", "cin_pad", "cout", "kh", "kw", "stride", "mode")
