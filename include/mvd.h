@@ -621,6 +621,58 @@ size_t mvd_compact_points_workspace_bytes(int H, int W);
 int mvd_compact_points_f32(const unsigned char* mask, const float* depth, const float* image, const float* backproject, int H, int W,
                            float* xyz, float* rgb, long long* count, void* workspace, size_t workspace_bytes, mvd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Point-cloud evaluation: the truncated nearest neighbour between two clouds, the scores of its distances, and voxel thinning.  The
+ * reference has NO counterpart: the definition is robustmvd_amd/cloud_eval.py (nearest_numpy, cloud_scores_numpy,
+ * voxel_downsample_numpy) and DESIGN.md.  A point with a non-finite coordinate is INVALID.  Every count is below 2^31.
+ *
+ * Cells.  i_a = floor((double(x_a) - origin_a) * inv) for a in x, y, z, two IEEE double operations and a floor, with inv formed by
+ * the host (1.0 / cell edge, or 1.0 / voxel), so that numpy on the host and the device agree on membership bit for bit.
+ * key = i_x << 42 | i_y << 21 | i_z with every index in [0, 2^21 - 1) (the caller checks the extent; the device clamps);
+ * an invalid point gets INT64_MAX, which no valid point can have, and sorts last.  Between mvd_cloud_cell_keys_f32 and its
+ * consumers the caller sorts the keys STABLY and keeps the permutation (perm[i] = the original index of sorted position i).
+ *
+ * Truncated nearest neighbour, queries Q (n), targets P (m), max_dist > 0:
+ *   dist[i]  = min(max_dist, min over valid j of |Q_i - P_j|)   (max_dist when Q_i is invalid or there is no valid target)
+ *   index[i] = the j of that minimum when it is < max_dist (strict), else -1
+ * |q - p| = sqrt(dx^2 + dy^2 + dz^2) of the float32 coordinate DIFFERENCES, never |q|^2 + |p|^2 - 2 q.p, which at coordinates
+ * around 10^3 and distances around 10^-2 has no correct digit.  Among targets with an equal sum of squares, as the device computed
+ * it, the smallest original index wins.  No atomic decides a value: two calls give the same bits. */
+#define MVD_CLOUD_MAX_THRESHOLDS 8
+int mvd_cloud_cell_keys_f32(const float* points, long long n, double origin_x, double origin_y, double origin_z, double inv,
+                            long long* keys, mvd_stream_t stream);
+
+/* records (n,4), 16-byte aligned: sorted position i holds x, y, z of points[perm[i]] and perm[i] as the bits of the fourth float. */
+int mvd_cloud_grid_build_f32(const float* points, const long long* perm, long long n, float* records, mvd_stream_t stream);
+
+/* query_records (n,4) and target_records (m,4): mvd_cloud_grid_build_f32's, both clouds keyed with this origin and inv (the queries'
+ * order only decides how well a wave's queries share cells; any order gives the same result); target_keys (m): the targets' sorted
+ * keys.  The cell edge 1 / inv must be at least max_dist (1 + 2^-10): then the 3 x 3 x 3 cells around a query's hold every target
+ * within max_dist (the argument is in csrc/cloud_eval.hip).  dist (n) and index (n) are written in the queries' ORIGINAL order.
+ * n == 0 writes nothing; m == 0 truncates every query. */
+int mvd_cloud_nearest_f32(const float* query_records, long long n, const float* target_records, const long long* target_keys,
+                          long long m, double origin_x, double origin_y, double origin_z, double inv, float max_dist, float* dist,
+                          int* index, mvd_stream_t stream);
+
+/* Over the VALID queries of one direction (points (n,3): the queries in original order, looked at only where index < 0; NULL = every
+ * query is valid): result (80 bytes, device, 8-byte aligned) = double sum of dist; int64 count of the valid queries; eight int64
+ * counts of dist < thresholds[t] (strict), zero for t >= T.  thresholds: T <= MVD_CLOUD_MAX_THRESHOLDS floats on the device.
+ * Workgroup partials summed in a fixed order; workspace: mvd_cloud_scores_workspace_bytes(n). */
+size_t mvd_cloud_scores_workspace_bytes(long long n);
+int mvd_cloud_scores_f32(const float* dist, const int* index, const float* points, long long n, const float* thresholds, int T,
+                         void* result, void* workspace, size_t workspace_bytes, mvd_stream_t stream);
+
+/* Voxel thinning from the sorted voxel keys and their permutation: one output point per occupied voxel in ascending key order, the
+ * float64 mean of the voxel's points in original order (a voxel of more than 64 points: 64 interleaved partial sums and a fixed
+ * tree), rounded to float32; colors (n,3) -> rgb likewise, both or neither NULL; counts = the voxel's number of points; invalid
+ * points are dropped.  xyz, rgb (n,3) and counts (n) hold n voxels; num_voxels (device, 8-byte aligned) receives their number.
+ * A deterministic compaction of the segment heads (ballot counts, one workgroup's scan, rank in the ballot), as
+ * mvd_compact_points_f32's.  workspace: mvd_voxel_reduce_workspace_bytes(n). */
+size_t mvd_voxel_reduce_workspace_bytes(long long n);
+int mvd_voxel_reduce_f32(const long long* keys, const long long* perm, const float* points, const float* colors, long long n,
+                         float* xyz, float* rgb, int* counts, long long* num_voxels, void* workspace, size_t workspace_bytes,
+                         mvd_stream_t stream);
+
 /* layout helpers used at the operator-level boundary (reference tensors are NCHW / NCDHW) */
 int mvd_nchw_to_nhwc_f32(const float* src, float* dst, int N, int C, long long HW, mvd_stream_t stream);
 int mvd_nhwc_to_nchw_f32(const float* src, float* dst, int N, int C, long long HW, mvd_stream_t stream);

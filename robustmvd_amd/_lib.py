@@ -145,7 +145,18 @@ SIGNATURES = {
     "mvd_compact_points_workspace_bytes": (_sz, [_i, _i]),
     "mvd_compact_points_f32": (_i, [ctypes.c_void_p] + [_c_float_p] * 3 + [_i, _i, _c_float_p, _c_float_p, ctypes.c_void_p,
                                                                           ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "mvd_cloud_cell_keys_f32": (_i, [_c_float_p, ctypes.c_longlong] + [ctypes.c_double] * 4 + [ctypes.c_void_p] * 2),
+    "mvd_cloud_grid_build_f32": (_i, [_c_float_p, ctypes.c_void_p, ctypes.c_longlong, _c_float_p, ctypes.c_void_p]),
+    "mvd_cloud_nearest_f32": (_i, [_c_float_p, ctypes.c_longlong, _c_float_p, ctypes.c_void_p, ctypes.c_longlong]
+                              + [ctypes.c_double] * 4 + [ctypes.c_float, _c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mvd_cloud_scores_workspace_bytes": (_sz, [ctypes.c_longlong]),
+    "mvd_cloud_scores_f32": (_i, [_c_float_p, ctypes.c_void_p, _c_float_p, ctypes.c_longlong, _c_float_p, _i, ctypes.c_void_p,
+                                  ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "mvd_voxel_reduce_workspace_bytes": (_sz, [ctypes.c_longlong]),
+    "mvd_voxel_reduce_f32": (_i, [ctypes.c_void_p] * 2 + [_c_float_p] * 2 + [ctypes.c_longlong, _c_float_p, _c_float_p]
+                             + [ctypes.c_void_p] * 3 + [_sz, ctypes.c_void_p]),
 }
+MVD_CLOUD_MAX_THRESHOLDS = 8
 
 # built into the product library only (csrc/Makefile PRODSRCS): the experiments library has no variants of these
 PRODUCT_ONLY = ("mvd_sweep_reduce_backward_workspace_bytes", "mvd_sweep_reduce_backward_f32")

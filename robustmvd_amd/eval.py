@@ -374,7 +374,9 @@ class MultiViewDepthEvaluation:
         self.results.to_pickle(self.results_file)
 
 
-_EVALUATIONS = {"mvd": MultiViewDepthEvaluation}
+from .cloud_eval import PointCloudEvaluation  # noqa: E402
+
+_EVALUATIONS = {"mvd": MultiViewDepthEvaluation, "cloud": PointCloudEvaluation}
 
 
 def list_evaluations():
@@ -383,7 +385,8 @@ def list_evaluations():
 
 
 def create_evaluation(evaluation_type, **kwargs):
-    """create_evaluation("mvd", out_dir=..., inputs=..., alignment=..., ...) -> MultiViewDepthEvaluation."""
+    """create_evaluation("mvd", out_dir=..., inputs=..., alignment=..., ...) -> MultiViewDepthEvaluation;
+    create_evaluation("cloud", thresholds=..., max_dist=..., voxel=...) -> cloud_eval.PointCloudEvaluation."""
     if evaluation_type not in _EVALUATIONS:
         raise ValueError(f"unknown evaluation {evaluation_type!r}; available: {list_evaluations()}")
     return _EVALUATIONS[evaluation_type](**kwargs)

@@ -731,6 +731,173 @@ def compact_points(mask, depth, backproject, image=None, count=None, out=None):
     return xyz, rgb, count
 
 
+CLOUD_INDEX_LIMIT = (1 << 21) - 1  # a cell or voxel index is in [0, 2^21 - 1): the all-ones key is the invalid points' own
+CLOUD_CELL_MARGIN = 1.0 + 2.0 ** -10  # cell edge = max_dist * margin (csrc/cloud_eval.hip: why 27 cells are enough)
+
+
+def _cloud_points(points, name, device=None):
+    p = L.as_f32(points, name, device=device)
+    if p.dim() != 2 or p.shape[1] != 3:
+        raise ValueError(f"{name} must be (n,3), got {tuple(p.shape)}")
+    if p.shape[0] >= 2 ** 31:
+        raise ValueError(f"{name}: {p.shape[0]} points, supported below 2^31")
+    return p
+
+
+def _cloud_extent(p):
+    """Per-axis min and max over the valid points of p (n,3) as float64 numpy, or None when there is none: one read of 6 floats."""
+    if p.shape[0] == 0:
+        return None
+    ok = torch.isfinite(p).all(dim=1, keepdim=True)
+    inf = torch.tensor(float("inf"), device=p.device)
+    both = torch.stack([torch.where(ok, p, inf).amin(dim=0), torch.where(ok, p, -inf).amax(dim=0)]).double().cpu().numpy()
+    return None if both[0, 0] == float("inf") else both
+
+
+def _cloud_origin(origin, name="origin"):
+    o = [float(v) for v in (origin.tolist() if hasattr(origin, "tolist") else origin)]
+    if len(o) != 3 or not all(abs(v) < float("inf") for v in o):
+        raise ValueError(f"{name} must be 3 finite numbers, got {o}")
+    return o
+
+
+def _check_cloud_indices(extent, origin, inv, what, edge):
+    """The host's check that every index floor((x - o) * inv) of a cloud fits the key: a ValueError that names extent and edge."""
+    if extent is None:
+        return
+    lo = [(extent[0, a] - origin[a]) * inv for a in range(3)]
+    hi = [(extent[1, a] - origin[a]) * inv for a in range(3)]
+    if min(lo) < 0 or max(hi) >= CLOUD_INDEX_LIMIT:
+        raise ValueError(f"{what}: the points span {extent[0].tolist()} .. {extent[1].tolist()} from origin {list(origin)}, which at an edge of "
+                         f"{edge:g} gives indices {min(lo):.0f} .. {max(hi):.0f}; each must be in [0, {CLOUD_INDEX_LIMIT})")
+
+
+def _cloud_sorted(p, origin, inv):
+    """Keys of p's cells, sorted stably, and the permutation -> (keys, perm).  The sort is torch's: plumbing between two kernels."""
+    n = p.shape[0]
+    keys = torch.empty(n, dtype=torch.int64, device=p.device)
+    call("mvd_cloud_cell_keys_f32", p.device, p, n, origin[0], origin[1], origin[2], inv, keys)
+    return torch.sort(keys, stable=True)
+
+
+class CloudGrid:
+    """A cloud sorted into the cells of a uniform grid (cloud_grid): points (n,3) as given, keys (n) int64 ascending, records (n,4)
+    = x, y, z and the original index's bits in key order, origin (3 floats), cell and inv = 1.0 / cell."""
+    __slots__ = ("points", "keys", "records", "origin", "cell", "inv")
+
+    def __init__(self, points, keys, records, origin, cell):
+        self.points, self.keys, self.records, self.origin, self.cell, self.inv = points, keys, records, origin, cell, 1.0 / cell
+
+
+@inference_only
+def cloud_grid(points, origin, cell, check=True):
+    """points (n,3) sorted into the cells of edge `cell` from `origin` (include/mvd.h: mvd_cloud_cell_keys_f32,
+    mvd_cloud_grid_build_f32) -> CloudGrid.  check: every valid point's cell indices must be in [0, 2^21 - 1), else ValueError
+    (a target grid needs it; check=False clamps instead, for a cloud that is only queried)."""
+    p = _cloud_points(points, "points")
+    origin, cell = _cloud_origin(origin), float(cell)
+    if not 0.0 < cell < float("inf"):
+        raise ValueError(f"cell must be finite and > 0, got {cell}")
+    inv = 1.0 / cell
+    if check:
+        _check_cloud_indices(_cloud_extent(p), origin, inv, "cloud_grid", cell)
+    keys, perm = _cloud_sorted(p, origin, inv)
+    records = torch.empty((p.shape[0], 4), dtype=torch.float32, device=p.device)
+    call("mvd_cloud_grid_build_f32", p.device, p, perm, p.shape[0], records)
+    return CloudGrid(p, keys, records, origin, cell)
+
+
+@inference_only
+def cloud_nearest(query, grid, max_dist):
+    """The truncated nearest neighbour of every query in the grid's cloud (include/mvd.h: mvd_cloud_nearest_f32).  query: (n,3)
+    points, sorted here by the grid's cells, or a CloudGrid of the same origin and cell (PointCloudEvaluation sorts each cloud once
+    for both directions).  grid.cell must be at least max_dist * (1 + 2^-10).
+    Returns (dist (n) float32, index (n) int32) in the query's original order; index -1 = nothing nearer than max_dist."""
+    if not isinstance(grid, CloudGrid):
+        raise ValueError(f"grid: expected a CloudGrid (ops.cloud_grid), got {type(grid).__name__}")
+    dev = grid.points.device
+    max_dist = float(torch.tensor(max_dist, dtype=torch.float32))  # the float32 the kernel compares with
+    if not 0.0 < max_dist < float("inf"):
+        raise ValueError(f"max_dist must be finite and > 0, got {max_dist}")
+    if grid.cell < max_dist * CLOUD_CELL_MARGIN * (1 - 1e-12):
+        raise ValueError(f"the grid's cell {grid.cell:g} is below max_dist * (1 + 2^-10) = {max_dist * CLOUD_CELL_MARGIN:g}")
+    if isinstance(query, CloudGrid):
+        if query.origin != grid.origin or query.cell != grid.cell or query.points.device != dev:
+            raise ValueError("query and target grids differ in origin, cell or device")
+        q = query
+    else:
+        q = cloud_grid(_cloud_points(query, "query", dev), grid.origin, grid.cell, check=False)
+    n, m = q.points.shape[0], grid.points.shape[0]
+    dist = torch.empty(n, dtype=torch.float32, device=dev)
+    index = torch.empty(n, dtype=torch.int32, device=dev)
+    call("mvd_cloud_nearest_f32", dev, q.records, n, grid.records, grid.keys, m, grid.origin[0], grid.origin[1], grid.origin[2], grid.inv,
+         max_dist, dist, index)
+    return dist, index
+
+
+@inference_only
+def cloud_scores(dist, index, thresholds, points=None, result=None):
+    """One direction's sums over the valid queries (include/mvd.h: mvd_cloud_scores_f32).  dist (n) float32 and index (n) int32 from
+    cloud_nearest; thresholds: T <= 8 numbers or a device tensor; points: the queries (n,3), so that the invalid ones among the
+    truncated are left out (None: every query counts).  Returns a device int64 tensor of 10 words, left on the device: the bits of
+    the float64 sum of dist, the count of valid queries, and eight counts of dist < thresholds[t] (read it with cloud_scores_read)."""
+    d = L.as_dtype(torch.float32, False, dist, "dist")
+    if d.dim() != 1:
+        raise ValueError(f"dist must be (n,), got {tuple(d.shape)}")
+    n, dev = d.shape[0], d.device
+    idx = L.as_dtype(torch.int32, False, index, "index", (n,), dev)
+    th = thresholds if isinstance(thresholds, torch.Tensor) else torch.tensor([float(t) for t in thresholds], dtype=torch.float32)
+    if th.dim() != 1 or not 1 <= th.shape[0] <= L.MVD_CLOUD_MAX_THRESHOLDS:
+        raise ValueError(f"{th.numel()} thresholds, supported 1..{L.MVD_CLOUD_MAX_THRESHOLDS}")
+    th = L.as_f32(th.to(dev), "thresholds")
+    pts = _cloud_points(points, "points", dev) if points is not None else None
+    if pts is not None and pts.shape[0] != n:
+        raise ValueError(f"{pts.shape[0]} points for {n} distances")
+    if result is None:
+        result = torch.empty(10, dtype=torch.int64, device=dev)
+    elif result.dtype != torch.int64 or result.device != dev or result.numel() != 10 or not result.is_contiguous():
+        raise ValueError("result must be 10 contiguous int64 on dist's device")
+    nbytes = L.load().mvd_cloud_scores_workspace_bytes(n)
+    ws = workspace(nbytes, dev)
+    call("mvd_cloud_scores_f32", dev, d, idx, pts, n, th, th.shape[0], result, ws, int(nbytes))
+    return result
+
+
+def cloud_scores_read(result, T):
+    """cloud_scores' block on the host -> (sum float, valid int, counts (T,) int64 numpy): the one read of a direction."""
+    r = result.cpu()
+    return float(r[:1].view(torch.float64)[0]), int(r[1]), r[2:2 + T].numpy().copy()
+
+
+@inference_only
+def voxel_downsample(points, voxel, colors=None, origin=None):
+    """One point per occupied voxel of edge `voxel` (include/mvd.h: mvd_voxel_reduce_f32): the float64 mean of the voxel's valid
+    points (and colours), in ascending order of the key floor((x - o) / voxel) per axis; origin defaults to the per-axis minimum
+    over the valid points.  Returns (xyz (k,3) float32, rgb (k,3) or None, counts (k,) int32)."""
+    p = _cloud_points(points, "points")
+    n, dev = p.shape[0], p.device
+    voxel = float(torch.tensor(float(voxel), dtype=torch.float32))  # the definition takes the voxel as float32: inv = 1 / float64(float32)
+    if not 0.0 < voxel < float("inf"):
+        raise ValueError(f"voxel must be finite and > 0, got {voxel}")
+    col = None
+    if colors is not None:
+        col = L.as_f32(colors, "colors", (n, 3), dev)
+    inv = 1.0 / voxel
+    extent = _cloud_extent(p)
+    o = _cloud_origin(origin) if origin is not None else ([0.0, 0.0, 0.0] if extent is None else extent[0].tolist())
+    _check_cloud_indices(extent, o, inv, "voxel_downsample", voxel)
+    keys, perm = _cloud_sorted(p, o, inv)
+    xyz = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    rgb = torch.empty((n, 3), dtype=torch.float32, device=dev) if col is not None else None
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    num = torch.empty(1, dtype=torch.int64, device=dev)
+    nbytes = L.load().mvd_voxel_reduce_workspace_bytes(n)
+    ws = workspace(nbytes, dev)
+    call("mvd_voxel_reduce_f32", dev, keys, perm, p, col, n, xyz, rgb, counts, num, ws, int(nbytes))
+    k = int(num.item())
+    return xyz[:k].clone(), None if rgb is None else rgb[:k].clone(), counts[:k].clone()
+
+
 class SplitConv2dWeights:
     """Packed split-operand weights of one 2-D layer (pack_conv2d_weights_split) with what conv2d_split needs to call it."""
     __slots__ = ("packed", "bias", "cin", "cin_pad", "cout", "kh", "kw", "stride", "mode")
