@@ -5,13 +5,14 @@
 //   mvd_cloud_grid_build_f32   the points gathered into key order as 16-byte records (x, y, z, original index)
 //   mvd_cloud_nearest_f32      per query the nearest target within max_dist: a wave stages the cells around its queries through LDS
 //   mvd_cloud_scores_f32       float64 sum of the distances, the count of valid points and the counts under T thresholds
-//   mvd_voxel_reduce_f32       one point per occupied voxel: the float64 mean of its points and colours, and their number
+//   mvd_voxel_reduce_f32       one point per occupied voxel: the float64 mean of its points and colours, and their number (the
+//                              voxels are numbered by the compaction of compact.h)
 // No atomics anywhere and fixed summation orders: two calls give the same bits.  The sort between the keys and their consumers is the
 // caller's (a stable sort of the keys and the permutation it returns).
 #include <math.h>
 #include <stdint.h>
 
-#include "mvd_common.h"
+#include "compact.h"
 
 namespace mvd {
 
@@ -20,7 +21,7 @@ constexpr int CE_LIMIT = (1 << CE_BITS) - 1;  // a cell index is in [0, CE_LIMIT
 constexpr long long CE_INVALID_KEY = 0x7fffffffffffffffLL;
 
 __device__ __forceinline__ bool finite3(float x, float y, float z) {
-    return fabsf(x) <= 3.402823466e38f && fabsf(y) <= 3.402823466e38f && fabsf(z) <= 3.402823466e38f;  // false for inf and NaN
+    return finite_f32(x) && finite_f32(y) && finite_f32(z);
 }
 
 // floor((double(v) - o) * inv), two IEEE double operations and a floor (the library is built without contraction): numpy forms the
@@ -258,75 +259,32 @@ static inline long long score_workgroups(long long n) { return (n + SC_PER_WG - 
 
 // ---- voxel reduce ------------------------------------------------------------------------------------------------------------------
 // Position i of the sorted keys is the head of a voxel's segment when its key is a valid point's and differs from the key before it.
-// The heads are compacted like the masked pixels of depth_fusion.hip (ballot counts per 256-key chunk, one workgroup's exclusive
-// scan, rank in the ballot), which numbers the voxels in key order and leaves each voxel's first position in seg[voxel];
-// seg[number of voxels] is the number of valid points.  Then one lane per voxel adds its points in sorted (= original, the sort
+// The heads are compacted by compact.h, as the masked pixels of depth_fusion.hip are (ballot counts per 256-key chunk, one
+// workgroup's exclusive scan, rank in the ballot), which numbers the voxels in key order and leaves each voxel's first position in
+// seg[voxel]; seg[number of voxels] is the number of valid points.  Then one lane per voxel adds its points in sorted (= original, the sort
 // is stable) order in float64; a segment of more than 64 points is added by the whole wave instead, lane l taking the points
 // l, l + 64, ... and the 64 sums meeting in an xor-shuffle tree, so a voxel that holds the whole cloud costs n / 64 steps.
-constexpr int VX_THREADS = 256;
+constexpr int VX_THREADS = 256;  // the mean kernel's own geometry: a lane per voxel
 constexpr int VX_WAVES = VX_THREADS / 64;
-constexpr int VX_SUB = 4;
-constexpr int VX_CHUNK = 64 * VX_SUB;
 constexpr int VX_LONG = 64;  // segments above this length are reduced by the wave
 
-static inline long long voxel_chunks(long long n) { return (n + VX_CHUNK - 1) / VX_CHUNK; }
-
-__device__ __forceinline__ bool voxel_head(const long long* __restrict__ keys, long long p, int n) {
-    if (p >= n) return false;
-    const long long k = keys[p];
-    return k != CE_INVALID_KEY && (p == 0 || keys[p - 1] != k);
-}
-
-__global__ void __launch_bounds__(VX_THREADS) voxel_count_kernel(const long long* __restrict__ keys, int n, unsigned* __restrict__ counts) {
-    const long long chunk = (long long)blockIdx.x * VX_WAVES + (threadIdx.x >> 6);
-    const long long base = chunk * VX_CHUNK + (threadIdx.x & 63);
-    unsigned c = 0u;
-#pragma unroll
-    for (int k = 0; k < VX_SUB; ++k) c += (unsigned)__popcll(__ballot(voxel_head(keys, base + 64 * k, n)));
-    if ((threadIdx.x & 63) == 0 && chunk * VX_CHUNK < n) counts[chunk] = c;
-}
-
-__global__ void __launch_bounds__(VX_THREADS) voxel_scan_kernel(unsigned* __restrict__ counts, long long nchunks,
-                                                                long long* __restrict__ total) {
-    __shared__ unsigned part[VX_THREADS];
-    const int t = threadIdx.x;
-    const long long per = (nchunks + VX_THREADS - 1) / VX_THREADS;
-    const long long b = min((long long)t * per, nchunks), e = min(b + per, nchunks);
-    unsigned acc = 0u;
-    for (long long i = b; i < e; ++i) acc += counts[i];
-    part[t] = acc;
-    __syncthreads();
-    for (int s = 1; s < VX_THREADS; s <<= 1) {  // inclusive scan of the 256 segment sums
-        const unsigned add = t >= s ? part[t - s] : 0u;
-        __syncthreads();
-        part[t] += add;
-        __syncthreads();
+struct VoxelHead {
+    const long long* keys;
+    __device__ bool operator()(long long p) const {
+        const long long k = keys[p];
+        return k != CE_INVALID_KEY && (p == 0 || keys[p - 1] != k);
     }
-    unsigned run = part[t] - acc;  // exclusive
-    for (long long i = b; i < e; ++i) {
-        const unsigned c = counts[i];
-        counts[i] = run;
-        run += c;
-    }
-    if (t == VX_THREADS - 1) total[0] = (long long)part[t];
-}
+};
 
-__global__ void __launch_bounds__(VX_THREADS) voxel_heads_kernel(const long long* __restrict__ keys, int n,
+__global__ void __launch_bounds__(CP_THREADS) voxel_heads_kernel(const long long* __restrict__ keys, int n,
                                                                  const unsigned* __restrict__ offsets,
                                                                  const long long* __restrict__ total, int* __restrict__ seg) {
-    const int lane = threadIdx.x & 63;
-    const long long chunk = (long long)blockIdx.x * VX_WAVES + (threadIdx.x >> 6);
-    if (chunk * VX_CHUNK >= n) return;  // the whole wave
-    const long long base = chunk * VX_CHUNK + lane;
-    long long run = offsets[chunk];
+    compact_walk(VoxelHead{keys}, offsets, n, [&](long long p, long long slot) { seg[slot] = (int)p; });
+    // the last valid point closes the last segment: not a part of the compaction, and no launch of its own
+    const long long base = compact_wave_chunk() * CP_CHUNK + (threadIdx.x & 63);
 #pragma unroll
-    for (int k = 0; k < VX_SUB; ++k) {
+    for (int k = 0; k < CP_SUB; ++k) {
         const long long p = base + 64 * k;
-        const bool head = voxel_head(keys, p, n);
-        const unsigned long long ballot = __ballot(head);
-        if (head) seg[run + __popcll(ballot & ((1ull << lane) - 1ull))] = (int)p;
-        run += __popcll(ballot);
-        // the last valid point closes the last segment
         if (p < n && keys[p] != CE_INVALID_KEY && (p + 1 == n || keys[p + 1] == CE_INVALID_KEY)) seg[total[0]] = (int)(p + 1);
     }
 }
@@ -433,7 +391,7 @@ extern "C" int mvd_cloud_nearest_f32(const float* query_records, long long n, co
     using namespace mvd;
     CE_REQUIRE_COUNT("cloud_nearest", n);
     CE_REQUIRE_COUNT("cloud_nearest", m);
-    MVD_REQUIRE(max_dist > 0.f && max_dist <= 3.402823466e38f, "cloud_nearest: max_dist must be finite and > 0, got %g", (double)max_dist);
+    MVD_REQUIRE(max_dist > 0.f && finite_f32(max_dist), "cloud_nearest: max_dist must be finite and > 0, got %g", (double)max_dist);
     MVD_REQUIRE(isfinite(origin_x) && isfinite(origin_y) && isfinite(origin_z), "cloud_nearest: the origin is not finite");
     MVD_REQUIRE(isfinite(inv) && inv > 0.0, "cloud_nearest: inv must be finite and > 0, got %g", inv);
     MVD_REQUIRE(inv * ((double)max_dist * (1.0 + 1.0 / 1024.0)) <= 1.0 + 1e-12,
@@ -475,7 +433,7 @@ extern "C" int mvd_cloud_scores_f32(const float* dist, const int* index, const f
 
 extern "C" size_t mvd_voxel_reduce_workspace_bytes(long long n) {
     if (n <= 0) return 0;
-    return mvd::align_up((size_t)mvd::voxel_chunks(n) * sizeof(unsigned), 256) + mvd::align_up((size_t)(n + 1) * sizeof(int), 256);
+    return mvd::compact_offsets_bytes(n) + mvd::align_up((size_t)(n + 1) * sizeof(int), 256);
 }
 
 extern "C" int mvd_voxel_reduce_f32(const long long* keys, const long long* perm, const float* points, const float* colors, long long n,
@@ -493,13 +451,12 @@ extern "C" int mvd_voxel_reduce_f32(const long long* keys, const long long* perm
     MVD_REQUIRE(keys && perm && points && xyz && counts, "voxel_reduce: NULL argument");
     MVD_REQUIRE(workspace && ((uintptr_t)workspace & 3) == 0 && workspace_bytes >= mvd_voxel_reduce_workspace_bytes(n),
                 "voxel_reduce: workspace too small or misaligned");
-    const long long nchunks = voxel_chunks(n);
-    const unsigned nwg = (unsigned)((nchunks + VX_WAVES - 1) / VX_WAVES);
+    const unsigned nwg = compact_workgroups(n);
     unsigned* chunk_counts = static_cast<unsigned*>(workspace);
-    int* seg = reinterpret_cast<int*>(static_cast<unsigned char*>(workspace) + align_up((size_t)nchunks * sizeof(unsigned), 256));
-    hipLaunchKernelGGL(voxel_count_kernel, dim3(nwg), dim3(VX_THREADS), 0, st, keys, (int)n, chunk_counts);
-    hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(VX_THREADS), 0, st, chunk_counts, nchunks, num_voxels);
-    hipLaunchKernelGGL(voxel_heads_kernel, dim3(nwg), dim3(VX_THREADS), 0, st, keys, (int)n, chunk_counts, num_voxels, seg);
+    int* seg = reinterpret_cast<int*>(static_cast<unsigned char*>(workspace) + compact_offsets_bytes(n));
+    hipLaunchKernelGGL(compact_count_kernel<VoxelHead>, dim3(nwg), dim3(CP_THREADS), 0, st, VoxelHead{keys}, n, chunk_counts);
+    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(CP_THREADS), 0, st, chunk_counts, compact_chunks(n), num_voxels);
+    hipLaunchKernelGGL(voxel_heads_kernel, dim3(nwg), dim3(CP_THREADS), 0, st, keys, (int)n, chunk_counts, num_voxels, seg);
     // one lane per voxel, at most n voxels: the waves past the count leave at once
     const unsigned mwg = (unsigned)((n + VX_THREADS - 1) / VX_THREADS);
     if (colors)

@@ -27,7 +27,7 @@ __device__ __forceinline__ float order_key_inv(unsigned k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 // np.nan_to_num(v, nan=r, posinf=r, neginf=r)
-__device__ __forceinline__ float finite_or(float v, float r) { return fabsf(v) <= 3.402823466e38f ? v : r; }
+__device__ __forceinline__ float finite_or(float v, float r) { return finite_f32(v) ? v : r; }
 
 // The four selections of the median alignment: sel = 2 * array + which, array 0 = gt, 1 = prediction; which 0 = the lower middle
 // element (rank (n - 1) / 2), 1 = the upper one (rank n / 2).  For an odd count the two are the same element.
@@ -177,7 +177,7 @@ __global__ void __launch_bounds__(EV_THREADS) median_select_kernel(SelectState* 
             if (st->nan_count) mp = nan;
         }
         const float ratio = mg / mp;
-        params[0] = (n && fabsf(ratio) <= 3.402823466e38f) ? ratio : nan;  // NaN = "do not scale"
+        params[0] = (n && finite_f32(ratio)) ? ratio : nan;  // NaN = "do not scale"
         params[1] = 0.f;
         params[2] = mg;
         params[3] = mp;

@@ -4,8 +4,9 @@
 //   mvd_geo_consistency_f32   per key pixel and source: project forward, blend the source depth, project back, test; the bit set of
 //                             the consistent sources, the mean of the agreeing depths and the mask
 //   mvd_compact_points_f32    the masked pixels in row-major order, back-projected to world coordinates, with their colour
+//                             (the compaction of compact.h; only the back-projection and the colour gather are here)
 // No atomics and fixed summation orders: two calls give the same bits.  The only LDS is the 1 KiB of the one-workgroup scan.
-#include "mvd_common.h"
+#include "compact.h"
 
 namespace mvd {
 
@@ -50,7 +51,7 @@ __device__ __forceinline__ Probe probe(const float* __restrict__ m, const float*
     return p;
 }
 
-__device__ __forceinline__ bool positive_finite(float f) { return f > 0.f && f <= 3.402823466e38f; }
+__device__ __forceinline__ bool positive_finite(float f) { return f > 0.f && finite_f32(f); }
 
 __global__ void __launch_bounds__(GC_TX * GC_TY) geo_consistency_kernel(const float* __restrict__ key, ViewPtrs srcs,
                                                                         const float* __restrict__ mats,
@@ -102,90 +103,32 @@ __global__ void __launch_bounds__(GC_TX * GC_TY) geo_consistency_kernel(const fl
 }
 
 // ---- point cloud -------------------------------------------------------------------------------------------------------------------
-// A chunk is 256 consecutive pixels, the four ballots of one wave, which keeps the one-workgroup scan at 14 counts per lane at
-// 768 x 1152.  count: chunk -> the popcounts of its ballots; scan: one workgroup turns the counts
-// into exclusive offsets in place and writes the total; scatter: slot = offset of the chunk + the popcounts of the chunk's earlier
-// ballots + the rank of the lane in its ballot.
-constexpr int CP_THREADS = 256;
-constexpr int CP_WAVES = CP_THREADS / 64;
-constexpr int CP_SUB = 4;              // ballots per chunk
-constexpr int CP_CHUNK = 64 * CP_SUB;  // pixels per chunk
-
-static inline long long compact_chunks(long long N) { return (N + CP_CHUNK - 1) / CP_CHUNK; }
-
-__global__ void __launch_bounds__(CP_THREADS) compact_count_kernel(const unsigned char* __restrict__ mask, long long N,
-                                                                   unsigned* __restrict__ counts) {
-    const long long chunk = (long long)blockIdx.x * CP_WAVES + (threadIdx.x >> 6);
-    const long long base = chunk * CP_CHUNK + (threadIdx.x & 63);
-    unsigned n = 0u;
-#pragma unroll
-    for (int k = 0; k < CP_SUB; ++k) {
-        const long long p = base + 64 * k;
-        const bool set = p < N && mask[p] != 0;
-        n += (unsigned)__popcll(__ballot(set));
-    }
-    if ((threadIdx.x & 63) == 0 && chunk * CP_CHUNK < N) counts[chunk] = n;
-}
-
-__global__ void __launch_bounds__(CP_THREADS) compact_scan_kernel(unsigned* __restrict__ counts, long long nchunks,
-                                                                  long long* __restrict__ total) {
-    __shared__ unsigned part[CP_THREADS];
-    const int t = threadIdx.x;
-    const long long per = (nchunks + CP_THREADS - 1) / CP_THREADS;
-    const long long b = min((long long)t * per, nchunks), e = min(b + per, nchunks);
-    unsigned acc = 0u;
-    for (long long i = b; i < e; ++i) acc += counts[i];
-    part[t] = acc;
-    __syncthreads();
-    for (int s = 1; s < CP_THREADS; s <<= 1) {  // inclusive scan of the 256 segment sums
-        const unsigned add = t >= s ? part[t - s] : 0u;
-        __syncthreads();
-        part[t] += add;
-        __syncthreads();
-    }
-    unsigned run = part[t] - acc;  // exclusive
-    for (long long i = b; i < e; ++i) {
-        const unsigned c = counts[i];
-        counts[i] = run;
-        run += c;
-    }
-    if (t == CP_THREADS - 1) total[0] = (long long)part[t];
-}
+// The compaction of compact.h over the mask: its count, its scan, and the walk below, which back-projects every set pixel into its
+// slot and gathers its colour.
+struct MaskSet {
+    const unsigned char* mask;
+    __device__ bool operator()(long long p) const { return mask[p] != 0; }
+};
 
 __global__ void __launch_bounds__(CP_THREADS) compact_scatter_kernel(const unsigned char* __restrict__ mask,
                                                                      const float* __restrict__ depth, const float* __restrict__ image,
                                                                      const float* __restrict__ bp, const unsigned* __restrict__ offsets,
                                                                      int W, long long N, float* __restrict__ xyz,
                                                                      float* __restrict__ rgb) {
-    const int lane = threadIdx.x & 63;
-    const long long chunk = (long long)blockIdx.x * CP_WAVES + (threadIdx.x >> 6);
-    if (chunk * CP_CHUNK >= N) return;  // the whole wave
-    const long long base = chunk * CP_CHUNK + lane;
-    bool set[CP_SUB];
-#pragma unroll
-    for (int k = 0; k < CP_SUB; ++k) set[k] = base + 64 * k < N && mask[base + 64 * k] != 0;
-    long long run = offsets[chunk];
-#pragma unroll
-    for (int k = 0; k < CP_SUB; ++k) {
-        const unsigned long long ballot = __ballot(set[k]);
-        if (set[k]) {
-            const long long p = base + 64 * k;
-            const long long slot = run + __popcll(ballot & ((1ull << lane) - 1ull));
-            const int py = (int)p / W;  // N < 2^31 (checked by the entry): a 32-bit division
-            const float x = (float)((int)p - py * W), y = (float)py, d = depth[p];
-            float* o = xyz + 3 * slot;
-            o[0] = fmaf(d, fmaf(bp[0], x, fmaf(bp[1], y, bp[2])), bp[9]);
-            o[1] = fmaf(d, fmaf(bp[3], x, fmaf(bp[4], y, bp[5])), bp[10]);
-            o[2] = fmaf(d, fmaf(bp[6], x, fmaf(bp[7], y, bp[8])), bp[11]);
-            if (rgb) {
-                float* c = rgb + 3 * slot;
-                c[0] = image[p];
-                c[1] = image[N + p];
-                c[2] = image[2 * N + p];
-            }
+    compact_walk(MaskSet{mask}, offsets, N, [&](long long p, long long slot) {
+        const int py = (int)p / W;  // N < 2^31 (checked by the entry): a 32-bit division
+        const float x = (float)((int)p - py * W), y = (float)py, d = depth[p];
+        float* o = xyz + 3 * slot;
+        o[0] = fmaf(d, fmaf(bp[0], x, fmaf(bp[1], y, bp[2])), bp[9]);
+        o[1] = fmaf(d, fmaf(bp[3], x, fmaf(bp[4], y, bp[5])), bp[10]);
+        o[2] = fmaf(d, fmaf(bp[6], x, fmaf(bp[7], y, bp[8])), bp[11]);
+        if (rgb) {
+            float* c = rgb + 3 * slot;
+            c[0] = image[p];
+            c[1] = image[N + p];
+            c[2] = image[2 * N + p];
         }
-        run += __popcll(ballot);
-    }
+    });
 }
 
 }  // namespace mvd
@@ -214,7 +157,7 @@ extern "C" int mvd_geo_consistency_f32(const float* key_depth, const float* cons
 
 extern "C" size_t mvd_compact_points_workspace_bytes(int H, int W) {
     if (H <= 0 || W <= 0) return 0;
-    return mvd::align_up((size_t)mvd::compact_chunks((long long)H * W) * sizeof(unsigned), 256);
+    return mvd::compact_offsets_bytes((long long)H * W);
 }
 
 extern "C" int mvd_compact_points_f32(const unsigned char* mask, const float* depth, const float* image, const float* backproject, int H,
@@ -227,11 +170,11 @@ extern "C" int mvd_compact_points_f32(const unsigned char* mask, const float* de
     MVD_REQUIRE(((uintptr_t)count & 7) == 0, "compact_points: count must be 8-byte aligned");
     MVD_REQUIRE(workspace && workspace_bytes >= mvd_compact_points_workspace_bytes(H, W), "compact_points: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    const long long N = (long long)H * W, nchunks = compact_chunks(N);
-    const unsigned nwg = (unsigned)((nchunks + CP_WAVES - 1) / CP_WAVES);
+    const long long N = (long long)H * W;
+    const unsigned nwg = compact_workgroups(N);
     unsigned* counts = static_cast<unsigned*>(workspace);
-    hipLaunchKernelGGL(compact_count_kernel, dim3(nwg), dim3(CP_THREADS), 0, st, mask, N, counts);
-    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(CP_THREADS), 0, st, counts, nchunks, count);
+    hipLaunchKernelGGL(compact_count_kernel<MaskSet>, dim3(nwg), dim3(CP_THREADS), 0, st, MaskSet{mask}, N, counts);
+    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(CP_THREADS), 0, st, counts, compact_chunks(N), count);
     hipLaunchKernelGGL(compact_scatter_kernel, dim3(nwg), dim3(CP_THREADS), 0, st, mask, depth, image, backproject, counts, W, N, xyz, rgb);
     return launch_status("compact_points");
 }

@@ -27,10 +27,8 @@ __device__ __forceinline__ float absmax_seen(const float* slot) { return slot ? 
 __device__ __forceinline__ void raise_absmax_seen(float* slot, float m, float seen) {
     if (m > seen) raise_absmax(slot, m);
 }
-__device__ __forceinline__ float finite_abs_or_zero(float v) {
-    const float a = fabsf(v);
-    return a <= 3.402823466e38f ? a : 0.f;  // false for inf and NaN
-}
+__host__ __device__ inline bool finite_f32(float v) { return fabsf(v) <= 3.402823466e38f; }  // false for inf and NaN
+__device__ __forceinline__ float finite_abs_or_zero(float v) { return finite_f32(v) ? fabsf(v) : 0.f; }
 
 // stride-1 3x3x3 convolution with ONE input channel (conv3d_backward.hip): what mvd_conv3d_bn_relu_f32 runs for Cin == 1
 bool conv3d_c1_ok(int Cout);

@@ -9,7 +9,6 @@ which metrics() and sparsification_curve() form the reference's numbers.  Per-pi
 bit for bit; quantities that come from sums (absrel, the curves, the least-squares parameters) are formed from float64 sums where
 the reference adds float32 pairwise.
 """
-import ctypes
 import functools
 from dataclasses import dataclass, field
 
@@ -231,19 +230,19 @@ class DeviceScorer:
 
     def __init__(self, gt, device, alignment=None, sparse_pred=False, clip=(0.1, 100.0)):
         import torch
-        from . import _lib as L
+        from . import ops  # here, not at the top: the numpy half of this module works without the library
         assert alignment in ALIGNMENTS, alignment
-        self.L, self.lib, self.torch = L, L.load(), torch
+        self.ops, self.torch = ops, torch
         self.device = torch.device(device)
         if not isinstance(gt, torch.Tensor):
             gt = torch.from_numpy(np.ascontiguousarray(gt, dtype=np.float32))
         if gt.ndim != 2:
             raise ValueError(f"gt: expected (H,W), got {tuple(gt.shape)}")
-        self.gt = L.as_f32(gt.to(self.device), "gt")
+        self.gt = ops.L.as_f32(gt.to(self.device), "gt")
         self.H, self.W = self.gt.shape
         self.alignment, self.sparse_pred, self.clip = alignment, bool(sparse_pred), clip
-        self.ws_bytes = self.lib.mvd_depth_eval_workspace_bytes(self.H, self.W)
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
+        self.ws_bytes = ops.L.load().mvd_depth_eval_workspace_bytes(self.H, self.W)
+        self.ws = ops.workspace(self.ws_bytes, self.device)
         self._tables = {}
 
     def tables(self, h, w):
@@ -257,40 +256,35 @@ class DeviceScorer:
             if t.numel() != t.shape[-2] * t.shape[-1]:
                 raise ValueError(f"{name}: expected one (h,w) map, got {tuple(t.shape)}")
             t = t.reshape(t.shape[-2], t.shape[-1])
-        return self.L.as_f32(t, name, shape, self.device)
+        return self.ops.L.as_f32(t, name, shape, self.device)
 
     def align_stats(self, pred, uncertainty=None, alignment="same"):
         """-> (params, sums): 8 floats and 5 doubles on the device (include/mvd.h: mvd_depth_align_stats_f32)."""
-        L, torch = self.L, self.torch
+        torch = self.torch
         alignment = self.alignment if alignment == "same" else alignment
         pred = self._map2d(pred, "pred")
         unc = self._map2d(uncertainty, "uncertainty", pred.shape) if uncertainty is not None else None
         row, col = self.tables(*pred.shape)
         params = torch.empty(8, dtype=torch.float32, device=self.device)
         sums = torch.zeros(5, dtype=torch.float64, device=self.device)
-        L.check(self.lib.mvd_depth_align_stats_f32(L.ptr(self.gt), L.ptr(pred), L.ptr(unc), L.ptr(row), L.ptr(col), self.H, self.W,
-                                                   pred.shape[0], pred.shape[1], _MODE[alignment], int(self.sparse_pred),
-                                                   L.ptr(params), L.ptr(sums), L.ptr(self.ws), self.ws_bytes, L.stream_of(pred)),
-                "mvd_depth_align_stats_f32")
+        self.ops.call("mvd_depth_align_stats_f32", self.device, self.gt, pred, unc, row, col, self.H, self.W, pred.shape[0],
+                      pred.shape[1], _MODE[alignment], int(self.sparse_pred), params, sums, self.ws, self.ws_bytes)
         return params, sums
 
     def score(self, pred, uncertainty=None, maps=False, params=None):
         """pred, uncertainty: GPU tensors with one (h,w) map -> Score (its maps stay on the device).  `params`: explicit alignment
         parameters, a sequence (ratio,) / (scale, shift) or a device tensor of at least 2 floats, instead of the computed ones."""
-        L, torch = self.L, self.torch
+        call, torch = self.ops.call, self.torch
         pred = self._map2d(pred, "pred")
         unc = self._map2d(uncertainty, "uncertainty", pred.shape) if uncertainty is not None else None
         row, col = self.tables(*pred.shape)
         h, w = pred.shape
-        st = L.stream_of(pred)
         out = torch.empty(9, dtype=torch.int64, device=self.device)  # 40 bytes of result, then the 8 floats of the parameters
         stats = out[5:].view(torch.float32)
         need_stats = unc is not None or (self.alignment is not None and params is None)
         if need_stats:
-            L.check(self.lib.mvd_depth_align_stats_f32(L.ptr(self.gt), L.ptr(pred), L.ptr(unc), L.ptr(row), L.ptr(col), self.H, self.W,
-                                                       h, w, _MODE[self.alignment] if params is None else 0, int(self.sparse_pred),
-                                                       ctypes.c_void_p(stats.data_ptr()), None, L.ptr(self.ws), self.ws_bytes, st),
-                    "mvd_depth_align_stats_f32")
+            call("mvd_depth_align_stats_f32", self.device, self.gt, pred, unc, row, col, self.H, self.W, h, w,
+                 _MODE[self.alignment] if params is None else 0, int(self.sparse_pred), stats, None, self.ws, self.ws_bytes)
         else:
             stats.fill_(float("nan"))
         if params is not None and self.alignment is not None:
@@ -303,12 +297,9 @@ class DeviceScorer:
         m_pred, m_inv, m_rel = (new(), new(), new()) if maps else (None, None, None)
         m_unc = new() if maps and unc is not None else None
         clip = self.clip
-        L.check(self.lib.mvd_depth_score_f32(L.ptr(self.gt), L.ptr(pred), L.ptr(unc), L.ptr(row), L.ptr(col), self.H, self.W, h, w,
-                                             _MODE[self.alignment], int(self.sparse_pred), int(clip is not None),
-                                             clip[0] if clip else 0.0, clip[1] if clip else 0.0, INLIER_THRESH, INLIER_THRESH + 1,
-                                             ctypes.c_void_p(stats.data_ptr()), ctypes.c_void_p(out.data_ptr()), L.ptr(m_pred),
-                                             L.ptr(m_inv), L.ptr(m_rel), L.ptr(m_unc), L.ptr(self.ws), self.ws_bytes, st),
-                "mvd_depth_score_f32")
+        call("mvd_depth_score_f32", self.device, self.gt, pred, unc, row, col, self.H, self.W, h, w, _MODE[self.alignment],
+             int(self.sparse_pred), int(clip is not None), float(clip[0]) if clip else 0.0, float(clip[1]) if clip else 0.0, INLIER_THRESH,
+             INLIER_THRESH + 1, stats, out, m_pred, m_inv, m_rel, m_unc, self.ws, self.ws_bytes)
         host = out.cpu().numpy()  # the run's one device-to-host read
         f = host[5:].view(np.float32)
         s = Score(float(host[:1].view(np.float64)[0]), int(host[1]), int(host[2]), int(host[3]), self.H * self.W,
@@ -324,18 +315,14 @@ class DeviceScorer:
 
     def rank_keys(self, u, u_min, pred_depth):
         """((u - u_min) + 1) * mask; u_min: a device tensor whose first float is the minimum."""
-        L = self.L
         keys = self.torch.empty(self.H * self.W, dtype=self.torch.float32, device=self.device)
-        L.check(self.lib.mvd_rank_keys_f32(L.ptr(u), ctypes.c_void_p(u_min.data_ptr()), L.ptr(self.gt), L.ptr(pred_depth),
-                                           int(self.sparse_pred), self.H * self.W, L.ptr(keys), L.stream_of(u)), "mvd_rank_keys_f32")
+        self.ops.call("mvd_rank_keys_f32", self.device, u, u_min, self.gt, pred_depth, int(self.sparse_pred), self.H * self.W, keys)
         return keys
 
     def ranked_step_sums(self, ranked, count, out=None):
         """ranked: the errors in ranked order; count: device int64 tensor -> 100 float64 sums on the device."""
-        L, torch = self.L, self.torch
-        out = torch.empty(NUM_STEPS, dtype=torch.float64, device=self.device) if out is None else out
-        L.check(self.lib.mvd_ranked_step_sums_f64(L.ptr(ranked), ranked.numel(), ctypes.c_void_p(count.data_ptr()), L.ptr(out),
-                                                  L.ptr(self.ws), self.ws_bytes, L.stream_of(ranked)), "mvd_ranked_step_sums_f64")
+        out = self.torch.empty(NUM_STEPS, dtype=self.torch.float64, device=self.device) if out is None else out
+        self.ops.call("mvd_ranked_step_sums_f64", self.device, ranked, ranked.numel(), count, out, self.ws, self.ws_bytes)
         return out
 
     def uncertainty_curves(self, score):

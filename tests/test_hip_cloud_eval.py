@@ -240,6 +240,8 @@ def voxel_points(case):
     rng = np.random.default_rng(12)
     if case[0] == "n" and case[1:].isdigit():
         return rng.uniform(-1, 1, (int(case[1:]), 3)).astype(np.float32), 0.25, None
+    if case == "n70000-fine":  # nearly every point its own voxel: every one of the 274 chunks of 256 keys adds to the scan
+        return rng.uniform(-1, 1, (70000, 3)).astype(np.float32), 0.02, None
     if case == "one-voxel":
         return rng.uniform(0.01, 0.99, (5000, 3)).astype(np.float32), 1.0, (0, 0, 0)
     if case == "own-voxel":
@@ -260,10 +262,12 @@ def voxel_points(case):
     return pts, 0.125, (0, 0, 0)
 
 
-@pytest.mark.parametrize("case", ["n1", "n64", "n65", "n5000", "one-voxel", "own-voxel", "faces-pow2", "faces-0.01", "negative",
-                                  "negative-origin", "invalid"])
+@pytest.mark.parametrize("case", ["n1", "n64", "n65", "n5000", "n70000", "n70000-fine", "one-voxel", "own-voxel", "faces-pow2",
+                                  "faces-0.01", "negative", "negative-origin", "invalid"])
 def test_voxel_kernel(case):
-    """Voxel order and counts exactly; coordinates and colours within 1 float32 ulp of the float64 mean rounded to float32."""
+    """Voxel order and counts exactly; coordinates and colours within 1 float32 ulp of the float64 mean rounded to float32.
+    n70000 (274 chunks of 256 keys) is the smallest round size at which a lane of the one-workgroup scan (csrc/compact.h) takes two
+    counts; its 512 voxels of about 137 points also take the wave-wide sum."""
     pts, voxel, origin = voxel_points(case)
     col = np.random.default_rng(8).uniform(0, 255, pts.shape).astype(np.float32)
     wx, wr, wc = CE.voxel_downsample_numpy(pts, voxel, col, origin)

@@ -127,12 +127,17 @@ def test_wrapper_errors():
         ops.compact_points(torch.zeros(d.shape, dtype=torch.bool, device=DEV), d, torch.zeros(12, device=DEV))
 
 
+# 66,563 pixels = 261 chunks of 256: the one-workgroup scan (csrc/compact.h) gives lanes 0-129 two counts each, lane 130 one and the
+# rest none, where both sizes of FC.SIZES (20 and 50 chunks) give every lane at most one
+SCAN_SIZE = (259, 257)
+
+
 def compaction_masks():
     out = []
-    for size in FC.SIZES:
+    for size in FC.SIZES + (SCAN_SIZE,):
         H, W = size
         single = np.zeros((H, W), dtype=np.uint8)
-        single.reshape(-1)[H * W - 3] = 1  # in the last ballot of the last chunk of 256, both partial at both sizes
+        single.reshape(-1)[H * W - 3] = 1  # in the last ballot of the last chunk of 256, both partial at every size
         assert (H * W) % 256 and (H * W) % 64 and H * W - 3 >= (H * W) // 64 * 64
         out += [(size, "zeros", np.zeros((H, W), dtype=np.uint8)), (size, "ones", np.ones((H, W), dtype=np.uint8)),
                 (size, "sceneA", FC.reference("A", H, W, 0)["f64"]["mask"]), (size, "single", single)]
