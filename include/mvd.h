@@ -677,6 +677,11 @@ int mvd_voxel_reduce_f32(const long long* keys, const long long* perm, const flo
 int mvd_nchw_to_nhwc_f32(const float* src, float* dst, int N, int C, long long HW, mvd_stream_t stream);
 int mvd_nhwc_to_nchw_f32(const float* src, float* dst, int N, int C, long long HW, mvd_stream_t stream);
 
+/* Zeroes the border of a zero-bordered channel-last map y (B, h + 3, w + 3, C), C a multiple of 4 (K3's staging layout,
+ * MVD_FEAT_NHWC_BORDER): row 0, rows h + 1 and h + 2, column 0, columns w + 1 and w + 2.  The interior (rows 1 .. h, columns 1 .. w)
+ * is not touched: its producer writes it. */
+int mvd_zero_border_nhwc_f32(float* y, int B, int h, int w, int C, mvd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,7 @@ SIGNATURES = {
     "mvd_resize_order1_f32": (_i, [_c_float_p, _c_float_p, ctypes.c_longlong, _i, _i, _i, _i, ctypes.c_void_p]),
     "mvd_nchw_to_nhwc_f32": (_i, [_c_float_p, _c_float_p, _i, _i, ctypes.c_longlong, ctypes.c_void_p]),
     "mvd_nhwc_to_nchw_f32": (_i, [_c_float_p, _c_float_p, _i, _i, ctypes.c_longlong, ctypes.c_void_p]),
+    "mvd_zero_border_nhwc_f32": (_i, [_c_float_p, _i, _i, _i, _i, ctypes.c_void_p]),
     "mvd_depth_eval_workspace_bytes": (_sz, [_i, _i]),
     "mvd_depth_align_stats_f32": (_i, [_c_float_p] * 3 + [ctypes.c_void_p] * 2 + [_i] * 6 + [_c_float_p, ctypes.c_void_p,
                                                                                             ctypes.c_void_p, _sz, ctypes.c_void_p]),

@@ -260,10 +260,13 @@ class FeatureNet(nn.Module):
         return pk
 
     @ops.inference_only
-    def forward_layout(self, x, out_layout, return_absmax=False):
+    def forward_layout(self, x, out_layout, return_absmax=False, out=None):
         """x (N,3,H,W) normalised images -> features at H/4 x W/4 in `out_layout` (L.LAYOUT_*).  return_absmax: also max |feature|
-        over the batch as a one-element device tensor (a by-product of the last layer's store epilogue)."""
+        over the batch as a one-element device tensor (a by-product of the last layer's store epilogue).  out (split layers,
+        LAYOUT_NHWC_BORDER): a contiguous (N, H/4 + 3, W/4 + 3, 32) fp32 buffer to fill instead of a fresh one, whatever it holds."""
         pk = self._prepare()
+        if out is not None and not (self.split_layers and out_layout == L.LAYOUT_NHWC_BORDER):
+            raise ValueError("out: only the split layers' LAYOUT_NHWC_BORDER output can be written into a caller's buffer")
         if not self.split_layers:
             for i, (w, cin, cout, k, stride, scale, shift, relu) in enumerate(pk.layers):
                 x = ops.conv2d_bn_relu(x, w, cin, cout, k, stride, scale, shift, relu=relu,
@@ -289,7 +292,12 @@ class FeatureNet(nn.Module):
                     slots[7:8] = ops.absmax(x)
             elif out_layout == L.LAYOUT_NHWC_BORDER:  # K3's zero-bordered staging map: the layer writes the interior
                 B, h, w_, _ = x.shape
-                buf = torch.zeros((B, h + 3, w_ + 3, wts.cout), dtype=torch.float32, device=x.device)
+                # only the border is zeroed (the fill of the whole map was 36 MB per frame); the layer writes the interior
+                if out is None:
+                    out = torch.empty((B, h + 3, w_ + 3, wts.cout), dtype=torch.float32, device=x.device)
+                elif tuple(out.shape) != (B, h + 3, w_ + 3, wts.cout):
+                    raise ValueError(f"out: shape {tuple(out.shape)}, expected {(B, h + 3, w_ + 3, wts.cout)}")
+                buf = ops.zero_border_nhwc(out)
                 ops.conv2d_split(x, a_in, wts, act=0, out=buf[:, 1:h + 1, 1:w_ + 1, :], out_absmax=slots[7:8])
                 x = buf
             else:

@@ -101,6 +101,7 @@ struct C2Params {
     int pad_y, pad_x;     // input row of tap ky for output row oy: oy * S - pad_y + ky
     int Cout, ncp;        // output channels; ncp = Cout padded to the launch's BN
     int tiles_x, tiles_y, nblocks, ksplit, chunks_per_split;
+    int tiles;            // the persistent form: tiles of the launch (a workgroup walks blockIdx.x, + gridDim.x, ...)
     int ncls;             // 1, or 4 = the output parity classes (a, b) of a transposed conv: pad - (a, b), output offset (a, b)
     long long cls_bytes;
     int act;              // 0 none, 1 LeakyReLU(slope), 2 ReLU
@@ -221,6 +222,95 @@ __device__ __forceinline__ void c2_finish(const C2Params& p, size_t o, int cb, c
     }
 }
 
+// a workgroup's tile: cout block nb (innermost, so that consecutive workgroups share a patch), K split ks, parity class, tile column and
+// row, output image b = (batch element bb, output plane od)
+struct C2Tile {
+    int nb, ks, cls, b, od, bb, oy0, ox0, iy0, ix0;
+};
+template <int S>
+__device__ __forceinline__ C2Tile c2_tile(const C2Params& p, int bx) {
+    C2Tile t;
+    t.nb = bx % p.nblocks; bx /= p.nblocks;
+    t.ks = bx % p.ksplit; bx /= p.ksplit;
+    t.cls = bx % p.ncls; bx /= p.ncls;
+    const int tx = bx % p.tiles_x; bx /= p.tiles_x;
+    const int ty = bx % p.tiles_y;
+    t.b = bx / p.tiles_y;
+    t.od = t.b % p.Do; t.bb = t.b / p.Do;
+    t.oy0 = ty * C2_TH; t.ox0 = tx * C2_TW;
+    t.iy0 = t.oy0 * S - (p.pad_y - (t.cls >> 1)); t.ix0 = t.ox0 * S - (p.pad_x - (t.cls & 1));  // class (0, 0) for a plain convolution
+    return t;
+}
+// activation scale 2^-e and its inverse, e = exponent(max |x|) - 14
+__device__ __forceinline__ void c2_xscale(const float* xamax, float& xsc, float& xsc_inv) {
+    const unsigned mb = __builtin_amdgcn_readfirstlane((int)__float_as_uint(*xamax));
+    const int ex = (int)((mb >> 23) & 0xffu) - 127;
+    const int e = max(-125, min(125, ex - 14));
+    xsc = __uint_as_float((unsigned)(127 - e) << 23);
+    xsc_inv = __uint_as_float((unsigned)(127 + e) << 23);
+}
+// two activations -> their packed hi and lo fp16 terms
+__device__ __forceinline__ void c2_split2(float xsc, float a0, float a1, unsigned& hi, unsigned& lo) {
+    const float one = 1.0f;
+    unsigned hp, lp;
+    float t0, t1;
+    asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "=v"(hp) : "v"(a0), "s"(xsc));
+    asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "+v"(hp) : "v"(a1), "s"(xsc));
+    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(t0) : "v"(a0), "s"(xsc), "v"(hp));
+    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(t1) : "v"(a1), "s"(xsc), "v"(hp));
+    asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "=v"(lp) : "v"(t0), "s"(one));
+    asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "+v"(lp) : "v"(t1), "s"(one));
+    hi = hp;
+    lo = lp;
+}
+// LDS byte offset of this lane's activation fragment per K step (row 0 of the wave's rows)
+template <class G, int KW, int S, int U8, int STEPS, bool NCHW3>
+__device__ __forceinline__ void c2_tapoff(int (&tapoff)[STEPS], int g, int px16, int row0) {
+#pragma unroll
+    for (int s = 0; s < STEPS; ++s) {
+        if constexpr (NCHW3) {  // step = kernel row, lane group g = the tap pair kx = 2g, 2g + 1
+            tapoff[s] = (s * G::PW + 2 * px16 + 2 * g) * G::PB + row0 * G::ROWB;
+        } else {
+            int unit = 4 * s + g;
+            if (unit >= G::UNITS) unit = 0;  // meets zero weights
+            const int tap = unit / U8, c8 = unit % U8, ky = tap / KW, kx = tap % KW;
+            tapoff[s] = ((ky * S + kx % S) * G::PWS + kx / S + px16) * G::PB + c8 * G::C8S + row0 * G::ROWB;
+        }
+    }
+}
+// one K step of a wave: its MTW pixel rows against its NTW weight fragments; activation fragments TWO pixel rows ahead (one row =
+// 3 NTW MFMAs = 48 .. 96 clocks: less than a conflicted LDS read)
+template <class G, int MTW, int NTW>
+__device__ __forceinline__ void c2_kstep(const char* a, const c2h8 (&wh)[NTW], const c2h8 (&wl)[NTW], c2f4 (&acc)[MTW][NTW]) {
+    constexpr int PLANE = G::PLANE;
+    c2h8 xh = *reinterpret_cast<const c2h8*>(a), xl = *reinterpret_cast<const c2h8*>(a + PLANE);
+    c2h8 yh = xh, yl = xl;
+    if (MTW > 1) {
+        yh = *reinterpret_cast<const c2h8*>(a + G::ROWB);
+        yl = *reinterpret_cast<const c2h8*>(a + G::ROWB + PLANE);
+    }
+#pragma unroll
+    for (int m = 0; m < MTW; ++m) {
+        const c2h8 ch = xh, cl = xl;
+        xh = yh; xl = yl;
+        if (m + 2 < MTW && !(C2_KO & 8)) {
+            yh = *reinterpret_cast<const c2h8*>(a + (m + 2) * G::ROWB);
+            yl = *reinterpret_cast<const c2h8*>(a + (m + 2) * G::ROWB + PLANE);
+        }
+#pragma unroll
+        for (int t = 0; t < NTW; ++t) {
+            if (C2_KO & 2) {
+                acc[m][t][0] += (float)ch[0] * (float)wh[t][0] + (float)cl[1] * (float)wl[t][1];
+                continue;
+            }
+            acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t], ch, acc[m][t], 0, 0, 0);
+            acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[t], ch, acc[m][t], 0, 0, 0);
+            acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t], cl, acc[m][t], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);  // keeps the compiler from hoisting every row's reads to the top (registers)
+    }
+}
+
 template <int KH, int KW, int S, int U8, int WM, int NTW, bool NCHW3>
 __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
     const float amax_seen = absmax_seen(p.part ? nullptr : p.yamax);  // read now, used by the epilogue
@@ -234,40 +324,13 @@ __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
     const int wm = wv / WN, wn = wv % WN;
     const int g = lane >> 4, px16 = lane & 15;
 
-    int bx = blockIdx.x;
-    const int nb = bx % p.nblocks; bx /= p.nblocks;
-    const int ks = bx % p.ksplit; bx /= p.ksplit;
-    const int cls = bx % p.ncls; bx /= p.ncls;
-    const int tx = bx % p.tiles_x; bx /= p.tiles_x;
-    const int ty = bx % p.tiles_y;
-    const int b = bx / p.tiles_y;               // output image: (batch element, output plane) for a 3-D layer
-    const int od = b % p.Do, bb = b / p.Do;
-    const int ca = cls >> 1, cb2 = cls & 1;  // (0, 0) for a plain convolution
-    const int oy0 = ty * C2_TH, ox0 = tx * C2_TW;
-    const int iy0 = oy0 * S - (p.pad_y - ca), ix0 = ox0 * S - (p.pad_x - cb2);
+    const C2Tile tl = c2_tile<S>(p, blockIdx.x);
+    const int nb = tl.nb, ks = tl.ks, cls = tl.cls, b = tl.b, od = tl.od, bb = tl.bb;
+    const int oy0 = tl.oy0, ox0 = tl.ox0, iy0 = tl.iy0, ix0 = tl.ix0;
 
-    // activation scale 2^-e, e = exponent(max |x|) - 14
     float xsc, xsc_inv;
-    {
-        const unsigned mb = __builtin_amdgcn_readfirstlane((int)__float_as_uint(*p.xamax));
-        const int ex = (int)((mb >> 23) & 0xffu) - 127;
-        const int e = max(-125, min(125, ex - 14));
-        xsc = __uint_as_float((unsigned)(127 - e) << 23);
-        xsc_inv = __uint_as_float((unsigned)(127 + e) << 23);
-    }
-    const float one = 1.0f;
-    auto split2 = [xsc, one](float a0, float a1, unsigned& hi, unsigned& lo) {
-        unsigned hp, lp;
-        float t0, t1;
-        asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "=v"(hp) : "v"(a0), "s"(xsc));
-        asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "+v"(hp) : "v"(a1), "s"(xsc));
-        asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(t0) : "v"(a0), "s"(xsc), "v"(hp));
-        asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(t1) : "v"(a1), "s"(xsc), "v"(hp));
-        asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "=v"(lp) : "v"(t0), "s"(one));
-        asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "+v"(lp) : "v"(t1), "s"(one));
-        hi = hp;
-        lo = lp;
-    };
+    c2_xscale(p.xamax, xsc, xsc_inv);
+    auto split2 = [xsc](float a0, float a1, unsigned& hi, unsigned& lo) { c2_split2(xsc, a0, a1, hi, lo); };
 
     // staging items of this thread: global offset (floats, without the chunk's channel offset; -1 = outside the image) and LDS byte
     long long goff[G::NIT];
@@ -288,19 +351,8 @@ __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
             loff[k] = live ? ((py * S + pxx % S) * G::PWS + pxx / S) * PB + c8 * G::C8S : -1;
         }
     }
-    // activation fragment address of this lane per K step (row 0 of the wave's rows)
     int tapoff[STEPS];
-#pragma unroll
-    for (int s = 0; s < STEPS; ++s) {
-        if constexpr (NCHW3) {  // step = kernel row, lane group g = the tap pair kx = 2g, 2g + 1
-            tapoff[s] = (s * G::PW + 2 * px16 + 2 * g) * PB + wm * MTW * G::ROWB;
-        } else {
-            int unit = 4 * s + g;
-            if (unit >= G::UNITS) unit = 0;  // meets zero weights
-            const int tap = unit / U8, c8 = unit % U8, ky = tap / KW, kx = tap % KW;
-            tapoff[s] = ((ky * S + kx % S) * G::PWS + kx / S + px16) * PB + c8 * G::C8S + wm * MTW * G::ROWB;
-        }
-    }
+    c2_tapoff<G, KW, S, U8, STEPS, NCHW3>(tapoff, g, px16, wm * MTW);
 
     // weights: this wave's cout tiles
     const int nt0 = nb * (WN * NTW) + wn * NTW;
@@ -385,34 +437,7 @@ __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
                 }
                 wc += 2048;
             }
-            const char* a = patch + tapoff[s];
-            // activation fragments TWO pixel rows ahead (one row = 3 NTW MFMAs = 48 .. 96 clocks: less than a conflicted LDS read)
-            c2h8 xh = *reinterpret_cast<const c2h8*>(a), xl = *reinterpret_cast<const c2h8*>(a + PLANE);
-            c2h8 yh = xh, yl = xl;
-            if (MTW > 1) {
-                yh = *reinterpret_cast<const c2h8*>(a + G::ROWB);
-                yl = *reinterpret_cast<const c2h8*>(a + G::ROWB + PLANE);
-            }
-#pragma unroll
-            for (int m = 0; m < MTW; ++m) {
-                const c2h8 ch = xh, cl = xl;
-                xh = yh; xl = yl;
-                if (m + 2 < MTW && !(C2_KO & 8)) {
-                    yh = *reinterpret_cast<const c2h8*>(a + (m + 2) * G::ROWB);
-                    yl = *reinterpret_cast<const c2h8*>(a + (m + 2) * G::ROWB + PLANE);
-                }
-#pragma unroll
-                for (int t = 0; t < NTW; ++t) {
-                    if (C2_KO & 2) {
-                        acc[m][t][0] += (float)ch[0] * (float)wh[t][0] + (float)cl[1] * (float)wl[t][1];
-                        continue;
-                    }
-                    acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t], ch, acc[m][t], 0, 0, 0);
-                    acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[t], ch, acc[m][t], 0, 0, 0);
-                    acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t], cl, acc[m][t], 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);  // keeps the compiler from hoisting every row's reads to the top (registers)
-            }
+            c2_kstep<G, MTW, NTW>(patch + tapoff[s], wh, wl, acc);
 #pragma unroll
             for (int t = 0; t < NTW; ++t) { wh[t] = nh[t]; wl[t] = nl[t]; }
         }
@@ -445,6 +470,152 @@ __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
         }
     }
     if (p.yamax && !p.part) {
+        for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+        if (lane == 0) wmax[wv] = amax;
+        __syncthreads();
+        if (tid == 0) {
+            amax = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+            raise_absmax_seen(p.yamax, amax, amax_seen);
+        }
+    }
+}
+
+// The persistent, software-pipelined form (non-image layers, no K split).  The product library builds ONE instance of it,
+// <3, 3, 1, 1, WM 4>: the 3 x 3 layers with 8-channel chunks (3 K steps) and a 16-channel tile, the only kind it measured faster
+// for (C2_PERSIST_WGS below); the other instances exist in the experiments library alone, as the record of that measurement.
+// a workgroup walks the tiles t = blockIdx.x, + gridDim.x, ... (a bound from the parameters alone: no ticket, no flag, no wait on
+// another workgroup), decoded as above.  Once per workgroup: the activation scale, the staging and fragment offsets, the max-|y|
+// atomic, and (while the cout block stays the same, i.e. a grid that is a multiple of nblocks) the per-channel constants.  The
+// patch of the NEXT chunk - at the end of a tile the first chunk of the next tile - is loaded into registers right after this
+// chunk's patch went to LDS, and lands under the K steps, the epilogue and its stores.  vmcnt retires in order, so everything the K
+// steps wait for is requested BEFORE that prefetch: all weight fragments of the chunk go out at its top, and the K loop issues no
+// global load; its waits are counted and leave the prefetch outstanding.  For the counts to be static every staging item loads
+// unconditionally (items outside the image from the plane's first pixel, zeroed when they are split) and the last chunk of the last
+// tile prefetches its own tile's first chunk again.  The sums and their order are those of conv2d_split_kernel: bit-identical.
+template <int KH, int KW, int S, int U8, int WM, int NTW, int WAVES>
+__global__ void __launch_bounds__(256, WAVES) conv2d_split_persist_kernel(C2Params p) {
+    const float amax_seen = absmax_seen(p.yamax);
+    using G = C2Geom<KH, KW, S, U8, false>;
+    constexpr int WN = 4 / WM, MTW = 16 / WM, STEPS = G::STEPS, PB = G::PB, PLANE = G::PLANE;
+    extern __shared__ __attribute__((aligned(16))) char patch[];
+    float* const wmax = reinterpret_cast<float*>(patch + 2 * PLANE);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int wm = wv / WN, wn = wv % WN;
+    const int g = lane >> 4, px16 = lane & 15;
+    int t = blockIdx.x;
+    if (t >= p.tiles) return;
+
+    float xsc, xsc_inv;
+    c2_xscale(p.xamax, xsc, xsc_inv);
+    int loff[G::NIT];
+#pragma unroll
+    for (int k = 0; k < G::NIT; ++k) {
+        const int it = tid + 256 * k, pix = it / U8, c8 = it % U8, py = pix / G::PW, pxx = pix % G::PW;
+        loff[k] = it < G::ITEMS ? ((py * S + pxx % S) * G::PWS + pxx / S) * PB + c8 * G::C8S : -1;
+    }
+    int tapoff[STEPS];
+    c2_tapoff<G, KW, S, U8, STEPS, false>(tapoff, g, px16, wm * MTW);
+    const size_t nt_stride = (size_t)p.nchunks * STEPS * 2048;
+    const size_t plane_floats = (size_t)p.Hi * p.Wi * p.xs;  // < 2^31 (launcher)
+
+    // the loads in flight: the patch of one chunk of one tile.  goff: offset in the plane (floats, -1 = outside the image)
+    int goff[G::NIT];
+    c2f4 v0[G::NIT], v1[G::NIT];
+    bool zlive;
+    auto prefetch = [&](const C2Tile& tl, int chunk, bool new_tile) {
+        if (new_tile) {
+#pragma unroll
+            for (int k = 0; k < G::NIT; ++k) {
+                const int it = tid + 256 * k, pix = it / U8, c8 = it % U8, py = pix / G::PW, pxx = pix % G::PW;
+                const int iy = tl.iy0 + py, ix = tl.ix0 + pxx;
+                const bool inside = it < G::ITEMS && iy >= 0 && iy < p.Hi && ix >= 0 && ix < p.Wi;
+                goff[k] = inside ? (iy * p.Wi + ix) * p.xs + c8 * 8 : -1;
+            }
+        }
+        const int kd = chunk / p.nchunks_c, zi = tl.od * p.SD - p.pad_d + kd;  // the input plane of this chunk (0 for a 2-D layer)
+        zlive = zi >= 0 && zi < p.Di;
+        const float* xim = p.x + ((size_t)tl.bb * p.Di + (zlive ? zi : 0)) * plane_floats + (size_t)(chunk - kd * p.nchunks_c) * G::CC;
+#pragma unroll
+        for (int k = 0; k < G::NIT; ++k) {
+            const float* a = xim + max(goff[k], 0);
+            v0[k] = *reinterpret_cast<const c2f4*>(a);
+            v1[k] = *reinterpret_cast<const c2f4*>(a + 4);
+        }
+    };
+
+    C2Tile tl = c2_tile<S>(p, t);
+    prefetch(tl, 0, true);
+    C2Chan kc[NTW];
+    int nb_have = -1;
+    float amax = 0.f;
+    for (;;) {
+        const int nt0 = tl.nb * (WN * NTW) + wn * NTW;
+        const char* const wlane = p.wpk + (size_t)tl.cls * p.cls_bytes + (size_t)nt0 * nt_stride + lane * 16;
+        if (tl.nb != nb_have) {
+#pragma unroll
+            for (int q = 0; q < NTW; ++q) kc[q] = c2_chan(p, (nt0 + q) * 16 + 4 * g, xsc_inv);
+            nb_have = tl.nb;
+        }
+        const int tn = t + (int)gridDim.x;
+        const bool more = tn < p.tiles;
+        const C2Tile tnext = c2_tile<S>(p, more ? tn : t);
+
+        c2f4 acc[MTW][NTW];
+#pragma unroll
+        for (int m = 0; m < MTW; ++m)
+#pragma unroll
+            for (int q = 0; q < NTW; ++q) acc[m][q] = c2f4{0, 0, 0, 0};
+
+        for (int chunk = 0; chunk < p.nchunks; ++chunk) {
+            // every weight fragment of the chunk, queued behind this chunk's patch (already in flight) and ahead of the next one's
+            c2h8 wh[STEPS][NTW], wl[STEPS][NTW];
+            const char* const wc = wlane + (size_t)chunk * STEPS * 2048;
+#pragma unroll
+            for (int s = 0; s < STEPS; ++s)
+#pragma unroll
+                for (int q = 0; q < NTW; ++q) {
+                    wh[s][q] = *reinterpret_cast<const c2h8*>(wc + s * 2048 + q * nt_stride);
+                    wl[s][q] = *reinterpret_cast<const c2h8*>(wc + s * 2048 + q * nt_stride + 1024);
+                }
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();  // every wave has finished reading the previous chunk's patch
+#pragma unroll
+            for (int k = 0; k < G::NIT; ++k) {
+                if (loff[k] < 0) continue;
+                if (goff[k] < 0 || !zlive) v0[k] = v1[k] = c2f4{0, 0, 0, 0};
+                unsigned h0, h1, h2, h3, l0, l1, l2, l3;
+                c2_split2(xsc, v0[k][0], v0[k][1], h0, l0);
+                c2_split2(xsc, v0[k][2], v0[k][3], h1, l1);
+                c2_split2(xsc, v1[k][0], v1[k][1], h2, l2);
+                c2_split2(xsc, v1[k][2], v1[k][3], h3, l3);
+                *reinterpret_cast<c2u4*>(patch + loff[k]) = c2u4{h0, h1, h2, h3};
+                *reinterpret_cast<c2u4*>(patch + loff[k] + PLANE) = c2u4{l0, l1, l2, l3};
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            const bool last = chunk + 1 == p.nchunks;
+            prefetch(last ? tnext : tl, last ? 0 : chunk + 1, last);
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();
+#pragma unroll
+            for (int s = 0; s < STEPS; ++s) c2_kstep<G, MTW, NTW>(patch + tapoff[s], wh[s], wl[s], acc);
+        }
+
+        // ---- epilogue: lane holds output channels cb .. cb + 3 of pixel (row m, column px16) ---------------------------------------
+        const int ox = tl.ox0 + px16;
+#pragma unroll
+        for (int q = 0; q < NTW; ++q) {
+            const int cb = (nt0 + q) * 16 + 4 * g;
+            if (cb >= p.Cout || ox >= p.Wo) continue;
+            const size_t o0 = c2_out_offset(p, tl.bb, tl.od, tl.oy0 + wm * MTW, ox, tl.cls, cb), ostep = c2_row_step(p);
+#pragma unroll
+            for (int m = 0; m < MTW; ++m)
+                if (tl.oy0 + wm * MTW + m < p.Ho) c2_finish(p, o0 + m * ostep, cb, acc[m][q], kc[q], amax);
+        }
+        if (!more) break;
+        t = tn;
+        tl = tnext;
+    }
+    if (p.yamax) {
         for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
         if (lane == 0) wmax[wv] = amax;
         __syncthreads();
@@ -640,7 +811,7 @@ static bool c2_shape(int KH, int KW, int stride, int mode, int cin_pad, C2Shape*
 
 // output channels per workgroup: the widest tile that does not leave most of it empty
 static int c2_bn(int cout) {
-    if (const char* e = exp_env("MVD_C2_BN")) {  // experiments library: forced channel tile (tools/sweep_conv2d_plan.py)
+    if (const char* e = exp_env("MVD_C2_BN")) {  // experiments library: forced channel tile (tools/sweep_conv2d_plan.py, both of its sweeps)
         const int v = atoi(e);
         if (v == 16 || v == 32 || v == 64 || v == 128) return v;
     }
@@ -658,9 +829,46 @@ static int c2_cpad(int cout) { return (cout + 127) / 128 * 128; }  // eun entrie
 struct C2Plan {
     int Ho, Wo, tiles_x, tiles_y, bn, nblocks, ncp, ncls, nchunks, ksplit;
     long long tiles;
+    long long persist;  // 0: one tile per workgroup; else the grid of conv2d_split_persist_kernel
     size_t part_bytes;
 };
-static C2Plan c2_plan(const C2Shape& s, int B, int Hi, int Wi, int cin_pad, int cout, int KH, int KW, int stride) {
+
+// The persistent form is built for the 3 x 3 (both chunk widths), 3 x 3 stride-2 and 5 x 5 stride-2 layers with up to 64 output
+// channels per workgroup.  C2_PERSIST_WGS[kind][bn index] = workgroups per CU of its grid where it is faster than one tile per
+// workgroup by more than the spread of the timing, layer by layer (profiles/c2_persistent_layers.txt) AND in the headline forward
+// (profiles/c2_persistent_frame.txt); 0 where the layer stays on conv2d_split_kernel.  Only the 3 x 3 layers with 8-channel chunks
+// and a 16-channel tile pass both: the 7- and 9-step chunks pay for all their weight fragments up front with the third wave per
+// SIMD (20 - 55 % slower), and the stride-2 layers gain 10 % alone but nothing between their neighbours in the frame.
+enum { C2_K33 = 0, C2_K33W = 1, C2_K33S2 = 2, C2_K55S2 = 3, C2_NOT_PERSISTENT = -1 };
+static int c2_persist_kind(const C2Shape& s) {
+    if (s.nchw3 || s.transposed) return C2_NOT_PERSISTENT;
+    if (s.KH == 3 && s.KW == 3 && s.S == 1) return s.U8 == 4 ? C2_K33W : s.U8 == 1 ? C2_K33 : C2_NOT_PERSISTENT;
+    if (s.KH == 3 && s.KW == 3 && s.S == 2 && s.U8 == 1) return C2_K33S2;
+    if (s.KH == 5 && s.KW == 5 && s.S == 2 && s.U8 == 1) return C2_K55S2;
+    return C2_NOT_PERSISTENT;
+}
+constexpr int C2_PERSIST_WGS[4][3] = {
+    // bn 16, 32, 64
+    {4, 0, 0},  // 3 x 3, 8-channel chunks: in the frame FeatureNet's conv3 80 -> 49 us, conv4 62 -> 47, the regulariser's conv2 132 -> 124
+    {0, 0, 0},  // 3 x 3, 32-channel chunks
+    {0, 0, 0},  // 3 x 3 stride 2: the regulariser's conv1 151 -> 155 us, conv5 54 -> 54 in the frame
+    {0, 0, 0},  // 5 x 5 stride 2
+};
+// grid of the persistent form (0 = not taken): at most 256 CUs x the table's workgroups, a multiple of nblocks so that a workgroup
+// keeps its cout block
+static long long c2_persist_grid(const C2Shape& s, const C2Plan& q, int Hi, int Wi, int xs) {
+    const int kind = c2_persist_kind(s);
+    if (kind == C2_NOT_PERSISTENT || q.bn > 64 || q.ksplit != 1 || q.tiles > 0x7fffffffLL || (long long)Hi * Wi * xs > 0x7fffffffLL) return 0;
+    const int wgs = C2_PERSIST_WGS[kind][q.bn == 16 ? 0 : q.bn == 32 ? 1 : 2];
+    if (const char* e = exp_env("MVD_C2_PERSIST")) {  // experiments library: 0 off, 1 the rule, n > 1 a grid of exactly n workgroups
+        const long long v = atoll(e);
+        if (v <= 0) return 0;
+        if (v > 1) return std::min<long long>(v, q.tiles);
+    }
+    if (wgs == 0) return 0;
+    return std::min(q.tiles, (256LL * wgs + q.nblocks - 1) / q.nblocks * q.nblocks);
+}
+static C2Plan c2_plan(const C2Shape& s, int B, int Hi, int Wi, int cin_pad, int xs, int cout, int KH, int KW, int stride) {
     C2Plan q{};
     if (s.transposed) { q.Ho = Hi; q.Wo = Wi; q.ncls = 4; }
     else { q.Ho = (Hi + 2 * (KH / 2) - KH) / stride + 1; q.Wo = (Wi + 2 * (KW / 2) - KW) / stride + 1; q.ncls = 1; }
@@ -679,6 +887,7 @@ static C2Plan c2_plan(const C2Shape& s, int B, int Hi, int Wi, int cin_pad, int 
         if (v >= 1 && v <= 32 && (v & (v - 1)) == 0 && v <= q.nchunks) q.ksplit = v;
     }
     q.part_bytes = q.ksplit > 1 ? (size_t)q.ksplit * q.ncls * B * q.Ho * q.Wo * q.ncp * sizeof(float) : 0;
+    q.persist = c2_persist_grid(s, q, Hi, Wi, xs);
     return q;
 }
 
@@ -693,6 +902,20 @@ static int c2_launch(const C2Params& p, long long nblk, hipStream_t st) {
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), lds, st, p);
     return launch_status("conv2d_split");
 }
+// the persistent form on a grid of `grid` workgroups; bounded to three waves per SIMD (168 registers) where a chunk's weight
+// fragments (8 STEPS registers), the prefetched patch (8 NIT) and the accumulators (64 / WM) fit that without spilling: the
+// 3-step chunks of the 3 x 3 layers, and of the stride-2 layers with a 16-channel tile.  (Four and five waves for the 16-channel
+// tiles spill 34 - 57 registers.)
+template <int KH, int KW, int S, int U8, int WM>
+static int c2_launch_persist(const C2Params& p, long long grid, hipStream_t st) {
+    using G = C2Geom<KH, KW, S, U8, false>;
+    constexpr int WAVES = (G::STEPS == 3 && (G::NIT <= 2 || WM == 4)) ? 3 : 2;
+    auto kern = conv2d_split_persist_kernel<KH, KW, S, U8, WM, 1, WAVES>;
+    constexpr int lds = 2 * G::PLANE + 16;
+    static_assert(lds <= 48 * 1024, "the persistent form: three workgroups per CU, no LDS attribute");
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, p);
+    return launch_status("conv2d_split: persistent");
+}
 
 // tile of output channels per workgroup: bn = 16 WN NTW
 template <int KH, int KW, int S, int U8, bool NCHW3>
@@ -705,8 +928,32 @@ static int c2_launch_bn(const C2Params& p, int bn, long long nblk, hipStream_t s
     }
     return MVD_ERR_INVALID_ARG;
 }
+template <int KH, int KW, int S, int U8>
+static int c2_launch_persist_bn(const C2Params& p, int bn, long long grid, hipStream_t st) {
+    switch (bn) {
+#ifdef MVD_EXPERIMENTS  // the tiles whose column of C2_PERSIST_WGS is all zeros
+        case 64: return c2_launch_persist<KH, KW, S, U8, 1>(p, grid, st);
+        case 32: return c2_launch_persist<KH, KW, S, U8, 2>(p, grid, st);
+#endif
+        case 16: return c2_launch_persist<KH, KW, S, U8, 4>(p, grid, st);
+    }
+    return MVD_ERR_INVALID_ARG;
+}
 
-static int c2_dispatch(const C2Shape& s, const C2Params& p, int bn, long long nblk, hipStream_t st) {
+// persist: the plan's persistent grid (0 = one tile per workgroup, nblk workgroups)
+static int c2_dispatch(const C2Shape& s, C2Params& p, int bn, long long nblk, long long persist, hipStream_t st) {
+    if (persist > 0 && p.ksplit == 1) {
+        p.tiles = (int)nblk;
+        switch (c2_persist_kind(s)) {
+            case C2_K33: return c2_launch_persist_bn<3, 3, 1, 1>(p, bn, persist, st);
+#ifdef MVD_EXPERIMENTS  // the kinds whose row of C2_PERSIST_WGS is all zeros: reachable through MVD_C2_PERSIST only
+            case C2_K33W: return c2_launch_persist_bn<3, 3, 1, 4>(p, bn, persist, st);
+            case C2_K33S2: return c2_launch_persist_bn<3, 3, 2, 1>(p, bn, persist, st);
+            case C2_K55S2: return c2_launch_persist_bn<5, 5, 2, 1>(p, bn, persist, st);
+#endif
+        }
+        return MVD_ERR_INVALID_ARG;
+    }
     if (s.nchw3) return c2_launch_bn<7, 7, 2, 1, true>(p, bn, nblk, st);
     if (s.KH == 1) return c2_launch_bn<1, 1, 1, 4, false>(p, bn, nblk, st);
     if (s.KH == 2) return s.U8 == 4 ? c2_launch_bn<2, 2, 1, 4, false>(p, bn, nblk, st) : c2_launch_bn<2, 2, 1, 2, false>(p, bn, nblk, st);
@@ -747,7 +994,7 @@ int mvd_pack_conv2d_weights_split(const float* w, int Cin, int Cin_pad, int Cout
 size_t mvd_conv2d_split_workspace_bytes(int B, int Hi, int Wi, int Cin_pad, int Cout, int KH, int KW, int stride, int mode) {
     mvd::C2Shape s;
     if (B <= 0 || Hi <= 0 || Wi <= 0 || Cin_pad <= 0 || Cout <= 0 || !mvd::c2_shape(KH, KW, stride, mode, Cin_pad, &s)) return 0;
-    return mvd::c2_plan(s, B, Hi, Wi, Cin_pad, Cout, KH, KW, stride).part_bytes;
+    return mvd::c2_plan(s, B, Hi, Wi, Cin_pad, Cin_pad, Cout, KH, KW, stride).part_bytes;
 }
 
 int mvd_conv2d_split_f32(const float* x, const float* x_absmax, const void* packed_w, const float* bias, float* y, float* y_absmax, int B,
@@ -774,7 +1021,7 @@ int mvd_conv2d_split_f32(const float* x, const float* x_absmax, const void* pack
     p.Cout = Cout; p.ys = y_pixel_stride; p.act = act; p.slope = slope;
     const size_t fb = mvd::c2_frag_bytes(s, Cin_pad, Cout);
     p.eun = reinterpret_cast<const float*>(static_cast<const char*>(packed_w) + fb);
-    const mvd::C2Plan q = mvd::c2_plan(s, B, Hi, Wi, Cin_pad, Cout, KH, KW, stride);
+    const mvd::C2Plan q = mvd::c2_plan(s, B, Hi, Wi, Cin_pad, x_pixel_stride, Cout, KH, KW, stride);
     p.Ho = q.Ho; p.Wo = q.Wo; p.ncls = q.ncls;
     if (s.transposed) {
         p.Hy = 2 * Hi; p.Wy = 2 * Wi; p.oy_mul = p.ox_mul = 2; p.pad_y = p.pad_x = 1;
@@ -800,7 +1047,7 @@ int mvd_conv2d_split_f32(const float* x, const float* x_absmax, const void* pack
     p.part = ksplit > 1 ? static_cast<float*>(workspace) : nullptr;
     const long long nblk = tiles * ksplit;
     MVD_REQUIRE(nblk <= 0x7fffffffLL, "conv2d_split: %lld workgroups exceed the grid limit", nblk);
-    int rc = mvd::c2_dispatch(s, p, bn, nblk, st);
+    int rc = mvd::c2_dispatch(s, p, bn, nblk, q.persist, st);
     if (rc != MVD_OK || ksplit == 1) return rc;
     const long long n = (long long)B * p.Ho * p.Wo * ((Cout + 3) / 4);
     MVD_REQUIRE(n < 0x7fffffffLL, "conv2d_split: split reduction over %lld outputs", n);
@@ -874,15 +1121,26 @@ static mvd::C2Plan c3_plan(const mvd::C2Shape& s, int B, int Di, int Hi, int Wi,
     *Do = Di / sd; q.Ho = Hi / sd; q.Wo = Wi / sd; q.ncls = 1;
     q.tiles_y = (q.Ho + mvd::C2_TH - 1) / mvd::C2_TH;
     q.tiles_x = (q.Wo + mvd::C2_TW - 1) / mvd::C2_TW;
-    q.bn = mvd::c2_bn(ncout);
+    q.bn = mvd::c2_bn(ncout);  // the packing rule's tile: any narrower one reads the same 16-channel fragments
+    const long long planes = (long long)q.tiles_x * q.tiles_y * B * *Do;
+    // a stride-1 level with too many tiles for a split of K (128+) and fewer than two per CU (conv6 of a 256-plane volume: 192):
+    // narrower channel tiles, more workgroups, each with a shorter chain of MFMAs per staged chunk (conv6 45 -> 43 us in the frame
+    // on 16 channels; the stride-2 layers are slower that way).  Smaller grids keep their tile and split K as before.
+    if (mode == MVD_CONV3D_STRIDE1 && !mvd::exp_env("MVD_C2_BN") && planes * ((ncout + q.bn - 1) / q.bn) >= 128)
+        while (q.bn > 16 && planes * ((ncout + q.bn - 1) / q.bn) < 512) q.bn /= 2;
     q.nblocks = (ncout + q.bn - 1) / q.bn;
     q.ncp = q.nblocks * q.bn;
     q.nchunks = (mode == MVD_DECONV3D_STRIDE2 ? 2 : 3) * (Cin / (8 * s.U8));
-    q.tiles = (long long)q.tiles_x * q.tiles_y * B * *Do * q.nblocks;
+    q.tiles = planes * q.nblocks;
     q.ksplit = 1;
     if (q.tiles < 128)
         while (q.tiles * q.ksplit < 320 && q.ksplit < 32 && q.nchunks / (q.ksplit * 2) >= 2) q.ksplit *= 2;
+    if (const char* e = mvd::exp_env("MVD_C2_KSPLIT")) {  // experiments library: forced split of the reduction
+        const int v = atoi(e);
+        if (v >= 1 && v <= 32 && (v & (v - 1)) == 0 && v <= q.nchunks) q.ksplit = v;
+    }
     q.part_bytes = q.ksplit > 1 ? (size_t)q.ksplit * B * *Do * q.Ho * q.Wo * q.ncp * sizeof(float) : 0;
+    q.persist = mvd::c2_persist_grid(s, q, Hi, Wi, Cin);
     return q;
 }
 
@@ -927,7 +1185,9 @@ int mvd_conv3d_bn_relu_igemm_f32(const float* x, const float* x_absmax, const vo
     p.part = ksplit > 1 ? static_cast<float*>(workspace) : nullptr;
     const long long nblk = q.tiles * ksplit;
     MVD_REQUIRE(nblk <= 0x7fffffffLL, "conv3d_igemm: %lld workgroups exceed the grid limit", nblk);
-    int rc = mvd::c2_dispatch(s, p, q.bn, nblk, st);
+    MVD_REQUIRE(q.nblocks * (q.bn / 16) <= mvd::c2_ntiles(ncout), "conv3d_igemm: channel tile %d reads past the %d packed fragments", q.bn,
+                mvd::c2_ntiles(ncout));
+    int rc = mvd::c2_dispatch(s, p, q.bn, nblk, q.persist, st);
     if (rc != MVD_OK || ksplit == 1) return rc;
     const long long n = (long long)p.B * p.Ho * p.Wo * ((p.Cout + 3) / 4);
     MVD_REQUIRE(n < 0x7fffffffLL, "conv3d_igemm: split reduction over %lld outputs", n);

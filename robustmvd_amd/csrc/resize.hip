@@ -53,7 +53,38 @@ __global__ void __launch_bounds__(256) resize_order1_kernel(const float* __restr
     dst[(plane * ho + y) * (size_t)wo + x] = (float)t;
 }
 
+// the zero border of K3's staging map (B, h + 3, w + 3, C): row 0, rows h + 1 and h + 2, column 0, columns w + 1 and w + 2.  One
+// thread = 4 channels of a border pixel; pixels 0 .. 3 (w + 3) - 1 are the three whole rows, the rest the three columns of rows 1 .. h
+__global__ void __launch_bounds__(256) zero_border_nhwc_kernel(float* __restrict__ y, int h, int w, int c4n, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int c4 = i % c4n, bp = i / c4n, wp = w + 3;
+    int row, col;
+    if (bp < 3 * wp) {
+        const int r = bp / wp;
+        row = r == 0 ? 0 : h + r;
+        col = bp - r * wp;
+    } else {
+        const int q = bp - 3 * wp, r = q / 3, k = q - 3 * r;
+        row = 1 + r;
+        col = k == 0 ? 0 : w + k;
+    }
+    float* o = y + (((size_t)blockIdx.y * (h + 3) + row) * wp + col) * (4 * (size_t)c4n) + 4 * c4;
+    *reinterpret_cast<float4*>(o) = float4{0.f, 0.f, 0.f, 0.f};
+}
+
 }  // namespace mvd
+
+extern "C" int mvd_zero_border_nhwc_f32(float* y, int B, int h, int w, int C, mvd_stream_t stream) {
+    MVD_REQUIRE(y, "zero_border_nhwc: NULL argument");
+    MVD_REQUIRE(B > 0 && B <= 65535 && h > 0 && w > 0 && C > 0 && C % 4 == 0, "zero_border_nhwc: bad dimensions (C a multiple of 4, B 1..65535)");
+    MVD_REQUIRE(((uintptr_t)y & 15) == 0, "zero_border_nhwc: y must be 16-byte aligned");
+    const long long n = (3LL * (w + 3) + 3LL * h) * (C / 4);
+    MVD_REQUIRE(n < 0x7fffffffLL, "zero_border_nhwc: %lld border items", n);
+    hipLaunchKernelGGL(mvd::zero_border_nhwc_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream, y, h, w,
+                       C / 4, (int)n);
+    return mvd::launch_status("zero_border_nhwc");
+}
 
 extern "C" int mvd_resize_order1_f32(const float* src, float* dst, long long planes, int hi, int wi, int ho, int wo,
                                      mvd_stream_t stream) {

@@ -1096,6 +1096,19 @@ def dispnet_head(x):
 
 
 @inference_only
+def zero_border_nhwc(buf):
+    """buf (B, h + 3, w + 3, C) contiguous fp32, K3's zero-bordered staging map: zeroes row 0, rows h + 1 and h + 2, column 0 and
+    columns w + 1 and w + 2 in place and leaves the interior to its producer.  Returns buf."""
+    if not (isinstance(buf, torch.Tensor) and buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous() and buf.dim() == 4):
+        raise ValueError("zero_border_nhwc: buf must be a contiguous (B, h + 3, w + 3, C) fp32 device tensor")
+    B, hp, wp, C = buf.shape
+    if hp < 4 or wp < 4 or C % 4:
+        raise ValueError(f"zero_border_nhwc: shape {tuple(buf.shape)} (h, w >= 1, C a multiple of 4)")
+    call("mvd_zero_border_nhwc_f32", buf.device, buf, B, hp - 3, wp - 3, C)
+    return buf
+
+
+@inference_only
 def to_channels_last_3d(x):
     """(B,C,D,h,w) -> (B,D,h,w,C) through the library's tiled transpose."""
     x = L.as_f32(x, "x")
