@@ -284,6 +284,22 @@ size_t mvd_conv3d_igemm_workspace_bytes(int B, int Di, int Hi, int Wi, int Cin, 
 int mvd_conv3d_bn_relu_igemm_f32(const float* x, const float* x_absmax, const void* packed_w, const float* scale, const float* shift,
                                  const float* skip, float* y, float* y_absmax, int B, int Di, int Hi, int Wi, int Cin, int Cout, int mode,
                                  int relu, void* workspace, size_t workspace_bytes, mvd_stream_t stream);
+/* K4's transposed layers on a kernel of their own (csrc/deconv3d_split.hip): ConvTranspose3d 3x3x3, stride 2, padding 1,
+ * output_padding 1 with split operands as above (each fp32 value two fp16 terms after an exact power-of-two scaling, products
+ * w_hi a_hi + w_lo a_hi + w_hi a_lo on v_mfma_f32_16x16x32_f16 into one fp32 accumulator), in the decomposition of the fp32 kernel: a
+ * workgroup stages 2 input planes x 5 rows once and writes all eight output parity classes, so no product is a structural zero.
+ * w: ConvTranspose3d layout (Cin, Cout, 3, 3, 3).  Cin = 32 or 64 with Cout = 16, 32, 48 or 64, and 16 -> 8; the packed size is 0 for
+ * any other pair.  x (B,Di,hi,wi,Cin) channel-last fp32 -> y (B,2Di,2hi,2wi,Cout); y = relu?(deconv * scale + shift) (+ skip, laid
+ * out like y, may be NULL).  x_absmax: DEVICE pointer to one float with max |x| over the whole input (any upper bound is safe); a
+ * value v is represented to |error| <= max(2^-22 |v|, 2^-39 max|x|).  y_absmax: NULL, or a device float that is RAISED to max |y|
+ * over the finite outputs, after the skip addition (one atomic maximum per workgroup: the caller zeroes it); the output is bit-identical
+ * either way.  inf / NaN inputs give inf / NaN outputs where they reach.  16 -> 8: the two w-parities of an output column pair share
+ * one MFMA (as in the fp32 kernel of that layer), so a non-finite input column c + 1 also reaches output column 2c. */
+size_t mvd_deconv3d_split_packed_weight_bytes(int Cin, int Cout);
+int mvd_pack_deconv3d_weights_split(const float* w, int Cin, int Cout, void* packed, mvd_stream_t stream);
+int mvd_deconv3d_bn_relu_f32_split(const float* x, const float* x_absmax, const void* packed_w, const float* scale, const float* shift,
+                                   const float* skip, float* y, float* y_absmax, int B, int Di, int hi, int wi, int Cin, int Cout, int relu,
+                                   mvd_stream_t stream);
 /* ---- Path A's 2-D CNN: split-operand implicit-GEMM convolutions ------------------------------------------------------------
  * Replace torch.nn.functional.conv2d / conv_transpose2d + bias + LeakyReLU (+ torch.cat of the inputs) of the DispNet blocks of
  * robust_mvd (rmvd/models/blocks/dispnet_encoder.py:6-27, dispnet_context_encoder.py, learned_fusion.py:8-20,

@@ -91,6 +91,9 @@ SIGNATURES = {
     "mvd_pack_conv3d_weights_split": (_i, [_c_float_p, _i, _i, ctypes.c_void_p, ctypes.c_void_p]),
     "mvd_conv3d_bn_relu_f32_split": (_i, [_c_float_p, _c_float_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p] + [_i] * 7
                                      + [ctypes.c_void_p]),
+    "mvd_deconv3d_split_packed_weight_bytes": (_sz, [_i, _i]),
+    "mvd_pack_deconv3d_weights_split": (_i, [_c_float_p, _i, _i, ctypes.c_void_p, ctypes.c_void_p]),
+    "mvd_deconv3d_bn_relu_f32_split": (_i, [_c_float_p, _c_float_p, ctypes.c_void_p] + [_c_float_p] * 5 + [_i] * 7 + [ctypes.c_void_p]),
     "mvd_conv2d_packed_weight_floats": (_sz, [_i, _i, _i]),
     "mvd_pack_conv2d_weights_f32": (_i, [_c_float_p, _i, _i, _i, _c_float_p, ctypes.c_void_p]),
     "mvd_conv2d_bn_relu_f32": (_i, [_c_float_p, _i, _c_float_p, _c_float_p, _c_float_p, _c_float_p, _i] + [_i] * 8

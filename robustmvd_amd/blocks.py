@@ -341,13 +341,18 @@ class CostRegNet(nn.Module):
     LAYERS = [("conv0", 32, 8, 1), ("conv1", 8, 16, 2), ("conv2", 16, 16, 1), ("conv3", 16, 32, 2), ("conv4", 32, 32, 1),
               ("conv5", 32, 64, 2), ("conv6", 64, 64, 1)]
     UPS = [("conv7", 64, 32), ("conv9", 32, 16), ("conv11", 16, 8)]
+    # the first of UPS that run on ops.deconv3d_bn_relu_split when conv0_split is on (a leading run of UPS: each is scaled by the
+    # max |y| its predecessor leaves behind)
+    UPS_SPLIT = ("conv7", "conv9", "conv11")
 
     def __init__(self, conv0_split=True):
         """conv0_split (default on): the fp32 operands of the stride-1 layers with 16 or 32 input channels (conv0: 32 -> 8 at
         full resolution, conv2: 16 -> 16, conv4: 32 -> 32) are split into two fp16 terms each, after an exact
         power-of-two range scaling, and multiplied on fp16 MFMA with fp32 accumulation (ops.conv3d_bn_relu_split); its
         results are at least as close to the exact convolution as the fp32 matrix instruction's (measured against a
-        float64 oracle over magnitudes 1e-30 .. 1e30: tests/test_hip_f16.py).  False: every layer on fp32 MFMA."""
+        float64 oracle over magnitudes 1e-30 .. 1e30: tests/test_hip_f16.py); conv1 .. conv6 then run on the split-operand implicit
+        GEMM and the transposed layers conv7, conv9, conv11 on their own split-operand kernel (ops.deconv3d_bn_relu_split,
+        tests/test_hip_deconv3d_split.py).  False: every layer on fp32 MFMA."""
         super().__init__()
         self.conv0_split = bool(conv0_split)
         for name, cin, cout, stride in self.LAYERS:
@@ -387,6 +392,8 @@ class CostRegNet(nn.Module):
                 if name != "conv0":
                     pk[name + "_igemm"] = ops.pack_conv3d_weights_igemm(getattr(self, name).conv.weight.detach(),
                                                                         L.CONV3D_STRIDE1 if stride == 1 else L.CONV3D_STRIDE2)
+            for name in self.UPS_SPLIT:  # the transposed layers below full resolution on their own split-operand kernel
+                pk[name + "_dsplit"] = ops.pack_deconv3d_weights_split(getattr(self, name)[0].weight.detach())
         self._packed, self._packed_key = pk, key
         return pk
 
@@ -422,8 +429,8 @@ class CostRegNet(nn.Module):
             conv0 = layer("conv0", x)
         if self.conv0_split:
             # conv1 .. conv6 on the implicit-GEMM split kernel of the 2-D engine (depth taps as chunks), each scaled by max |x| of its
-            # input, which the layer before leaves behind as a by-product of its store epilogue; the transposed layers and `prob`
-            # on the fp32 matrix instruction / vector ALU (measured faster there: tools/bench_k4_igemm.py)
+            # input, which the layer before leaves behind as a by-product of its store epilogue; conv11 and `prob`
+            # on the fp32 matrix instruction / vector ALU
             slots = torch.zeros(8, dtype=torch.float32, device=x.device)  # the layers' max-|y| slots: one fill for all
             nslot = [0]
 
@@ -443,17 +450,35 @@ class CostRegNet(nn.Module):
             t, a = ig("conv3", conv2, a)
             conv4, a = ig("conv4", t, a)
             t, a = ig("conv5", conv4, a)
-            y = ig("conv6", t, a, want_absmax=False)
+            # the fp16-feature variant keeps the fp32 transposed kernels
+            ups = self.UPS_SPLIT if x.dtype == torch.float32 else ()
+            y = ig("conv6", t, a, want_absmax=bool(ups))
+            if ups:
+                y, a = y
         else:
+            ups = ()
             conv2 = layer("conv2", layer("conv1", conv0))
             conv4 = layer("conv4", layer("conv3", conv2))
             y = layer("conv6", layer("conv5", conv4))
-        y = layer("conv7", y, skip=conv4)
-        del conv4
-        y = layer("conv9", y, skip=conv2)
-        del conv2
-        y = layer("conv11", y, skip=conv0)
-        del conv0
+        # the transposed layers: those of UPS_SPLIT on their own split-operand kernel (csrc/deconv3d_split.hip), scaled like
+        # conv1 .. conv6 (the layer before leaves max |y| behind, after its skip addition); the others on the fp32 kernels
+        skips = {"conv7": conv4, "conv9": conv2, "conv11": conv0}
+        del conv4, conv2, conv0
+        for i, (name, cin, cout) in enumerate(self.UPS):
+            skip = skips.pop(name)
+            if name in ups:
+                want = i + 1 < len(self.UPS) and self.UPS[i + 1][0] in ups
+                out_a = None
+                if want:
+                    out_a = slots[nslot[0]:nslot[0] + 1]
+                    nslot[0] += 1
+                y = ops.deconv3d_bn_relu_split(y, a, pk[name + "_dsplit"], cin, cout, pk[name][3], pk[name][4], relu=True, skip=skip,
+                                               return_absmax=want, out_absmax=out_a)
+                if want:
+                    y, a = y
+            else:
+                y = layer(name, y, skip=skip)
+            del skip
         return layer("prob", y, relu=False).squeeze(-1)
 
     @ops.inference_only

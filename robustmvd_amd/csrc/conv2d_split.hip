@@ -26,6 +26,7 @@
 //
 // Transposed convolutions (4 x 4, stride 2, padding 1) run as four 2 x 2 stride-1 layers, one per output parity class.
 #include "mvd_common.h"
+#include "split_operand.h"
 #include <algorithm>
 #include <stdlib.h>
 
@@ -240,28 +241,6 @@ __device__ __forceinline__ C2Tile c2_tile(const C2Params& p, int bx) {
     t.oy0 = ty * C2_TH; t.ox0 = tx * C2_TW;
     t.iy0 = t.oy0 * S - (p.pad_y - (t.cls >> 1)); t.ix0 = t.ox0 * S - (p.pad_x - (t.cls & 1));  // class (0, 0) for a plain convolution
     return t;
-}
-// activation scale 2^-e and its inverse, e = exponent(max |x|) - 14
-__device__ __forceinline__ void c2_xscale(const float* xamax, float& xsc, float& xsc_inv) {
-    const unsigned mb = __builtin_amdgcn_readfirstlane((int)__float_as_uint(*xamax));
-    const int ex = (int)((mb >> 23) & 0xffu) - 127;
-    const int e = max(-125, min(125, ex - 14));
-    xsc = __uint_as_float((unsigned)(127 - e) << 23);
-    xsc_inv = __uint_as_float((unsigned)(127 + e) << 23);
-}
-// two activations -> their packed hi and lo fp16 terms
-__device__ __forceinline__ void c2_split2(float xsc, float a0, float a1, unsigned& hi, unsigned& lo) {
-    const float one = 1.0f;
-    unsigned hp, lp;
-    float t0, t1;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "=v"(hp) : "v"(a0), "s"(xsc));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "+v"(hp) : "v"(a1), "s"(xsc));
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(t0) : "v"(a0), "s"(xsc), "v"(hp));
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(t1) : "v"(a1), "s"(xsc), "v"(hp));
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "=v"(lp) : "v"(t0), "s"(one));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "+v"(lp) : "v"(t1), "s"(one));
-    hi = hp;
-    lo = lp;
 }
 // LDS byte offset of this lane's activation fragment per K step (row 0 of the wave's rows)
 template <class G, int KW, int S, int U8, int STEPS, bool NCHW3>

@@ -449,6 +449,49 @@ def conv3d_bn_relu_igemm(x, x_absmax, packed, Cin, Cout, scale, shift, mode, rel
 
 
 @inference_only
+def pack_deconv3d_weights_split(weight):
+    """weight: ConvTranspose3d (Cin,Cout,3,3,3) fp32; Cin 32 or 64 with Cout 16, 32, 48 or 64, or 16 -> 8 -> the hi / lo fp16 fragments
+    for deconv3d_bn_relu_split, followed by the channels' power-of-two scales."""
+    wt = L.as_f32(weight, "weight")
+    cin, cout = _conv3d_channels(wt, L.DECONV3D_STRIDE2)
+    n = L.load().mvd_deconv3d_split_packed_weight_bytes(cin, cout)
+    if n == 0:
+        raise ValueError(f"deconv3d split: {cin} -> {cout} channels is not built (32 or 64 -> 16, 32, 48 or 64; 16 -> 8)")
+    packed = torch.empty(n, dtype=torch.uint8, device=wt.device)
+    call("mvd_pack_deconv3d_weights_split", wt.device, wt, cin, cout, packed)
+    return packed
+
+
+@inference_only
+def deconv3d_bn_relu_split(x, x_absmax, packed, Cin, Cout, scale, shift, relu=True, skip=None, return_absmax=False, out_absmax=None):
+    """K4's transposed layers (conv7: 64 -> 32, conv9: 32 -> 16, conv11: 16 -> 8), split-operand form: x (B,D,h,w,Cin) channel-last
+    fp32, x_absmax one-element device tensor with max |x| -> (B,2D,2h,2w,Cout); skip (like the output) is added after the
+    activation.  return_absmax: also max |y| over the finite outputs, a by-product of the store epilogue (out_absmax: a zeroed
+    one-element device tensor to raise instead of a fresh one)."""
+    lib = L.load()
+    x = L.as_f32(x, "x")
+    if x.dim() != 5 or x.shape[-1] != Cin:
+        raise ValueError(f"x must be (B,D,h,w,{Cin}) channel-last, got {tuple(x.shape)}")
+    B, Di, hi, wi, _ = x.shape
+    dev = x.device
+    oshape = (B, 2 * Di, 2 * hi, 2 * wi, Cout)
+    n = lib.mvd_deconv3d_split_packed_weight_bytes(Cin, Cout)
+    if n == 0 or packed.numel() != n:
+        raise ValueError(f"packed weights of {packed.numel()} bytes do not belong to a transposed {Cin} -> {Cout} layer")
+    scale = L.as_f32(scale, "scale", (Cout,), dev)
+    shift = L.as_f32(shift, "shift", (Cout,), dev)
+    if skip is not None:
+        skip = L.as_f32(skip, "skip", oshape, dev)
+    xam = L.as_f32(x_absmax, "x_absmax", (1,), dev)
+    y = torch.empty(oshape, dtype=torch.float32, device=dev)
+    yam = None
+    if return_absmax:
+        yam = torch.zeros(1, dtype=torch.float32, device=dev) if out_absmax is None else L.as_f32(out_absmax, "out_absmax", (1,), dev)
+    call("mvd_deconv3d_bn_relu_f32_split", dev, x, xam, packed, scale, shift, skip, y, yam, B, Di, hi, wi, Cin, Cout, int(bool(relu)))
+    return (y, yam) if return_absmax else y
+
+
+@inference_only
 def pack_conv2d_weights(weight):
     """weight: Conv2d (Cout,Cin,k,k), k in (3, 5) -> (packed, Cin, Cout, k)."""
     wt = L.as_f32(weight, "weight")
