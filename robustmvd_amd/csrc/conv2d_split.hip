@@ -3,13 +3,12 @@
 // dispnet_costvolume_encoder.py:7-50, dispnet_decoder.py:36-138) as ONE implicit-GEMM kernel family on fp16 MFMA with
 // split fp32 operands: fp32-grade results at several times the fp32 matrix rate, no layout transposes, no im2col, no `cat`.
 //
-// Arithmetic (the 2-D form of conv3d_split.hip): every fp32 activation a and weight w becomes two fp16 terms,
-//     a 2^-e = a_hi + a_lo,  a_hi = fp16(a 2^-e),  a_lo = fp16(a 2^-e - a_hi)            (same for w with 2^-k_c per cout)
-// and a w is evaluated as a_hi w_hi + a_hi w_lo + a_lo w_hi on v_mfma_f32_16x16x32_f16 with ONE fp32 accumulator (the lo terms
-// are not rescaled here: with the block scaling below they stay in fp16's range, denormals included).  e puts max |x| of the
-// whole input tensor into [2^14, 2^15), k_c puts max |w_c| into [2^10, 2^11); the epilogue multiplies by 2^(e + k_c).  A value v
-// is represented to |error| <= max(2^-22 |v|, 2^-39 max|x|).  max |x| comes from the producer's epilogue (every kernel here can
-// leave max |y| behind: one atomicMax per workgroup) or from mvd_absmax_f32.
+// Arithmetic (the 2-D form of conv3d_split.hip): every fp32 activation a and weight w becomes two fp16 terms after an exact
+// power-of-two scaling, a 2^-e = a_hi + a_lo and w 2^-k_c = w_hi + w_lo per cout (split_operand.h, lo-term factor 1: with the
+// block scaling the lo terms stay in fp16's range as they are, denormals included), and a w is evaluated as
+// a_hi w_hi + a_hi w_lo + a_lo w_hi on v_mfma_f32_16x16x32_f16 with ONE fp32 accumulator; the epilogue multiplies by
+// 2^(e + k_c).  A value v is represented to |error| <= max(2^-22 |v|, 2^-39 max|x|).  max |x| comes from the producer's
+// epilogue (every kernel here can leave max |y| behind: one atomicMax per workgroup) or from mvd_absmax_f32.
 //
 // Data layout: activations NHWC fp32 with a free pixel stride (so that a layer can read or write a channel slice of a wider
 // buffer: the decoder's concat inputs are never copied together), channel count a multiple of 8 (pad channels hold zeros and
@@ -29,6 +28,7 @@
 #include "split_operand.h"
 #include <algorithm>
 #include <stdlib.h>
+#include <string>
 
 // knock-out builds for tools/ko_conv2d.sh (timing only, WRONG results): 1 stage only a workgroup's first chunk, 2 no MFMAs,
 // 4 weights loaded once, 8 activation fragments read once per step, 16 no stores
@@ -109,29 +109,22 @@ struct C2Params {
     float slope;
 };
 
-// per output channel 2^k_c, k_c = exponent(max |w_c|) - 10 (0 for an all-zero channel); Conv2d (Cout, Cin, KH, KW) or
-// ConvTranspose2d (Cin, Cout, KH, KW) layout
-__global__ void c2_wscale_kernel(const float* __restrict__ w, float* __restrict__ eun, int Cin, int Cout, int taps, int transposed, int cpad) {
-    __shared__ float red[256];
-    const int c = blockIdx.x;
-    float m = 0.f;
-    if (c < Cout)
-        for (int e = threadIdx.x; e < Cin * taps; e += 256) {
-            const int ci = e / taps, t = e % taps;
-            const float v = fabsf(transposed ? w[((size_t)ci * Cout + c) * taps + t] : w[((size_t)c * Cin + ci) * taps + t]);
-            m = (v <= 3.4e38f && v > m) ? v : m;
-        }
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && c < cpad) {
-        const int ex = (int)((__float_as_uint(red[0]) >> 23) & 0xffu) - 127;
-        const int k = red[0] > 0.f ? max(-100, min(100, ex - 10)) : 0;
-        eun[c] = ldexpf(1.0f, k);
-    }
+// element e of a packed buffer [...][cout tile nt][chunk][step][term hi, lo][lane 64][8 halves]: lane l holds GEMM row 16 nt + l % 16
+// and unit 4 step + l / 16 of the chunk, unit u = (tap u / U8, 8-channel group u % U8), halves j = the group's channels
+struct C2FragIdx {
+    int j, term, row, g, step, chunk;  // row = l % 16, g = l / 16
+    long long rest;                    // what is left of e above the chunk: nt, and the class above it where there is one
+};
+__device__ __forceinline__ C2FragIdx c2_frag_decode(long long e, int steps, int nchunks) {
+    C2FragIdx f;
+    const int lane = (int)((e >> 3) & 63);
+    f.j = (int)(e & 7); f.term = (int)((e >> 9) & 1);
+    long long r = e >> 10;
+    f.step = (int)(r % steps); r /= steps;
+    f.chunk = (int)(r % nchunks);
+    f.rest = r / nchunks;
+    f.row = lane & 15; f.g = lane >> 4;
+    return f;
 }
 
 // -> [class][cout tile (16)][chunk][step][term hi, lo][lane 64][8 halves]; lane l: cout 16 nt + l % 16, unit 4 step + l / 16,
@@ -142,17 +135,14 @@ __global__ void c2_pack_kernel(const float* __restrict__ w, const float* __restr
                                int KH, int KW, int U8, int nchunks, int ntiles, int steps, int transposed, long long total) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= total) return;
-    const int j = (int)(e & 7), lane = (int)((e >> 3) & 63), term = (int)((e >> 9) & 1);
-    long long r = e >> 10;
-    const int step = (int)(r % steps); r /= steps;
-    const int chunk = (int)(r % nchunks); r /= nchunks;
-    const int nt = (int)(r % ntiles);
-    const int cls = (int)(r / ntiles);
-    const int cout = nt * 16 + (lane & 15), unit = 4 * step + (lane >> 4);
-    int tap = unit / U8, cin = chunk * 8 * U8 + 8 * (unit % U8) + j;
+    const C2FragIdx f = c2_frag_decode(e, steps, nchunks);
+    const int j = f.j, term = f.term, unit = 4 * f.step + f.g;
+    const int nt = (int)(f.rest % ntiles), cls = (int)(f.rest / ntiles);
+    const int cout = nt * 16 + f.row;
+    int tap = unit / U8, cin = f.chunk * 8 * U8 + 8 * (unit % U8) + j;
     if (transposed == 2) {  // image layer: step = kernel row, lane group = the tap pair kx = 2g, 2g + 1, 4 halves per pixel
-        const int kx = 2 * (lane >> 4) + j / 4;
-        tap = kx < KW ? step * KW + kx : KH * KW;
+        const int kx = 2 * f.g + j / 4;
+        tap = kx < KW ? f.step * KW + kx : KH * KW;
         cin = j % 4;
     }
     float v = 0.f;
@@ -166,8 +156,9 @@ __global__ void c2_pack_kernel(const float* __restrict__ w, const float* __restr
         }
         v = v / eun[cout];
     }
-    const _Float16 hi = (_Float16)v;
-    packed[e] = term == 0 ? hi : (_Float16)(v - (float)hi);
+    _Float16 hi, lo;
+    split_weight(v, 1.0f, hi, lo);
+    packed[e] = term == 0 ? hi : lo;
 }
 
 // epilogue of 4 consecutive output channels cb .. cb + 3 of output pixel (oy, ox) of image bi (main kernel and split-K reduce)
@@ -308,8 +299,7 @@ __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
     const int oy0 = tl.oy0, ox0 = tl.ox0, iy0 = tl.iy0, ix0 = tl.ix0;
 
     float xsc, xsc_inv;
-    c2_xscale(p.xamax, xsc, xsc_inv);
-    auto split2 = [xsc](float a0, float a1, unsigned& hi, unsigned& lo) { c2_split2(xsc, a0, a1, hi, lo); };
+    split_xscale(p.xamax, xsc, xsc_inv);
 
     // staging items of this thread: global offset (floats, without the chunk's channel offset; -1 = outside the image) and LDS byte
     long long goff[G::NIT];
@@ -384,15 +374,15 @@ __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
             for (int k = 0; k < G::NIT; ++k) {
                 if (loff[k] < 0) continue;
                 unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-                split2(v0[k][0], v0[k][1], h0, l0);
-                split2(v0[k][2], v0[k][3], h1, l1);
+                split2(xsc, v0[k][0], v0[k][1], h0, l0);
+                split2(xsc, v0[k][2], v0[k][3], h1, l1);
                 if constexpr (NCHW3) {
                     *reinterpret_cast<unsigned long long*>(patch + loff[k]) = (unsigned long long)h0 | ((unsigned long long)h1 << 32);
                     *reinterpret_cast<unsigned long long*>(patch + loff[k] + PLANE) = (unsigned long long)l0 | ((unsigned long long)l1 << 32);
                     continue;
                 }
-                split2(v1[k][0], v1[k][1], h2, l2);
-                split2(v1[k][2], v1[k][3], h3, l3);
+                split2(xsc, v1[k][0], v1[k][1], h2, l2);
+                split2(xsc, v1[k][2], v1[k][3], h3, l3);
                 *reinterpret_cast<c2u4*>(patch + loff[k]) = c2u4{h0, h1, h2, h3};
                 *reinterpret_cast<c2u4*>(patch + loff[k] + PLANE) = c2u4{l0, l1, l2, l3};
             }
@@ -485,7 +475,7 @@ __global__ void __launch_bounds__(256, WAVES) conv2d_split_persist_kernel(C2Para
     if (t >= p.tiles) return;
 
     float xsc, xsc_inv;
-    c2_xscale(p.xamax, xsc, xsc_inv);
+    split_xscale(p.xamax, xsc, xsc_inv);
     int loff[G::NIT];
 #pragma unroll
     for (int k = 0; k < G::NIT; ++k) {
@@ -563,10 +553,10 @@ __global__ void __launch_bounds__(256, WAVES) conv2d_split_persist_kernel(C2Para
                 if (loff[k] < 0) continue;
                 if (goff[k] < 0 || !zlive) v0[k] = v1[k] = c2f4{0, 0, 0, 0};
                 unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-                c2_split2(xsc, v0[k][0], v0[k][1], h0, l0);
-                c2_split2(xsc, v0[k][2], v0[k][3], h1, l1);
-                c2_split2(xsc, v1[k][0], v1[k][1], h2, l2);
-                c2_split2(xsc, v1[k][2], v1[k][3], h3, l3);
+                split2(xsc, v0[k][0], v0[k][1], h0, l0);
+                split2(xsc, v0[k][2], v0[k][3], h1, l1);
+                split2(xsc, v1[k][0], v1[k][1], h2, l2);
+                split2(xsc, v1[k][2], v1[k][3], h3, l3);
                 *reinterpret_cast<c2u4*>(patch + loff[k]) = c2u4{h0, h1, h2, h3};
                 *reinterpret_cast<c2u4*>(patch + loff[k] + PLANE) = c2u4{l0, l1, l2, l3};
             }
@@ -615,13 +605,8 @@ __global__ void __launch_bounds__(256) c2_reduce_kernel(C2Params p) {
     const int npix = p.B * p.Ho * p.Wo;
     const int c4n = (p.Cout + 3) / 4;
     const int cls = blockIdx.y;
-    float xsc_inv;
-    {
-        const unsigned mb = __float_as_uint(*p.xamax);
-        const int ex = (int)((mb >> 23) & 0xffu) - 127;
-        const int e = max(-125, min(125, ex - 14));
-        xsc_inv = __uint_as_float((unsigned)(127 + e) << 23);
-    }
+    float xsc, xsc_inv;
+    split_xscale_of(__float_as_uint(*p.xamax), xsc, xsc_inv);
     float amax = 0.f;
     // grid-stride: a workgroup ends with at most one atomic
     for (int i = blockIdx.x * 256 + threadIdx.x; i < npix * c4n; i += gridDim.x * 256) {
@@ -649,13 +634,8 @@ __global__ void __launch_bounds__(256) c2_reduce_kernel(C2Params p) {
         c2_finish(p, c2_out_offset(p, bb, od, oy, ox, cls, cb), cb, s, c2_chan(p, cb, xsc_inv), amax);
     }
     if (p.yamax) {
-        for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-        if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = amax;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            amax = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-            raise_absmax(p.yamax, amax);
-        }
+        amax = workgroup_max(amax, wmax, threadIdx.x);
+        if (threadIdx.x == 0) raise_absmax(p.yamax, amax);
     }
 }
 
@@ -682,13 +662,8 @@ __global__ void __launch_bounds__(256) upsample2x_nhwc_kernel(const float* __res
         }
     }
     if (yamax) {
-        for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-        if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = amax;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            amax = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-            raise_absmax(yamax, amax);
-        }
+        amax = workgroup_max(amax, wmax, threadIdx.x);
+        if (threadIdx.x == 0) raise_absmax(yamax, amax);
     }
 }
 
@@ -705,13 +680,10 @@ __global__ void c3_pack_kernel(const float* __restrict__ w, const float* __restr
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= total) return;
     const int KD = transposed ? 2 : 3, KP = transposed ? 2 : 3;  // depth taps, in-plane taps per dimension
-    const int j = (int)(e & 7), lane = (int)((e >> 3) & 63), term = (int)((e >> 9) & 1);
-    long long r = e >> 10;
-    const int step = (int)(r % steps); r /= steps;
-    const int chunk = (int)(r % (KD * nchunks_c)); r /= KD * nchunks_c;
-    const int nt = (int)r;
-    const int kd = chunk / nchunks_c, cc = chunk % nchunks_c;
-    const int ce = nt * 16 + (lane & 15), unit = 4 * step + (lane >> 4);
+    const C2FragIdx f = c2_frag_decode(e, steps, KD * nchunks_c);
+    const int j = f.j, term = f.term, unit = 4 * f.step + f.g;
+    const int kd = f.chunk / nchunks_c, cc = f.chunk % nchunks_c;
+    const int ce = (int)f.rest * 16 + f.row;
     const int tap = unit / U8, cin = cc * 8 * U8 + 8 * (unit % U8) + j;
     const int ncout = transposed ? 8 * Cout : Cout;
     float v = 0.f;
@@ -726,32 +698,9 @@ __global__ void c3_pack_kernel(const float* __restrict__ w, const float* __restr
         }
         v = v / eun[ce];
     }
-    const _Float16 hi = (_Float16)v;
-    packed[e] = term == 0 ? hi : (_Float16)(v - (float)hi);
-}
-
-// 2^k_c per (class,) channel: max |w| over all of the channel's weights (for the transposed form shared by its 8 classes)
-__global__ void c3_wscale_kernel(const float* __restrict__ w, float* __restrict__ eun, int Cin, int Cout, int transposed, int ncout, int cpad) {
-    __shared__ float red[256];
-    const int ce = blockIdx.x, c = ce % Cout;
-    float m = 0.f;
-    if (ce < ncout)
-        for (int e = threadIdx.x; e < Cin * 27; e += 256) {
-            const int ci = e / 27, t = e % 27;
-            const float v = fabsf(transposed ? w[((size_t)ci * Cout + c) * 27 + t] : w[((size_t)c * Cin + ci) * 27 + t]);
-            m = (v <= 3.4e38f && v > m) ? v : m;
-        }
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && ce < cpad) {
-        const int ex = (int)((__float_as_uint(red[0]) >> 23) & 0xffu) - 127;
-        const int k = red[0] > 0.f ? max(-100, min(100, ex - 10)) : 0;
-        eun[ce] = ldexpf(1.0f, k);
-    }
+    _Float16 hi, lo;
+    split_weight(v, 1.0f, hi, lo);
+    packed[e] = term == 0 ? hi : lo;
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
@@ -847,6 +796,23 @@ static long long c2_persist_grid(const C2Shape& s, const C2Plan& q, int Hi, int 
     if (wgs == 0) return 0;
     return std::min(q.tiles, (256LL * wgs + q.nblocks - 1) / q.nblocks * q.nblocks);
 }
+// over how many workgroups the reduction of a grid of `tiles` workgroups with `nchunks` chunks each is split
+static int c2_ksplit(long long tiles, int nchunks) {
+    int ksplit = 1;  // a grid of 128+ workgroups runs as it is: the second pass would cost more than the idle CUs
+    if (tiles < 128)
+        while (tiles * ksplit < 320 && ksplit < 32 && nchunks / (ksplit * 2) >= 2) ksplit *= 2;
+    if (const char* e = exp_env("MVD_C2_KSPLIT")) {  // experiments library: forced split of the reduction
+        const int v = atoi(e);
+        if (v >= 1 && v <= 32 && (v & (v - 1)) == 0 && v <= nchunks) ksplit = v;
+    }
+    return ksplit;
+}
+// what both plans end with: the K split, its workspace (B = output images of the launch) and the persistent grid
+static void c2_plan_finish(const C2Shape& s, C2Plan& q, int B, int Hi, int Wi, int xs) {
+    q.ksplit = c2_ksplit(q.tiles, q.nchunks);
+    q.part_bytes = q.ksplit > 1 ? (size_t)q.ksplit * q.ncls * B * q.Ho * q.Wo * q.ncp * sizeof(float) : 0;
+    q.persist = c2_persist_grid(s, q, Hi, Wi, xs);
+}
 static C2Plan c2_plan(const C2Shape& s, int B, int Hi, int Wi, int cin_pad, int xs, int cout, int KH, int KW, int stride) {
     C2Plan q{};
     if (s.transposed) { q.Ho = Hi; q.Wo = Wi; q.ncls = 4; }
@@ -858,15 +824,7 @@ static C2Plan c2_plan(const C2Shape& s, int B, int Hi, int Wi, int cin_pad, int 
     q.ncp = q.nblocks * q.bn;
     q.nchunks = cin_pad / (8 * s.U8);
     q.tiles = (long long)q.tiles_x * q.tiles_y * B * q.nblocks * q.ncls;
-    q.ksplit = 1;  // a grid of 128+ workgroups runs as it is: the second pass would cost more than the idle CUs
-    if (q.tiles < 128)
-        while (q.tiles * q.ksplit < 320 && q.ksplit < 32 && q.nchunks / (q.ksplit * 2) >= 2) q.ksplit *= 2;
-    if (const char* e = exp_env("MVD_C2_KSPLIT")) {  // experiments library: forced split of the reduction
-        const int v = atoi(e);
-        if (v >= 1 && v <= 32 && (v & (v - 1)) == 0 && v <= q.nchunks) q.ksplit = v;
-    }
-    q.part_bytes = q.ksplit > 1 ? (size_t)q.ksplit * q.ncls * B * q.Ho * q.Wo * q.ncp * sizeof(float) : 0;
-    q.persist = c2_persist_grid(s, q, Hi, Wi, xs);
+    c2_plan_finish(s, q, B, Hi, Wi, xs);
     return q;
 }
 
@@ -942,6 +900,24 @@ static int c2_dispatch(const C2Shape& s, C2Params& p, int bn, long long nblk, lo
     return c2_launch_bn<3, 3, 1, 1, false>(p, bn, nblk, st);
 }
 
+// the tail of both entry points (`what`: the entry's name in messages; p.B, p.Ho, p.Wo, p.Cout, p.ncls, p.nchunks set): K split
+// only with a workspace for it, the grid limit, the main kernel, and the reduce kernel behind a split
+static int c2_run(const char* what, const C2Shape& s, C2Params& p, const C2Plan& q, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    int ksplit = q.ksplit;
+    if (ksplit > 1 && (!workspace || workspace_bytes < q.part_bytes)) ksplit = 1;  // no workspace: the plain grid
+    p.ksplit = ksplit;
+    p.chunks_per_split = (p.nchunks + ksplit - 1) / ksplit;
+    p.part = ksplit > 1 ? static_cast<float*>(workspace) : nullptr;
+    const long long nblk = q.tiles * ksplit;
+    MVD_REQUIRE(nblk <= 0x7fffffffLL, "%s: %lld workgroups exceed the grid limit", what, nblk);
+    int rc = c2_dispatch(s, p, q.bn, nblk, q.persist, st);
+    if (rc != MVD_OK || ksplit == 1) return rc;
+    const long long n = (long long)p.B * p.Ho * p.Wo * ((p.Cout + 3) / 4);
+    MVD_REQUIRE(n < 0x7fffffffLL, "%s: split reduction over %lld outputs", what, n);
+    hipLaunchKernelGGL(c2_reduce_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 1024), (unsigned)p.ncls), dim3(256), 0, st, p);
+    return launch_status((std::string(what) + ": reduce").c_str());
+}
+
 }  // namespace mvd
 
 extern "C" {
@@ -962,8 +938,7 @@ int mvd_pack_conv2d_weights_split(const float* w, int Cin, int Cin_pad, int Cout
     hipStream_t st = (hipStream_t)stream;
     const size_t fb = mvd::c2_frag_bytes(s, Cin_pad, Cout);
     float* eun = reinterpret_cast<float*>(static_cast<char*>(packed) + fb);
-    const int cpad = mvd::c2_cpad(Cout);
-    hipLaunchKernelGGL(mvd::c2_wscale_kernel, dim3(cpad), dim3(256), 0, st, w, eun, Cin, Cout, KH * KW, s.transposed ? 1 : 0, cpad);
+    mvd::split_wscale_launch(w, eun, Cin, Cout, KH * KW, s.transposed, Cout, mvd::c2_cpad(Cout), st);
     const long long total = (long long)(fb / 2);
     hipLaunchKernelGGL(mvd::c2_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, eun, (_Float16*)packed, Cin, Cout, s.KH,
                        s.KW, s.U8, Cin_pad / (8 * s.U8), mvd::c2_ntiles(Cout), s.steps, s.transposed ? 1 : s.nchw3 ? 2 : 0, total);
@@ -1015,23 +990,9 @@ int mvd_conv2d_split_f32(const float* x, const float* x_absmax, const void* pack
     p.wpk = static_cast<const char*>(packed_w);
     p.cls_bytes = (long long)(fb / p.ncls);
     p.tiles_y = q.tiles_y; p.tiles_x = q.tiles_x;
-    const int bn = q.bn;
     p.nblocks = q.nblocks;
     p.ncp = q.ncp;
-    const long long tiles = q.tiles;
-    int ksplit = q.ksplit;
-    if (ksplit > 1 && (!workspace || workspace_bytes < q.part_bytes)) ksplit = 1;  // no workspace: the plain grid
-    p.ksplit = ksplit;
-    p.chunks_per_split = (p.nchunks + ksplit - 1) / ksplit;
-    p.part = ksplit > 1 ? static_cast<float*>(workspace) : nullptr;
-    const long long nblk = tiles * ksplit;
-    MVD_REQUIRE(nblk <= 0x7fffffffLL, "conv2d_split: %lld workgroups exceed the grid limit", nblk);
-    int rc = mvd::c2_dispatch(s, p, bn, nblk, q.persist, st);
-    if (rc != MVD_OK || ksplit == 1) return rc;
-    const long long n = (long long)B * p.Ho * p.Wo * ((Cout + 3) / 4);
-    MVD_REQUIRE(n < 0x7fffffffLL, "conv2d_split: split reduction over %lld outputs", n);
-    hipLaunchKernelGGL(mvd::c2_reduce_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 1024), (unsigned)p.ncls), dim3(256), 0, st, p);
-    return mvd::launch_status("conv2d_split: reduce");
+    return mvd::c2_run("conv2d_split", s, p, q, workspace, workspace_bytes, st);
 }
 
 int mvd_upsample2x_nhwc_f32(const float* x, float* y, float* y_absmax, int B, int C, int h, int w, int y_pixel_stride, mvd_stream_t stream) {
@@ -1086,8 +1047,9 @@ int mvd_pack_conv3d_weights_igemm(const float* w, int Cin, int Cout, int mode, v
     hipStream_t st = (hipStream_t)stream;
     const size_t fb = mvd::c3_frag_bytes(s, Cin, ncout, mode);
     float* eun = reinterpret_cast<float*>(static_cast<char*>(packed) + fb);
-    const int cpad = mvd::c2_cpad(ncout), tr = mode == MVD_DECONV3D_STRIDE2 ? 1 : 0;
-    hipLaunchKernelGGL(mvd::c3_wscale_kernel, dim3(cpad), dim3(256), 0, st, w, eun, Cin, Cout, tr, ncout, cpad);
+    const int tr = mode == MVD_DECONV3D_STRIDE2 ? 1 : 0;
+    // 2^k_c per (class, channel) row: max |w| over all of the channel's weights, shared by the 8 classes of the transposed form
+    mvd::split_wscale_launch(w, eun, Cin, Cout, 27, tr != 0, ncout, mvd::c2_cpad(ncout), st);
     const long long total = (long long)(fb / 2);
     hipLaunchKernelGGL(mvd::c3_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, eun, (_Float16*)packed, Cin, Cout, s.U8,
                        Cin / (8 * s.U8), mvd::c2_ntiles(ncout), s.steps, tr, total);
@@ -1111,15 +1073,7 @@ static mvd::C2Plan c3_plan(const mvd::C2Shape& s, int B, int Di, int Hi, int Wi,
     q.ncp = q.nblocks * q.bn;
     q.nchunks = (mode == MVD_DECONV3D_STRIDE2 ? 2 : 3) * (Cin / (8 * s.U8));
     q.tiles = planes * q.nblocks;
-    q.ksplit = 1;
-    if (q.tiles < 128)
-        while (q.tiles * q.ksplit < 320 && q.ksplit < 32 && q.nchunks / (q.ksplit * 2) >= 2) q.ksplit *= 2;
-    if (const char* e = mvd::exp_env("MVD_C2_KSPLIT")) {  // experiments library: forced split of the reduction
-        const int v = atoi(e);
-        if (v >= 1 && v <= 32 && (v & (v - 1)) == 0 && v <= q.nchunks) q.ksplit = v;
-    }
-    q.part_bytes = q.ksplit > 1 ? (size_t)q.ksplit * B * *Do * q.Ho * q.Wo * q.ncp * sizeof(float) : 0;
-    q.persist = mvd::c2_persist_grid(s, q, Hi, Wi, Cin);
+    mvd::c2_plan_finish(s, q, B * *Do, Hi, Wi, Cin);
     return q;
 }
 
@@ -1157,20 +1111,8 @@ int mvd_conv3d_bn_relu_igemm_f32(const float* x, const float* x_absmax, const vo
     p.ys_row = (long long)p.Wy * Cout; p.ys_img = (long long)p.Hy * p.ys_row;
     p.tiles_x = q.tiles_x; p.tiles_y = q.tiles_y; p.nblocks = q.nblocks; p.ncls = 1; p.cls_bytes = 0;
     p.act = relu ? 2 : 0; p.slope = 0.f;
-    int ksplit = q.ksplit;
-    if (ksplit > 1 && (!workspace || workspace_bytes < q.part_bytes)) ksplit = 1;
-    p.ksplit = ksplit;
-    p.chunks_per_split = (p.nchunks + ksplit - 1) / ksplit;
-    p.part = ksplit > 1 ? static_cast<float*>(workspace) : nullptr;
-    const long long nblk = q.tiles * ksplit;
-    MVD_REQUIRE(nblk <= 0x7fffffffLL, "conv3d_igemm: %lld workgroups exceed the grid limit", nblk);
     MVD_REQUIRE(q.nblocks * (q.bn / 16) <= mvd::c2_ntiles(ncout), "conv3d_igemm: channel tile %d reads past the %d packed fragments", q.bn,
                 mvd::c2_ntiles(ncout));
-    int rc = mvd::c2_dispatch(s, p, q.bn, nblk, q.persist, st);
-    if (rc != MVD_OK || ksplit == 1) return rc;
-    const long long n = (long long)p.B * p.Ho * p.Wo * ((p.Cout + 3) / 4);
-    MVD_REQUIRE(n < 0x7fffffffLL, "conv3d_igemm: split reduction over %lld outputs", n);
-    hipLaunchKernelGGL(mvd::c2_reduce_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 1024)), dim3(256), 0, st, p);
-    return mvd::launch_status("conv3d_igemm: reduce");
+    return mvd::c2_run("conv3d_igemm", s, p, q, workspace, workspace_bytes, st);
 }
 }

@@ -13,19 +13,19 @@
 // fp32 MFMAs of 32 cycles: the layer turns from matrix-bound into an LDS / memory pass.
 //
 // Range: fp16 spans 2^-24 .. 65504, fp32 operands do not.  Both operands are therefore multiplied by exact powers of two
-// before the split and the result by the inverse afterwards (block floating point, nothing is rounded by the scaling):
-//   * activations by 2^-e, e = exponent(max |x| over the whole input) - 14, so that the largest magnitude lands in
-//     [2^14, 2^15).  The caller supplies max |x| in device memory (mvd_absmax_f32, or the by-product of
-//     mvd_warp_variance_absmax_f32 which costs nothing extra); any upper bound is safe, a tight one is most precise.
-//     A value v is then represented to |error| <= max(2^-22 |v|, 2^-50 max|x|): fp32-grade for everything within 2^-26 of the
-//     largest magnitude, and an ABSOLUTE error below fp32's own rounding of the larger terms for what lies underneath.
-//   * each output channel's weights by 2^-k_c, k_c = exponent(max |w_c|) - 10 (computed when the weights are packed).
+// before the split and the result by the inverse afterwards (block floating point, nothing is rounded by the scaling): the
+// activations by 2^-e from max |x|, each output channel's weights by 2^-k_c, both as split_operand.h defines them, with the
+// lo-term factor 2^11.  The caller supplies max |x| in device memory (mvd_absmax_f32, or the by-product of
+// mvd_warp_variance_absmax_f32 which costs nothing extra); any upper bound is safe, a tight one is most precise.
+// A value v is then represented to |error| <= max(2^-22 |v|, 2^-50 max|x|): fp32-grade for everything within 2^-26 of the
+// largest magnitude, and an ABSOLUTE error below fp32's own rounding of the larger terms for what lies underneath.
 // The epilogue multiplies by 2^(e + k_c) before the batch-norm affine.  Inputs of any uniform magnitude (1e-30 .. 1e30,
 // denormals included) give the same relative accuracy; inf / NaN inputs give inf / NaN outputs where they reach, as on fp32.
 //
 // Workgroup (4 waves) = 4 x 32 tile marching through TD + 2 input planes (see the kernel); the fp32 volume is converted to
 // the two fp16 terms while it is staged (global -> registers -> LDS), all 27 weight fragments stay in registers.
 #include "mvd_common.h"
+#include "split_operand.h"
 
 // Knock-out / tuning macros for tools/ko_conv0_split.sh (timing only: the results of a knocked-out build are wrong).
 #ifndef SPLIT_KO
@@ -44,6 +44,7 @@ typedef unsigned int su32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int S_TH = 4, S_TW = 32, S_ROWS = S_TH + 2;
+constexpr float S_LO_FACTOR = 2048.0f;  // the lo terms of both operands are stored times 2^11 (split_operand.h)
 // geometry by input channel count.  CIN = 32: one voxel's channels are one MFMA K (64 bytes per term), three fragments per
 // (kd, kh) — one per kw.  CIN = 16: a 64-byte fragment spans TWO x-adjacent voxels, so the kw taps go in pairs (0,1), (2, zero
 // weights): two fragments per (kd, kh); the staged tile gets a 35th, always-zero column for the pad tap to read.
@@ -62,32 +63,10 @@ struct SplitGeom {
     static_assert(NF - 8 == 4 * NLOAD, "pass B interleaves 8 epilogue groups and 4 staging groups per item");
 };
 
-// per output channel: 2^k_c with k_c = exponent(max |w_c|) - 10 (0 for an all-zero channel), appended to the packed buffer
-__global__ void conv0_split_wscale_kernel(const float* __restrict__ w, float* __restrict__ wscale, int cin) {
-    __shared__ float red[256];
-    const int c = blockIdx.x;
-    float m = 0.f;
-    for (int e = threadIdx.x; e < cin * 27; e += 256) {
-        const float v = fabsf(w[(size_t)c * cin * 27 + e]);
-        m = (v <= 3.4e38f && v > m) ? v : m;  // finite values only
-    }
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const int ex = (int)((__float_as_uint(red[0]) >> 23) & 0xffu) - 127;
-        const int k = red[0] > 0.f ? max(-100, min(100, ex - 10)) : 0;
-        wscale[c] = ldexpf(1.0f, k);
-    }
-}
-
 // w (Cout, CIN, 3, 3, 3) fp32 -> [cout block Cout/8][fragment NT][lane 64][8 halves]: lane l = column l%16 (0..7: w_hi of cout
 // 8 cb + l%16, 8..15: w_lo of cout 8 cb + l%16 - 8), K values 8*(l/16) .. +7 of the fragment: CIN = 32: fragment = tap, K = cin;
 // CIN = 16: fragment = (kd, kh, kw pair g), K = 16 * (kw - 2g) + cin, kw = 3 is the zero pad.  Weights divided by the
-// channel's 2^k_c first (exact).
+// channel's 2^k_c first (exact); wscale (split_wscale_kernel's Cout floats) is appended to the packed buffer.
 template <int CIN>
 __global__ void pack_conv0_split_kernel(const float* __restrict__ w, const float* __restrict__ wscale, _Float16* __restrict__ packed, int ncb) {
     using G = SplitGeom<CIN>;
@@ -99,8 +78,8 @@ __global__ void pack_conv0_split_kernel(const float* __restrict__ w, const float
     if constexpr (CIN == 32) { tap = t; cin = k; }
     else { const int kw = 2 * (t % 2) + k / 16; tap = kw < 3 ? (t / 2) * 3 + kw : -1; cin = k % 16; }
     const float v = tap >= 0 ? w[((size_t)cout * CIN + cin) * 27 + tap] / wscale[cout] : 0.0f;
-    const _Float16 hi = (_Float16)v;
-    const _Float16 lo = (_Float16)((v - (float)hi) * 2048.0f);
+    _Float16 hi, lo;
+    split_weight(v, S_LO_FACTOR, hi, lo);
     packed[e] = col < 8 ? hi : lo;
 }
 
@@ -188,31 +167,10 @@ __global__ void __launch_bounds__(256, 2) conv0_split_kernel(SplitParams p) {
         }
     };
     char* const dump = ring + 2 * S_PLANE_BYTES + tid * 16;
-    // split two fp32 values into the packed fp16 pairs (hi, lo * 2^11): hi = fp16(a), t = a - hi (exact, mixed-precision fma
-    // straight from the packed half), lo = fp16(t * 2^11) written into its half.  5 instructions per pair; the compiler's own
-    // sequence for the same arithmetic is 10 (it converts every hi twice and back).
-    // activation scale 2^-e, e = exponent(max |x|) - 14 clamped to what a normal fp32 power of two can express
-    float k2048 = 2048.0f, xs, xs_inv;
-    {
-        const unsigned mb = __builtin_amdgcn_readfirstlane((int)__float_as_uint(*p.absmax));
-        const int ex = (int)((mb >> 23) & 0xffu) - 127;
-        const int e = max(-125, min(125, ex - 14));
-        xs = __uint_as_float((unsigned)(127 - e) << 23);
-        xs_inv = __uint_as_float((unsigned)(127 + e) << 23);
-    }
-    auto split2 = [k2048, xs](float a0, float a1, unsigned& hi, unsigned& lo) {
-        unsigned hp, lp;
-        float t0, t1;
-        // hi = fp16(a * 2^-e) (one rounding: the scaling is exact), t = a * 2^-e - hi (exact), lo = fp16(t * 2^11)
-        asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "=v"(hp) : "v"(a0), "s"(xs));
-        asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "+v"(hp) : "v"(a1), "s"(xs));
-        asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(t0) : "v"(a0), "s"(xs), "v"(hp));
-        asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(t1) : "v"(a1), "s"(xs), "v"(hp));
-        asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "=v"(lp) : "v"(t0), "s"(k2048));
-        asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "+v"(lp) : "v"(t1), "s"(k2048));
-        hi = hp;
-        lo = lp;
-    };
+    // two fp32 values -> the packed fp16 pairs (hi, lo * 2^11)
+    float xs, xs_inv;
+    split_xscale(p.absmax, xs, xs_inv);
+    auto split2 = [xs](float a0, float a1, unsigned& hi, unsigned& lo) { mvd::split2(xs, a0, a1, hi, lo, S_LO_FACTOR); };
     auto stash = [&](int d) {  // prologue only: the loop below stages inside the MFMA stream
         char* slot = ring + (d & 1) * S_PLANE_BYTES;
 #pragma unroll
@@ -423,7 +381,7 @@ int mvd_pack_conv3d_weights_split(const float* w, int Cin, int Cout, void* packe
     MVD_REQUIRE(split_shape_ok(Cin, Cout), "pack_conv3d_weights_split: 16 or 32 input channels and 8, 16, ... 64 output channels are built (got %d -> %d)", Cin, Cout);
     const int ncb = Cout / 8;
     float* wscale = reinterpret_cast<float*>(static_cast<char*>(packed) + split_frag_bytes(Cin, Cout));
-    hipLaunchKernelGGL(mvd::conv0_split_wscale_kernel, dim3(Cout), dim3(256), 0, (hipStream_t)stream, w, wscale, Cin);
+    mvd::split_wscale_launch(w, wscale, Cin, Cout, 27, false, Cout, Cout, (hipStream_t)stream);
     const unsigned nb = (unsigned)((split_frag_bytes(Cin, Cout) / 2 + 255) / 256);
     if (Cin == 32) hipLaunchKernelGGL(mvd::pack_conv0_split_kernel<32>, dim3(nb), dim3(256), 0, (hipStream_t)stream, w, wscale, (_Float16*)packed, ncb);
     else hipLaunchKernelGGL(mvd::pack_conv0_split_kernel<16>, dim3(nb), dim3(256), 0, (hipStream_t)stream, w, wscale, (_Float16*)packed, ncb);

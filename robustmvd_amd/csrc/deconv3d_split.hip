@@ -8,13 +8,12 @@
 // (TW + 1) columns ONCE and produces the 2 x 8 x 2 TW output block of all eight classes: no structural zeros among the products,
 // and the two w-parities of an output row are stored back to back.
 //
-// Arithmetic: every activation a and weight w becomes two fp16 terms after an exact power-of-two scaling,
-//     a 2^-e = a_hi + a_lo   (e puts max |x| of the whole input into [2^14, 2^15): c2_xscale / c2_split2 of split_operand.h),
-//     w 2^-k_c = w_hi + w_lo (k_c puts max |w_c| of output channel c into [2^10, 2^11)),
-// and a w is evaluated as w_hi a_hi + w_lo a_hi + w_hi a_lo on v_mfma_f32_16x16x32_f16 into ONE fp32 accumulator: 3 MFMAs per
-// (tap, 32 input channels, 16 voxels x 16 output channels) against 8 fp32 MFMAs of twice the length.  The epilogue multiplies
-// by 2^(e + k_c), applies the folded batch-norm affine, the ReLU and the skip addition.  A value v is represented to
-// |error| <= max(2^-22 |v|, 2^-39 max|x|).  inf / NaN inputs give inf / NaN outputs where they reach.
+// Arithmetic: every activation a and weight w becomes two fp16 terms after an exact power-of-two scaling, a 2^-e = a_hi + a_lo and
+// w 2^-k_c = w_hi + w_lo (split_operand.h, lo-term factor 1), and a w is evaluated as w_hi a_hi + w_lo a_hi + w_hi a_lo on
+// v_mfma_f32_16x16x32_f16 into ONE fp32 accumulator: 3 MFMAs per (tap, 32 input channels, 16 voxels x 16 output channels) against 8
+// fp32 MFMAs of twice the length.  The epilogue multiplies by 2^(e + k_c), applies the folded batch-norm affine, the ReLU and the
+// skip addition.  A value v is represented to |error| <= max(2^-22 |v|, 2^-39 max|x|).  inf / NaN inputs give inf / NaN outputs where
+// they reach.
 //
 // GEMM view: A = weights (16 output channels x K 32), B = activations (K 32 x 16 voxels of one input row), so a lane ends up with
 // 4 consecutive output channels of one voxel (float4 stores that tile the channel-last output).  K = 32 input channels (CIN = 64:
@@ -59,33 +58,11 @@ struct DSGeom {
 static constexpr int ds_nfrag(int cin) { return cin == 16 ? 9 : 27 * (cin / 32); }
 static constexpr size_t DS_FRAG_BYTES = 2 * 64 * 16;
 
-// per output channel 2^k_c, k_c = exponent(max |w_c|) - 10 (0 for an all-zero channel), as conv0_split_wscale_kernel; ConvTranspose3d
-// layout (Cin, Cout, 3, 3, 3).  Entry r of the CIN = 16 form is GEMM row r = (w-parity, channel r & 7).
-__global__ void deconv_split_wscale_kernel(const float* __restrict__ w, float* __restrict__ eun, int Cin, int Cout) {
-    __shared__ float red[256];
-    const int c = blockIdx.x % Cout;
-    float m = 0.f;
-    for (int e = threadIdx.x; e < Cin * 27; e += 256) {
-        const float v = fabsf(w[((size_t)(e / 27) * Cout + c) * 27 + e % 27]);
-        m = (v <= 3.4e38f && v > m) ? v : m;  // finite values only
-    }
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const int ex = (int)((__float_as_uint(red[0]) >> 23) & 0xffu) - 127;
-        const int k = red[0] > 0.f ? max(-100, min(100, ex - 10)) : 0;
-        eun[blockIdx.x] = ldexpf(1.0f, k);
-    }
-}
-
 // w (Cin, Cout, 3, 3, 3) -> [row tile][fragment][term hi, lo][lane 64][8 halves]; lane l = GEMM row l % 16, K values 8 (l / 16) .. + 7.
 // CIN = 32 / 64: row = output channel 16 nt + l % 16, fragment = (tap, K step ks), K = input channel - 32 ks.
 // CIN = 16: row = (w-parity pw, channel), fragment = (kd, kh), K = 16 s + input channel, s = 0: input column c (kw = 1 for pw = 0,
-// kw = 2 for pw = 1), s = 1: column c + 1 (kw = 0 for pw = 1, nothing for pw = 0).
+// kw = 2 for pw = 1), s = 1: column c + 1 (kw = 0 for pw = 1, nothing for pw = 0).  eun: split_wscale_kernel's 2^k_c per GEMM row
+// (entry r of the CIN = 16 form is row r = (w-parity, channel r & 7)), appended to the packed buffer.
 __global__ void deconv_split_pack_kernel(const float* __restrict__ w, const float* __restrict__ eun, _Float16* __restrict__ packed, int Cin,
                                          int Cout, int nfrag, long long total) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -105,8 +82,9 @@ __global__ void deconv_split_pack_kernel(const float* __restrict__ w, const floa
         tap = f / (Cin / 32);
     }
     const float v = tap >= 0 ? w[((size_t)cin * Cout + cout) * 27 + tap] / eun[nt * 16 + row] : 0.f;
-    const _Float16 hi = (_Float16)v;
-    packed[e] = term == 0 ? hi : (_Float16)(v - (float)hi);
+    _Float16 hi, lo;
+    split_weight(v, 1.0f, hi, lo);
+    packed[e] = term == 0 ? hi : lo;
 }
 
 struct DSParams {
@@ -145,7 +123,7 @@ __global__ void __launch_bounds__(256) deconv3d_split_kernel(DSParams p) {
     const int r0 = th * DS_TH, c0 = tw * G::TW;
 
     float xsc, xsc_inv;
-    c2_xscale(p.xamax, xsc, xsc_inv);
+    split_xscale(p.xamax, xsc, xsc_inv);
 
     // weight fragments of one (kd, kh) step in one batch, fetched one step ahead of the MFMAs that use them where both batches
     // fit the register file (as deconv3d_all_kernel)
@@ -210,10 +188,10 @@ __global__ void __launch_bounds__(256) deconv3d_split_kernel(DSParams p) {
             const int e = tid + 256 * i;
             const int g = e % NG, pix = e / NG;
             unsigned h[4], l[4];
-            c2_split2(xsc, pf[i][0].x, pf[i][0].y, h[0], l[0]);
-            c2_split2(xsc, pf[i][0].z, pf[i][0].w, h[1], l[1]);
-            c2_split2(xsc, pf[i][1].x, pf[i][1].y, h[2], l[2]);
-            c2_split2(xsc, pf[i][1].z, pf[i][1].w, h[3], l[3]);
+            split2(xsc, pf[i][0].x, pf[i][0].y, h[0], l[0]);
+            split2(xsc, pf[i][0].z, pf[i][0].w, h[1], l[1]);
+            split2(xsc, pf[i][1].x, pf[i][1].y, h[2], l[2]);
+            split2(xsc, pf[i][1].z, pf[i][1].w, h[3], l[3]);
             dsu4 hv = {h[0], h[1], h[2], h[3]}, lv = {l[0], l[1], l[2], l[3]};
             if (!ok[i]) { hv = dsu4{0, 0, 0, 0}; lv = dsu4{0, 0, 0, 0}; }
             if (e < G::ITEMS) {
@@ -343,15 +321,12 @@ __global__ void __launch_bounds__(256) deconv3d_split_kernel(DSParams p) {
                 }
         }
         if constexpr (YAMAX) {  // what the next split-operand layer scales its activations by: ONE atomic per workgroup
-            for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-            float* wm = reinterpret_cast<float*>(dslab + G::LDS);  // 16 bytes behind the slab, which other waves may still read
-            if (lane == 0) wm[wave] = amax;
-            __syncthreads();
+            // the four floats: 16 bytes behind the slab, which other waves may still read
+            const float m = workgroup_max(amax, reinterpret_cast<float*>(dslab + G::LDS), tid);
             // Against the slot as it was when the workgroup started, and then an atomic whose result nobody waits for: a second
             // look at the slot (raise_absmax) is a dependent load at the very end of the workgroup, and while the slot is still
             // rising, in the first round of resident workgroups of every forward, all of them queue for that one address.
             if (tid == 0) {
-                const float m = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
                 if (m > amax_seen) atomicMax(reinterpret_cast<unsigned*>(p.yamax), __float_as_uint(m));
             }
         }
@@ -406,7 +381,7 @@ int mvd_pack_deconv3d_weights_split(const float* w, int Cin, int Cout, void* pac
                 Cin, Cout);
     float* eun = reinterpret_cast<float*>(static_cast<char*>(packed) + ds_frag_bytes(Cin, Cout));
     const int rows = ds_row_tiles(Cin, Cout) * 16;
-    hipLaunchKernelGGL(mvd::deconv_split_wscale_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, w, eun, Cin, Cout);
+    mvd::split_wscale_launch(w, eun, Cin, Cout, 27, true, rows, rows, (hipStream_t)stream);
     const long long total = (long long)(ds_frag_bytes(Cin, Cout) / 2);
     hipLaunchKernelGGL(mvd::deconv_split_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, eun,
                        (_Float16*)packed, Cin, Cout, mvd::ds_nfrag(Cin), total);

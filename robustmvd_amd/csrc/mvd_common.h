@@ -29,6 +29,17 @@ __device__ __forceinline__ void raise_absmax_seen(float* slot, float m, float se
 }
 __host__ __device__ inline bool finite_f32(float v) { return fabsf(v) <= 3.402823466e38f; }  // false for inf and NaN
 __device__ __forceinline__ float finite_abs_or_zero(float v) { return finite_f32(v) ? fabsf(v) : 0.f; }
+// The maximum of every lane's m over a workgroup of 256 threads (four waves): a butterfly inside the wave, one float per wave into
+// wmax (four floats of LDS that nobody else touches until the barrier inside has passed), thread 0 combines the four.  Thread 0
+// returns the workgroup's maximum, every other thread its wave's.  What happens to it (raise_absmax, raise_absmax_seen, a plain
+// store) is the caller's business: the call sites differ there on purpose.  tid is the caller's threadIdx.x.
+__device__ __forceinline__ float workgroup_max(float m, float* wmax, int tid) {
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((tid & 63) == 0) wmax[tid >> 6] = m;
+    __syncthreads();
+    if (tid == 0) m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    return m;
+}
 
 // stride-1 3x3x3 convolution with ONE input channel (conv3d_backward.hip): what mvd_conv3d_bn_relu_f32 runs for Cin == 1
 bool conv3d_c1_ok(int Cout);

@@ -362,6 +362,31 @@ def conv3d_bn_relu_f16in(x, packed, scale, shift, relu=True):
     return y
 
 
+def _split3d_inputs(x, cin, cout, out_size, scale, shift, skip, x_absmax):
+    """What the 3-D split-operand wrappers check and coerce alike: x (B,D,h,w,cin) channel-last fp32, scale and shift of cout floats,
+    skip None or shaped like the output (B, *out_size(D,h,w), cout), x_absmax one float.  -> x, scale, shift, skip, x_absmax, output shape."""
+    x = L.as_f32(x, "x")
+    if x.dim() != 5 or x.shape[-1] != cin:
+        raise ValueError(f"x must be (B,D,h,w,{cin}) channel-last, got {tuple(x.shape)}")
+    dev = x.device
+    oshape = (x.shape[0], *out_size(*x.shape[1:4]), cout)
+    scale = L.as_f32(scale, "scale", (cout,), dev)
+    shift = L.as_f32(shift, "shift", (cout,), dev)
+    if skip is not None:
+        skip = L.as_f32(skip, "skip", oshape, dev)
+    return x, scale, shift, skip, L.as_f32(x_absmax, "x_absmax", (1,), dev), oshape
+
+
+def _absmax_slot(return_absmax, out_absmax, dev):
+    """The one-float max |y| slot of a layer call that raises it by atomic maximum: None unless asked for; the caller's out_absmax
+    (zeroed by the caller), or a fresh zeroed one."""
+    if not return_absmax:
+        return None
+    if out_absmax is not None:
+        return L.as_f32(out_absmax, "out_absmax", (1,), dev)
+    return torch.zeros(1, dtype=torch.float32, device=dev)
+
+
 @inference_only
 def pack_conv3d_weights_split(weight):
     """weight: Conv3d (Cout,Cin,3,3,3) fp32, Cin 16 or 32, Cout in 8, 16, ... 64 -> per block of 8 output channels the
@@ -425,23 +450,14 @@ def conv3d_bn_relu_igemm(x, x_absmax, packed, Cin, Cout, scale, shift, mode, rel
     is added after the activation.  return_absmax: also max |y| (out_absmax: a zeroed one-element device tensor to raise instead of a
     fresh one: several layers' slots can come from one zeroed buffer)."""
     lib = L.load()
-    x = L.as_f32(x, "x")
-    if x.dim() != 5 or x.shape[-1] != Cin:
-        raise ValueError(f"x must be (B,D,h,w,{Cin}) channel-last, got {tuple(x.shape)}")
+    x, scale, shift, skip, xam, oshape = _split3d_inputs(x, Cin, Cout, lambda d, h, w: _conv3d_out_size(mode, d, h, w), scale, shift, skip,
+                                                         x_absmax)
     B, Di, hi, wi, _ = x.shape
     dev = x.device
-    oshape = (B, *_conv3d_out_size(mode, Di, hi, wi), Cout)
     if packed.numel() != lib.mvd_conv3d_igemm_packed_weight_bytes(Cin, Cout, mode):
         raise ValueError(f"packed weights of {packed.numel()} bytes do not belong to a {Cin} -> {Cout} layer of mode {mode}")
-    scale = L.as_f32(scale, "scale", (Cout,), dev)
-    shift = L.as_f32(shift, "shift", (Cout,), dev)
-    if skip is not None:
-        skip = L.as_f32(skip, "skip", oshape, dev)
-    xam = L.as_f32(x_absmax, "x_absmax", (1,), dev)
     y = torch.empty(oshape, dtype=torch.float32, device=dev)
-    yam = None
-    if return_absmax:
-        yam = torch.zeros(1, dtype=torch.float32, device=dev) if out_absmax is None else L.as_f32(out_absmax, "out_absmax", (1,), dev)
+    yam = _absmax_slot(return_absmax, out_absmax, dev)
     wsb = lib.mvd_conv3d_igemm_workspace_bytes(B, Di, hi, wi, Cin, Cout, mode)
     call("mvd_conv3d_bn_relu_igemm_f32", dev, x, xam, packed, scale, shift, skip, y, yam, B, Di, hi, wi, Cin, Cout, mode,
           int(bool(relu)), workspace(wsb, dev) if wsb else None, wsb)
@@ -468,25 +484,14 @@ def deconv3d_bn_relu_split(x, x_absmax, packed, Cin, Cout, scale, shift, relu=Tr
     fp32, x_absmax one-element device tensor with max |x| -> (B,2D,2h,2w,Cout); skip (like the output) is added after the
     activation.  return_absmax: also max |y| over the finite outputs, a by-product of the store epilogue (out_absmax: a zeroed
     one-element device tensor to raise instead of a fresh one)."""
-    lib = L.load()
-    x = L.as_f32(x, "x")
-    if x.dim() != 5 or x.shape[-1] != Cin:
-        raise ValueError(f"x must be (B,D,h,w,{Cin}) channel-last, got {tuple(x.shape)}")
+    x, scale, shift, skip, xam, oshape = _split3d_inputs(x, Cin, Cout, lambda d, h, w: (2 * d, 2 * h, 2 * w), scale, shift, skip, x_absmax)
     B, Di, hi, wi, _ = x.shape
     dev = x.device
-    oshape = (B, 2 * Di, 2 * hi, 2 * wi, Cout)
-    n = lib.mvd_deconv3d_split_packed_weight_bytes(Cin, Cout)
+    n = L.load().mvd_deconv3d_split_packed_weight_bytes(Cin, Cout)
     if n == 0 or packed.numel() != n:
         raise ValueError(f"packed weights of {packed.numel()} bytes do not belong to a transposed {Cin} -> {Cout} layer")
-    scale = L.as_f32(scale, "scale", (Cout,), dev)
-    shift = L.as_f32(shift, "shift", (Cout,), dev)
-    if skip is not None:
-        skip = L.as_f32(skip, "skip", oshape, dev)
-    xam = L.as_f32(x_absmax, "x_absmax", (1,), dev)
     y = torch.empty(oshape, dtype=torch.float32, device=dev)
-    yam = None
-    if return_absmax:
-        yam = torch.zeros(1, dtype=torch.float32, device=dev) if out_absmax is None else L.as_f32(out_absmax, "out_absmax", (1,), dev)
+    yam = _absmax_slot(return_absmax, out_absmax, dev)
     call("mvd_deconv3d_bn_relu_f32_split", dev, x, xam, packed, scale, shift, skip, y, yam, B, Di, hi, wi, Cin, Cout, int(bool(relu)))
     return (y, yam) if return_absmax else y
 
