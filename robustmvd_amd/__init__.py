@@ -21,7 +21,7 @@ from .sweep_modes import cvp_proj_cost, vis_cost_volumes, sweep_reduce  # noqa: 
 from . import eval  # noqa: F401,E402
 from .eval import create_evaluation, list_evaluations, MultiViewDepthEvaluation  # noqa: F401,E402
 from . import depth_fusion  # noqa: F401,E402
-from .depth_fusion import DepthFusion, fuse_numpy, write_ply  # noqa: F401,E402
+from .depth_fusion import DepthFusion, fuse_numpy, merge_numpy, normals_numpy, write_ply  # noqa: F401,E402
 from . import cloud_eval  # noqa: F401,E402
 from .cloud_eval import (PointCloudEvaluation, CloudScore, evaluate_scene, read_ply, nearest_numpy,  # noqa: F401,E402
                          cloud_scores_numpy, voxel_downsample_numpy)

@@ -149,6 +149,11 @@ SIGNATURES = {
     "mvd_compact_points_workspace_bytes": (_sz, [_i, _i]),
     "mvd_compact_points_f32": (_i, [ctypes.c_void_p] + [_c_float_p] * 3 + [_i, _i, _c_float_p, _c_float_p, ctypes.c_void_p,
                                                                           ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "mvd_compact_points_attr_f32": (_i, [ctypes.c_void_p] + [_c_float_p] * 4 + [_i, _i] + [_c_float_p] * 3
+                                    + [ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "mvd_depth_normals_f32": (_i, [_c_float_p, _c_float_p, _i, _i, _c_float_p, ctypes.c_void_p]),
+    "mvd_geo_merge_f32": (_i, [_c_float_p, _pp, _c_float_p, _c_float_p, _i, _i, _i, ctypes.c_float, ctypes.c_float, _i, ctypes.c_float,
+                               ctypes.c_void_p, _pp, _c_float_p, _pp, _c_float_p, _pp] + [ctypes.c_void_p] * 7),
     "mvd_cloud_cell_keys_f32": (_i, [_c_float_p, ctypes.c_longlong] + [ctypes.c_double] * 4 + [ctypes.c_void_p] * 2),
     "mvd_cloud_grid_build_f32": (_i, [_c_float_p, ctypes.c_void_p, ctypes.c_longlong, _c_float_p, ctypes.c_void_p]),
     "mvd_cloud_nearest_f32": (_i, [_c_float_p, ctypes.c_longlong, _c_float_p, ctypes.c_void_p, ctypes.c_longlong]

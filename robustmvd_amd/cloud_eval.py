@@ -281,10 +281,11 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def read_ply(path):
+def read_ply(path, normals=False):
     """-> (points (n,3) float32, colors (n,3) float32 in 0..255 or None): the counterpart of depth_fusion.write_ply.  Reads ASCII and
     binary little-endian files whose first element is `vertex`; x / y / z may be float or double; uchar red / green / blue are the
-    colours when all three are there; other scalar vertex properties and later elements (faces) are skipped."""
+    colours when all three are there; other scalar vertex properties and later elements (faces) are skipped.
+    normals=True -> (points, colors, normals (n,3) float32 or None): nx / ny / nz, float or double, when all three are there."""
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError(f"{path}: not a PLY file")
@@ -330,4 +331,7 @@ def read_ply(path):
     colors = None
     if all(c in names and dict(props)[c] == "u1" for c in ("red", "green", "blue")):
         colors = np.stack([column(c) for c in ("red", "green", "blue")], axis=1).astype(np.float32)
-    return points, colors
+    if not normals:
+        return points, colors
+    have = all(c in names and dict(props)[c] in ("f4", "f8") for c in ("nx", "ny", "nz"))
+    return points, colors, np.stack([column(c) for c in ("nx", "ny", "nz")], axis=1).astype(np.float32) if have else None

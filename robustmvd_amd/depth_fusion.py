@@ -18,8 +18,28 @@ max_uncertainty are given, uncertainty <= max_uncertainty (false for a NaN).  Th
 
 The point cloud is the masked pixels in row-major (np.nonzero) order, X = Tk^-1 (fused Kk^-1 (x,y,1)), with the pixel's colour.
 
-Two implementations: fuse_numpy / points_numpy on the host, and the HIP kernels of csrc/depth_fusion.hip (ops.geo_consistency,
-ops.compact_points) for maps that are GPU tensors.  DepthFusion picks by where its inputs are.
+Normals (normals=True; normals_numpy).  With B the 3x3 of compose_backprojection, P(x,y) = depth(x,y) B (x,y,1): the world point
+without the camera centre c, which cancels in the differences below and would only cost digits at world coordinates far from the
+origin.  n = (P(x+1,y) - P(x-1,y)) x (P(x,y+1) - P(x,y-1)), normalised, and negated when n . B (x,y,1) > 0, so that it points towards
+the camera.  The normal is (0,0,0), which means invalid, on the image border, where one of the five depths is not finite or <= 0, and
+where the cross product's length is zero or not finite.  There is no depth-discontinuity guard: a stencil that straddles an edge gives
+a normal of neither surface; the consistency mask removes most of those pixels.
+
+Merge mode (merge=True; merge_numpy): one point per surface sample instead of one per view that sees it, fusibile-style.  Every view i
+has a byte map claimed[i], all zero at the start, and the views are processed in index order.  For view i, view_bits, count and fused
+are fuse_numpy's, unchanged; mask = fuse_numpy's mask and not claimed[i], with claimed[i] as it is before view i runs.  For every
+pixel with mask set and every consistent source s, which is view j, the target is the source pixel (tx, ty) = (rint(u), rint(v)),
+half to even: it is one of the four bilinear taps, so it is inside the image and has a valid depth.  claimed[j][ty,tx] is set; the
+pixel and its targets are the members of the merged point.  merged_rgb = (the pixel's colour + the targets' colours in source order)
+/ (count + 1); merged_normal = the normalised sum of the members' normals (an invalid one is zero and adds nothing), (0,0,0) when no
+member has a valid normal or the sum has zero length.  Both are 0 where mask is 0.  A later view still uses a claimed pixel's depth
+for its consistency checks and its means: only the emission is suppressed.  A view among its own sources is refused, because
+claimed[i] must not change while view i runs.  THE RESULT DEPENDS ON THE ORDER OF THE VIEWS, by design: the first view that sees a
+surface sample emits it, at its own pixel.  normals=True without merge gives each point its key view's own normal.
+
+Two implementations: fuse_numpy / points_numpy / normals_numpy / merge_numpy on the host, and the HIP kernels of csrc/depth_fusion.hip
+(ops.geo_consistency, ops.compact_points, ops.depth_normals, ops.geo_merge) for maps that are GPU tensors.  DepthFusion picks by where
+its inputs are.
 """
 from dataclasses import dataclass
 
@@ -162,10 +182,112 @@ def points_numpy(mask, fused, key_K, key_T, image=None):
     return xyz, rgb
 
 
-def write_ply(path, points, colors=None):
-    """Binary little-endian PLY: float32 x y z and, with colors, uchar red green blue.  colors: (M,3) in 0..255 (rounded and clipped)."""
+def normals_numpy(depth, K, T, dtype=np.float64):
+    """World-frame normals (3,H,W) of one depth map, the module docstring's definition as a numpy chain; (0,0,0) where invalid.
+    dtype=np.float32 evaluates the same chain in float32 on the float32-rounded B, as fuse_numpy does for its chain."""
+    ft = np.dtype(dtype).type
+    d = np.asarray(depth).astype(ft)
+    if d.ndim != 2:
+        raise ValueError(f"depth must be (H,W), got {d.shape}")
+    H, W = d.shape
+    out = np.zeros((3, H, W), dtype=ft)
+    if H < 3 or W < 3:
+        return out
+    B = compose_backprojection(K, T)[:9].reshape(3, 3).astype(ft)
+    y, x = np.meshgrid(np.arange(1, H - 1, dtype=ft), np.arange(1, W - 1, dtype=ft), indexing="ij")
+    ray = lambda x, y: [B[i, 0] * x + B[i, 1] * y + B[i, 2] for i in range(3)]
+    one = ft(1)
+    dc, dl, dr, du, dd = d[1:-1, 1:-1], d[1:-1, :-2], d[1:-1, 2:], d[:-2, 1:-1], d[2:, 1:-1]
+    with np.errstate(all="ignore"):
+        rc, rl, rr, ru, rd = ray(x, y), ray(x - one, y), ray(x + one, y), ray(x, y - one), ray(x, y + one)
+        a = [dr * rr[i] - dl * rl[i] for i in range(3)]
+        b = [dd * rd[i] - du * ru[i] for i in range(3)]
+        n = [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+        length = np.sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2])
+        ok = np.isfinite(length) & (length > 0)
+        for t in (dc, dl, dr, du, dd):
+            ok &= np.isfinite(t) & (t > 0)
+        towards = n[0] * rc[0] + n[1] * rc[1] + n[2] * rc[2]
+        scale = np.where(towards > 0, -length, length)
+        for i in range(3):
+            out[i, 1:-1, 1:-1] = np.where(ok, n[i] / scale, ft(0))
+    return out
+
+
+def default_sources(N):
+    return [[j for j in range(N) if j != i] for i in range(N)]
+
+
+def merge_numpy(depths, Ks, Ts, sources=None, uncertainties=None, images=None, normals=False, min_consistent_views=None,
+                max_reproj_error=1.0, max_rel_depth_diff=0.01, max_uncertainty=None, dtype=np.float64, details=False):
+    """Merge mode for a whole scene, the module docstring's definition as a numpy chain; the result depends on the order of the views.
+    depths N x (H,W); sources: per view the indices of its source views (default: all others); images N x (3,H,W) or None.
+    -> dict of lists of N maps: view_bits, count, fused (fuse_numpy's), mask (uint8, the claimed pixels taken out), merged_rgb
+    (3,H,W) or None without images, merged_normal (3,H,W) or None without normals, normals (every view's normals_numpy, or None) and
+    claimed (uint8, after the last view).  details=True adds claimed_before: claimed[i] as it was when view i ran."""
+    ft = np.dtype(dtype).type
+    N = len(depths)
+    sources = default_sources(N) if sources is None else [list(s) for s in sources]
+    for i, src in enumerate(sources):
+        if i in src:
+            raise ValueError(f"view {i} is among its own sources {src}: merge mode reads claimed[{i}] while it writes its sources' maps")
+    depths = [np.asarray(d) for d in depths]
+    imgs = None if images is None else [np.asarray(im).astype(ft) for im in images]
+    nrm = [normals_numpy(depths[i], Ks[i], Ts[i], dtype) for i in range(N)] if normals else None
+    claimed = [np.zeros(d.shape, dtype=np.uint8) for d in depths]
+    out = {k: [] for k in ("view_bits", "count", "fused", "mask", "merged_rgb", "merged_normal", "claimed_before")}
+    for i, src in enumerate(sources):
+        r = fuse_numpy(depths[i], Ks[i], Ts[i], [depths[j] for j in src], [Ks[j] for j in src], [Ts[j] for j in src],
+                       None if uncertainties is None else uncertainties[i], min_consistent_views, max_reproj_error, max_rel_depth_diff,
+                       max_uncertainty, dtype=dtype, details=True)
+        out["claimed_before"].append(claimed[i].copy())
+        mask = r["mask"] & (claimed[i] == 0)
+        ys, xs = np.nonzero(mask)
+        rgb = nsum = None
+        if imgs is not None:
+            rgb = np.zeros((3,) + mask.shape, dtype=ft)
+            rgb[:, ys, xs] = imgs[i][:, ys, xs]
+        if nrm is not None:
+            nsum = np.zeros((3,) + mask.shape, dtype=ft)
+            nsum[:, ys, xs] = nrm[i][:, ys, xs]
+        for s, j in enumerate(src):
+            member = ((r["view_bits"][ys, xs] >> np.uint32(s)) & np.uint32(1)).astype(bool)
+            py, px = ys[member], xs[member]
+            tx, ty = np.rint(r["u"][s][py, px]).astype(np.int64), np.rint(r["v"][s][py, px]).astype(np.int64)
+            claimed[j][ty, tx] = 1
+            if rgb is not None:
+                rgb[:, py, px] += imgs[j][:, ty, tx]  # the (py, px) are distinct pixels: a plain indexed sum
+            if nsum is not None:
+                nsum[:, py, px] += nrm[j][:, ty, tx]
+        if rgb is not None:
+            rgb[:, ys, xs] /= r["count"][ys, xs].astype(ft) + ft(1)
+        if nsum is not None:
+            with np.errstate(all="ignore"):
+                length = np.sqrt(nsum[0] * nsum[0] + nsum[1] * nsum[1] + nsum[2] * nsum[2])
+                nsum = np.where(np.isfinite(length) & (length > 0), nsum / length, ft(0))
+        for k, v in (("view_bits", r["view_bits"]), ("count", r["count"]), ("fused", r["fused"]), ("mask", mask.astype(np.uint8)),
+                     ("merged_rgb", rgb), ("merged_normal", nsum)):
+            out[k].append(v)
+    out["claimed"], out["normals"] = claimed, nrm
+    if imgs is None:
+        out["merged_rgb"] = None
+    if nrm is None:
+        out["merged_normal"] = None
+    if not details:
+        del out["claimed_before"]
+    return out
+
+
+def write_ply(path, points, colors=None, normals=None):
+    """Binary little-endian PLY: float32 x y z, with normals float32 nx ny nz, and with colors uchar red green blue.  colors: (M,3)
+    in 0..255 (rounded and clipped)."""
     pts = np.asarray(_to_numpy(points), dtype="<f4").reshape(-1, 3)
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        nrm = np.asarray(_to_numpy(normals), dtype="<f4").reshape(-1, 3)
+        if len(nrm) != len(pts):
+            raise ValueError(f"{len(nrm)} normals for {len(pts)} points")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
     if colors is not None:
         col = np.clip(np.rint(np.asarray(_to_numpy(colors), dtype=np.float64).reshape(-1, 3)), 0, 255).astype(np.uint8)
         if len(col) != len(pts):
@@ -173,10 +295,14 @@ def write_ply(path, points, colors=None):
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
     rec = np.empty(len(pts), dtype=fields)
     rec["x"], rec["y"], rec["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
+    if normals is not None:
+        rec["nx"], rec["ny"], rec["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
     if colors is not None:
         rec["red"], rec["green"], rec["blue"] = col[:, 0], col[:, 1], col[:, 2]
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(pts)}", "property float x", "property float y",
               "property float z"]
+    if normals is not None:
+        header += ["property float nx", "property float ny", "property float nz"]
     if colors is not None:
         header += ["property uchar red", "property uchar green", "property uchar blue"]
     header.append("end_header")
@@ -208,7 +334,9 @@ def _map2d(a, name):
 class FusionResult:
     """Per view (lists of N maps, GPU tensors on the device path): mask uint8, fused_depth, num_consistent uint8, view_bits uint32
     (bit j of view i = the j-th entry of sources[i] is consistent).  Concatenated in view order: points (M,3) float32, colors (M,3)
-    or None, view_index (M,) int64."""
+    or None, view_index (M,) int64.  normals (M,3) float32 unit vectors ((0,0,0): invalid) or None; claimed: in merge mode the N byte
+    maps after the last view, else None.  In merge mode mask has the pixels an earlier view claimed taken out, and colors / normals
+    are the means over each point's members."""
     mask: list
     fused_depth: list
     num_consistent: list
@@ -217,6 +345,8 @@ class FusionResult:
     colors: object
     view_index: object
     sources: list
+    normals: object = None
+    claimed: list = None
 
 
 class DepthFusion:
@@ -225,9 +355,15 @@ class DepthFusion:
         fusion = DepthFusion(max_uncertainty=0.5)
         out = fusion(depths, intrinsics, poses, uncertainties=unc, images=images)
         write_ply("scene.ply", out.points, out.colors)
+
+    merge=True emits every surface sample once, by the first view that sees it, with the mean colour of the pixels merged into it
+    (the result depends on the order of the views); normals=True adds world-frame normals (write_ply(..., normals=out.normals)).
     """
 
-    def __init__(self, min_consistent_views=None, max_reproj_error=1.0, max_rel_depth_diff=0.01, max_uncertainty=None):
+    def __init__(self, min_consistent_views=None, max_reproj_error=1.0, max_rel_depth_diff=0.01, max_uncertainty=None, merge=False,
+                 normals=False):
+        self.merge = bool(merge)
+        self.normals = bool(normals)
         self.min_consistent_views = min_consistent_views
         self.max_reproj_error = float(max_reproj_error)
         self.max_rel_depth_diff = float(max_rel_depth_diff)
@@ -247,9 +383,7 @@ class DepthFusion:
         for name, opt in (("uncertainties", uncertainties), ("images", images)):
             if opt is not None and len(opt) != N:
                 raise ValueError(f"{len(opt)} {name} for {N} views")
-        if sources is None:
-            sources = [[j for j in range(N) if j != i] for i in range(N)]
-        sources = [list(s) for s in sources]
+        sources = default_sources(N) if sources is None else [list(s) for s in sources]
         if len(sources) != N:
             raise ValueError(f"{len(sources)} source lists for {N} views")
         for i, s in enumerate(sources):
@@ -257,6 +391,8 @@ class DepthFusion:
                 raise ValueError(f"view {i}: {len(s)} source views, supported 1..{MAX_SOURCES}")
             if any(not 0 <= j < N for j in s):
                 raise ValueError(f"view {i}: source index out of range in {s}")
+            if self.merge and i in s:
+                raise ValueError(f"view {i} is among its own sources {s}: merge mode cannot claim pixels of the view it is emitting")
         Ks = [_to_numpy(K).astype(np.float64).reshape(3, 3) for K in intrinsics]
         Ts = [_to_numpy(T).astype(np.float64).reshape(4, 4) for T in poses]
         places = {_place(m) for m in list(depths) + list(uncertainties or [])}
@@ -271,28 +407,39 @@ class DepthFusion:
         depths = [_to_numpy(d) for d in depths]
         uncs = None if uncs is None else [_to_numpy(u) for u in uncs]
         images = None if images is None else [_to_numpy(im) for im in images]
-        out = FusionResult([], [], [], [], None, None, None, sources)
-        pts, cols, idx = [], [], []
-        for i, src in enumerate(sources):
-            r = fuse_numpy(depths[i], Ks[i], Ts[i], [depths[j] for j in src], [Ks[j] for j in src], [Ts[j] for j in src],
-                           None if uncs is None else uncs[i], self.min_consistent_views, self.max_reproj_error,
-                           self.max_rel_depth_diff, self.max_uncertainty)
-            fused = r["fused"].astype(np.float32)
-            out.mask.append(r["mask"]); out.fused_depth.append(fused)
-            out.num_consistent.append(r["count"]); out.view_bits.append(r["view_bits"])
-            if images is not None and images[i].shape != (3,) + fused.shape:
-                raise ValueError(f"images[{i}]: shape {images[i].shape}, expected {(3,) + fused.shape}")
-            xyz, rgb = points_numpy(r["mask"], fused, Ks[i], Ts[i], None if images is None else images[i])
+        for i, im in enumerate(images or []):
+            if im.shape != (3,) + depths[i].shape:
+                raise ValueError(f"images[{i}]: shape {im.shape}, expected {(3,) + depths[i].shape}")
+        thresholds = (self.min_consistent_views, self.max_reproj_error, self.max_rel_depth_diff, self.max_uncertainty)
+        if self.merge:
+            r = merge_numpy(depths, Ks, Ts, sources, uncs, images, self.normals, *thresholds)
+            colours, normals = r["merged_rgb"], r["merged_normal"]
+        else:
+            per_view = [fuse_numpy(depths[i], Ks[i], Ts[i], [depths[j] for j in src], [Ks[j] for j in src], [Ts[j] for j in src],
+                                   None if uncs is None else uncs[i], *thresholds) for i, src in enumerate(sources)]
+            r = {k: [v[k] for v in per_view] for k in ("mask", "fused", "count", "view_bits")}
+            colours = images
+            normals = [normals_numpy(depths[i], Ks[i], Ts[i]) for i in range(len(depths))] if self.normals else None
+        out = FusionResult(r["mask"], [f.astype(np.float32) for f in r["fused"]], r["count"], r["view_bits"], None, None, None, sources,
+                           claimed=r.get("claimed"))
+        pts, cols, nrms, idx = [], [], [], []
+        for i, mask in enumerate(out.mask):
+            xyz, rgb = points_numpy(mask, out.fused_depth[i], Ks[i], Ts[i], None if colours is None else colours[i])
             pts.append(xyz.astype(np.float32))
             idx.append(np.full(len(xyz), i, dtype=np.int64))
             if rgb is not None:
                 cols.append(rgb.astype(np.float32))
+            if normals is not None:
+                ys, xs = np.nonzero(mask)
+                nrms.append(normals[i][:, ys, xs].T.astype(np.float32))
         out.points, out.view_index = np.concatenate(pts), np.concatenate(idx)
         out.colors = np.concatenate(cols) if images is not None else None
+        out.normals = np.concatenate(nrms) if normals is not None else None
         return out
 
     def _run_device(self, depths, Ks, Ts, uncs, images, sources):
         import torch
+        from . import _lib as L
         from . import ops
         dev = depths[0].device
         N = len(depths)
@@ -308,24 +455,40 @@ class DepthFusion:
             tables += [m, compose_backprojection(Ks[i], Ts[i])]
         table = torch.from_numpy(np.concatenate(tables).astype(np.float32)).to(dev)
         out = FusionResult([], [], [], [], None, None, None, sources)
-        # one pair of H*W-point buffers for all views: each view's points are copied out at their exact size after the one
-        # 8-byte read of its count, so that the call holds M points and one pair, not N pairs
-        buffers, pts, cols, m = None, [], [], []
+        backproject = lambda i: table[offsets[i] + 24 * len(sources[i]):offsets[i] + 24 * len(sources[i]) + 12]
+        normals = [ops.depth_normals(depths[i], backproject(i)) for i in range(N)] if self.normals else None
+        if self.merge:
+            # the merge kernel gathers the sources' colours: every image as the kernel takes it, once
+            images = None if images is None else [L.as_f32(im, f"images[{i}]", (3,) + tuple(depths[i].shape), dev)
+                                                  for i, im in enumerate(images)]
+            out.claimed = [torch.zeros(d.shape, dtype=torch.uint8, device=dev) for d in depths]
+        thresholds = (self.min_consistent_views, self.max_reproj_error, self.max_rel_depth_diff, self.max_uncertainty)
+        # one set of H*W-point buffers for all views: each view's points are copied out at their exact size after the one
+        # 8-byte read of its count, so that the call holds M points and one set, not N sets
+        buffers, pts, cols, nrms, m = None, [], [], [], []
         for i, src in enumerate(sources):
             V, o = len(src), offsets[i]
-            bits, fused, mask, count = ops.geo_consistency(
-                depths[i], [depths[j] for j in src], table[o:o + 24 * V].view(V, 24), None if uncs is None else uncs[i],
-                self.min_consistent_views, self.max_reproj_error, self.max_rel_depth_diff, self.max_uncertainty)
-            xyz, rgb, n = ops.compact_points(mask, fused, table[o + 24 * V:o + 24 * V + 12], None if images is None else images[i],
-                                             out=buffers)
-            buffers = (xyz, rgb)
+            args = (depths[i], [depths[j] for j in src], table[o:o + 24 * V].view(V, 24))
+            unc = None if uncs is None else uncs[i]
+            if self.merge:
+                pick = lambda maps: (None, None) if maps is None else (maps[i], [maps[j] for j in src])
+                bits, fused, mask, count, colour, normal = ops.geo_merge(*args, out.claimed[i], [out.claimed[j] for j in src], unc,
+                                                                         *thresholds, *pick(images), *pick(normals))
+            else:
+                bits, fused, mask, count = ops.geo_consistency(*args, unc, *thresholds)
+                colour, normal = None if images is None else images[i], None if normals is None else normals[i]
+            xyz, rgb, n, *nrm = ops.compact_points(mask, fused, backproject(i), colour, out=buffers, normals=normal)
+            buffers = (xyz, rgb, *nrm)
             m.append(int(n.item()))
             pts.append(xyz[:m[-1]].clone())
             if rgb is not None:
                 cols.append(rgb[:m[-1]].clone())
+            if nrm:
+                nrms.append(nrm[0][:m[-1]].clone())
             out.mask.append(mask); out.fused_depth.append(fused); out.num_consistent.append(count); out.view_bits.append(bits)
         out.points = torch.cat(pts)
         out.colors = torch.cat(cols) if images is not None else None
+        out.normals = torch.cat(nrms) if normals is not None else None
         out.view_index = torch.repeat_interleave(torch.arange(N, device=dev), torch.tensor(m, device=dev))
         return out
 

@@ -744,12 +744,83 @@ def geo_consistency(key_depth, src_depths, matrices, uncertainty=None, min_consi
 
 
 @inference_only
-def compact_points(mask, depth, backproject, image=None, count=None, out=None):
+def depth_normals(depth, backproject):
+    """World-frame normals (3,H,W) of one depth map (H,W) (include/mvd.h: mvd_depth_normals_f32; depth_fusion.normals_numpy is the
+    definition).  backproject: the 12 floats of depth_fusion.compose_backprojection on the device.  (0,0,0) marks an invalid normal."""
+    d = L.as_f32(depth, "depth")
+    if d.dim() != 2:
+        raise ValueError(f"depth must be (H,W), got {tuple(d.shape)}")
+    H, W = d.shape
+    bp = L.as_f32(backproject, "backproject", device=d.device)
+    if bp.numel() != 12:
+        raise ValueError(f"backproject must hold 12 floats, got {tuple(bp.shape)}")
+    normals = torch.empty((3, H, W), dtype=torch.float32, device=d.device)
+    call("mvd_depth_normals_f32", d.device, d, bp, H, W, normals)
+    return normals
+
+
+@inference_only
+def geo_merge(key_depth, src_depths, matrices, key_claimed, src_claimed, uncertainty=None, min_consistent_views=None,
+              max_reproj_error=1.0, max_rel_depth_diff=0.01, max_uncertainty=None, key_image=None, src_images=None, key_normal=None,
+              src_normals=None):
+    """geo_consistency for a scene fused view by view (include/mvd.h: mvd_geo_merge_f32; depth_fusion.merge_numpy is the definition).
+    key_claimed (H,W) uint8 is read: a pixel an earlier view has claimed is not emitted.  src_claimed: V x (H,W) uint8, UPDATED IN
+    PLACE: every emitted pixel sets the byte of the source pixel nearest to its projection in each consistent source.  key_image and
+    src_images (planar (3,H,W)), key_normal and src_normals (depth_normals' maps) are each given together or not at all.
+    Returns (view_bits, fused, mask, num_consistent, merged_rgb, merged_normal): the first four as geo_consistency's with the claimed
+    pixels taken out of the mask; merged_rgb and merged_normal (3,H,W), or None without their inputs, are 0 where mask is 0."""
+    d = L.as_f32(key_depth, "key_depth")
+    if d.dim() != 2 or d.shape[0] < 2 or d.shape[1] < 2:
+        raise ValueError(f"key_depth must be (H,W) with H, W >= 2, got {tuple(d.shape)}")
+    H, W = d.shape
+    dev = d.device
+    srcs = [L.as_f32(s, f"src_depths[{i}]", (H, W), dev) for i, s in enumerate(views(src_depths, "src_depths"))]
+    V = len(srcs)
+    mats = L.as_f32(matrices, "matrices", (V, 24), dev)
+    unc = None
+    if uncertainty is not None and max_uncertainty is not None:
+        unc = L.as_f32(uncertainty, "uncertainty", (H, W), dev)
+    min_views = min(3, V) if min_consistent_views is None else int(min_consistent_views)
+    # the claimed maps are written in place: they are taken as they are, never converted or made contiguous into a copy
+    claims = [key_claimed] + views(src_claimed, "src_claimed", V)
+    for i, c in enumerate(claims):
+        name = "key_claimed" if i == 0 else f"src_claimed[{i - 1}]"
+        L.as_dtype(torch.uint8, False, c, name, (H, W), dev)
+        if not c.is_contiguous():
+            raise ValueError(f"{name}: must be contiguous")
+    if any(c.data_ptr() == key_claimed.data_ptr() for c in claims[1:]):
+        raise ValueError("key_claimed is among src_claimed: a view cannot be its own source in merge mode")
+
+    def attribute(key, srcs_, name):
+        if (key is None) != (srcs_ is None):
+            raise ValueError(f"key_{name} and src_{name}s go together")
+        if key is None:
+            return None, None, None
+        return (L.as_f32(key, f"key_{name}", (3, H, W), dev),
+                [L.as_f32(s, f"src_{name}s[{i}]", (3, H, W), dev) for i, s in enumerate(views(srcs_, f"src_{name}s", V))],
+                torch.empty((3, H, W), dtype=torch.float32, device=dev))
+
+    k_img, s_img, rgb = attribute(key_image, src_images, "image")
+    k_nrm, s_nrm, nrm = attribute(key_normal, src_normals, "normal")
+    bits = torch.empty((H, W), dtype=torch.uint32, device=dev)
+    fused = torch.empty((H, W), dtype=torch.float32, device=dev)
+    mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    count = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    call("mvd_geo_merge_f32", dev, d, srcs, mats, unc, V, H, W, float(max_reproj_error), float(max_rel_depth_diff), min_views,
+         float(max_uncertainty) if unc is not None else 0.0, key_claimed, claims[1:], k_img, s_img, k_nrm, s_nrm, bits, fused, mask,
+         count, rgb, nrm)
+    return bits, fused, mask, count, rgb, nrm
+
+
+@inference_only
+def compact_points(mask, depth, backproject, image=None, count=None, out=None, normals=None):
     """The set pixels of mask (H,W) uint8 in row-major order as world points (include/mvd.h: mvd_compact_points_f32): xyz =
     depth * B (x,y,1) + c with backproject = (B (9), c (3)) on the device; image: planar (3,H,W), gathered into rgb.
     Returns (xyz (H*W,3), rgb (H*W,3) or None, count): the first count[0] rows are the points; count is a device int64 tensor of
     one element (the caller's own, where given), left on the device so that the caller decides when to read it.  out: the
-    (xyz, rgb) of an earlier call on maps of this size, written again instead of two new buffers."""
+    (xyz, rgb) of an earlier call on maps of this size, written again instead of two new buffers.
+    normals: planar (3,H,W), gathered like the image (mvd_compact_points_attr_f32); the result is then (xyz, rgb, count, normals
+    (H*W,3)), and `out` may carry that buffer as a third element."""
     m = L.as_dtype(torch.uint8, False, mask, "mask")
     if m.dim() != 2:
         raise ValueError(f"mask must be (H,W), got {tuple(m.shape)}")
@@ -764,19 +835,25 @@ def compact_points(mask, depth, backproject, image=None, count=None, out=None):
         count = torch.empty(1, dtype=torch.int64, device=dev)
     elif count.dtype != torch.int64 or count.device != dev or count.numel() != 1:
         raise ValueError("count must be one int64 on the mask's device")
+    nrm = L.as_f32(normals, "normals", (3, H, W), dev) if normals is not None else None
     if out is None:
         xyz = torch.empty((H * W, 3), dtype=torch.float32, device=dev)
         rgb = torch.empty((H * W, 3), dtype=torch.float32, device=dev) if img is not None else None
+        nrm_out = torch.empty((H * W, 3), dtype=torch.float32, device=dev) if nrm is not None else None
     else:
-        xyz, rgb = out
-        for t, want in ((xyz, True), (rgb, img is not None)):
+        xyz, rgb, nrm_out = out if len(out) == 3 else (*out, None)
+        for t, want in ((xyz, True), (rgb, img is not None), (nrm_out, nrm is not None)):
             if (t is not None) != want or (want and (t.dtype != torch.float32 or t.device != dev or t.shape != (H * W, 3)
                                                      or not t.is_contiguous())):
-                raise ValueError(f"out must be (xyz, rgb) contiguous float32 ({H * W},3) tensors on {dev}, rgb None without an image")
+                raise ValueError(f"out must be (xyz, rgb[, normals]) contiguous float32 ({H * W},3) tensors on {dev}, rgb None without "
+                                 "an image, normals there exactly when normals are gathered")
     nbytes = L.load().mvd_compact_points_workspace_bytes(H, W)
     ws = workspace(nbytes, dev)
-    call("mvd_compact_points_f32", dev, m, d, img, bp, H, W, xyz, rgb, count, ws, int(nbytes))
-    return xyz, rgb, count
+    if nrm is None:
+        call("mvd_compact_points_f32", dev, m, d, img, bp, H, W, xyz, rgb, count, ws, int(nbytes))
+        return xyz, rgb, count
+    call("mvd_compact_points_attr_f32", dev, m, d, img, nrm, bp, H, W, xyz, rgb, nrm_out, count, ws, int(nbytes))
+    return xyz, rgb, count, nrm_out
 
 
 CLOUD_INDEX_LIMIT = (1 << 21) - 1  # a cell or voxel index is in [0, 2^21 - 1): the all-ones key is the invalid points' own

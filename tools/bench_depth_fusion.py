@@ -13,7 +13,15 @@ source views, in one process on one GPU:
       the warm-up the kernels and the torch composition alike read it from the 256 MB Infinity Cache: the shares of the streaming
       rate compare cache-warm launches with an HBM rate and say how far a launch is from that floor, not what HBM delivers.
 The torch composition treats a sample as valid when the interpolated validity is above 0.999, so it differs from the definition on
-a few pixels next to holes; the tool prints the agreement and refuses a composition that disagrees on more than 0.5 % of the pixels."""
+a few pixels next to holes; the tool prints the agreement and refuses a composition that disagrees on more than 0.5 % of the pixels.
+
+Merge mode and normals (profiles/depth_merge.txt, same process, 768 x 1152): the normals kernel (mvd_depth_normals_f32), the merge kernel
+(mvd_geo_merge_f32 with colours and normals, all-zero claimed maps: every passing pixel is emitted and runs the second loop, the most
+work the kernel can have) at V = 4 and V = 10 next to the plain mvd_geo_consistency_f32 of the same bracket series, and the compaction
+with colours and normals (mvd_compact_points_attr_f32) next to mvd_compact_points_f32.  Then the scene level, host clock around whole
+calls that end in a device synchronise: DepthFusion(merge=True) over all five views of the V = 4 scene against what served the
+purpose before, plain DepthFusion followed by ops.voxel_downsample at a voxel of one pixel's footprint at the median depth, with the
+point counts of both."""
 import argparse
 import os
 import sys
@@ -92,6 +100,117 @@ def numpy_ms(fn, repeats):
     return float(np.median(times))
 
 
+def host_ms(fn, warmup, repeats):
+    """Median (min, max) of a host clock around fn and a device synchronise: for whole calls that read counts back in between."""
+    times = []
+    for k in range(warmup + repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        if k >= warmup:
+            times.append(1000 * (time.perf_counter() - t0))
+    return float(np.median(times)), float(np.min(times)), float(np.max(times))
+
+
+def merge_rows(args, dev, lib, stream_gbs):
+    H, W = 768, 1152
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    ms = lambda t: f"{t[0]:8.4f} ms ({t[1]:.4f}, {t[2]:.4f})"
+    out = [f"depth fusion, merge mode and normals, {H} x {W} on {torch.cuda.get_device_name(0)}; commit {args.commit or tree_label()}; "
+           f"tools/bench_depth_fusion.py --warmup {args.warmup} --repeats {args.repeats} --inner {args.inner}",
+           "kernel rows: ms = median (min, max) per launch over HIP-event brackets, cache-warm like profiles/depth_fusion.txt; the plain "
+           "kernels are timed again here, next to the new ones", ""]
+    for V in (4, 10):
+        K, Ts, depths, image = bench_scene(H, W, V)
+        mats = up(DF.compose_matrices(K, Ts[0], [K] * V, Ts[1:]).astype(np.float32))
+        maps = [up(d) for d in depths]
+        bps = [up(DF.compose_backprojection(K, T).astype(np.float32)) for T in Ts]
+        rng = np.random.default_rng(100 + V)
+        images = [up(rng.random((3, H, W)).astype(np.float32) * 255) for _ in Ts]
+        min_views = min(3, V)
+        bits = torch.empty((H, W), dtype=torch.uint32, device=dev)
+        fused, mask, count = torch.empty((H, W), device=dev), torch.empty((H, W), dtype=torch.uint8, device=dev), torch.empty((H, W), dtype=torch.uint8, device=dev)
+        m_rgb, m_nrm = torch.empty((3, H, W), device=dev), torch.empty((3, H, W), device=dev)
+        normals = [torch.empty((3, H, W), device=dev) for _ in Ts]
+        key_claimed = torch.zeros((H, W), dtype=torch.uint8, device=dev)
+        src_claimed = [torch.zeros((H, W), dtype=torch.uint8, device=dev) for _ in range(V)]
+        xyz, rgb, nrm = (torch.empty((H * W, 3), device=dev) for _ in range(3))
+        m_dev = torch.empty(1, dtype=torch.int64, device=dev)
+        ws_bytes = lib.mvd_compact_points_workspace_bytes(H, W)
+        ws = ops.workspace(ws_bytes, dev)
+
+        def k_normals():
+            ops.call("mvd_depth_normals_f32", dev, maps[0], bps[0], H, W, normals[0])
+
+        def k_plain():
+            ops.call("mvd_geo_consistency_f32", dev, maps[0], maps[1:], mats, None, V, H, W, 1.0, 0.01, min_views, 0.0, bits, fused, mask, count)
+
+        def k_merge():
+            ops.call("mvd_geo_merge_f32", dev, maps[0], maps[1:], mats, None, V, H, W, 1.0, 0.01, min_views, 0.0, key_claimed, src_claimed,
+                     images[0], images[1:], normals[0], normals[1:], bits, fused, mask, count, m_rgb, m_nrm)
+
+        def k_merge_claims_only():
+            ops.call("mvd_geo_merge_f32", dev, maps[0], maps[1:], mats, None, V, H, W, 1.0, 0.01, min_views, 0.0, key_claimed, src_claimed,
+                     None, None, None, None, bits, fused, mask, count, None, None)
+
+        def k_points():
+            ops.call("mvd_compact_points_f32", dev, mask, fused, m_rgb, bps[0], H, W, xyz, rgb, m_dev, ws, int(ws_bytes))
+
+        def k_points_attr():
+            ops.call("mvd_compact_points_attr_f32", dev, mask, fused, m_rgb, m_nrm, bps[0], H, W, xyz, rgb, nrm, m_dev, ws, int(ws_bytes))
+
+        for i in range(V + 1):
+            ops.call("mvd_depth_normals_f32", dev, maps[i], bps[i], H, W, normals[i])
+        k_merge()
+        k_points_attr()
+        M = int(m_dev.item())
+        pairs = int(count.to(torch.int64)[mask.bool()].sum().item())
+        t = {name: event_ms(fn, args.warmup, args.repeats, args.inner)
+             for name, fn in (("plain", k_plain), ("merge", k_merge), ("claims", k_merge_claims_only), ("plain2", k_plain),
+                              ("normals", k_normals), ("points", k_points), ("attr", k_points_attr))}
+        plain = min(t["plain"][0], t["plain2"][0])
+        bytes_n = (4 + 12) * H * W
+        out += [f"V = {V}: {M} of {H * W} pixels emitted (all-zero claimed maps), {pairs} consistent pairs of emitted pixels",
+                f"  mvd_geo_consistency_f32                {ms(t['plain'])}   again after the merge rows {ms(t['plain2'])}",
+                f"  mvd_geo_merge_f32, claims only         {ms(t['claims'])}   {t['claims'][0] / plain:5.2f}x the plain kernel",
+                f"  mvd_geo_merge_f32, colours + normals   {ms(t['merge'])}   {t['merge'][0] / plain:5.2f}x the plain kernel",
+                f"  mvd_depth_normals_f32 (one view)       {ms(t['normals'])}   bytes {bytes_n / 1e6:.2f} MB = {bytes_n / stream_gbs * 1e-6:.4f} ms at the "
+                f"streaming rate of {stream_gbs:.0f} GB/s",
+                f"  mvd_compact_points_f32 (colours)       {ms(t['points'])}",
+                f"  mvd_compact_points_attr_f32 (+normals) {ms(t['attr'])}   {t['attr'][0] / t['points'][0]:5.2f}x", ""]
+        if V == 4:
+            voxel = float(np.median(depths[0][depths[0] > 0]) / K[0, 0])
+            Ks = [K] * (V + 1)
+            res = {}
+
+            def scene_merge():
+                res["merge"] = DF.DepthFusion(merge=True, normals=True)(maps, Ks, Ts, images=images)
+
+            def scene_merge_no_normals():
+                res["merge_c"] = DF.DepthFusion(merge=True)(maps, Ks, Ts, images=images)
+
+            def scene_plain():
+                res["plain"] = DF.DepthFusion()(maps, Ks, Ts, images=images)
+
+            def scene_voxel():
+                r = DF.DepthFusion()(maps, Ks, Ts, images=images)
+                res["voxel"] = ops.voxel_downsample(r.points, voxel, r.colors)
+
+            s = {name: host_ms(fn, args.warmup, args.repeats) for name, fn in (("plain", scene_plain), ("voxel", scene_voxel),
+                                                                               ("merge_c", scene_merge_no_normals), ("merge", scene_merge))}
+            ms3 = lambda t: f"{t[0]:8.3f} ms ({t[1]:.3f}, {t[2]:.3f})"
+            scene_rows = [f"scene level, {V + 1} views, every view against the other {V}; host clock around the whole call and a synchronise, median (min, max) "
+                          f"of {args.repeats}:",
+                          f"  DepthFusion()                                   {ms3(s['plain'])}   {len(res['plain'].points)} points",
+                          f"  DepthFusion() + ops.voxel_downsample({voxel:.5f})  {ms3(s['voxel'])}   {len(res['voxel'][0])} points (voxel = median depth / fx, "
+                          "one pixel's footprint)",
+                          f"  DepthFusion(merge=True)                         {ms3(s['merge_c'])}   {len(res['merge_c'].points)} points",
+                          f"  DepthFusion(merge=True, normals=True)           {ms3(s['merge'])}   {len(res['merge'].points)} points, "
+                          f"{int((res['merge'].normals != 0).any(1).sum())} with a valid normal", ""]
+    return out + scene_rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=3)
@@ -99,6 +218,7 @@ def main():
     ap.add_argument("--inner", type=int, default=10, help="launches per HIP-event bracket")
     ap.add_argument("--numpy-repeats", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "depth_fusion.txt"))
+    ap.add_argument("--merge-out", default=os.path.join(ROOT, "profiles", "depth_merge.txt"))
     ap.add_argument("--commit", default=None, help="commit to name in the header (default: the checkout's)")
     args = ap.parse_args()
     assert args.repeats >= 20, "the figures are medians of at least 20 brackets"
@@ -169,6 +289,10 @@ def main():
     print(text)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
+        f.write(text)
+    text = "\n".join(merge_rows(args, dev, lib, stream_gbs)) + "\n"
+    print(text)
+    with open(args.merge_out, "w") as f:
         f.write(text)
 
 
