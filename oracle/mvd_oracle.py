@@ -567,25 +567,29 @@ def planesweep_correlation_backward(feat_key, intrinsics_key, feat_sources, sour
     return dkey, dsrcs
 
 
-def fuse_views_backward(corrs, masks, scores, gfused):
+def fuse_views_backward(corrs, masks, scores, gfused, dtype=np.float64, out_dtype=F32):
     """VJP of fuse_views (learned_fusion.py:32-48) w.r.t. corrs[v] and scores[v]; masks and the fused mask are constants.
-    w = softmax_v(score) + 1e-9, u_v = w_v m_v, W = sum u, fused = fm * (sum c_v u_v) / (W + 1e-9)."""
+    w = softmax_v(score) + 1e-9, u_v = w_v m_v, W = sum u, fused = fm * (sum c_v u_v) / (W + 1e-9).
+    dtype: the precision every step is evaluated in (float32: the formula's own rounding error, for a test's tolerance);
+    out_dtype: that of the returned arrays."""
     V = len(corrs)
-    s = np.stack(scores, 0).astype(np.float64)
+    corrs, masks = [np.asarray(c, dtype) for c in corrs], [np.asarray(m, dtype) for m in masks]
+    tiny = dtype(1e-9)
+    s = np.stack(scores, 0).astype(dtype)
     e = np.exp(s - s.max(0, keepdims=True))
     p = e / e.sum(0, keepdims=True)  # softmax over views, (V,N,1,h,w)
-    u = [(p[v] + 1e-9) * masks[v] for v in range(V)]
+    u = [(p[v] + tiny) * masks[v] for v in range(V)]
     W = sum(u)
-    fm = (W != 0).astype(np.float64)
+    fm = (W != 0).astype(dtype)
     num = sum(c * x for c, x in zip(corrs, u))
-    den = W + 1e-9
-    g = gfused.astype(np.float64) * fm
-    dcorrs = [(g * u[v] / den).astype(F32) for v in range(V)]
+    den = W + tiny
+    g = gfused.astype(dtype) * fm
+    dcorrs = [(g * u[v] / den).astype(out_dtype) for v in range(V)]
     # d fused / d u_v = (c_v - num/den) / den ; u_v = (p_v + 1e-9) m_v ; p = softmax(score) over v, score broadcast over S
     du = [g * (corrs[v] - num / den) / den * masks[v] for v in range(V)]           # = d loss / d p_v, per (N,S,h,w)
     dp = np.stack([d.sum(1, keepdims=True) for d in du], 0)                        # scores are (N,1,h,w): sum over S
     dscore = p * (dp - (p * dp).sum(0, keepdims=True))
-    return dcorrs, [dscore[v].astype(F32) for v in range(V)]
+    return dcorrs, [dscore[v].astype(out_dtype) for v in range(V)]
 
 
 # =============================================================================================

@@ -1363,10 +1363,20 @@ class _SweepCorr(torch.autograd.Function):
         return tuple(out)
 
 
+K1_BACKWARD_CHANNELS = (64, 128, 192, 256)  # sweep_corr_backward_kernel<C / 64> (csrc/backward.hip)
+
+
 def sweep_corr_autograd(feat_key, feat_sources, K_key, K_sources, T_src2key, invdepths, corr_scale=None):
-    """Differentiable K1: returns (corrs[V], masks[V]); gradients to feat_key and feat_sources."""
+    """Differentiable K1: returns (corrs[V], masks[V]); gradients to feat_key and feat_sources.  The VJP kernel is built for
+    K1_BACKWARD_CHANNELS only: another channel count that the forward accepts (a multiple of 64 above 256) is refused here, before
+    any kernel runs, when a gradient will be asked for; without one it is computed as by sweep_corr."""
     srcs = views(feat_sources, "feat_sources")
     V = len(srcs)
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in [feat_key] + srcs):
+        C = feat_key.shape[1] if isinstance(feat_key, torch.Tensor) and feat_key.dim() == 4 else None
+        if C is not None and C % 64 == 0 and C not in K1_BACKWARD_CHANNELS:
+            raise ValueError(f"sweep_corr_autograd: feature channels C={C} have no backward kernel (supported with gradients: "
+                             f"{', '.join(map(str, K1_BACKWARD_CHANNELS))}); run it under torch.no_grad() or on detached features")
     outs = _SweepCorr.apply(K_key, invdepths, V, corr_scale, feat_key, *srcs, *views(K_sources, "intrinsics_sources", V),
                             *views(T_src2key, "source_to_key_transforms", V))
     return list(outs[:V]), list(outs[V:])

@@ -3,7 +3,12 @@
 (a) a float64 restatement of the three sweep reductions and of the warp-only sweep, local to this module, whose autograd
     gradients are pinned against the reference's own (tests/golden/g15_sweep_grads.npz).  The GPU tests
     (tests/test_hip_sweep_grads.py) use it as their checker on the shapes the reference was never run on;
-(b) the argument validation of the two C entry points, which runs before any GPU call;
+    The same for K1 (sweep_corr_restated: the warp-only gather, the dot product with the key, sampling mask x visibility), pinned
+    against g10_grads.npz and the oracle's VJP, with the cases of tests/test_hip_backward_shapes.py and the check that none of
+    their samples sits on a decision boundary of the float32 chain.  The restatements' dtype follows their leaves, so one
+    function gives the float64 reference and the float32 evaluation that measures the formula's own rounding;
+(b) the argument validation of the two C entry points, which runs before any GPU call, and sweep_corr_autograd's refusal of a
+    channel count without a backward kernel at the call;
 (c) the inference entries still refuse an input that requires grad (ops.inference_only).
 
 The restatement computes the sampling positions in float32 with the kernels' formulas (a fused multiply-add is taken as the
@@ -46,12 +51,12 @@ def reduce_positions(M, depth, h, w, pix_offset, stretch):
 
 def _gather4(src, cell_y, cell_x, wts):
     """src (B,C,hs,ws) float64 tensor; cell_y/x (B,D,h,w) integer top-left tap in the map padded by (1 before, 2 after); wts: four
-    (B,D,h,w) float32 weights (nw, ne, sw, se) -> (B,C,D,h,w) float64 samples, differentiable w.r.t. src."""
+    (B,D,h,w) float32 weights (nw, ne, sw, se) -> (B,C,D,h,w) samples in src's dtype, differentiable w.r.t. src."""
     P = torch.nn.functional.pad(src, (1, 2, 1, 2))
     out = []
     for b in range(src.shape[0]):
         y0, x0 = torch.from_numpy(cell_y[b].astype(np.int64)), torch.from_numpy(cell_x[b].astype(np.int64))
-        w4 = [torch.from_numpy(wk[b].astype(np.float64)) for wk in wts]
+        w4 = [torch.from_numpy(np.ascontiguousarray(wk[b], f32)).to(src.dtype) for wk in wts]
         out.append(P[b][:, y0, x0] * w4[0] + P[b][:, y0, x0 + 1] * w4[1] + P[b][:, y0 + 1, x0] * w4[2] + P[b][:, y0 + 1, x0 + 1] * w4[3])
     return torch.stack(out)
 
@@ -78,9 +83,11 @@ def sweep_reduce_restated(key, srcs, Ms, depth, mode, groups=1, pix_offset=0.0, 
     return s2 / N - (s1 / N) ** 2
 
 
-def warp_cells(K_key, K_src, T, invd, h, w, hs, ws):
-    """sweep_epipolar.h's grid chain in float32, one rounding per operation: K_* (N,3,3) relative intrinsics, T (N,4,4),
-    invd (1 or N, S) -> cell_y, cell_x (N,S,h,w), four tap weights (zero where out of bounds) and the 0/1 sampling mask."""
+def warp_chain(K_key, K_src, T, invd, h, w, hs, ws):
+    """sweep_epipolar.h's chain in float32, one rounding per operation: K_* (N,3,3) relative intrinsics, T (N,4,4), invd (1 or N, S)
+    or per key pixel (N,S,h,w) -> dict of (N,S,h,w) arrays: cell_y, cell_x, wts (four tap weights, zero where out of bounds), inb
+    (their sum), mask (the 0/1 sampling mask), visible (sweep_sample's visibility, bool) and the values it is decided on: k_inf,
+    z_pole (N,1,h,w) and zs."""
     Kk, Ks, T = np.asarray(K_key, f32), np.asarray(K_src, f32), np.asarray(T, f32)
     N = Kk.shape[0]
     c = lambda a: a.reshape(N, 1, 1, 1)
@@ -102,10 +109,17 @@ def warp_cells(K_key, K_src, T, invd, h, w, hs, ws):
     yc = (np.arange(h, dtype=f32) + f32(0.5))[None, None, :, None]
     u_inf, v_inf, k_inf = (Ea * xc + Eb * yc) + Ec, (Ef * xc + Eg * yc) + Eh, (Ej * xc + Ek * yc) + El
     invd = np.asarray(invd, f32)
-    ds = np.broadcast_to(invd, (N, invd.shape[1]))[:, :, None, None]
+    if invd.ndim == 4:  # per key pixel
+        assert invd.shape[0] == N and invd.shape[2:] == (h, w), invd.shape
+        ds = invd
+    else:
+        ds = np.broadcast_to(invd, (N, invd.shape[1]))[:, :, None, None]
     with np.errstate(all="ignore"):
         den = k_inf + Em * ds
         us, vs = (u_inf + Ee * ds) / den, (v_inf + Ei * ds) / den
+        zs = np.broadcast_to(f32(1) / ds, us.shape).astype(f32)
+        z_pole = (-(Em / k_inf)).astype(f32)
+        visible = (zs > 0) & (((k_inf > 0) & (zs > z_pole)) | ((k_inf < 0) & (zs < z_pole)) | ((k_inf == 0) & (Em > 0)))
 
     def fix(v):
         v = np.where(np.isinf(v), np.where(v > 0, f32(1e9), f32(-1e9)), v)
@@ -127,11 +141,19 @@ def warp_cells(K_key, K_src, T, invd, h, w, hs, ws):
     mask = np.where(inb < f32(0.9999), f32(0), f32(1)).astype(f32)
     cell_x = np.clip(x0, -1, ws - 1).astype(np.int64) + 1
     cell_y = np.clip(y0, -1, hs - 1).astype(np.int64) + 1
-    return cell_y, cell_x, wts, mask
+    all_in = (x0 >= 0) & (x1 <= ws - 1) & (y0 >= 0) & (y1 <= hs - 1)
+    return dict(cell_y=cell_y, cell_x=cell_x, wts=wts, inb=inb, all_in=all_in, mask=mask, visible=visible, k_inf=k_inf.astype(f32),
+                z_pole=z_pole, zs=zs)
+
+
+def warp_cells(K_key, K_src, T, invd, h, w, hs, ws):
+    """warp_chain's cell_y, cell_x (N,S,h,w), four tap weights, the 0/1 sampling mask and the visibility term (bool)."""
+    g = warp_chain(K_key, K_src, T, invd, h, w, hs, ws)
+    return g["cell_y"], g["cell_x"], g["wts"], g["mask"], g["visible"]
 
 
 def sweep_warp_restated(srcs, K_key, K_srcs, Ts, invd, key_size, normalize=False):
-    """PlanesweepCorrelation(warp_only=True): srcs float64 tensors (N,C,hs,ws) -> (warped[V] (N,S,C,h,w) float64, masks[V])."""
+    """PlanesweepCorrelation(warp_only=True): srcs tensors (N,C,hs,ws) -> (warped[V] (N,S,C,h,w) in their dtype, masks[V])."""
     h, w = key_size
     nrm = lambda x, dim: x / (torch.linalg.norm(x, dim=dim, keepdim=True) + 1e-9)
     warped, masks = [], []
@@ -139,23 +161,41 @@ def sweep_warp_restated(srcs, K_key, K_srcs, Ts, invd, key_size, normalize=False
         hs, ws = s.shape[-2:]
         if normalize == "before":
             s = nrm(s, 1)
-        cy, cx, wts, mask = warp_cells(K_key, Ks, T, invd, h, w, hs, ws)
+        cy, cx, wts, mask, _ = warp_cells(K_key, Ks, T, invd, h, w, hs, ws)
         x = _gather4(s, cy, cx, wts).transpose(1, 2)  # (N,S,C,h,w)
         if normalize is True or normalize == "after":
             x = nrm(x, 2)
-        warped.append(x * torch.from_numpy(mask.astype(np.float64)).unsqueeze(2))
+        warped.append(x * torch.from_numpy(mask).to(x.dtype).unsqueeze(2))
         masks.append(mask)
     return warped, masks
 
 
-def grads_of(outs, cots, inputs):
-    """autograd.grad of sum_i sum(outs[i] * cots[i]) w.r.t. inputs -> float32 arrays."""
-    loss = sum((o * torch.from_numpy(np.asarray(c, np.float64))).sum() for o, c in zip(outs, cots))
-    return [x.numpy().astype(f32) for x in torch.autograd.grad(loss, inputs)]
+def sweep_corr_restated(key, srcs, K_key, K_srcs, Ts, invd, corr_scale):
+    """PlanesweepCorrelation (K1): key (N,C,h,w), srcs V x (N,C,hs,ws) tensors -> (corrs[V] (N,S,h,w) in the leaves' dtype, masks[V]):
+    the warped sample's dot product with the key times corr_scale times the mask, which is sampling mask x visibility, a constant."""
+    h, w = key.shape[-2:]
+    k = key.unsqueeze(2)
+    corrs, masks = [], []
+    for s, Ks, T in zip(srcs, K_srcs, Ts):
+        cy, cx, wts, mask, visible = warp_cells(K_key, Ks, T, invd, h, w, *s.shape[-2:])
+        mask = mask * visible.astype(f32)
+        corrs.append((k * _gather4(s, cy, cx, wts)).sum(1) * corr_scale * torch.from_numpy(mask).to(key.dtype))
+        masks.append(mask)
+    return corrs, masks
+
+
+def grads_of(outs, cots, inputs, dtype=f32, retain=False):
+    """autograd.grad of sum_i sum(outs[i] * cots[i]) w.r.t. inputs -> arrays of `dtype`."""
+    loss = sum((o * torch.from_numpy(np.asarray(c, np.float64)).to(o.dtype)).sum() for o, c in zip(outs, cots))
+    return [x.numpy().astype(dtype) for x in torch.autograd.grad(loss, inputs, retain_graph=retain)]
 
 
 def leaf64(a):
     return torch.from_numpy(np.asarray(a, np.float64)).requires_grad_(True)
+
+
+def leaf32(a):
+    return torch.from_numpy(np.array(a, f32)).requires_grad_(True)
 
 
 def cvp_Ms(g):
@@ -236,6 +276,164 @@ def test_restated_warp_only_gradients_match_reference(name, norm):
         _close(got[v], gr[f"warp_{name}_dsrc{v}"], f"warp_{name}_dsrc{v}")
 
 
+# ------------------------------------------------------------------------------------------------ K1 and the shape sweep's cases
+# The cases of tests/test_hip_backward_shapes.py, built here so that their inputs are checked without a GPU.
+# K1: (N, C, h, w, hs, ws, S, V, inverse-depth mode, seed); warp-only: (N, C, hs, ws, (h, w), S, V, mode, seed).
+K1_CASES = [
+    (2, 128, 6, 7, 5, 9, 70, 2, "batched", 101),   # <2>, two passes, tail of 6, N = 2, source size differs
+    (1, 256, 5, 6, 5, 6, 130, 2, "shared", 102),   # <4>, three passes, tail of 2
+    (1, 192, 4, 9, 6, 7, 65, 1, "shared", 103),    # <3>, tail of 1
+    (2, 64, 3, 5, 3, 5, 64, 3, "batched", 104),    # exactly one full pass; 30 waves: the last block is partial
+    (1, 256, 4, 5, 4, 5, 256, 1, "shared", 105),   # the model's own C and S
+    (2, 64, 4, 5, 4, 5, 67, 2, "pixel", 106),      # per key pixel
+]
+WARP_CASES = [
+    (1, 65, 5, 6, (5, 6), 70, 2, "shared", 201),
+    (2, 100, 4, 7, (5, 6), 65, 1, "batched", 202),
+    (1, 130, 4, 5, (4, 5), 9, 2, "shared", 203),
+    (1, 192, 4, 5, (4, 5), 64, 1, "shared", 204),
+    (1, 256, 3, 5, (3, 5), 130, 1, "shared", 205),
+    (1, 1, 6, 7, (6, 7), 5, 1, "shared", 206),
+    (2, 16, 4, 5, (4, 5), 67, 2, "pixel", 207),
+]
+
+
+def one_hot_planes(S, warp_only=False):
+    """The cotangent supports of the one-hot cases, which make a dropped plane a 100 % error (K1: the cases with S = 67 and 130,
+    warp-only: S = 130): the last plane, the first plane of the second pass, and the two planes either side of the pass boundary
+    (a run that may share a cell across it)."""
+    return [(S - 1,), (64,), (63, 64)] if S in ((130,) if warp_only else (67, 130)) else []
+
+
+def sweep_case(N, C, h, w, hs, ws, S, V, mode, seed, with_key=True):
+    """Seeded inputs with the calibration of test_hip_shapes.test_sweep_corr_vs_oracle."""
+    from oracle import mvd_oracle as O
+    rng = np.random.default_rng(seed)
+    fk = rng.standard_normal((N, C, h, w)).astype(f32) if with_key else None
+    fs = [rng.standard_normal((N, C, hs, ws)).astype(f32) for _ in range(V)]
+    Kk = np.stack([np.array([[0.72, 0, 0.5], [0, 1.28, 0.5], [0, 0, 1]], f32)] * N)
+    Ks = [Kk * np.array([[1.0 + 0.05 * v], [1.0 - 0.03 * v], [1.0]], f32) for v in range(V)]
+    Ts = [np.stack([gc.synthetic_pose(rng, 0.08, 0.2) for _ in range(N)]) for _ in range(V)]
+    n = 1 if mode == "shared" else N
+    inv = O.compute_sampling_invdepths(np.full(n, 0.4, f32), np.linspace(100.0, 1000.0, n).astype(f32), S)
+    if mode == "pixel":
+        inv = (inv[:, :, None, None] * (1 + 0.05 * rng.uniform(-1, 1, (N, S, h, w)))).astype(f32)
+    return dict(fk=fk, fs=fs, Kk=Kk, Ks=Ks, Ts=Ts, inv=inv, key_size=(h, w))
+
+
+def k1_case(case):
+    return sweep_case(*case)
+
+
+def warp_case(case):
+    N, C, hs, ws, (h, w), S, V, mode, seed = case
+    return sweep_case(N, C, h, w, hs, ws, S, V, mode, seed, with_key=False)
+
+
+@pytest.mark.parametrize("case", K1_CASES + WARP_CASES, ids=str)
+def test_shape_sweep_inputs_are_off_the_decision_boundaries(case):
+    """No sample of a case sits where one float32 rounding decides a mask entry: the sampling mask's threshold (inb against 0.9999,
+    for the samples with a tap out of bounds; the others sum to 1), the sign of k_inf, and zs against the pole's depth.  Under this
+    condition the GPU tests demand masks EQUAL to the restated ones.  Every view of every one-hot plane keeps a live sample, so
+    that no one-hot case is vacuous."""
+    c = k1_case(case) if len(case) == 10 else warp_case(case)
+    (h, w), (hs, ws) = c["key_size"], c["fs"][0].shape[-2:]
+    S = c["inv"].shape[1]
+    for v, (Ks, T) in enumerate(zip(c["Ks"], c["Ts"])):
+        g = warp_chain(c["Kk"], Ks, T, c["inv"], h, w, hs, ws)
+        edge = ~g["all_in"]
+        d_inb = np.abs(g["inb"][edge] - f32(0.9999)).min() if edge.any() else np.inf
+        d_k = np.abs(g["k_inf"]).min()
+        d_z = (np.abs(g["zs"] - g["z_pole"]) / np.abs(g["z_pole"])).min()
+        print(f"{case} view {v}: |inb - 0.9999| >= {d_inb:.2e}, |k_inf| >= {d_k:.2e}, |zs - z_pole| / |z_pole| >= {d_z:.2e}")
+        assert d_inb > 1e-6 and d_k > 1e-6 and d_z > 1e-5
+        assert np.abs(g["inb"][g["all_in"]] - 1).max(initial=0) < 1e-5
+        live = g["mask"] * (g["visible"] if len(case) == 10 else 1)
+        for planes in one_hot_planes(S, warp_only=len(case) != 10):
+            assert all(live[:, s].any() for s in planes), (v, planes)
+
+
+# The g10 gradients are float32 autograd through the reference: sums of <= S x 4 = 32 products of magnitude <= ~3 per key element
+# (more per source element where samples crowd), each rounded to 6e-8 relative, and positions restated operation by operation.
+# A few 1e-6 absolute at most; measured 2.4e-7 on gradients of magnitude 1-2.
+K1_GOLDEN = dict(atol=5e-6, rtol=1e-5)
+
+
+@pytest.mark.parametrize("name,V", [("toy", 2), ("behind", 1)])
+def test_restated_sweep_corr_gradients_match_reference(name, V):
+    g = load_golden("g10_grads")
+    key, srcs = leaf64(gc.rng_array(1101, (1, 64, 12, 18))), [leaf64(gc.rng_array(1102 + i, (1, 64, 12, 18))) for i in range(V)]
+    K = g[f"k1_{name}_K"]
+    corrs, masks = sweep_corr_restated(key, srcs, K, [K] * V, [g[f"k1_{name}_T{v}"] for v in range(V)],
+                                       g[f"k1_{name}_invdepths"].reshape(1, -1), 1.0 / 8.0)
+    for v in range(V):
+        want = g[f"k1_{name}_corr{v}"]
+        print(f"k1_{name}_corr{v}: max |diff| {np.abs(corrs[v].detach().numpy() - want).max():.3e}, max |want| {np.abs(want).max():.3e}")
+        np.testing.assert_allclose(corrs[v].detach().numpy(), want, **K1_GOLDEN)
+    got = grads_of(corrs, [gc.rng_array(1110 + v, tuple(c.shape)) for v, c in enumerate(corrs)], [key] + srcs)
+    for a, k in zip(got, ["dkey"] + [f"dsrc{v}" for v in range(V)]):
+        want = g[f"k1_{name}_{k}"]
+        print(f"k1_{name}_{k}: max |diff| {np.abs(a - want).max():.3e}, max |want| {np.abs(want).max():.3e}")
+        np.testing.assert_allclose(a, want, err_msg=k, **K1_GOLDEN)
+
+
+def test_restated_sweep_corr_matches_oracle_backward():
+    """a shape no golden has: two batch elements with their own planes, source maps of another size than the key's.  The oracle
+    accumulates in float64 on float32 positions like the restatement; its corr_scale is 1/sqrt(C) rounded to float32 (6e-8)."""
+    from oracle import mvd_oracle as O
+    c = sweep_case(2, 64, 5, 6, 4, 7, 9, 2, "batched", 301)
+    key, srcs = leaf64(c["fk"]), [leaf64(f) for f in c["fs"]]
+    corrs, masks = sweep_corr_restated(key, srcs, c["Kk"], c["Ks"], c["Ts"], c["inv"], 1.0 / 8.0)
+    ref_c, ref_m, _ = O.planesweep_correlation(c["fk"], c["Kk"], c["fs"], c["Ts"], c["Ks"], sampling_invdepths=c["inv"])
+    for v in range(2):
+        assert np.array_equal(masks[v], ref_m[v]) and 0 < masks[v].mean() < 1
+        np.testing.assert_allclose(corrs[v].detach().numpy(), ref_c[v], atol=2e-5, rtol=1e-5)  # the oracle's forward sums in float32
+    rng = np.random.default_rng(302)
+    cots = [rng.standard_normal(tuple(x.shape)).astype(f32) for x in corrs]
+    got = grads_of(corrs, cots, [key] + srcs)
+    dkey, dsrcs = O.planesweep_correlation_backward(c["fk"], c["Kk"], c["fs"], c["Ts"], c["inv"], cots, c["Ks"])
+    for a, b, k in zip(got, [dkey] + dsrcs, ("dkey", "dsrc0", "dsrc1")):
+        print(f"{k}: max |diff| {np.abs(a - b).max():.3e}, max |want| {np.abs(b).max():.3e}")
+        np.testing.assert_allclose(a, b, err_msg=k, **K1_GOLDEN)
+
+
+def test_restated_per_pixel_invdepths_broadcast():
+    """per-pixel inverse depths (N,S,h,w) that are constant on each plane against the (N,S) path: the same values, whole and plane by
+    plane (this pins warp_chain's per-pixel indexing: batch element, plane and pixel each land on their own axis)"""
+    c = sweep_case(2, 64, 4, 5, 3, 6, 5, 2, "batched", 303)
+    N, S, (h, w) = 2, 5, c["key_size"]
+    pp = np.ascontiguousarray(np.broadcast_to(c["inv"][:, :, None, None], (N, S, h, w)))
+    rng = np.random.default_rng(304)
+    cots = [rng.standard_normal((N, S, h, w)).astype(f32) for _ in range(2)]
+
+    def run(inv, cot):
+        key, srcs = leaf64(c["fk"]), [leaf64(f) for f in c["fs"]]
+        corrs, masks = sweep_corr_restated(key, srcs, c["Kk"], c["Ks"], c["Ts"], inv, 0.125)
+        return [x.detach().numpy() for x in corrs], masks, grads_of(corrs, cot, [key] + srcs, dtype=np.float64)
+
+    corr_pp, mask_pp, grad_pp = run(pp, cots)
+    corr_ns, mask_ns, grad_ns = run(c["inv"], cots)
+    for a, b in zip(corr_pp + mask_pp + grad_pp, corr_ns + mask_ns + grad_ns):
+        assert np.array_equal(a, b)
+    total = [0, 0, 0]
+    for s in range(S):
+        corr_s, mask_s, grad_s = run(c["inv"][:, s:s + 1], [x[:, s:s + 1] for x in cots])
+        for v in range(2):
+            assert np.array_equal(mask_s[v][:, 0], mask_pp[v][:, s])
+            np.testing.assert_allclose(corr_s[v][:, 0], corr_pp[v][:, s], atol=1e-12, rtol=1e-12)  # float64 sums in another order
+        total = [t + x for t, x in zip(total, grad_s)]
+    for a, b in zip(total, grad_pp):
+        np.testing.assert_allclose(a, b, atol=1e-12, rtol=1e-12)
+    # a per-pixel map that is NOT constant moves each pixel's samples on its own
+    live = np.argwhere((mask_pp[0] == 1) & (np.arange(N).reshape(N, 1, 1, 1) == 1))
+    at = tuple(live[len(live) // 2])  # a live sample of view 0 in the second batch element
+    pp2 = pp.copy()
+    pp2[at] *= f32(1.5)
+    corr2 = run(pp2, cots)[0]
+    changed = [np.argwhere(a != b) for a, b in zip(corr2, corr_pp)]
+    assert all((ch == at).all() for ch in changed) and len(changed[0]) == 1
+
+
 # ------------------------------------------------------------------------------------------------ (b) validation, no GPU
 def _arr(n, value=0x1000):
     return (ctypes.c_void_p * n)(*([value] * n))
@@ -292,6 +490,25 @@ def test_sweep_warp_backward_validates_before_any_gpu_call():
     assert _warp_backward(lib, mode=3) == 1 and "invdepth_mode 3" in err()
     assert _warp_backward(lib, C=0) == 1 and _warp_backward(lib, C=257) == 1 and "C=257" in err()
     assert _warp_backward(lib, V=0) == 1 and _warp_backward(lib, S=0) == 1 and "bad dimensions" in err()
+
+
+def test_sweep_corr_autograd_refuses_unsupported_channels_before_any_gpu_call():
+    """C = 320 is a forward-only channel count: asked for a gradient, sweep_corr_autograd raises when it is CALLED (CPU tensors
+    reach the check, so nothing has touched a device), not from inside backward(); without a gradient to come it goes on to the
+    forward (which refuses the CPU tensors)"""
+    from robustmvd_amd import ops
+    K, Tm, inv = torch.eye(3)[None], torch.eye(4)[None], torch.ones(1, 4)
+    for C in (320, 512):
+        key, src = torch.zeros(1, C, 4, 4, requires_grad=True), torch.zeros(1, C, 4, 4)
+        for a, b in ((key, src), (src, key)):
+            with pytest.raises(ValueError, match=f"C={C}.*64, 128, 192, 256"):
+                ops.sweep_corr_autograd(a, [b], K, [K], [Tm], inv)
+        with torch.no_grad(), pytest.raises(ValueError, match="cuda"):
+            ops.sweep_corr_autograd(key, [src], K, [K], [Tm], inv)
+        with pytest.raises(ValueError, match="cuda"):
+            ops.sweep_corr_autograd(src, [src], K, [K], [Tm], inv)
+    with pytest.raises(ValueError, match="cuda"):  # a supported count passes the check
+        ops.sweep_corr_autograd(torch.zeros(1, 256, 4, 4, requires_grad=True), [torch.zeros(1, 256, 4, 4)], K, [K], [Tm], inv)
 
 
 # ------------------------------------------------------------------------------------------------ (c) inference entries
