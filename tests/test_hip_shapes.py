@@ -58,13 +58,18 @@ def test_warp_variance_vs_oracle(B, C, h, w, D, V, channels_last, dev):
     np.testing.assert_allclose(got.cpu().numpy(), ref, atol=ATOL, rtol=RTOL)
 
 
-def test_warp_variance_wide_baseline_vs_oracle(dev):
-    """large rotations / translations: most samples leave the image, some planes go behind a source camera"""
+@pytest.mark.parametrize("channels_last", [False, True])
+def test_warp_variance_wide_baseline_vs_oracle(channels_last, dev):
+    """large rotations / translations: most samples leave the image, some planes go behind a source camera (the gather kernel, and
+    channel-last the tile kernel, every chunk of which sees a probe corner with Z <= 0).  The third view's samples all leave the
+    map; tests/test_hip_k3_forward.py holds a wide-baseline case in which every view takes part."""
     from robustmvd_amd import ops
     feats, projs, key_inv, depth = mvs_inputs(1, 32, 24, 40, 8, 3, seed=77, rot=0.7, trans=0.8, dmin=0.2, dmax=3.0)
     ref = CO.warp_variance(feats[0], feats[1:], projs, key_inv, depth)
     got = ops.warp_variance(T(feats[0], dev), [T(f, dev) for f in feats[1:]], [T(p, dev) for p in projs], T(key_inv, dev),
-                            T(depth, dev))
+                            T(depth, dev), channels_last=channels_last)
+    if channels_last:
+        got = got.permute(0, 4, 1, 2, 3)
     np.testing.assert_allclose(got.cpu().numpy(), ref, atol=ATOL, rtol=RTOL)
 
 
@@ -72,7 +77,11 @@ def test_warp_variance_wide_baseline_vs_oracle(dev):
                                                        (1, 256, 17, 16, 17, 16, 33, 2, False),
                                                        (1, 64, 9, 14, 9, 14, 5, 20, False), (2, 64, 6, 9, 7, 8, 4, 32, True),
                                                        # C above 256: the cells form (sweep_corr_kernel)
-                                                       (1, 320, 7, 12, 7, 12, 6, 2, False)])
+                                                       (1, 320, 7, 12, 7, 12, 6, 2, False),
+                                                       # its other instantiations <6>, <7>, <8>, and <5> with S = 70: two passes of the
+                                                       # lane = plane loop, the second with 58 dead lanes
+                                                       (1, 384, 5, 6, 5, 6, 6, 1, False), (1, 448, 5, 6, 5, 6, 6, 1, False),
+                                                       (1, 512, 5, 6, 5, 6, 6, 1, False), (1, 320, 7, 12, 7, 12, 70, 2, False)])
 def test_sweep_corr_vs_oracle(N, C, h, w, hs, ws, S, V, batched, dev):
     from robustmvd_amd import ops
     rng = np.random.default_rng(N * 100 + C)
