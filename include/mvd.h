@@ -719,6 +719,48 @@ int mvd_voxel_reduce_f32(const long long* keys, const long long* perm, const flo
                          float* xyz, float* rgb, int* counts, long long* num_voxels, void* workspace, size_t workspace_bytes,
                          mvd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * TSDF volume: the views' depth maps averaged into a truncated signed distance volume, and its surface as a triangle mesh.  The
+ * reference has NO counterpart: the definition is robustmvd_amd/tsdf.py (its docstring, integrate_numpy, extract_numpy) and DESIGN.md.
+ *
+ * Volume (nx,ny,nz), nx ny nz < 2^31: voxel (i,j,k) sits at origin + voxel (i,j,k).  tsdf and weight (nz,ny,nx) float32, x fastest;
+ * color NULL or (3,nz,ny,nx) planar; all three 16-byte aligned, dense (no padding of the rows), zero before the first view.
+ *
+ * mvd_tsdf_integrate_f32 applies V <= MVD_MAX_VIEWS views of one size (H,W >= 1) in order, in one launch.  depth: host array of V
+ * device pointers to (H,W) maps; weight_maps: NULL (every pixel weighs 1) or V maps (H,W); images: NULL or V planar (3,H,W) maps,
+ * read only when color is not NULL.  matrices (V,12) on the device, row-major 3x4, composed by the host in float64:
+ * M = K T[:3] [[voxel I, origin], [0, 1]] with K the intrinsics and T the world-to-view pose, so that (Qx,Qy,Qz) = M (i,j,k,1).
+ * Per voxel and view, skipping the view at the first condition that fails:  Qz > 0;  px = rint(Qx / Qz), py = rint(Qy / Qz), half to
+ * even, with 0 <= px <= W-1 and 0 <= py <= H-1;  dm = depth[py,px] and wm = weight_maps[py,px] both finite and > 0;
+ * sdf = dm - Qz >= -trunc.  Then f = min(1, sdf / trunc);  W' = W + wm;  F' = (F W + f wm) / W';  C' = (C W + c wm) / W' per channel;
+ * W' = min(W', max_weight) when max_weight > 0 (<= 0: no cap).  (The kernel forms Qx / Qz and sdf / trunc with a reciprocal.)
+ * A voxel that no view updates keeps its bits.  V views in one call give the bits of V calls of one view.  No atomics. */
+int mvd_tsdf_integrate_f32(float* tsdf, float* weight, float* color, int nx, int ny, int nz, const float* const* depth,
+                           const float* const* weight_maps, const float* const* images, const float* matrices, int V, int H, int W,
+                           float trunc, float max_weight, mvd_stream_t stream);
+
+/* Marching tetrahedra on the Kuhn subdivision.  A voxel is observed when weight >= min_weight and inside when tsdf < 0 (0 counts as
+ * outside).  Edge kinds 0..6 run from the owner voxel p to p + (1,0,0), (0,1,0), (0,0,1), (1,1,0), (1,0,1), (0,1,1), (1,1,1).  An edge
+ * carries a vertex iff both ends are in the grid and observed and exactly one is inside: t = Fa / (Fa - Fb) with a the owner,
+ * position = origin + voxel (p + t delta), colour = Ca + t (Cb - Ca); vertices are ordered by (owner's linear index (k ny + j) nx + i,
+ * kind).  A cell whose 8 corners are observed is cut into 6 tetrahedra, v0 = 0, v1 = e_a, v2 = e_a + e_b, v3 = (1,1,1) for the
+ * permutations (a,b,c) of (0,1,2) in lexicographic order; its triangles, their vertex order and orientation (normals point from
+ * inside to outside) are tsdf.py's tri_table(), compiled in as csrc/tsdf_tables.h; triangles are ordered by (cell's linear index,
+ * tetrahedron, slot).  Vertices that no triangle references (on edges none of whose cells is fully observed) stay.
+ *
+ * One entry, two uses.  With vertices == NULL (then triangles and colors are NULL too) it classifies and counts only.  With them it
+ * also writes vertices (M,3), colors (M,3) (NULL, or with color) and triangles (T,3) int32: a slot at or past max_vertices /
+ * max_triangles (both <= 2^31 - 1) is not written.  counts (device, 16-byte aligned) always receives the true M and T, two int64, exact
+ * while each is below 2^32: the caller reads them (one 16-byte copy), refuses 2^31 and more, and allocates.  classified != 0: the
+ * workspace still holds the classification of an earlier call on this volume with this min_weight, and it is not formed again.
+ * workspace: mvd_tsdf_extract_workspace_bytes(nx, ny, nz), 256-byte aligned.  No atomic decides a position: two calls give the same
+ * bits. */
+size_t mvd_tsdf_extract_workspace_bytes(int nx, int ny, int nz);
+int mvd_tsdf_extract_f32(const float* tsdf, const float* weight, const float* color, int nx, int ny, int nz, float origin_x,
+                         float origin_y, float origin_z, float voxel, float min_weight, int classified, float* vertices, float* colors,
+                         int* triangles, long long max_vertices, long long max_triangles, long long* counts, void* workspace,
+                         size_t workspace_bytes, mvd_stream_t stream);
+
 /* layout helpers used at the operator-level boundary (reference tensors are NCHW / NCDHW) */
 int mvd_nchw_to_nhwc_f32(const float* src, float* dst, int N, int C, long long HW, mvd_stream_t stream);
 int mvd_nhwc_to_nchw_f32(const float* src, float* dst, int N, int C, long long HW, mvd_stream_t stream);

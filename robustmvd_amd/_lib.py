@@ -164,6 +164,13 @@ SIGNATURES = {
     "mvd_voxel_reduce_workspace_bytes": (_sz, [ctypes.c_longlong]),
     "mvd_voxel_reduce_f32": (_i, [ctypes.c_void_p] * 2 + [_c_float_p] * 2 + [ctypes.c_longlong, _c_float_p, _c_float_p]
                              + [ctypes.c_void_p] * 3 + [_sz, ctypes.c_void_p]),
+    "mvd_tsdf_integrate_f32": (_i, [_c_float_p] * 3 + [_i] * 3 + [_pp] * 3 + [_c_float_p, _i, _i, _i, ctypes.c_float, ctypes.c_float,
+                                                                            ctypes.c_void_p]),
+    "mvd_tsdf_extract_workspace_bytes": (_sz, [_i] * 3),
+    "mvd_tsdf_extract_f32": (_i, [_c_float_p] * 3 + [_i] * 3 + [ctypes.c_float] * 5 + [_i, _c_float_p, _c_float_p, ctypes.c_void_p,
+                                                                                      ctypes.c_longlong, ctypes.c_longlong,
+                                                                                      ctypes.c_void_p, ctypes.c_void_p, _sz,
+                                                                                      ctypes.c_void_p]),
 }
 MVD_CLOUD_MAX_THRESHOLDS = 8
 

@@ -281,15 +281,17 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def read_ply(path, normals=False):
+def read_ply(path, normals=False, faces=False):
     """-> (points (n,3) float32, colors (n,3) float32 in 0..255 or None): the counterpart of depth_fusion.write_ply.  Reads ASCII and
     binary little-endian files whose first element is `vertex`; x / y / z may be float or double; uchar red / green / blue are the
     colours when all three are there; other scalar vertex properties and later elements (faces) are skipped.
-    normals=True -> (points, colors, normals (n,3) float32 or None): nx / ny / nz, float or double, when all three are there."""
+    normals=True -> (points, colors, normals (n,3) float32 or None): nx / ny / nz, float or double, when all three are there.
+    faces=True appends faces (T,3) int32 or None to the result: the second element where it is `face` with the one property
+    `list <count type> <index type> vertex_indices` (or vertex_index), every face a triangle."""
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError(f"{path}: not a PLY file")
-        fmt, count, props, elements = None, None, [], 0
+        fmt, count, props, elements, face_count, face_list = None, None, [], 0, None, None
         while True:
             line = f.readline()
             if not line:
@@ -307,6 +309,13 @@ def read_ply(path, normals=False):
                     if w[1] != "vertex":
                         raise ValueError(f"{path}: the first element is {w[1]!r}, expected 'vertex'")
                     count = int(w[2])
+                elif elements == 2 and w[1] == "face":
+                    face_count = int(w[2])
+            elif w[0] == "property" and elements == 2 and face_count is not None:
+                if face_list is not None or len(w) != 5 or w[1] != "list" or w[2] not in _PLY_TYPES or w[3] not in _PLY_TYPES:
+                    face_list = ()  # not the one list property: no faces to read
+                else:
+                    face_list = (_PLY_TYPES[w[2]], _PLY_TYPES[w[3]])
             elif w[0] == "property" and elements == 1:
                 if w[1] == "list" or w[1] not in _PLY_TYPES:
                     raise ValueError(f"{path}: unsupported vertex property {' '.join(w[1:])!r}")
@@ -316,8 +325,16 @@ def read_ply(path, normals=False):
         names = [n for n, _ in props]
         if len(set(names)) != len(names) or not all(a in names for a in "xyz"):
             raise ValueError(f"{path}: vertex properties {names} must hold x, y, z once each")
+        want_faces = faces and bool(face_list)
+        tri = None
         if fmt == "ascii":
-            rows = np.loadtxt(f, dtype=np.float64, max_rows=count, ndmin=2) if count else np.zeros((0, len(props)))
+            lines = [ln for ln in f.read().decode("ascii", errors="replace").splitlines() if ln.strip()]
+            rows = np.loadtxt(lines[:count], dtype=np.float64, ndmin=2) if count else np.zeros((0, len(props)))
+            if want_faces:
+                tri = np.loadtxt(lines[count:count + face_count], dtype=np.int64, ndmin=2) if face_count else np.zeros((0, 4), np.int64)
+                if tri.shape != (face_count, 4) or (tri[:, 0] != 3).any():
+                    raise ValueError(f"{path}: expected {face_count} triangles")
+                tri = tri[:, 1:].astype(np.int32)
             if rows.shape != (count, len(props)):
                 raise ValueError(f"{path}: expected {count} vertices of {len(props)} values, got {rows.shape}")
             column = lambda name: rows[:, names.index(name)]
@@ -327,11 +344,18 @@ def read_ply(path, normals=False):
             if len(rec) != count:
                 raise ValueError(f"{path}: {len(rec)} of {count} vertices")
             column = lambda name: rec[name]
+            if want_faces:
+                ft = np.dtype([("n", "<" + face_list[0]), ("v", "<" + face_list[1], (3,))])
+                frec = np.frombuffer(f.read(face_count * ft.itemsize), dtype=ft)
+                if len(frec) != face_count or (frec["n"] != 3).any():
+                    raise ValueError(f"{path}: expected {face_count} triangles")
+                tri = frec["v"].astype(np.int32)
     points = np.stack([column(a) for a in "xyz"], axis=1).astype(np.float32)
     colors = None
     if all(c in names and dict(props)[c] == "u1" for c in ("red", "green", "blue")):
         colors = np.stack([column(c) for c in ("red", "green", "blue")], axis=1).astype(np.float32)
-    if not normals:
-        return points, colors
-    have = all(c in names and dict(props)[c] in ("f4", "f8") for c in ("nx", "ny", "nz"))
-    return points, colors, np.stack([column(c) for c in ("nx", "ny", "nz")], axis=1).astype(np.float32) if have else None
+    out = (points, colors)
+    if normals:
+        have = all(c in names and dict(props)[c] in ("f4", "f8") for c in ("nx", "ny", "nz"))
+        out += (np.stack([column(c) for c in ("nx", "ny", "nz")], axis=1).astype(np.float32) if have else None,)
+    return out + (tri,) if faces else out

@@ -278,9 +278,10 @@ def merge_numpy(depths, Ks, Ts, sources=None, uncertainties=None, images=None, n
     return out
 
 
-def write_ply(path, points, colors=None, normals=None):
+def write_ply(path, points, colors=None, normals=None, faces=None):
     """Binary little-endian PLY: float32 x y z, with normals float32 nx ny nz, and with colors uchar red green blue.  colors: (M,3)
-    in 0..255 (rounded and clipped)."""
+    in 0..255 (rounded and clipped).  faces: (T,3) vertex indices (a Mesh's triangles), written as `element face` with
+    `property list uchar int vertex_indices`."""
     pts = np.asarray(_to_numpy(points), dtype="<f4").reshape(-1, 3)
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     if normals is not None:
@@ -305,10 +306,19 @@ def write_ply(path, points, colors=None, normals=None):
         header += ["property float nx", "property float ny", "property float nz"]
     if colors is not None:
         header += ["property uchar red", "property uchar green", "property uchar blue"]
+    if faces is not None:
+        tri = np.asarray(_to_numpy(faces)).reshape(-1, 3)
+        if len(tri) and (tri.min() < 0 or tri.max() >= len(pts)):
+            raise ValueError(f"faces index outside the {len(pts)} points")
+        frec = np.empty(len(tri), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+        frec["n"], frec["v"] = 3, tri
+        header += [f"element face {len(tri)}", "property list uchar int vertex_indices"]
     header.append("end_header")
     with open(path, "wb") as f:
         f.write(("\n".join(header) + "\n").encode("ascii"))
         f.write(rec.tobytes())
+        if faces is not None:
+            f.write(frec.tobytes())
 
 
 def _is_tensor(a):

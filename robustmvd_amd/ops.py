@@ -856,6 +856,80 @@ def compact_points(mask, depth, backproject, image=None, count=None, out=None, n
     return xyz, rgb, count, nrm_out
 
 
+def _tsdf_state(tsdf, weight, color, writable):
+    """The state of a TSDF volume as the kernels take it: float32, contiguous, on one GPU; where it is written, as it is (never a
+    converted or contiguous copy).  -> (tsdf, weight, color or None, (nx, ny, nz))."""
+    convert = not writable
+    f = L.as_dtype(torch.float32, convert, tsdf, "tsdf")
+    if f.dim() != 3:
+        raise ValueError(f"tsdf must be (nz,ny,nx), got {tuple(f.shape)}")
+    if f.numel() == 0 or f.numel() >= 2 ** 31:
+        raise ValueError(f"tsdf {tuple(f.shape)}: nx ny nz must be in 1 .. 2^31 - 1")
+    w = L.as_dtype(torch.float32, convert, weight, "weight", tuple(f.shape), f.device)
+    c = None if color is None else L.as_dtype(torch.float32, convert, color, "color", (3,) + tuple(f.shape), f.device)
+    if writable:
+        for name, t in (("tsdf", tsdf), ("weight", weight), ("color", color)):
+            if t is not None and not t.is_contiguous():
+                raise ValueError(f"{name}: must be contiguous (it is updated in place)")
+    nz, ny, nx = f.shape
+    return f, w, c, (nx, ny, nz)
+
+
+@inference_only
+def tsdf_integrate(tsdf, weight, color, depths, matrices, trunc, max_weight=None, weights=None, images=None):
+    """Integrates V <= 32 depth maps of one size into a TSDF volume IN PLACE, in list order and in one launch (include/mvd.h:
+    mvd_tsdf_integrate_f32; tsdf.integrate_numpy is the definition).  tsdf, weight (nz,ny,nx) and color (3,nz,ny,nx) or None:
+    contiguous float32.  depths: V x (H,W); matrices (V,12): tsdf.compose_matrix's rows; weights: V x (H,W) per-pixel weights (any
+    dtype, taken as float32) or None; images: V x (3,H,W), read only when the volume has colour.  max_weight None: no cap."""
+    f, w, c, (nx, ny, nz) = _tsdf_state(tsdf, weight, color, writable=True)
+    dev = f.device
+    depths = views(depths, "depths")
+    V = len(depths)
+    d0 = L.as_f32(depths[0], "depths[0]", device=dev)
+    if d0.dim() != 2 or d0.numel() == 0:
+        raise ValueError(f"depths[0] must be (H,W) with H, W >= 1, got {tuple(d0.shape)}")
+    H, W = d0.shape
+    ds = [d0] + [L.as_f32(d, f"depths[{i + 1}]", (H, W), dev) for i, d in enumerate(depths[1:])]
+    mats = L.as_f32(matrices, "matrices", (V, 12), dev)
+    ws = None if weights is None else [L.as_f32(m, f"weights[{i}]", (H, W), dev) for i, m in enumerate(views(weights, "weights", V))]
+    ims = None
+    if images is not None and c is not None:
+        ims = [L.as_f32(im, f"images[{i}]", (3, H, W), dev) for i, im in enumerate(views(images, "images", V))]
+    if not float(trunc) > 0:
+        raise ValueError(f"trunc must be positive, got {trunc}")
+    if max_weight is not None and not float(max_weight) > 0:
+        raise ValueError(f"max_weight must be positive, got {max_weight}")
+    call("mvd_tsdf_integrate_f32", dev, f, w, c, nx, ny, nz, ds, ws, ims, mats, V, H, W, float(trunc),
+         0.0 if max_weight is None else float(max_weight))
+
+
+@inference_only
+def tsdf_extract(tsdf, weight, color=None, origin=(0.0, 0.0, 0.0), voxel=1.0, min_weight=1.0):
+    """The surface of a TSDF volume as a triangle mesh (include/mvd.h: mvd_tsdf_extract_f32; tsdf.extract_numpy is the definition).
+    Returns (vertices (M,3) float32, triangles (T,3) int32, colors (M,3) float32 or None) at their exact sizes: the volume is
+    classified and counted, M and T are read (the call's one synchronisation, 16 bytes), and the second call writes the mesh from
+    the classification the workspace still holds."""
+    f, w, c, (nx, ny, nz) = _tsdf_state(tsdf, weight, color, writable=False)
+    dev = f.device
+    o = [float(a) for a in origin]
+    if len(o) != 3:
+        raise ValueError(f"origin must hold 3 values, got {len(o)}")
+    nbytes = L.load().mvd_tsdf_extract_workspace_bytes(nx, ny, nz)
+    ws = workspace(nbytes, dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    head = (f, w, c, nx, ny, nz, o[0], o[1], o[2], float(voxel), float(min_weight))
+    call("mvd_tsdf_extract_f32", dev, *head, 0, None, None, None, 0, 0, counts, ws, int(nbytes))
+    M, T = (int(n) for n in counts.tolist())
+    if M >= 2 ** 31 or T >= 2 ** 31:
+        raise ValueError(f"the mesh has {M} vertices and {T} triangles: both must be below 2^31")
+    vertices = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    triangles = torch.empty((T, 3), dtype=torch.int32, device=dev)
+    colors = torch.empty((M, 3), dtype=torch.float32, device=dev) if c is not None else None
+    if M:
+        call("mvd_tsdf_extract_f32", dev, *head, 1, vertices, colors, triangles, M, T, counts, ws, int(nbytes))
+    return vertices, triangles, colors
+
+
 CLOUD_INDEX_LIMIT = (1 << 21) - 1  # a cell or voxel index is in [0, 2^21 - 1): the all-ones key is the invalid points' own
 CLOUD_CELL_MARGIN = 1.0 + 2.0 ** -10  # cell edge = max_dist * margin (csrc/cloud_eval.hip: why 27 cells are enough)
 
