@@ -373,6 +373,16 @@ size_t mvd_conv2d_head_tile_count(int B, int H, int W);
 int mvd_conv2d_head_f32(const float* image, const float* w0, const float* scale0, const float* shift0, const float* w1,
                         const float* scale1, const float* shift1, float* y, float* tile_absmax, int B, int H, int W,
                         mvd_stream_t stream);
+/* The same pair with conv1 on the fp16 matrix instruction: conv0 as above (fp32, vector ALU), its outputs kept in LDS as two fp16
+ *   terms under a per-tile power-of-two scale (max |conv0| over the finite values of the workgroup's patch), conv1's weights as two
+ *   fp16 terms under a per-channel power of two, fp32 accumulation: fp32-grade for inputs of any uniform magnitude.
+ *   w1 (8,8,3,3): conv1's Conv2d weight as it is; mvd_pack_conv2d_head_split_weights packs it once per model into
+ *   mvd_conv2d_head_split_packed_bytes() bytes (16-byte aligned).  Everything else as mvd_conv2d_head_f32. */
+size_t mvd_conv2d_head_split_packed_bytes(void);
+int mvd_pack_conv2d_head_split_weights(const float* w1, void* packed, mvd_stream_t stream);
+int mvd_conv2d_head_split_f32(const float* image, const float* w0, const float* scale0, const float* shift0, const void* w1_packed,
+                              const float* scale1, const float* shift1, float* y, float* tile_absmax, int B, int H, int W,
+                              mvd_stream_t stream);
 
 /* K5 — replaces F.softmax + depth_regression + the 4-bin confidence of MVSNet.forward
  *   rmvd/models/mvsnet.py:139-160, rmvd/models/blocks/utils.py:271-274.

@@ -100,6 +100,9 @@ SIGNATURES = {
                                + [ctypes.c_void_p]),
     "mvd_conv2d_head_tile_count": (_sz, [_i] * 3),
     "mvd_conv2d_head_f32": (_i, [_c_float_p] * 9 + [_i] * 3 + [ctypes.c_void_p]),
+    "mvd_conv2d_head_split_packed_bytes": (_sz, []),
+    "mvd_pack_conv2d_head_split_weights": (_i, [_c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mvd_conv2d_head_split_f32": (_i, [_c_float_p] * 4 + [ctypes.c_void_p] + [_c_float_p] * 4 + [_i] * 3 + [ctypes.c_void_p]),
     "mvd_conv2d_bn_relu_absmax_f32": (_i, [_c_float_p, _i, _c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, _i] + [_i] * 8
                                       + [ctypes.c_void_p]),
     "mvd_softmax_regress_f32": (_i, [_c_float_p, _c_float_p, _i, _i, _i, _i, _c_float_p, _c_float_p, ctypes.c_void_p]),

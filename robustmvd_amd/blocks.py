@@ -200,11 +200,12 @@ def fold_bn(bn):
 class FeatureNetWeights:
     """What FeatureNet._prepare packs.  layers: conv0 .. conv6 and `feature` as ops.conv2d_bn_relu's arguments
     (packed, cin, cout, k, stride, scale, shift, relu), also read as pk[i].  With split_layers, split: conv2 .. `feature` as
-    (SplitConv2dWeights, relu) for ops.conv2d_split, and head: ops.conv2d_head's (w0, scale0, shift0, w1, scale1, shift1)."""
-    __slots__ = ("layers", "split", "head")
+    (SplitConv2dWeights, relu) for ops.conv2d_split, head: ops.conv2d_head's (w0, scale0, shift0, w1, scale1, shift1), and
+    head_w1: conv1's weight packed for ops.conv2d_head_split (it takes w1's place in head)."""
+    __slots__ = ("layers", "split", "head", "head_w1")
 
     def __init__(self):
-        self.layers, self.split, self.head = [], [], ()
+        self.layers, self.split, self.head, self.head_w1 = [], [], (), None
 
     def __getitem__(self, i):
         return self.layers[i]
@@ -227,6 +228,7 @@ class FeatureNet(nn.Module):
         self.inplanes = 32
         self.split_layers = bool(split_layers)
         self.fused_head = True  # with split_layers: conv0 and conv1 as one launch (False: two launches of the fp32-MFMA kernel)
+        self.head_split = True  # with fused_head: conv1 of that launch on the fp16 matrix instruction (False: both layers fp32, vector ALU)
         for i, s in enumerate(self.SPEC):
             setattr(self, f"conv{i}", ConvBnReLU(*s))
         self.feature = nn.Conv2d(32, 32, 3, 1, 1)
@@ -256,6 +258,7 @@ class FeatureNet(nn.Module):
             for i in range(2):
                 _, _, _, _, _, scale, shift, _ = pk.layers[i]
                 pk.head += (getattr(self, f"conv{i}").conv.weight.detach().permute(2, 3, 1, 0).contiguous(), scale, shift)
+            pk.head_w1 = ops.pack_conv2d_head_weights_split(self.conv1.conv.weight.detach())
         self._packed, self._packed_key = pk, key
         return pk
 
@@ -274,7 +277,10 @@ class FeatureNet(nn.Module):
             return (x, ops.absmax(x)) if return_absmax else x
         slots = torch.zeros(8, dtype=torch.float32, device=x.device)  # max-|y| slots of the layers, raised by their producers
         if self.fused_head:  # the 8-channel full-resolution intermediate never leaves the chip; max |conv1| from per-tile maxima
-            x, a_in = ops.conv2d_head(x, *pk.head, return_absmax=True)
+            if self.head_split:
+                x, a_in = ops.conv2d_head_split(x, *pk.head[:3], pk.head_w1, *pk.head[4:], return_absmax=True)
+            else:
+                x, a_in = ops.conv2d_head(x, *pk.head, return_absmax=True)
         else:
             for w, cin, cout, k, stride, scale, shift, relu in pk.layers[:2]:
                 x = ops.conv2d_bn_relu(x, w, cin, cout, k, stride, scale, shift, relu=relu)

@@ -1217,12 +1217,147 @@ static int launch_deconv_all(const ConvParams& p0, hipStream_t st) {
 }
 
 // `prob`: 3x3x3, 8 -> 1 channels, stride 1 (mvsnet_components.py:109).  One GEMM row of 16 would be used on
-// the matrix cores, so this layer runs on the vector ALU: one lane per output voxel, the three input planes
-// of a 4 x 64 tile resident in LDS (48-B pixels: conflict-free ds_read_b128 across consecutive columns), the
-// 216 weights through the scalar cache.  packed weights here are [tap 27][cin 8].
+// the matrix cores, so this layer runs on the vector ALU: one lane per output voxel, two input planes of a
+// 4 x 64 tile in LDS, the current one and the next (48-B pixels: conflict-free ds_read_b128 across consecutive
+// columns), the 216 weights through the scalar cache.  packed weights here are [tap 27][cin 8].
 constexpr int C8_DZ = 16;  // output planes a workgroup of the 8 -> 1 kernel walks
 constexpr int C8_TW = 62;  // output columns per tile row: 64 slab columns (one per lane) minus the two halo columns
+
+// the partial sums of one output plane that is in flight: per kw two chains of packed FMAs over the channel pairs
+// (0,1),(4,5) and (2,3),(6,7) as they sit in the 128-bit LDS reads
+struct C8Acc {
+    f32x2 a[3], b[3];
+};
+
 __global__ void __launch_bounds__(256, 4) conv3d_c8_to_1_kernel(ConvParams p) {
+    // Plane-stationary depth march over the 4 x 64 tile: ONE input plane per step.  Lane l owns slab COLUMN l (input pixel
+    // c0 - 1 + l) and, for l = 1..62, output column c0 + l - 1.  A step reads the lane's own pixel of the three kh rows once
+    // (6 ds_read_b128) and feeds the three output planes that input plane pl touches: kd = 0 of plane pl + 1 (started
+    // here), kd = 1 of plane pl, kd = 2 of plane pl - 1, which is complete after it: the three partial sums Q_kw =
+    // sum_{kd,kh,c} W[kd,kh,kw,c] * x[own pixel] are added up, Q_0[l-1] + Q_1[l] + Q_2[l+1] by two lane shifts, and stored.
+    // The three accumulator sets change roles every step (the march is unrolled by three, no register moves).
+    // Every chain receives its terms in (kd, kh) order with the same four FMAs per tap as the ring kernel below, planes
+    // outside the volume as zeros from LDS: the results are bit-identical to it.  The steps at the ends of a chunk skip the
+    // output planes of the neighbouring chunks, so an output costs 108 packed FMAs.
+    // LDS: two planes (the one computed on, and the next one, written from the prefetch registers while this one is computed:
+    // one barrier per step) of 48-byte pixels: consecutive lanes' ds_read_b128 fall on distinct banks.  36 KB, four
+    // workgroups per CU.
+    constexpr int CIN = 8, TW = C8_TW, ROWS = CONV_TH + 2, COLS = TW + 2, PSTR = CIN + CONV_PAD, SLAB = ROWS * COLS * PSTR;
+    static_assert(COLS == 64, "one slab column per lane");
+    constexpr int NEL = ROWS * COLS * 2, NPF = (NEL + 255) / 256, DZ = C8_DZ;
+    constexpr int DUMMY = (2 * SLAB) / 4;
+    __shared__ __attribute__((aligned(16))) float planes[2 * SLAB + 4];  // 36 KB + dummy slot
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int tw, th;
+    const int bx = decode_tile(p, tile_index(p), tw, th);
+    const int nzc = (p.Do + DZ - 1) / DZ;
+    const int zc = bx % nzc;
+    const int b = bx / nzc;
+    const int r0 = th * CONV_TH, c0 = tw * TW;
+    const int z0 = zc * DZ, z1 = min(z0 + DZ, p.Do);
+
+    int loff[NPF], goff[NPF];
+#pragma unroll
+    for (int i = 0; i < NPF; ++i) {
+        const int e = tid + 256 * i;
+        const int row = e / (COLS * 2), rem = e - row * (COLS * 2);
+        const int col = rem >> 1, c4 = rem & 1;
+        const int gr = r0 - 1 + row, gc = c0 - 1 + col;
+        loff[i] = e < NEL ? ((row * COLS + col) * PSTR) / 4 + c4 : DUMMY;  // float4 units (see conv3d_march_kernel)
+        goff[i] = (e < NEL && gr >= 0 && gr < p.hi && gc >= 0 && gc < p.wi) ? (gr * p.wi + gc) * 2 + c4 : -1;
+    }
+    const size_t plane_f4 = (size_t)p.hi * p.wi * 2;
+    const float4* __restrict__ xb = reinterpret_cast<const float4*>(p.x) + (size_t)b * p.Di * plane_f4;
+    float4* __restrict__ planes4 = reinterpret_cast<float4*>(planes);
+    float4 pf[NPF];
+    bool pf_ok = false;
+    auto load_plane = [&](int plane) {
+        const bool ok = plane >= 0 && plane < p.Di;
+        const float4* __restrict__ xp = xb + (size_t)(ok ? plane : 0) * plane_f4;
+        pf_ok = ok;
+#pragma unroll
+        for (int i = 0; i < NPF; ++i) pf[i] = xp[max(goff[i], 0)];  // raw: zeroing happens at store time, so that
+    };                                                              // nothing touches pf while the loads are in flight
+    auto store_plane = [&](int slot) {
+#pragma unroll
+        for (int i = 0; i < NPF; ++i)
+            planes4[loff[i] == DUMMY ? DUMMY : slot * (SLAB / 4) + loff[i]] =
+                (pf_ok && goff[i] >= 0) ? pf[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    };
+
+    const int orow = r0 + wave, ocol = c0 + lane - 1;
+    const bool live = lane >= 1 && lane <= TW && orow < p.ho && ocol < p.wo;
+    const float sc = p.scale[0], sh = p.shift[0];
+    f32x4 xa[3], xc[3];  // the lane's pixel in rows wave + kh of the current input plane
+    // the nine (kh, kw) taps of kernel plane KD into one output plane's chains
+    auto taps = [&](auto kdc, C8Acc& q) {
+        constexpr int KD = decltype(kdc)::value;
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw) {
+                // constant address space: the loads are invariant for the compiler, so the (uniform) address goes
+                // through the scalar cache and the weights arrive as SGPR-pair operands of the packed FMAs
+                typedef const __attribute__((address_space(4))) f32x4* cf4;
+                const cf4 wp = (cf4)(unsigned long long)(p.wpk + ((KD * 3 + kh) * 3 + kw) * 8);
+                const f32x4 w0 = wp[0], w1 = wp[1];
+                q.a[kw] = __builtin_elementwise_fma(xa[kh].xy, w0.xy, q.a[kw]);
+                q.b[kw] = __builtin_elementwise_fma(xa[kh].zw, w0.zw, q.b[kw]);
+                q.a[kw] = __builtin_elementwise_fma(xc[kh].xy, w1.xy, q.a[kw]);
+                q.b[kw] = __builtin_elementwise_fma(xc[kh].zw, w1.zw, q.b[kw]);
+            }
+    };
+    // input plane pl: fin = output plane pl - 1, mid = pl, nxt = pl + 1.  On entry pf holds plane pl + 1.
+    auto step = [&](int pl, C8Acc& fin, C8Acc& mid, C8Acc& nxt) {
+        __syncthreads();  // plane pl is in its buffer, and nobody reads plane pl - 1 from the other one any more
+        if (pl + 1 <= z1) store_plane((pl + 1) & 1);
+        if (pl + 2 <= z1) load_plane(pl + 2);
+        const float* __restrict__ slab = planes + (pl & 1) * SLAB;
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh) {
+            const f32x4* sp = reinterpret_cast<const f32x4*>(slab + ((wave + kh) * COLS + lane) * PSTR);
+            xa[kh] = sp[0];
+            xc[kh] = sp[1];
+        }
+        if (pl + 1 < z1) {
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw) { nxt.a[kw] = f32x2{0.f, 0.f}; nxt.b[kw] = f32x2{0.f, 0.f}; }
+            taps(std::integral_constant<int, 0>{}, nxt);
+        }
+        if (pl >= z0 && pl < z1) taps(std::integral_constant<int, 1>{}, mid);
+        if (pl > z0) {
+            taps(std::integral_constant<int, 2>{}, fin);
+            float q[3];
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw) q[kw] = (fin.a[kw].x + fin.a[kw].y) + (fin.b[kw].x + fin.b[kw].y);
+            // output column o = pixel l takes kw = 0 from pixel l-1, kw = 1 from itself, kw = 2 from pixel l+1
+            const float acc = (__shfl_up(q[0], 1) + q[1]) + __shfl_down(q[2], 1);
+            if (live) {
+                const size_t o = (((size_t)b * p.Do + (pl - 1)) * p.ho + orow) * p.wo + ocol;
+                float val = fmaf(acc, sc, sh);
+                if (p.relu) val = fmaxf(val, 0.f);
+                if (p.skip) val += p.skip[o];
+                p.y[o] = val;
+            }
+        }
+    };
+    load_plane(z0 - 1);
+    store_plane((z0 - 1) & 1);
+    load_plane(z0);
+    C8Acc q0 = {}, q1 = {}, q2 = {};
+    for (int pl = z0 - 1;; pl += 3) {  // input planes z0 - 1 .. z1
+        step(pl, q0, q1, q2);
+        if (pl + 1 > z1) break;
+        step(pl + 1, q1, q2, q0);
+        if (pl + 2 > z1) break;
+        step(pl + 2, q2, q0, q1);
+        if (pl + 3 > z1) break;
+    }
+}
+
+#ifdef MVD_EXPERIMENTS
+// MVD_K4_PROB_RING: the output-stationary form that the kernel above replaced (what its results are compared with)
+__global__ void __launch_bounds__(256, 4) conv3d_c8_to_1_ring_kernel(ConvParams p) {
     // depth-marching like conv3d_march_kernel: 3 input planes of the 4 x 64 tile in an LDS ring, the next plane
     // prefetched into registers while the current output plane is computed
     // Lane l owns slab COLUMN l (input pixel c0 - 1 + l) and, for l = 1..62, output column c0 + l - 1.  Instead of reading
@@ -1329,6 +1464,7 @@ __global__ void __launch_bounds__(256, 4) conv3d_c8_to_1_kernel(ConvParams p) {
         }
     }
 }
+#endif
 
 __global__ void pack_c8_to_1_kernel(const float* __restrict__ w, float* __restrict__ packed) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;  // packed [tap][cin] <- w (1, 8, 27)
@@ -1357,6 +1493,9 @@ static int launch_c8_to_1(const ConvParams& p0, hipStream_t st) {
     p.tiles_w = (p.wo + C8_TW - 1) / C8_TW;
     const long long nblk = (long long)p.tiles_w * p.tiles_h * ((p.Do + C8_DZ - 1) / C8_DZ) * p.B;
     p.per_xcd = xcd_run(nblk, 0);
+#ifdef MVD_EXPERIMENTS
+    if (exp_env("MVD_K4_PROB_RING")) return launch_tiles(conv3d_c8_to_1_ring_kernel, nblk, 256, 0, "conv3d_c8_to_1", p, st);
+#endif
     return launch_tiles(conv3d_c8_to_1_kernel, nblk, 256, 0, "conv3d_c8_to_1", p, st);
 }
 

@@ -530,6 +530,38 @@ def conv2d_head(image, w0, scale0, shift0, w1, scale1, shift1, return_absmax=Fal
     return (y, absmax(tiles)) if return_absmax else y
 
 
+@inference_only
+def pack_conv2d_head_weights_split(weight1):
+    """conv1's Conv2d weight (8,8,3,3) fp32 -> the [w_hi | w_lo] fp16 fragments of conv2d_head_split, followed by the channels'
+    power-of-two scales.  Once per model."""
+    wt = L.as_f32(weight1, "weight1")
+    if tuple(wt.shape) != (8, 8, 3, 3):
+        raise ValueError(f"conv2d_head split: conv1's weight is (8,8,3,3), got {tuple(wt.shape)}")
+    packed = torch.empty(L.load().mvd_conv2d_head_split_packed_bytes(), dtype=torch.uint8, device=wt.device)
+    call("mvd_pack_conv2d_head_split_weights", wt.device, wt, packed)
+    return packed
+
+
+@inference_only
+def conv2d_head_split(image, w0, scale0, shift0, w1_packed, scale1, shift1, return_absmax=False):
+    """conv2d_head with conv1 on the fp16 matrix instruction (split operands, fp32 accumulation; fp32-grade).  w1_packed:
+    pack_conv2d_head_weights_split of conv1's weight; everything else as conv2d_head."""
+    x = L.as_f32(image, "image")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"image must be (B,3,H,W), got {tuple(x.shape)}")
+    B, _, H, W = x.shape
+    dev = x.device
+    w0 = L.as_f32(w0, "w0", (3, 3, 3, 8), dev)
+    n = L.load().mvd_conv2d_head_split_packed_bytes()
+    if w1_packed.dtype != torch.uint8 or w1_packed.numel() != n or w1_packed.device != dev or not w1_packed.is_contiguous():
+        raise ValueError(f"w1_packed: pack_conv2d_head_weights_split's {n} bytes on {dev} expected")
+    vs = [L.as_f32(v, n_, (8,), dev) for v, n_ in ((scale0, "scale0"), (shift0, "shift0"), (scale1, "scale1"), (shift1, "shift1"))]
+    y = torch.empty((B, H, W, 8), dtype=torch.float32, device=dev)
+    tiles = torch.empty(L.load().mvd_conv2d_head_tile_count(B, H, W), dtype=torch.float32, device=dev) if return_absmax else None
+    call("mvd_conv2d_head_split_f32", dev, x, w0, vs[0], vs[1], w1_packed, vs[2], vs[3], y, tiles, B, H, W)
+    return (y, absmax(tiles)) if return_absmax else y
+
+
 def conv2d_bn_relu(x, packed, Cin, Cout, ksize, stride, scale, shift, relu=True, out_layout=L.LAYOUT_NHWC, out=None, out_absmax=None):
     """K6. x: (B,3,H,W) image when Cin == 3, else channel-last (B,h,w,Cin).  Returns (B,ho,wo,Cout) for LAYOUT_NHWC,
     (B,Cout,ho,wo) for LAYOUT_NCHW, or the zero-bordered (B,ho+3,wo+3,Cout) staging map for LAYOUT_NHWC_BORDER

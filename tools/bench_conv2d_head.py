@@ -43,3 +43,9 @@ print(f"max |one launch - two launches| = {float((a - b).abs().max()):.3g} (max 
 t2, t1 = timed(two), timed(lambda: ops.conv2d_head(img, *pk.head))
 mb = (B * 3 * H * W + B * 8 * H * W) * 4 / 1e6
 print(f"two launches {t2:.1f} us, one launch {t1:.1f} us ({mb:.0f} MB algorithmic -> {mb / t1 * 1e3:.0f} GB/s)")
+# conv1 on the fp16 matrix instruction (mvd_conv2d_head_split_f32) beside the fp32 launch, taken alternately
+split = lambda: ops.conv2d_head_split(img, *pk.head[:3], pk.head_w1, *pk.head[4:])
+print(f"max |split - fp32| = {float((split() - b).abs().max()):.3g}")
+for rep in range(3):
+    t1, ts = timed(lambda: ops.conv2d_head(img, *pk.head)), timed(split)
+    print(f"rep {rep}: fp32 {t1:.1f} us, conv1 split {ts:.1f} us ({mb / ts * 1e3:.0f} GB/s)")
