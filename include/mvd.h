@@ -771,6 +771,48 @@ int mvd_tsdf_extract_f32(const float* tsdf, const float* weight, const float* co
                          int* triangles, long long max_vertices, long long max_triangles, long long* counts, void* workspace,
                          size_t workspace_bytes, mvd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Mesh rendering: a triangle mesh rasterised into V <= MVD_MAX_VIEWS pinhole views of one size (H,W).  The reference has NO
+ * counterpart: the definition is robustmvd_amd/render.py (its docstring and render_numpy) and DESIGN.md, restated here.
+ *
+ * vertices (M,3) float32 world coordinates, triangles (T,3) int32 with 0 <= index < M (the caller checks the range; a triangle with an
+ * index outside it is skipped), colors NULL or (M,3) float32.  matrices (V,12) on the device, row-major 3x4, composed by the host in
+ * float64: P = K T[:3] with K the intrinsics and T the world-to-view pose.  Pixel (px,py) is sampled at the image point (px,py).
+ *  1. Vertex: (qx,qy,qz) = P (X,1), each row summed left to right; valid iff qz > near and x = qx / qz, y = qy / qz are finite; z = qz.
+ *  2. Triangle (i0,i1,i2): skipped if a vertex is invalid (no near-plane clipping); skipped unless the signed area
+ *     A = (x1-x0)(y2-y0) - (y1-y0)(x2-x0) is < 0 or > 0; skipped if its pixel box [ceil(min x), floor(max x)] x [ceil(min y),
+ *     floor(max y)], clamped to the image, is empty.  Front-facing iff A < 0 (x right, y down, z forward: a winding normal
+ *     (p1-p0) x (p2-p0) that points at the camera).  cull: MVD_CULL_NONE, MVD_CULL_BACK skips A > 0, MVD_CULL_FRONT skips A < 0.
+ *  3. Edge value: for the vertex pair a < b by index, e_ab(p) = (x_b-x_a)(p_y-y_a) - (y_b-y_a)(p_x-x_a), evaluated as written, one
+ *     rounding per operation.  The oriented edge (i,j) is +e_ij where i < j and -e_ji otherwise.  w0, w1, w2 = the oriented edges
+ *     (i1,i2), (i2,i0), (i0,i1) times sign(A).  Covered iff w0, w1, w2 >= 0 and s = (w0 + w1) + w2 > 0.  Two triangles that share an
+ *     edge compute the same bits with opposite sign: no pixel between them is lost, a pixel exactly on the edge belongs to both.
+ *  4. Depth: b_k = w_k / s, u_k = b_k / z_k, z = 1 / ((u0 + u1) + u2); a pixel whose z is not finite is not covered.
+ *  5. Winner: the smallest 64-bit key (float bits of z) << 32 | triangle index: the nearest triangle, among equals the lowest index.
+ *  6. Maps, dense, 16-byte aligned: depth (V,H,W) float32, the winner's z or 0; triangle (V,H,W) int32, its index or -1; NULL or
+ *     (V,3,H,W) float32 each: bary (b0,b1,b2), out_colors z ((u0 c0 + u1 c1) + u2 c2) (needs colors), normals the winner's unit
+ *     winding normal n / |n|, n = (p1-p0) x (p2-p0) in world coordinates, (0,0,0) where |n| is 0 or not finite; all 0 on empty pixels.
+ * Left out: near-plane clipping, anti-aliasing, vertex normals.
+ *
+ * A triangle whose clamped box holds at most max_small pixels is rasterised by one lane, a larger one cooperatively by waves; every
+ * max_small >= 0 gives the same bits.  The winner is kept with 64-bit integer min atomics: two calls give the same bits.  H W V and T
+ * are at most 2^31 - 1, V T below 2^32.  workspace: mvd_mesh_render_workspace_bytes(M, T, V, H, W), 256-byte aligned.
+ * flags, all for measurements: MVD_RENDER_LOAD_FIRST: a plain load of the key before the atomic, which is skipped when the key has lost
+ * already (measured slower, profiles/mesh_render.txt; the bits are the same).  The stages can be run apart on one workspace: MVD_RENDER_KEEP_PROJECT (the workspace still holds the screen vertices of these arguments: not projected again),
+ * MVD_RENDER_KEEP_KEYS (it still holds the keys: not rasterised again), MVD_RENDER_NO_RESOLVE (the maps are not written). */
+#define MVD_CULL_NONE 0
+#define MVD_CULL_BACK 1
+#define MVD_CULL_FRONT 2
+#define MVD_RENDER_LOAD_FIRST 1
+#define MVD_RENDER_KEEP_PROJECT 16
+#define MVD_RENDER_KEEP_KEYS 32
+#define MVD_RENDER_NO_RESOLVE 64
+size_t mvd_mesh_render_workspace_bytes(long long M, long long T, int V, int H, int W);
+int mvd_mesh_render_f32(const float* vertices, long long M, const int* triangles, long long T, const float* colors,
+                        const float* matrices, int V, int H, int W, float near_plane, int cull, int max_small, int flags, float* depth,
+                        int* triangle, float* bary, float* out_colors, float* normals, void* workspace, size_t workspace_bytes,
+                        mvd_stream_t stream);
+
 /* layout helpers used at the operator-level boundary (reference tensors are NCHW / NCDHW) */
 int mvd_nchw_to_nhwc_f32(const float* src, float* dst, int N, int C, long long HW, mvd_stream_t stream);
 int mvd_nhwc_to_nchw_f32(const float* src, float* dst, int N, int C, long long HW, mvd_stream_t stream);

@@ -27,3 +27,5 @@ from .cloud_eval import (PointCloudEvaluation, CloudScore, evaluate_scene, read_
                          cloud_scores_numpy, voxel_downsample_numpy)
 from . import tsdf  # noqa: F401,E402
 from .tsdf import TSDFVolume, Mesh, integrate_numpy, extract_numpy, bounds_from_points  # noqa: F401,E402
+from . import render  # noqa: F401,E402
+from .render import render_mesh, render_numpy, RenderResult  # noqa: F401,E402

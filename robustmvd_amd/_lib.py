@@ -174,7 +174,14 @@ SIGNATURES = {
                                                                                       ctypes.c_longlong, ctypes.c_longlong,
                                                                                       ctypes.c_void_p, ctypes.c_void_p, _sz,
                                                                                       ctypes.c_void_p]),
+    "mvd_mesh_render_workspace_bytes": (_sz, [ctypes.c_longlong, ctypes.c_longlong, _i, _i, _i]),
+    "mvd_mesh_render_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, _c_float_p, _c_float_p, _i, _i, _i,
+                                 ctypes.c_float, _i, _i, _i, _c_float_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p,
+                                 ctypes.c_void_p, _sz, ctypes.c_void_p]),
 }
+CULL_NONE, CULL_BACK, CULL_FRONT = 0, 1, 2  # MVD_CULL_*
+RENDER_LOAD_FIRST, RENDER_KEEP_PROJECT, RENDER_KEEP_KEYS, RENDER_NO_RESOLVE = 1, 16, 32, 64  # MVD_RENDER_*
+MESH_RENDER_MAX_SMALL = 64  # ops.mesh_render's default threshold between the lane and the wave path (profiles/mesh_render.txt)
 MVD_CLOUD_MAX_THRESHOLDS = 8
 
 # built into the product library only (csrc/Makefile PRODSRCS): the experiments library has no variants of these

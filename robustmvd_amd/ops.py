@@ -962,7 +962,53 @@ def tsdf_extract(tsdf, weight, color=None, origin=(0.0, 0.0, 0.0), voxel=1.0, mi
     return vertices, triangles, colors
 
 
-CLOUD_INDEX_LIMIT = (1 << 21) - 1  # a cell or voxel index is in [0, 2^21 - 1): the all-ones key is the invalid points' own
+@inference_only
+def mesh_render(vertices, triangles, matrices, size, colors=None, normals=False, bary=False, cull=None, near=0.0, max_small=None,
+                load_first=False, check_indices=True, stages=0, workspace_=None, out=None):
+    """Renders a triangle mesh into V <= 32 views of one size in one call (include/mvd.h: mvd_mesh_render_f32; render.render_numpy is
+    the definition).  vertices (M,3) float32, triangles (T,3) int32, colors None or (M,3) float32, matrices (V,12):
+    render.compose_projection's rows; size (H,W); cull None, "back" or "front".  -> dict: depth (V,H,W) float32 (0: empty), triangle
+    (V,H,W) int32 (-1: empty), and bary / colors / normals (V,3,H,W) float32 or None.
+    max_small: the largest pixel box one lane rasterises by itself (None: L.MESH_RENDER_MAX_SMALL); load_first: a plain load of the key
+    before the atomic (measured slower).  Neither changes a bit of the result.  check_indices: one reduction and synchronisation that refuses a vertex index
+    outside 0 .. M - 1 (the kernels skip such a triangle).  stages, workspace_, out: for measurements (tools/bench_render.py), the
+    MVD_RENDER_KEEP_* / NO_RESOLVE bits with the workspace and the result of an earlier call on the same arguments."""
+    from . import render as R
+    v = L.as_f32(vertices, "vertices")
+    dev = v.device
+    t = L.as_dtype(torch.int32, True, triangles, "triangles", device=dev)
+    c = None if colors is None else L.as_f32(colors, "colors", device=dev)
+    M, T = R.check_mesh(v, t, c)
+    mats = L.as_f32(matrices, "matrices", device=dev)
+    if mats.dim() != 2 or mats.shape[1] != 12 or not 1 <= mats.shape[0] <= L.MVD_MAX_VIEWS:
+        raise ValueError(f"matrices must be (V,12) with V in 1..{L.MVD_MAX_VIEWS}, got {tuple(mats.shape)}")
+    V = int(mats.shape[0])
+    _, H, W = R.check_views([None] * V, [None] * V, size)
+    if V * T >= 2 ** 32:
+        raise ValueError(f"V T = {V * T} must be below 2^32: render fewer views per call")
+    code = R.check_cull(cull)
+    max_small = L.MESH_RENDER_MAX_SMALL if max_small is None else int(max_small)
+    if not 0 <= max_small < 2 ** 31:
+        raise ValueError(f"max_small must be in 0 .. 2^31 - 1, got {max_small}")
+    if check_indices and T:
+        lo, hi = torch.aminmax(t)
+        R.check_index_range(int(lo), int(hi), M)
+    if out is None:
+        maps = lambda on: torch.empty((V, 3, H, W), dtype=torch.float32, device=dev) if on else None
+        out = {"depth": torch.empty((V, H, W), dtype=torch.float32, device=dev),
+               "triangle": torch.empty((V, H, W), dtype=torch.int32, device=dev),
+               "bary": maps(bary), "colors": maps(c is not None), "normals": maps(normals)}
+    nbytes = L.load().mvd_mesh_render_workspace_bytes(M, T, V, H, W)
+    ws = workspace(nbytes, dev) if workspace_ is None else workspace_
+    if ws.numel() < nbytes:
+        raise ValueError(f"workspace_ holds {ws.numel()} bytes, needed {nbytes}")
+    flags = (L.RENDER_LOAD_FIRST if load_first else 0) | int(stages)
+    call("mvd_mesh_render_f32", dev, v if M else None, M, t if T else None, T, c, mats, V, H, W, float(near), code, max_small, flags,
+         out["depth"], out["triangle"], out["bary"], out["colors"], out["normals"], ws, int(nbytes))
+    return out
+
+
+CLOUD_INDEX_LIMIT = (1 << 21) - 1 # a cell or voxel index is in [0, 2^21 - 1): the all-ones key is the invalid points' own
 CLOUD_CELL_MARGIN = 1.0 + 2.0 ** -10  # cell edge = max_dist * margin (csrc/cloud_eval.hip: why 27 cells are enough)
 
 

@@ -312,6 +312,11 @@ class Mesh:
     triangles: object
     colors: object = None
 
+    def render(self, intrinsics, poses, size, **kw):
+        """-> RenderResult: the mesh seen from V views of one size (render.render_mesh; colors=True renders the mesh's own)."""
+        from .render import render_mesh
+        return render_mesh(self, intrinsics, poses, size, **kw)
+
 
 class TSDFVolume:
     """A dense TSDF volume (module docstring) on the host (device=None: the numpy forms) or on one GPU (the HIP kernels).
@@ -455,6 +460,11 @@ class TSDFVolume:
         from . import ops
         v, t, c = ops.tsdf_extract(self.tsdf, self.weight, self.color, self.origin, self.voxel, min_weight)
         return Mesh(v, t, c)
+
+    def render(self, intrinsics, poses, size, min_weight=1.0, **kw):
+        """-> RenderResult: extract_mesh(min_weight).render(...), the volume's surface seen from V views: per view the denoised and
+        hole-filled depth map with, on request, a normal and a colour per pixel."""
+        return self.extract_mesh(min_weight).render(intrinsics, poses, size, **kw)
 
 
 if __name__ == "__main__":
