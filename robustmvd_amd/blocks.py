@@ -4,13 +4,15 @@ state-dict keys; their forward passes run on the HIP 
   PlanesweepCorrelation   rmvd/models/blocks/planesweep_corr.py:371-521   -> K1 mvd_sweep_corr_f32
   LearnedFusion           rmvd/models/blocks/learned_fusion.py:6-54       -> MIOpen score convs + K2 mvd_fuse_views_f32
   homo_warp               rmvd/models/blocks/utils.py:222-268             -> mvd_homo_warp_f32
-  CostRegNet              rmvd/models/blocks/mvsnet_components.py:69-123  -> K4 mvd_conv3d_bn_relu_f32 x 11
+  CostRegNet              rmvd/models/blocks/mvsnet_components.py:69-123  -> K4 x 11 (which entry point per layer: CostRegNet.__init__)
   depth_regression        rmvd/models/blocks/utils.py:271-274             (plain expectation; the fused K5 is ops.softmax_regress)
 
   FeatureNet              rmvd/models/blocks/mvsnet_components.py:44-66   -> K6 mvd_conv2d_bn_relu_f32 x 8
 
 The DispNet encoder/decoder 2-D CNN around the Path-A sweep is an ordinary torch module that runs on MIOpen.
 """
+from typing import NamedTuple
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -197,8 +199,89 @@ def fold_bn(bn):
     return scale.detach().contiguous(), (bn.bias - bn.running_mean * scale).detach().contiguous()
 
 
+class PackedWeights:
+    """Mixin: the cache of the weights an owner packs for the engine.  _prepare() returns what the owner's _pack() made, and calls
+    _pack() again only when a parameter or buffer of _packed_from() has moved to other storage or been written in place
+    ((data_ptr, _version) of each).  An owner that folds BatchNorm names itself in FOLDS_BN and refuses to pack in training mode."""
+    FOLDS_BN = None
+    _packed = None
+    _packed_key = None
+
+    def _packed_from(self):
+        """The modules whose parameters and buffers _pack() reads."""
+        return (self,)
+
+    def _prepare(self):
+        # every forward pays for this key: one walk over the modules' own tensor dicts (m.parameters() and m.buffers() walk once each
+        # and build every tensor's dotted name on the way: 155 us against 83 us for RobustMVD's 58 tensors)
+        key = tuple((t.data_ptr(), t._version) for owner in self._packed_from() for m in owner.modules()
+                    for t in (*m._parameters.values(), *m._buffers.values()) if t is not None)
+        if self._packed is None or self._packed_key != key:
+            if self.FOLDS_BN and self.training:
+                raise RuntimeError(f"{self.FOLDS_BN} HIP path folds BatchNorm running statistics: call .eval() first")
+            self._packed, self._packed_key = self._pack(), key
+        return self._packed
+
+
+class Slots:
+    """The max-|x| slots of one forward: one zeroed float buffer, handed out one element at a time.  The layers raise them
+    atomically, so they must read zero first: Slots(n, device) allocates the buffer (one fill), Slots(buf=...) zeroes a caller's."""
+
+    def __init__(self, n=None, device=None, buf=None):
+        self.buf = torch.zeros(n, dtype=torch.float32, device=device) if buf is None else buf.zero_()
+        self.taken = 0
+
+    def take(self):
+        """The next slot, as a one-element view of the buffer."""
+        if self.taken == self.buf.numel():
+            raise RuntimeError(f"all {self.taken} max-|x| slots of this forward are taken")
+        self.taken += 1
+        return self.buf[self.taken - 1:self.taken]
+
+
+class Conv3dLayer(NamedTuple):
+    """One fused 3-D layer (convolution, per-channel scale and shift, ReLU, skip) as ops.conv3d_bn_relu's arguments."""
+    w: torch.Tensor
+    cin: int
+    cout: int
+    scale: torch.Tensor
+    shift: torch.Tensor
+    mode: int
+
+    @classmethod
+    def pack(cls, weight, mode, bn=None, bias=None):
+        """weight: the layer's weight as ops.pack_conv3d_weights takes it for `mode`.  bn: the eval-mode BatchNorm behind it, folded
+        into scale and shift; without one the scale is 1 and the shift is `bias`, or 0."""
+        w, cin, cout = ops.pack_conv3d_weights(weight.detach(), mode)
+        if bn is not None:
+            scale, shift = fold_bn(bn)
+        else:
+            scale = torch.ones(cout, device=w.device)
+            shift = torch.zeros(cout, device=w.device) if bias is None else bias.detach().contiguous()
+        return cls(w, cin, cout, scale, shift, mode)
+
+    def __call__(self, t, relu=True, skip=None):
+        return ops.conv3d_bn_relu(t, *self, relu=relu, skip=skip)
+
+
+class Conv2dLayer(NamedTuple):
+    """One fused 2-D layer of FeatureNet as ops.conv2d_bn_relu's arguments."""
+    w: torch.Tensor
+    cin: int
+    cout: int
+    k: int
+    stride: int
+    scale: torch.Tensor
+    shift: torch.Tensor
+    relu: bool
+
+    def __call__(self, x, out_layout=L.LAYOUT_NHWC):
+        return ops.conv2d_bn_relu(x, self.w, self.cin, self.cout, self.k, self.stride, self.scale, self.shift, relu=self.relu,
+                                  out_layout=out_layout)
+
+
 class FeatureNetWeights:
-    """What FeatureNet._prepare packs.  layers: conv0 .. conv6 and `feature` as ops.conv2d_bn_relu's arguments
+    """What FeatureNet packs.  layers: conv0 .. conv6 and `feature` as Conv2dLayer records, ops.conv2d_bn_relu's arguments
     (packed, cin, cout, k, stride, scale, shift, relu), also read as pk[i].  With split_layers, split: conv2 .. `feature` as
     (SplitConv2dWeights, relu) for ops.conv2d_split, head: ops.conv2d_head's (w0, scale0, shift0, w1, scale1, shift1), and
     head_w1: conv1's weight packed for ops.conv2d_head_split (it takes w1's place in head)."""
@@ -211,11 +294,12 @@ class FeatureNetWeights:
         return self.layers[i]
 
 
-class FeatureNet(nn.Module):
+class FeatureNet(PackedWeights, nn.Module):
     """2-D feature pyramid of MVSNet (mvsnet_components.py:44-66).  Parameters live in ordinary nn.Conv2d /
     nn.BatchNorm2d modules (the reference's checkpoints load); forward folds BN (eval mode) and runs 8 fused HIP
     layers (K6, ops.conv2d_bn_relu) on channel-last activations."""
 
+    FOLDS_BN = "FeatureNet"
     SPEC = [(3, 8, 3, 1, 1), (8, 8, 3, 1, 1), (8, 16, 5, 2, 2), (16, 16, 3, 1, 1), (16, 16, 3, 1, 1),
             (16, 32, 5, 2, 2), (32, 32, 3, 1, 1)]
 
@@ -232,34 +316,26 @@ class FeatureNet(nn.Module):
         for i, s in enumerate(self.SPEC):
             setattr(self, f"conv{i}", ConvBnReLU(*s))
         self.feature = nn.Conv2d(32, 32, 3, 1, 1)
-        self._packed = None
-        self._packed_key = None
 
-    def _prepare(self):
-        """Packs weights into MFMA fragment order and folds BN; cached until a parameter changes."""
-        key = tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
-        if self._packed is not None and self._packed_key == key:
-            return self._packed
-        if self.training:
-            raise RuntimeError("FeatureNet HIP path folds BatchNorm running statistics: call .eval() first")
+    def _pack(self):
+        """Packs weights into MFMA fragment order and folds BN."""
         pk = FeatureNetWeights()
         for i, (cin, cout, k, stride, _) in enumerate(self.SPEC):
             m = getattr(self, f"conv{i}")
             w, _, _, _ = ops.pack_conv2d_weights(m.conv.weight.detach())
-            pk.layers.append((w, cin, cout, k, stride, *fold_bn(m.bn), True))
+            pk.layers.append(Conv2dLayer(w, cin, cout, k, stride, *fold_bn(m.bn), True))
         w, _, _, _ = ops.pack_conv2d_weights(self.feature.weight.detach())
-        pk.layers.append((w, 32, 32, 3, 1, torch.ones(32, device=w.device), self.feature.bias.detach().contiguous(), False))
+        pk.layers.append(Conv2dLayer(w, 32, 32, 3, 1, torch.ones(32, device=w.device), self.feature.bias.detach().contiguous(), False))
         if self.split_layers:  # layers 2 .. 7 for the split-operand kernel: BN scale folded into the weights, shift as the bias
             for i in range(2, 8):
                 conv = getattr(self, f"conv{i}").conv if i < 7 else self.feature
-                _, _, _, _, stride, scale, shift, relu = pk.layers[i]
-                pk.split.append((ops.pack_conv2d_weights_split(conv.weight.detach() * scale.view(-1, 1, 1, 1), shift, stride=stride), relu))
+                lay = pk.layers[i]
+                pk.split.append((ops.pack_conv2d_weights_split(conv.weight.detach() * lay.scale.view(-1, 1, 1, 1), lay.shift,
+                                                               stride=lay.stride), lay.relu))
             # conv0 -> conv1 in one launch (ops.conv2d_head): weights as [ky][kx][cin][cout]
-            for i in range(2):
-                _, _, _, _, _, scale, shift, _ = pk.layers[i]
-                pk.head += (getattr(self, f"conv{i}").conv.weight.detach().permute(2, 3, 1, 0).contiguous(), scale, shift)
+            for conv, lay in ((self.conv0.conv, pk.layers[0]), (self.conv1.conv, pk.layers[1])):
+                pk.head += (conv.weight.detach().permute(2, 3, 1, 0).contiguous(), lay.scale, lay.shift)
             pk.head_w1 = ops.pack_conv2d_head_weights_split(self.conv1.conv.weight.detach())
-        self._packed, self._packed_key = pk, key
         return pk
 
     @ops.inference_only
@@ -271,46 +347,43 @@ class FeatureNet(nn.Module):
         if out is not None and not (self.split_layers and out_layout == L.LAYOUT_NHWC_BORDER):
             raise ValueError("out: only the split layers' LAYOUT_NHWC_BORDER output can be written into a caller's buffer")
         if not self.split_layers:
-            for i, (w, cin, cout, k, stride, scale, shift, relu) in enumerate(pk.layers):
-                x = ops.conv2d_bn_relu(x, w, cin, cout, k, stride, scale, shift, relu=relu,
-                                       out_layout=out_layout if i == len(pk.layers) - 1 else L.LAYOUT_NHWC)
+            for layer in pk.layers[:-1]:
+                x = layer(x)
+            x = pk.layers[-1](x, out_layout)
             return (x, ops.absmax(x)) if return_absmax else x
-        slots = torch.zeros(8, dtype=torch.float32, device=x.device)  # max-|y| slots of the layers, raised by their producers
+        slots = Slots(8, x.device)  # max-|y| slots of the layers, raised by their producers
         if self.fused_head:  # the 8-channel full-resolution intermediate never leaves the chip; max |conv1| from per-tile maxima
             if self.head_split:
                 x, a_in = ops.conv2d_head_split(x, *pk.head[:3], pk.head_w1, *pk.head[4:], return_absmax=True)
             else:
                 x, a_in = ops.conv2d_head(x, *pk.head, return_absmax=True)
         else:
-            for w, cin, cout, k, stride, scale, shift, relu in pk.layers[:2]:
-                x = ops.conv2d_bn_relu(x, w, cin, cout, k, stride, scale, shift, relu=relu)
+            x = pk.layers[1](pk.layers[0](x))
             # max |conv1| by a pass of its own (29 us for 141 MB): as a by-product of conv1's store epilogue (out_absmax=) it cost 65 us
             # in the frame, where the maximum grows across the image and many of the layer's 69,000 waves reach the atomic
             a_in = ops.absmax(x)
-        for j, (wts, relu) in enumerate(pk.split):
-            last = j == len(pk.split) - 1
-            if not last:
-                x = ops.conv2d_split(x, a_in, wts, act=2 if relu else 0, out_absmax=slots[j:j + 1])
-                a_in = slots[j:j + 1]
-            elif out_layout == L.LAYOUT_NCHW:
-                x = ops.conv2d_split(x, a_in, wts, act=0, planar_out=True)
-                if return_absmax:
-                    slots[7:8] = ops.absmax(x)
-            elif out_layout == L.LAYOUT_NHWC_BORDER:  # K3's zero-bordered staging map: the layer writes the interior
-                B, h, w_, _ = x.shape
-                # only the border is zeroed (the fill of the whole map was 36 MB per frame); the layer writes the interior
-                if out is None:
-                    out = torch.empty((B, h + 3, w_ + 3, wts.cout), dtype=torch.float32, device=x.device)
-                elif tuple(out.shape) != (B, h + 3, w_ + 3, wts.cout):
-                    raise ValueError(f"out: shape {tuple(out.shape)}, expected {(B, h + 3, w_ + 3, wts.cout)}")
-                buf = ops.zero_border_nhwc(out)
-                ops.conv2d_split(x, a_in, wts, act=0, out=buf[:, 1:h + 1, 1:w_ + 1, :], out_absmax=slots[7:8])
-                x = buf
-            else:
-                x = ops.conv2d_split(x, a_in, wts, act=0, out_absmax=slots[7:8])
-        if return_absmax:
-            return x, slots[7:8]
-        return x
+        for wts, relu in pk.split[:-1]:
+            a_out = slots.take()
+            x = ops.conv2d_split(x, a_in, wts, act=2 if relu else 0, out_absmax=a_out)
+            a_in = a_out
+        wts, a_out = pk.split[-1][0], slots.take()  # `feature`: no activation, max |feature| into the last slot taken
+        if out_layout == L.LAYOUT_NCHW:
+            x = ops.conv2d_split(x, a_in, wts, act=0, planar_out=True)
+            if return_absmax:
+                a_out.copy_(ops.absmax(x))
+        elif out_layout == L.LAYOUT_NHWC_BORDER:  # K3's zero-bordered staging map: the layer writes the interior
+            B, h, w_, _ = x.shape
+            # only the border is zeroed (the fill of the whole map was 36 MB per frame); the layer writes the interior
+            if out is None:
+                out = torch.empty((B, h + 3, w_ + 3, wts.cout), dtype=torch.float32, device=x.device)
+            elif tuple(out.shape) != (B, h + 3, w_ + 3, wts.cout):
+                raise ValueError(f"out: shape {tuple(out.shape)}, expected {(B, h + 3, w_ + 3, wts.cout)}")
+            buf = ops.zero_border_nhwc(out)
+            ops.conv2d_split(x, a_in, wts, act=0, out=buf[:, 1:h + 1, 1:w_ + 1, :], out_absmax=a_out)
+            x = buf
+        else:
+            x = ops.conv2d_split(x, a_in, wts, act=0, out_absmax=a_out)
+        return (x, a_out) if return_absmax else x
 
     def forward(self, x):
         """Reference layout: (N,3,H,W) -> (N,32,H/4,W/4)."""
@@ -339,26 +412,53 @@ def _deconv_block(cin, cout):
                          nn.BatchNorm3d(cout), nn.ReLU(inplace=True))
 
 
-class CostRegNet(nn.Module):
+class CostRegWeights:
+    """What CostRegNet packs.  layers: name -> Conv3dLayer, each of the eleven layers for the fp32 kernels (ops.conv3d_bn_relu),
+    also read as pk[name]; conv0_f16: conv0's weight for ops.conv3d_bn_relu_f16in.  With conv0_split, the split-operand forms:
+    conv0_split: conv0's weight for ops.conv3d_bn_relu_split; conv0_bound: the (gain, offset) of the bound on max |conv0|;
+    igemm: name -> the weight of conv1 .. conv6 for ops.conv3d_bn_relu_igemm; dsplit: name -> the weight of conv7, conv9, conv11
+    for ops.deconv3d_bn_relu_split.  Their scale and shift are the layer record's."""
+
+    def __init__(self):
+        self.layers, self.igemm, self.dsplit = {}, {}, {}
+        self.conv0_f16 = self.conv0_split = self.conv0_bound = None
+
+    def get(self, key):
+        """pk[key] or None.  Beside the layer names, the string keys the other forms once had: "conv0_f16", "conv0_split",
+        "conv0_bound", "<name>_igemm", "<name>_dsplit"."""
+        name, _, form = key.rpartition("_")
+        if form in ("igemm", "dsplit"):
+            return getattr(self, form).get(name)
+        return self.layers.get(key, getattr(self, key, None) if name == "conv0" else None)
+
+    def __getitem__(self, key):
+        found = self.get(key)
+        if found is None:
+            raise KeyError(key)
+        return found
+
+    def __contains__(self, key):
+        return self.get(key) is not None
+
+
+class CostRegNet(PackedWeights, nn.Module):
     """3-D U-Net regulariser.  Parameters live in ordinary nn.Conv3d / nn.BatchNorm3d modules (so the
     reference's checkpoints load); forward folds BN (eval mode) and runs 11 fused HIP layers on
     channel-last activations."""
 
+    FOLDS_BN = "CostRegNet"
     LAYERS = [("conv0", 32, 8, 1), ("conv1", 8, 16, 2), ("conv2", 16, 16, 1), ("conv3", 16, 32, 2), ("conv4", 32, 32, 1),
               ("conv5", 32, 64, 2), ("conv6", 64, 64, 1)]
     UPS = [("conv7", 64, 32), ("conv9", 32, 16), ("conv11", 16, 8)]
-    # the first of UPS that run on ops.deconv3d_bn_relu_split when conv0_split is on (a leading run of UPS: each is scaled by the
-    # max |y| its predecessor leaves behind)
-    UPS_SPLIT = ("conv7", "conv9", "conv11")
 
     def __init__(self, conv0_split=True):
-        """conv0_split (default on): the fp32 operands of the stride-1 layers with 16 or 32 input channels (conv0: 32 -> 8 at
-        full resolution, conv2: 16 -> 16, conv4: 32 -> 32) are split into two fp16 terms each, after an exact
-        power-of-two range scaling, and multiplied on fp16 MFMA with fp32 accumulation (ops.conv3d_bn_relu_split); its
-        results are at least as close to the exact convolution as the fp32 matrix instruction's (measured against a
-        float64 oracle over magnitudes 1e-30 .. 1e30: tests/test_hip_f16.py); conv1 .. conv6 then run on the split-operand implicit
-        GEMM and the transposed layers conv7, conv9, conv11 on their own split-operand kernel (ops.deconv3d_bn_relu_split,
-        tests/test_hip_deconv3d_split.py).  False: every layer on fp32 MFMA."""
+        """conv0_split (default on): every layer but `prob` multiplies on fp16 MFMA with fp32 accumulation, its fp32 operands split
+        into two fp16 terms each after an exact power-of-two range scaling; the results are at least as close to the exact
+        convolution as the fp32 matrix instruction's (measured against a float64 oracle over magnitudes 1e-30 .. 1e30:
+        tests/test_hip_f16.py).  conv0 (32 -> 8 at full resolution) runs on the plane-marching kernel (ops.conv3d_bn_relu_split),
+        conv1 .. conv6 on the split-operand implicit GEMM (ops.conv3d_bn_relu_igemm) and the transposed layers conv7, conv9, conv11
+        on their own split-operand kernel (ops.deconv3d_bn_relu_split, tests/test_hip_deconv3d_split.py); `prob` (8 -> 1) stays on
+        the fp32 kernel.  False: every layer on fp32 MFMA."""
         super().__init__()
         self.conv0_split = bool(conv0_split)
         for name, cin, cout, stride in self.LAYERS:
@@ -366,41 +466,27 @@ class CostRegNet(nn.Module):
         for name, cin, cout in self.UPS:
             setattr(self, name, _deconv_block(cin, cout))
         self.prob = nn.Conv3d(8, 1, 3, stride=1, padding=1)
-        self._packed = None
-        self._packed_key = None
 
-    def _prepare(self):
-        """Packs weights into MFMA fragment order and folds BN; cached until a parameter changes."""
-        key = tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
-        if self._packed is not None and self._packed_key == key:
-            return self._packed
-        if self.training:
-            raise RuntimeError("CostRegNet HIP path folds BatchNorm running statistics: call .eval() first")
-        pk = {}
-        for name, cin, cout, stride in self.LAYERS:
+    def _pack(self):
+        """Packs weights into MFMA fragment order and folds BN."""
+        pk = CostRegWeights()
+        for name, _, _, stride in self.LAYERS:
             m = getattr(self, name)
-            mode = L.CONV3D_STRIDE1 if stride == 1 else L.CONV3D_STRIDE2
-            w, _, _ = ops.pack_conv3d_weights(m.conv.weight.detach(), mode)
-            pk[name] = (w, cin, cout, *fold_bn(m.bn), mode)
-        for name, cin, cout in self.UPS:
+            pk.layers[name] = Conv3dLayer.pack(m.conv.weight, L.CONV3D_STRIDE1 if stride == 1 else L.CONV3D_STRIDE2, bn=m.bn)
+        for name, _, _ in self.UPS:
             m = getattr(self, name)
-            w, _, _ = ops.pack_conv3d_weights(m[0].weight.detach(), L.DECONV3D_STRIDE2)
-            pk[name] = (w, cin, cout, *fold_bn(m[1]), L.DECONV3D_STRIDE2)
-        w, _, _ = ops.pack_conv3d_weights(self.prob.weight.detach(), L.CONV3D_STRIDE1)
-        pk["prob"] = (w, 8, 1, torch.ones(1, device=w.device), self.prob.bias.detach().contiguous(), L.CONV3D_STRIDE1)
+            pk.layers[name] = Conv3dLayer.pack(m[0].weight, L.DECONV3D_STRIDE2, bn=m[1])
+        pk.layers["prob"] = Conv3dLayer.pack(self.prob.weight, L.CONV3D_STRIDE1, bias=self.prob.bias)
         # fp16-feature variant (BASELINE configs[3]): conv0's weights rounded to fp16 in fp16-MFMA fragment order
-        pk["conv0_f16"] = ops.pack_conv3d_weights_f16(self.conv0.conv.weight.detach())
+        pk.conv0_f16 = ops.pack_conv3d_weights_f16(self.conv0.conv.weight.detach())
         if self.conv0_split:  # split-operand kernels: conv0 on the plane-marching one, conv1 .. conv6 on the implicit GEMM
-            pk["conv0_split"] = ops.pack_conv3d_weights_split(self.conv0.conv.weight.detach())
-            sc0, sh0 = pk["conv0"][3], pk["conv0"][4]
-            pk["conv0_bound"] = ((self.conv0.conv.weight.detach().abs().sum(dim=(1, 2, 3, 4)) * sc0.abs()).contiguous(), sh0.abs().contiguous())
-            for name, _, _, stride in self.LAYERS:
-                if name != "conv0":
-                    pk[name + "_igemm"] = ops.pack_conv3d_weights_igemm(getattr(self, name).conv.weight.detach(),
-                                                                        L.CONV3D_STRIDE1 if stride == 1 else L.CONV3D_STRIDE2)
-            for name in self.UPS_SPLIT:  # the transposed layers below full resolution on their own split-operand kernel
-                pk[name + "_dsplit"] = ops.pack_deconv3d_weights_split(getattr(self, name)[0].weight.detach())
-        self._packed, self._packed_key = pk, key
+            w0, conv0 = self.conv0.conv.weight.detach(), pk.layers["conv0"]
+            pk.conv0_split = ops.pack_conv3d_weights_split(w0)
+            pk.conv0_bound = ((w0.abs().sum(dim=(1, 2, 3, 4)) * conv0.scale.abs()).contiguous(), conv0.shift.abs().contiguous())
+            for name, _, _, _ in self.LAYERS[1:]:
+                pk.igemm[name] = ops.pack_conv3d_weights_igemm(getattr(self, name).conv.weight.detach(), pk.layers[name].mode)
+            for name, _, _ in self.UPS:  # the transposed layers on their own split-operand kernel
+                pk.dsplit[name] = ops.pack_deconv3d_weights_split(getattr(self, name)[0].weight.detach())
         return pk
 
     @ops.inference_only
@@ -411,81 +497,71 @@ class CostRegNet(nn.Module):
         if x.shape[1] % 8 or x.shape[2] % 8 or x.shape[3] % 8:
             raise ValueError(f"CostRegNet needs D,h,w divisible by 8, got {tuple(x.shape[1:4])}")
         pk = self._prepare()
+        first = pk["conv0"]
+        # the fp16-feature variant keeps the fp32 transposed kernels
+        split_decoder = self.conv0_split and x.dtype == torch.float32
 
-        def layer(name, t, relu=True, skip=None):
-            w, cin, cout, scale, shift, mode = pk[name]
-            return ops.conv3d_bn_relu(t, w, cin, cout, scale, shift, mode, relu=relu, skip=skip)
-
+        # ---- conv0: fp16 in, split operands, or fp32
         if x.dtype == torch.float16:  # the fp16 volume of ops.warp_variance_f16: first layer on fp16 MFMA, fp32 out
-            _, _, _, scale0, shift0, _ = pk["conv0"]
-            conv0 = ops.conv3d_bn_relu_f16in(x, pk["conv0_f16"], scale0, shift0, relu=True)
-            a0 = None
+            conv0 = ops.conv3d_bn_relu_f16in(x, pk.conv0_f16, first.scale, first.shift, relu=True)
         elif self.conv0_split:
-            _, _, _, scale0, shift0, _ = pk["conv0"]
             # The range of conv0's output for conv1: an upper BOUND from max |x| and the layer's weights instead of a measurement
             # (|y_c| <= |scale_c| sum|w_c| max|x| + |shift_c|).  Measuring costs a pass over 453 MB (85 us) or, as a by-product of the
             # kernel's store epilogue, 58 us; the bound is 10-50x loose, which moves the absolute error floor of conv1's activations
             # from 2^-39 to about 2^-33 of the true maximum: still below fp32's own rounding of the sums they enter.
             if x_absmax is None:
                 x_absmax = ops.absmax(x)
-            conv0 = ops.conv3d_bn_relu_split(x, pk["conv0_split"], scale0, shift0, relu=True, x_absmax=x_absmax)
-            gain0, off0 = pk["conv0_bound"]
+            conv0 = ops.conv3d_bn_relu_split(x, pk.conv0_split, first.scale, first.shift, relu=True, x_absmax=x_absmax)
+            gain0, off0 = pk.conv0_bound
             a0 = (gain0 * x_absmax + off0).amax().reshape(1)
         else:
-            conv0 = layer("conv0", x)
+            conv0 = first(x)
+
+        # ---- encoder, conv1 .. conv6: the split-operand implicit GEMM (depth taps as chunks of the reduction), or fp32.  An implicit-
+        # GEMM layer scales its input by max |x|, which the layer before leaves in a slot as a by-product of its store epilogue;
+        # conv6 leaves one only for a split decoder
         if self.conv0_split:
-            # conv1 .. conv6 on the implicit-GEMM split kernel of the 2-D engine (depth taps as chunks), each scaled by max |x| of its
-            # input, which the layer before leaves behind as a by-product of its store epilogue; conv11 and `prob`
-            # on the fp32 matrix instruction / vector ALU
-            slots = torch.zeros(8, dtype=torch.float32, device=x.device)  # the layers' max-|y| slots: one fill for all
-            nslot = [0]
+            slots = Slots(8, x.device)  # one fill for all layers
 
-            def ig(name, t, a, want_absmax=True):
-                _, cin, cout, sc, sh, mode = pk[name]
-                out_a = None
-                if want_absmax:
-                    out_a = slots[nslot[0]:nslot[0] + 1]
-                    nslot[0] += 1
-                return ops.conv3d_bn_relu_igemm(t, a, pk[name + "_igemm"], cin, cout, sc, sh, mode, relu=True, return_absmax=want_absmax,
-                                                out_absmax=out_a)
+            def igemm(name, t, a, leave_absmax=True):  # -> (y, max |y| or None)
+                lay = pk[name]
+                y = ops.conv3d_bn_relu_igemm(t, a, pk.igemm[name], lay.cin, lay.cout, lay.scale, lay.shift, lay.mode, relu=True,
+                                             return_absmax=leave_absmax, out_absmax=slots.take() if leave_absmax else None)
+                return y if leave_absmax else (y, None)
 
-            if a0 is None:
+            if x.dtype == torch.float16:  # no bound through the fp16 first layer: one pass over its output
                 a0 = ops.absmax(conv0)
-            t, a = ig("conv1", conv0, a0)
-            conv2, a = ig("conv2", t, a)
-            t, a = ig("conv3", conv2, a)
-            conv4, a = ig("conv4", t, a)
-            t, a = ig("conv5", conv4, a)
-            # the fp16-feature variant keeps the fp32 transposed kernels
-            ups = self.UPS_SPLIT if x.dtype == torch.float32 else ()
-            y = ig("conv6", t, a, want_absmax=bool(ups))
-            if ups:
-                y, a = y
+            t, a = igemm("conv1", conv0, a0)
+            conv2, a = igemm("conv2", t, a)
+            t, a = igemm("conv3", conv2, a)
+            conv4, a = igemm("conv4", t, a)
+            t, a = igemm("conv5", conv4, a)
+            y, a = igemm("conv6", t, a, leave_absmax=split_decoder)
         else:
-            ups = ()
-            conv2 = layer("conv2", layer("conv1", conv0))
-            conv4 = layer("conv4", layer("conv3", conv2))
-            y = layer("conv6", layer("conv5", conv4))
-        # the transposed layers: those of UPS_SPLIT on their own split-operand kernel (csrc/deconv3d_split.hip), scaled like
-        # conv1 .. conv6 (the layer before leaves max |y| behind, after its skip addition); the others on the fp32 kernels
-        skips = {"conv7": conv4, "conv9": conv2, "conv11": conv0}
-        del conv4, conv2, conv0
-        for i, (name, cin, cout) in enumerate(self.UPS):
-            skip = skips.pop(name)
-            if name in ups:
-                want = i + 1 < len(self.UPS) and self.UPS[i + 1][0] in ups
-                out_a = None
-                if want:
-                    out_a = slots[nslot[0]:nslot[0] + 1]
-                    nslot[0] += 1
-                y = ops.deconv3d_bn_relu_split(y, a, pk[name + "_dsplit"], cin, cout, pk[name][3], pk[name][4], relu=True, skip=skip,
-                                               return_absmax=want, out_absmax=out_a)
-                if want:
-                    y, a = y
-            else:
-                y = layer(name, y, skip=skip)
-            del skip
-        return layer("prob", y, relu=False).squeeze(-1)
+            conv2 = pk["conv2"](pk["conv1"](conv0))
+            conv4 = pk["conv4"](pk["conv3"](conv2))
+            y, a = pk["conv6"](pk["conv5"](conv4)), None
+
+        # ---- decoder, conv7, conv9, conv11: their own split-operand kernel (csrc/deconv3d_split.hip), scaled like conv1 .. conv6 (conv7
+        # and conv9 leave max |y| behind, after the skip addition; conv11 feeds `prob`, which needs none), or fp32.  Every skip
+        # tensor is dropped as soon as its layer has read it
+        def deconv(name, t, a, skip, leave_absmax=True):  # -> (y, max |y| or None)
+            lay = pk[name]
+            if not split_decoder:
+                return lay(t, skip=skip), None
+            y = ops.deconv3d_bn_relu_split(t, a, pk.dsplit[name], lay.cin, lay.cout, lay.scale, lay.shift, relu=True, skip=skip,
+                                           return_absmax=leave_absmax, out_absmax=slots.take() if leave_absmax else None)
+            return y if leave_absmax else (y, None)
+
+        y, a = deconv("conv7", y, a, conv4)
+        del conv4
+        y, a = deconv("conv9", y, a, conv2)
+        del conv2
+        y, _ = deconv("conv11", y, a, conv0, leave_absmax=False)
+        del conv0
+
+        # ---- prob: 8 -> 1 on the fp32 kernel, no activation
+        return pk["prob"](y, relu=False).squeeze(-1)
 
     @ops.inference_only
     def forward(self, x):

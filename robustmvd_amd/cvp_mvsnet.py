@@ -25,7 +25,7 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from . import ops
-from .blocks import ConvBnReLU3D, _deconv_block, fold_bn
+from .blocks import Conv3dLayer, ConvBnReLU3D, PackedWeights, Slots, _deconv_block
 from .models import _as_batch, _key_positions, _stack_views, _upscale_to_multiple
 from .registry import build_model_with_cfg, register_model
 from .sweep_modes import _cvp_transform
@@ -97,7 +97,7 @@ def _conv_leaky(cin, cout):
     return nn.Sequential(nn.Conv2d(cin, cout, kernel_size=3, stride=1, padding=1, bias=True), nn.LeakyReLU(0.1))
 
 
-class FeaturePyramid(nn.Module):
+class FeaturePyramid(PackedWeights, nn.Module):
     """cvp_mvsnet_components.py:40-82.  Parameters live in the reference's nn.Sequential(Conv2d, LeakyReLU) blocks (its checkpoints
     load); forward_levels runs the nine layers of every scale on the split-operand kernel, channel-last."""
     LAYERS = [("conv0aa", 3, 64), ("conv0ba", 64, 64), ("conv0bb", 64, 64), ("conv0bc", 64, 32), ("conv0bd", 32, 32),
@@ -107,16 +107,10 @@ class FeaturePyramid(nn.Module):
         super().__init__()
         for name, cin, cout in self.LAYERS:
             setattr(self, name, _conv_leaky(cin, cout))
-        self._packed = None
-        self._packed_key = None
 
-    def _prepare(self):
-        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
-        if self._packed is None or self._packed_key != key:
-            self._packed = [ops.pack_conv2d_weights_split(getattr(self, name)[0].weight.detach(), getattr(self, name)[0].bias,
-                                                          cin_pad=(cin + 7) // 8 * 8) for name, cin, _ in self.LAYERS]
-            self._packed_key = key
-        return self._packed
+    def _pack(self):
+        return [ops.pack_conv2d_weights_split(getattr(self, name)[0].weight.detach(), getattr(self, name)[0].bias,
+                                              cin_pad=(cin + 7) // 8 * 8) for name, cin, _ in self.LAYERS]
 
     @ops.inference_only
     def forward_levels(self, images, n_key, image_bufs, src_bufs):
@@ -124,7 +118,7 @@ class FeaturePyramid(nn.Module):
         channels 3 .. 7 read zero; src_bufs[s] (M - n_key, h+3, w+3, 16) whose border reads zero.  Returns the key features per scale,
         (n_key,h,w,16) dense channel-last; the source features are written into the interior of src_bufs[s]."""
         wts = self._prepare()
-        slots = torch.zeros(len(image_bufs) * len(wts), dtype=torch.float32, device=images.device)  # max-|x| slots, one fill for all
+        slots = Slots(len(image_bufs) * len(wts), images.device)  # one fill for all scales
         keys = []
         img = images
         for s, (ibuf, sbuf) in enumerate(zip(image_bufs, src_bufs)):
@@ -132,8 +126,8 @@ class FeaturePyramid(nn.Module):
                 img = F.interpolate(img, scale_factor=0.5, mode="bilinear", align_corners=None)
             ibuf[..., :3].copy_(img.permute(0, 2, 3, 1))
             x, a = ibuf, ops.absmax(img)
-            for j, wt in enumerate(wts[:-1]):
-                a_out = slots[s * len(wts) + j:s * len(wts) + j + 1]
+            for wt in wts[:-1]:
+                a_out = slots.take()
                 x = ops.conv2d_split(x, a, wt, act=1, slope=0.1, out_absmax=a_out)
                 a = a_out
             h, w = x.shape[1], x.shape[2]
@@ -142,10 +136,11 @@ class FeaturePyramid(nn.Module):
         return keys
 
 
-class CVPCostRegNet(nn.Module):
+class CVPCostRegNet(PackedWeights, nn.Module):
     """cvp_mvsnet_components.py:85-127, the reference's parameter names; forward_channels_last folds BN (eval mode) and runs the
     eleven layers on ops.conv3d_bn_relu, channel-last.  conv5 is a STRIDE-1 ConvTranspose3d: packed once as the stride-1 convolution
     it equals (taps flipped, channel axes swapped).  The two skip additions follow the ReLU, which is what the kernel's `skip` does."""
+    FOLDS_BN = "CVPCostRegNet"
     CONVS = [("conv0", 16, 16, 1), ("conv0a", 16, 16, 1), ("conv1", 16, 32, 2), ("conv2", 32, 32, 1), ("conv2a", 32, 32, 1),
              ("conv3", 32, 64, 1), ("conv4", 64, 64, 1), ("conv4a", 64, 64, 1)]
 
@@ -157,27 +152,16 @@ class CVPCostRegNet(nn.Module):
                                    nn.BatchNorm3d(32), nn.ReLU(inplace=True))
         self.conv6 = _deconv_block(32, 16)
         self.prob0 = nn.Conv3d(16, 1, 3, stride=1, padding=1)
-        self._packed = None
-        self._packed_key = None
 
-    def _prepare(self):
-        key = tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
-        if self._packed is not None and self._packed_key == key:
-            return self._packed
-        if self.training:
-            raise RuntimeError("CVPCostRegNet HIP path folds BatchNorm running statistics: call .eval() first")
+    def _pack(self):
         pk = {}
-        for name, cin, cout, stride in self.CONVS:
+        for name, _, _, stride in self.CONVS:
             m = getattr(self, name)
-            mode = L.CONV3D_STRIDE1 if stride == 1 else L.CONV3D_STRIDE2
-            pk[name] = (ops.pack_conv3d_weights(m.conv.weight.detach(), mode)[0], cin, cout, *fold_bn(m.bn), mode)
+            pk[name] = Conv3dLayer.pack(m.conv.weight, L.CONV3D_STRIDE1 if stride == 1 else L.CONV3D_STRIDE2, bn=m.bn)
         w5 = self.conv5[0].weight.detach().flip(2, 3, 4).transpose(0, 1).contiguous()  # (Cin,Cout,k,k,k) deconv -> (Cout,Cin,k,k,k) conv
-        pk["conv5"] = (ops.pack_conv3d_weights(w5, L.CONV3D_STRIDE1)[0], 64, 32, *fold_bn(self.conv5[1]), L.CONV3D_STRIDE1)
-        pk["conv6"] = (ops.pack_conv3d_weights(self.conv6[0].weight.detach(), L.DECONV3D_STRIDE2)[0], 32, 16, *fold_bn(self.conv6[1]),
-                       L.DECONV3D_STRIDE2)
-        w = ops.pack_conv3d_weights(self.prob0.weight.detach(), L.CONV3D_STRIDE1)[0]
-        pk["prob0"] = (w, 16, 1, torch.ones(1, device=w.device), self.prob0.bias.detach().contiguous(), L.CONV3D_STRIDE1)
-        self._packed, self._packed_key = pk, key
+        pk["conv5"] = Conv3dLayer.pack(w5, L.CONV3D_STRIDE1, bn=self.conv5[1])
+        pk["conv6"] = Conv3dLayer.pack(self.conv6[0].weight, L.DECONV3D_STRIDE2, bn=self.conv6[1])
+        pk["prob0"] = Conv3dLayer.pack(self.prob0.weight, L.CONV3D_STRIDE1, bias=self.prob0.bias)
         return pk
 
     @ops.inference_only
@@ -186,17 +170,12 @@ class CVPCostRegNet(nn.Module):
         if x.dim() != 5 or x.shape[4] != 16 or x.shape[1] % 2 or x.shape[2] % 2 or x.shape[3] % 2:
             raise ValueError(f"CVPCostRegNet needs (B,D,h,w,16) with even D, h, w, got {tuple(x.shape)}")
         pk = self._prepare()
-
-        def layer(name, t, relu=True, skip=None):
-            w, cin, cout, scale, shift, mode = pk[name]
-            return ops.conv3d_bn_relu(t, w, cin, cout, scale, shift, mode, relu=relu, skip=skip)
-
-        conv0 = layer("conv0a", layer("conv0", x))
-        conv2 = layer("conv2a", layer("conv2", layer("conv1", conv0)))
-        conv4 = layer("conv4a", layer("conv4", layer("conv3", conv2)))
-        conv5 = layer("conv5", conv4, skip=conv2)
-        conv6 = layer("conv6", conv5, skip=conv0)
-        return layer("prob0", conv6, relu=False).squeeze(-1)
+        conv0 = pk["conv0a"](pk["conv0"](x))
+        conv2 = pk["conv2a"](pk["conv2"](pk["conv1"](conv0)))
+        conv4 = pk["conv4a"](pk["conv4"](pk["conv3"](conv2)))
+        conv5 = pk["conv5"](conv4, skip=conv2)
+        conv6 = pk["conv6"](conv5, skip=conv0)
+        return pk["prob0"](conv6, relu=False).squeeze(-1)
 
     def forward(self, x):
         """Reference layout: (B,16,D,h,w) -> (B,D,h,w)."""

@@ -19,26 +19,27 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .blocks import PackedWeights, Slots
 
 
-class DispnetEngine:
+class DispnetEngine(PackedWeights):
     """Packed weights + the forward of RobustMVD's network part on the engine.  Built lazily by RobustMVD, re-packed when a
     parameter changes."""
 
     def __init__(self, model):
         self.model = model
-        self._key = None
-        self.w = None
         self._bufs = {}
         self._sides = {}
         self.side_stream = True  # key view's encoder chain beside the source views' (tools/path_a_engine.py measures both)
 
+    w = property(lambda self: self._packed)  # name -> the layer's packed weights; None before the first forward
+
     # ------------------------------------------------------------------------------------------------------------------
-    def _prepare(self):
+    def _packed_from(self):
+        return (self.model,)
+
+    def _pack(self):
         m = self.model
-        key = tuple((p.data_ptr(), p._version) for p in m.parameters())
-        if self.w is not None and self._key == key:
-            return self.w
         w = {}
 
         def pack(name, conv, mode=L.CONV2D, cin_pad=None):
@@ -60,7 +61,6 @@ class DispnetEngine:
             conv = getattr(dec, f"rfeat{lvl}")[0]
             pack(f"rfeat{lvl}", conv, cin_pad=(conv.in_channels + 7) // 8 * 8)
             pack(f"pred_{lvl}", getattr(dec, f"pred_{lvl}")[0])
-        self.w, self._key = w, key
         return w
 
     def _buffers(self, n, H, W, V, dev):
@@ -100,12 +100,7 @@ class DispnetEngine:
         S = m.SWEEP["num_sampling_points"]
         e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         bufs = self._buffers(n, H, W, V, dev)
-        slots = bufs["slots"].zero_()  # max-|x| slots, raised atomically by the producers
-        _next = [0]
-
-        def slot():
-            _next[0] += 1
-            return slots[_next[0] - 1:_next[0]]
+        slot = Slots(buf=bufs["slots"]).take  # raised atomically by the producers
 
         def layer(name, x, ax, **kw):
             """One convolution into a buffer of its own -> (output, its max-|x| slot)."""

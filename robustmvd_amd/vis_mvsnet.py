@@ -29,7 +29,7 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from . import ops
-from .blocks import fold_bn
+from .blocks import Conv3dLayer, PackedWeights
 from .models import _as_batch, _key_positions, _stack_views, _upscale_to_multiple
 from .registry import build_model_with_cfg, register_model
 from .sweep_modes import _vis_transform
@@ -178,50 +178,34 @@ def split_concat_weight(w):
     return w[:, :f].contiguous(), w[:, f:].contiguous()
 
 
-class Reg3d(nn.Module):
+class Reg3d(PackedWeights, nn.Module):
     """The pair regulariser Reg and the fused one RegFuse (vis_mvsnet_singlestage.py:21-54): UNet(8, 1, 0, 4, [], [8, 16], [], prefix,
     dim=3), and RegFuse's final 8 -> 1 convolution.  forward is the reference's on torch (NCDHW); forward_channels_last runs the nine
     fused layers on ops.conv3d_bn_relu."""
+    FOLDS_BN = "Vis-MVSNet's"
 
     def __init__(self, prefix, final):
         super().__init__()
         self.unet = UNet(8, 1, 0, 4, [8, 16], prefix, 3)
         if final:
             self.final_conv = nn.Conv3d(8, 1, 3, 1, 1, bias=False)
-        self._packed = None
-        self._packed_key = None
 
     def forward(self, x):
         out = self.unet(x)[-1]
         return self.final_conv(out) if hasattr(self, "final_conv") else out
 
-    def _prepare(self):
-        key = tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
-        if self._packed is not None and self._packed_key == key:
-            return self._packed
-        if self.training:
-            raise RuntimeError("Vis-MVSNet's HIP path folds BatchNorm running statistics: call .eval() first")
+    def _pack(self):
         b0, b1 = self.unet.enc_blocks[0][0], self.unet.enc_blocks[1][0]
         deconv, post = self.unet.dec_blocks[0][0], self.unet.dec_blocks[0][1]
-        dev = deconv.weight.device
-        one = lambda c: (torch.ones(c, device=dev), torch.zeros(c, device=dev))
-        pk = {}
-
-        def put(name, weight, mode, scale_shift):
-            w, cin, cout = ops.pack_conv3d_weights(weight.detach(), mode)
-            pk[name] = (w, cin, cout, *scale_shift, mode)
-
-        put("b0c1", b0.conv1.weight, L.CONV3D_STRIDE1, fold_bn(b0.bn1))
-        put("b0c2", b0.conv2.weight, L.CONV3D_STRIDE1, fold_bn(b0.bn2))
-        put("b1c1", b1.conv1.weight, L.CONV3D_STRIDE2, fold_bn(b1.bn1))
-        put("b1down", center_tap_weight(b1.downsample[0].weight.detach()), L.CONV3D_STRIDE2, fold_bn(b1.downsample[1]))
-        put("b1c2", b1.conv2.weight, L.CONV3D_STRIDE1, fold_bn(b1.bn2))
-        put("deconv", deconv.weight, L.DECONV3D_STRIDE2, one(8))
         wa, wb = split_concat_weight(post.weight.detach())
-        put("post_a", wa, L.CONV3D_STRIDE1, one(8))
-        put("post_b", wb, L.CONV3D_STRIDE1, one(8))
-        self._packed, self._packed_key = pk, key
-        return pk
+        return {"b0c1": Conv3dLayer.pack(b0.conv1.weight, L.CONV3D_STRIDE1, bn=b0.bn1),
+                "b0c2": Conv3dLayer.pack(b0.conv2.weight, L.CONV3D_STRIDE1, bn=b0.bn2),
+                "b1c1": Conv3dLayer.pack(b1.conv1.weight, L.CONV3D_STRIDE2, bn=b1.bn1),
+                "b1down": Conv3dLayer.pack(center_tap_weight(b1.downsample[0].weight.detach()), L.CONV3D_STRIDE2, bn=b1.downsample[1]),
+                "b1c2": Conv3dLayer.pack(b1.conv2.weight, L.CONV3D_STRIDE1, bn=b1.bn2),
+                "deconv": Conv3dLayer.pack(deconv.weight, L.DECONV3D_STRIDE2),
+                "post_a": Conv3dLayer.pack(wa, L.CONV3D_STRIDE1),
+                "post_b": Conv3dLayer.pack(wb, L.CONV3D_STRIDE1)}
 
     @ops.inference_only
     def forward_channels_last(self, x, mark=None):
@@ -230,20 +214,16 @@ class Reg3d(nn.Module):
             raise ValueError(f"the Vis-MVSNet regulariser needs (B,D,h,w,8) with even D, h, w, got {tuple(x.shape)}")
         pk = self._prepare()
 
-        def layer(name, t, relu=True, skip=None):
-            w, cin, cout, scale, shift, mode = pk[name]
-            return ops.conv3d_bn_relu(t, w, cin, cout, scale, shift, mode, relu=relu, skip=skip)
-
         def relu_(t):
             t = torch.relu_(t)
             if mark is not None:
                 mark("relu")
             return t
 
-        e0 = relu_(layer("b0c2", layer("b0c1", x), relu=False, skip=x))
-        e1 = relu_(layer("b1c2", layer("b1c1", e0), relu=False, skip=layer("b1down", e0, relu=False)))
-        up = layer("deconv", e1, relu=False)
-        return layer("post_b", e0, relu=False, skip=layer("post_a", up, relu=False))
+        e0 = relu_(pk["b0c2"](pk["b0c1"](x), relu=False, skip=x))
+        e1 = relu_(pk["b1c2"](pk["b1c1"](e0), relu=False, skip=pk["b1down"](e0, relu=False)))
+        up = pk["deconv"](e1, relu=False)
+        return pk["post_b"](e0, relu=False, skip=pk["post_a"](up, relu=False))
 
 
 class RegPair(nn.Module):
@@ -272,12 +252,6 @@ class UncertNet(nn.Module):
         return [conv(out) for conv in self.head_convs]
 
 
-def _final_conv(conv):
-    """An 8 -> 1 convolution without BN as conv3d_bn_relu's arguments."""
-    w, cin, cout = ops.pack_conv3d_weights(conv.weight.detach(), L.CONV3D_STRIDE1)
-    return w, cin, cout, torch.ones(1, device=w.device), torch.zeros(1, device=w.device), L.CONV3D_STRIDE1
-
-
 def scale_camera(cam, scale):
     """blocks/utils.py:189-218: cam (B,2,4,4) [extrinsic; intrinsic] with the two focal lengths and the principal point times
     `scale`; every other entry, the skew included, as it is."""
@@ -287,7 +261,7 @@ def scale_camera(cam, scale):
     return cam
 
 
-class SingleStage(nn.Module):
+class SingleStage(PackedWeights, nn.Module):
     """vis_mvsnet_singlestage.py:78-348 on the engine (see the module's header)."""
 
     def __init__(self):
@@ -296,29 +270,25 @@ class SingleStage(nn.Module):
         self.reg_fuse = Reg3d("reg2", final=True)
         self.reg_pair = RegPair()
         self.uncert_net = UncertNet(2)
-        self._final = None
-        self._final_key = None
 
-    def _finals(self):
-        convs = (self.reg_pair.final_conv, self.reg_fuse.final_conv)
-        key = tuple((c.weight.data_ptr(), c.weight._version) for c in convs)
-        if self._final is None or self._final_key != key:
-            self._final, self._final_key = [_final_conv(c) for c in convs], key
-        return self._final
+    def _packed_from(self):
+        return self.reg_pair.final_conv, self.reg_fuse.final_conv
+
+    def _pack(self):
+        """The two 8 -> 1 convolutions without BN: (reg_pair's, reg_fuse's)."""
+        return [Conv3dLayer.pack(conv.weight, L.CONV3D_STRIDE1) for conv in self._packed_from()]
 
     @ops.inference_only
     def pair_scores(self, volumes, mark=None):
         """volumes (M,D,h,w,8) channel-last, the cost volumes of M pairs -> (interm (M,D,h,w,8), score (M,D,h,w)): Reg, reg_pair."""
         interm = self.reg.forward_channels_last(volumes, mark)
-        w, cin, cout, scale, shift, mode = self._finals()[0]
-        return interm, ops.conv3d_bn_relu(interm, w, cin, cout, scale, shift, mode, relu=False).squeeze(-1)
+        return interm, self._prepare()[0](interm, relu=False).squeeze(-1)
 
     @ops.inference_only
     def fused_score(self, fused, mark=None):
         """fused (B,D,h,w,8) channel-last -> score (B,D,h,w): RegFuse."""
         out = self.reg_fuse.forward_channels_last(fused, mark)
-        w, cin, cout, scale, shift, mode = self._finals()[1]
-        return ops.conv3d_bn_relu(out, w, cin, cout, scale, shift, mode, relu=False).squeeze(-1)
+        return self._prepare()[1](out, relu=False).squeeze(-1)
 
     @ops.inference_only
     def forward(self, key_feat, src_feats, ref_cam, srcs_cam, depth_num, depth_start, depth_interval, s_scale, mark=None):
