@@ -730,6 +730,38 @@ int mvd_voxel_reduce_f32(const long long* keys, const long long* perm, const flo
                          mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Point-cloud registration (ICP): the per-iteration work around mvd_cloud_nearest_f32.  The reference has NO counterpart: the
+ * definition is robustmvd_amd/cloud_register.py (transform_numpy, pair_sums_numpy) and DESIGN.md.
+ *
+ * transform: 12 doubles ON THE HOST, the rows of [M | t], all finite; it travels with the launch.  A point moves as
+ *   q_a = float32(((M[a,0] x + M[a,1] y) + M[a,2] z) + t[a])   in float64 in exactly this order, rounded once;
+ * a row with a non-finite coordinate before or after the move becomes (NaN, NaN, NaN) with the bits 0x7fc00000.  A normal goes
+ * through M alone (the same order) and is divided by its float64 length; an invalid or vanishing one becomes (0, 0, 0).
+ * normals / out_normals: both or neither NULL. */
+int mvd_cloud_transform_f32(const float* points, const float* normals, long long n, const double* transform, float* out_points,
+                            float* out_normals, mvd_stream_t stream);
+
+/* mvd_cloud_grid_build_f32 of the MOVED points: sorted position i holds T(points[perm[i]]) and perm[i]'s bits; the moved cloud is
+ * never stored in its own order. */
+int mvd_cloud_transform_records_f32(const float* points, const long long* perm, long long n, const double* transform, float* records,
+                                    mvd_stream_t stream);
+
+/* The sums of one ICP iteration.  Source point i pairs with target j = index[i] (mvd_cloud_nearest_f32's, in the source's original
+ * order) when 0 <= j < m, q_i = T(source_i) (recomputed: the records' bits) and target_j are valid and, with target_normals, that
+ * normal is finite and not (0,0,0).  With c = pivot, a = double(q_i) - c, b = double(target_j) - c, d = a - b, all float64:
+ *   target_normals == NULL: N; sum a (3); sum b (3); sum a_r b_c (9, row-major); sum (a_x a_x + a_y a_y) + a_z a_z; the same of b; of d
+ *   else, u = double(normal_j), r = (d_x u_x + d_y u_y) + d_z u_z, J = (a_y u_z - a_z u_y, a_z u_x - a_x u_z, a_x u_y - a_y u_x, u):
+ *                           N; sum J_i J_k for i <= k (21, row-major); sum J_k r (6); sum r r
+ * result (256 bytes, device, 8-byte aligned): N as int64, then the doubles in this order, then zeros.  Every workgroup adds
+ * MVD_CLOUD_PAIR_SUMS_PER_WORKGROUP consecutive points in a fixed order and one workgroup adds the partials: no atomics, two calls give
+ * the same bits; n == 0 or no pair writes zeros.  workspace: mvd_cloud_pair_sums_workspace_bytes(n). */
+#define MVD_CLOUD_PAIR_SUMS_PER_WORKGROUP 2048
+size_t mvd_cloud_pair_sums_workspace_bytes(long long n);
+int mvd_cloud_pair_sums_f32(const float* source, long long n, const double* transform, const int* index, const float* target,
+                            const float* target_normals, long long m, double pivot_x, double pivot_y, double pivot_z, void* result,
+                            void* workspace, size_t workspace_bytes, mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * TSDF volume: the views' depth maps averaged into a truncated signed distance volume, and its surface as a triangle mesh.  The
  * reference has NO counterpart: the definition is robustmvd_amd/tsdf.py (its docstring, integrate_numpy, extract_numpy) and DESIGN.md.
  *

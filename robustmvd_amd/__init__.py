@@ -25,6 +25,8 @@ from .depth_fusion import DepthFusion, fuse_numpy, merge_numpy, normals_numpy, w
 from . import cloud_eval  # noqa: F401,E402
 from .cloud_eval import (PointCloudEvaluation, CloudScore, evaluate_scene, read_ply, nearest_numpy,  # noqa: F401,E402
                          cloud_scores_numpy, voxel_downsample_numpy)
+from . import cloud_register  # noqa: F401,E402
+from .cloud_register import register_clouds, register_numpy, Registration  # noqa: F401,E402
 from . import tsdf  # noqa: F401,E402
 from .tsdf import TSDFVolume, Mesh, integrate_numpy, extract_numpy, bounds_from_points  # noqa: F401,E402
 from . import render  # noqa: F401,E402

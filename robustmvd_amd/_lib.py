@@ -167,6 +167,11 @@ SIGNATURES = {
     "mvd_voxel_reduce_workspace_bytes": (_sz, [ctypes.c_longlong]),
     "mvd_voxel_reduce_f32": (_i, [ctypes.c_void_p] * 2 + [_c_float_p] * 2 + [ctypes.c_longlong, _c_float_p, _c_float_p]
                              + [ctypes.c_void_p] * 3 + [_sz, ctypes.c_void_p]),
+    "mvd_cloud_transform_f32": (_i, [_c_float_p, _c_float_p, ctypes.c_longlong, ctypes.c_void_p, _c_float_p, _c_float_p, ctypes.c_void_p]),
+    "mvd_cloud_transform_records_f32": (_i, [_c_float_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, _c_float_p, ctypes.c_void_p]),
+    "mvd_cloud_pair_sums_workspace_bytes": (_sz, [ctypes.c_longlong]),
+    "mvd_cloud_pair_sums_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p,
+                                     ctypes.c_longlong] + [ctypes.c_double] * 3 + [ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
     "mvd_tsdf_integrate_f32": (_i, [_c_float_p] * 3 + [_i] * 3 + [_pp] * 3 + [_c_float_p, _i, _i, _i, ctypes.c_float, ctypes.c_float,
                                                                             ctypes.c_void_p]),
     "mvd_tsdf_extract_workspace_bytes": (_sz, [_i] * 3),
@@ -183,6 +188,7 @@ CULL_NONE, CULL_BACK, CULL_FRONT = 0, 1, 2  # MVD_CULL_*
 RENDER_LOAD_FIRST, RENDER_KEEP_PROJECT, RENDER_KEEP_KEYS, RENDER_NO_RESOLVE = 1, 16, 32, 64  # MVD_RENDER_*
 MESH_RENDER_MAX_SMALL = 64  # ops.mesh_render's default threshold between the lane and the wave path (profiles/mesh_render.txt)
 MVD_CLOUD_MAX_THRESHOLDS = 8
+MVD_CLOUD_PAIR_SUMS_PER_WORKGROUP = 2048  # the points one workgroup of mvd_cloud_pair_sums_f32 adds: its tests sit on the edges
 
 # built into the product library only (csrc/Makefile PRODSRCS): the experiments library has no variants of these
 PRODUCT_ONLY = ("mvd_sweep_reduce_backward_workspace_bytes", "mvd_sweep_reduce_backward_f32")

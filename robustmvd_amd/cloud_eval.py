@@ -99,7 +99,8 @@ class CloudScore:
     """accuracy, completeness, overall: floats; precision, recall, fscore: (T,) float64 over the thresholds; n_pred, n_gt: the valid
     points of the evaluated prediction (after thinning) and of the ground truth; dist_pred (n,), dist_gt (m,) float32: the truncated
     distances per point, for colouring an error cloud (GPU tensors on the device path); pred_points, pred_colors: the evaluated
-    prediction, i.e. the thinned cloud that dist_pred belongs to."""
+    prediction, i.e. the thinned (and, with align, registered) cloud that dist_pred belongs to; registration: the
+    cloud_register.Registration that aligned it, or None."""
     accuracy: float
     completeness: float
     overall: float
@@ -114,6 +115,7 @@ class CloudScore:
     max_dist: float
     pred_points: object = None
     pred_colors: object = None
+    registration: object = None
 
 
 def _combine(sum_p, n_p, cnt_p, sum_g, n_g, cnt_g, **fields):
@@ -198,32 +200,64 @@ class PointCloudEvaluation:
         score = evaluation(out.points, gt_points, out.colors)                       # out = DepthFusion(...).reconstruct(...)
         score.fscore, score.accuracy, score.dist_pred
 
-    max_dist defaults to 4 x the largest threshold.  With voxel, the prediction is thinned first (its colours with it)."""
+    max_dist defaults to 4 x the largest threshold.  With voxel, the prediction is thinned first (its colours with it).
+    align = "rigid", "similarity" or "plane": the thinned prediction is registered onto the ground truth first
+    (cloud_register.register_clouds, at the radii align_max_dist, by default (4, 2, 1) x max_dist; "plane" needs gt_normals (m,3), given
+    here or per call) and the ALIGNED prediction is scored; the score's `registration` tells how it went."""
 
-    def __init__(self, thresholds, max_dist=None, voxel=None):
+    def __init__(self, thresholds, max_dist=None, voxel=None, align=None, align_max_dist=None, gt_normals=None):
         self.thresholds, self.max_dist = _thresholds(thresholds, max_dist)
         if voxel is not None and not (np.float32(voxel) > 0 and np.isfinite(np.float32(voxel))):
             raise ValueError(f"voxel must be finite and > 0, got {voxel}")
         self.voxel = None if voxel is None else float(np.float32(voxel))
+        self.align, self.align_max_dist, self.gt_normals = align, None, gt_normals
+        if align is not None:
+            from .cloud_register import MODES, _radii
+            if align not in MODES:
+                raise ValueError(f"align must be None or one of {MODES}, got {align!r}")
+            self.align_max_dist = _radii([4.0 * self.max_dist, 2.0 * self.max_dist, self.max_dist] if align_max_dist is None
+                                         else align_max_dist)
+        elif align_max_dist is not None or gt_normals is not None:
+            raise ValueError("align_max_dist and gt_normals belong to align=...")
 
-    def __call__(self, pred_points, gt_points, pred_colors=None):
+    def _register(self, pred, gt, gt_normals):
+        """-> (the aligned prediction, the Registration), or (pred, None) without align"""
+        if self.align is None:
+            if gt_normals is not None:
+                raise ValueError("gt_normals belong to align=...")
+            return pred, None
+        from .cloud_register import register_clouds
+        normals = self.gt_normals if gt_normals is None else gt_normals
+        if self.align == "plane" and normals is None:
+            raise ValueError("align='plane' needs gt_normals")
+        if normals is not None and _place(normals) != _place(gt):
+            if _place(gt) == "host":
+                normals = _to_numpy(normals)
+            else:
+                import torch
+                normals = torch.as_tensor(_to_numpy(normals), dtype=torch.float32).to(gt.device)
+        reg = register_clouds(pred, gt, self.align_max_dist, mode=self.align, target_normals=normals if self.align == "plane" else None)
+        return reg.apply(pred), reg
+
+    def __call__(self, pred_points, gt_points, pred_colors=None, gt_normals=None):
         """pred_points (n,3), gt_points (m,3), pred_colors (n,3) or None: numpy arrays or torch tensors.  Clouds on the GPU run the HIP
         kernels and the result's dist_pred / dist_gt / pred_points are GPU tensors; clouds on the host run the numpy specification.
         Both clouds must be in the same place: a mixed pair raises instead of being moved silently (colours follow the points)."""
         places = {_place(pred_points), _place(gt_points)}
         if len(places) != 1:
             raise ValueError(f"the predicted and the ground-truth cloud are in different places ({sorted(places)}): move them to one first")
-        return (self._run_host if places == {"host"} else self._run_device)(pred_points, gt_points, pred_colors)
+        return (self._run_host if places == {"host"} else self._run_device)(pred_points, gt_points, pred_colors, gt_normals)
 
-    def _run_host(self, pred, gt, colors):
+    def _run_host(self, pred, gt, colors, gt_normals=None):
         pred, gt = _points(pred, "pred_points"), _points(gt, "gt_points")
         if self.voxel is not None:
             pred, colors, _ = voxel_downsample_numpy(pred, self.voxel, colors)
+        pred, reg = self._register(pred, gt, gt_normals)
         score = cloud_scores_numpy(pred, gt, self.thresholds, self.max_dist)
-        score.pred_colors = colors
+        score.pred_colors, score.registration = colors, reg
         return score
 
-    def _run_device(self, pred, gt, colors):
+    def _run_device(self, pred, gt, colors, gt_normals=None):
         import torch
         from . import ops
         dev = pred.device
@@ -235,6 +269,7 @@ class PointCloudEvaluation:
         if self.voxel is not None:
             pred, colors, _ = ops.voxel_downsample(pred, self.voxel, colors)
         pred, gt = ops._cloud_points(pred, "pred_points"), ops._cloud_points(gt, "gt_points", dev)
+        pred, reg = self._register(pred, gt, gt_normals)
         md, T = float(self.max_dist), len(self.thresholds)
         cell = md * ops.CLOUD_CELL_MARGIN
         # one grid for both clouds: each is sorted once and serves as the queries of one direction and the targets of the other
@@ -251,13 +286,15 @@ class PointCloudEvaluation:
         sp, np_, cp = ops.cloud_scores_read(blocks[0], T)
         sg, ng, cg = ops.cloud_scores_read(blocks[1], T)
         return _combine(sp, np_, cp, sg, ng, cg, dist_pred=dp, dist_gt=dg, thresholds=self.thresholds, max_dist=md, pred_points=pred,
-                        pred_colors=colors)
+                        pred_colors=colors, registration=reg)
 
 
-def evaluate_scene(model, images, intrinsics, poses, gt_points, fusion=None, num_sources=None, evaluation=None, **evaluation_args):
+def evaluate_scene(model, images, intrinsics, poses, gt_points, fusion=None, num_sources=None, evaluation=None, gt_normals=None,
+                   **evaluation_args):
     """model -> depth maps -> fused cloud -> CloudScore: DepthFusion.reconstruct chained into PointCloudEvaluation, so that a registered
     model reaches the fusion and the scoring kernels end to end.  images, intrinsics, poses, num_sources: reconstruct's; fusion: a
-    DepthFusion (default DepthFusion()); evaluation: a PointCloudEvaluation, or its arguments as keywords (thresholds=..., voxel=...).
+    DepthFusion (default DepthFusion()); evaluation: a PointCloudEvaluation, or its arguments as keywords (thresholds=..., voxel=...,
+    align=..., align_max_dist=...); gt_normals: the ground truth's normals for align="plane".
     The scene is fused where reconstruct puts it (the model's GPU; a ground truth that is a GPU tensor asks for its device) and the
     ground truth is taken there."""
     if evaluation is None:
@@ -274,7 +311,7 @@ def evaluate_scene(model, images, intrinsics, poses, gt_points, fusion=None, num
     elif _place(gt_points) != _place(out.points):
         import torch
         gt_points = torch.as_tensor(_to_numpy(gt_points), dtype=torch.float32).to(out.points.device)
-    return evaluation(out.points, gt_points, out.colors)
+    return evaluation(out.points, gt_points, out.colors, gt_normals=gt_normals)
 
 
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",

@@ -6,6 +6,7 @@ The first part holds the inference entry points: an input that requires grad whi
 (see inference_only).  The second part holds their differentiable forms (*_autograd), torch.autograd.Function wrappers
 whose backward runs the engine's gradient kernels.
 """
+import ctypes
 import functools
 import itertools
 
@@ -1144,6 +1145,99 @@ def cloud_scores_read(result, T):
     """cloud_scores' block on the host -> (sum float, valid int, counts (T,) int64 numpy): the one read of a direction."""
     r = result.cpu()
     return float(r[:1].view(torch.float64)[0]), int(r[1]), r[2:2 + T].numpy().copy()
+
+
+CLOUD_PAIR_SUMS_PER_WG = L.MVD_CLOUD_PAIR_SUMS_PER_WORKGROUP  # the points one workgroup of cloud_pair_sums adds
+CLOUD_PAIR_SUMS_WORDS = 32  # cloud_pair_sums' block: 256 bytes
+
+
+def _transform12(transform):
+    """A (4,4) or (3,4) transform [M | t] (cloud_register.py) -> the 12 finite doubles the C entries take, as a ctypes array."""
+    from .cloud_register import _affine
+    M, t = _affine(transform)
+    return (ctypes.c_double * 12)(*[float(v) for a in range(3) for v in (M[a, 0], M[a, 1], M[a, 2], t[a])])
+
+
+@inference_only
+def cloud_transform(points, transform, normals=None):
+    """points (n,3) through x -> M x + t in float64, rounded once (include/mvd.h: mvd_cloud_transform_f32; bit for bit
+    cloud_register.transform_numpy) -> (n,3) float32, or (points, normals) with the normals (n,3) through M and re-normalised."""
+    p = _cloud_points(points, "points")
+    n, dev = p.shape[0], p.device
+    T = _transform12(transform)
+    nrm = L.as_f32(normals, "normals", (n, 3), dev) if normals is not None else None
+    out = torch.empty_like(p)
+    out_n = torch.empty_like(p) if nrm is not None else None
+    call("mvd_cloud_transform_f32", dev, p, nrm, n, T, out, out_n)
+    return out if nrm is None else (out, out_n)
+
+
+@inference_only
+def cloud_transform_records(points, perm, transform):
+    """cloud_grid's records of the MOVED points (include/mvd.h: mvd_cloud_transform_records_f32): sorted position i holds
+    T(points[perm[i]]) and perm[i].  perm (n) int64: the permutation of a stable sort of the cell keys -> records (n,4) float32."""
+    p = _cloud_points(points, "points")
+    n, dev = p.shape[0], p.device
+    perm = L.as_dtype(torch.int64, False, perm, "perm", (n,), dev)
+    records = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    call("mvd_cloud_transform_records_f32", dev, p, perm, n, _transform12(transform), records)
+    return records
+
+
+@inference_only
+def cloud_nearest_records(records, grid, max_dist):
+    """cloud_nearest for query records (n,4) that are already there (cloud_transform_records): -> (dist (n) float32, index (n) int32)
+    in the order of the records' original indices."""
+    if not isinstance(grid, CloudGrid):
+        raise ValueError(f"grid: expected a CloudGrid (ops.cloud_grid), got {type(grid).__name__}")
+    dev = grid.points.device
+    max_dist = float(torch.tensor(max_dist, dtype=torch.float32))
+    if not 0.0 < max_dist < float("inf"):
+        raise ValueError(f"max_dist must be finite and > 0, got {max_dist}")
+    if grid.cell < max_dist * CLOUD_CELL_MARGIN * (1 - 1e-12):
+        raise ValueError(f"the grid's cell {grid.cell:g} is below max_dist * (1 + 2^-10) = {max_dist * CLOUD_CELL_MARGIN:g}")
+    rec = L.as_dtype(torch.float32, False, records, "records", device=dev)
+    if rec.dim() != 2 or rec.shape[1] != 4:
+        raise ValueError(f"records must be (n,4), got {tuple(rec.shape)}")
+    n, m = rec.shape[0], grid.points.shape[0]
+    dist = torch.empty(n, dtype=torch.float32, device=dev)
+    index = torch.empty(n, dtype=torch.int32, device=dev)
+    call("mvd_cloud_nearest_f32", dev, rec, n, grid.records, grid.keys, m, grid.origin[0], grid.origin[1], grid.origin[2], grid.inv,
+         max_dist, dist, index)
+    return dist, index
+
+
+@inference_only
+def cloud_pair_sums(source, transform, index, target, pivot, target_normals=None, result=None):
+    """The sums of one ICP iteration (include/mvd.h: mvd_cloud_pair_sums_f32; cloud_register.pair_sums_numpy).  source (n,3), index
+    (n) int32 from cloud_nearest of the moved source, target (m,3), pivot: 3 numbers, target_normals (m,3): plane mode.  Returns a
+    device int64 tensor of 32 words, left on the device: the count of pairs, then the bits of the float64 sums (read it with
+    cloud_pair_sums_read)."""
+    s = _cloud_points(source, "source")
+    n, dev = s.shape[0], s.device
+    idx = L.as_dtype(torch.int32, False, index, "index", (n,), dev)
+    p = _cloud_points(target, "target", dev)
+    m = p.shape[0]
+    nrm = L.as_f32(target_normals, "target_normals", (m, 3), dev) if target_normals is not None else None
+    if nrm is not None and m == 0:
+        nrm = torch.zeros((1, 3), dtype=torch.float32, device=dev)  # plane mode is told by a pointer: one row nobody reads
+    c = _cloud_origin(pivot, "pivot")
+    if result is None:
+        result = torch.empty(CLOUD_PAIR_SUMS_WORDS, dtype=torch.int64, device=dev)
+    elif result.dtype != torch.int64 or result.device != dev or result.numel() != CLOUD_PAIR_SUMS_WORDS or not result.is_contiguous():
+        raise ValueError(f"result must be {CLOUD_PAIR_SUMS_WORDS} contiguous int64 on the source's device")
+    nbytes = L.load().mvd_cloud_pair_sums_workspace_bytes(n)
+    ws = workspace(nbytes, dev)
+    call("mvd_cloud_pair_sums_f32", dev, s, n, _transform12(transform), idx, p if m else None, nrm, m, c[0], c[1], c[2], result, ws,
+         int(nbytes))
+    return result
+
+
+def cloud_pair_sums_read(result, plane):
+    """cloud_pair_sums' block on the host -> (N int, sums (18,) or (28,) float64 numpy): the one read of an iteration."""
+    r = result.cpu()
+    k = 28 if plane else 18
+    return int(r[0]), r[1:1 + k].view(torch.float64).numpy().copy()
 
 
 @inference_only
