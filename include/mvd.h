@@ -845,6 +845,87 @@ int mvd_mesh_render_f32(const float* vertices, long long M, const int* triangles
                         int* triangle, float* bary, float* out_colors, float* normals, void* workspace, size_t workspace_bytes,
                         mvd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Mesh clean-up: the connected components of a triangle mesh, their table, the filter that drops components, and area-weighted
+ * vertex normals.  The reference has NO counterpart: the definition is robustmvd_amd/mesh_clean.py (components_numpy,
+ * component_table_numpy, clean_numpy, vertex_normals_numpy) and DESIGN.md.
+ *
+ * triangles (T,3) int32 with 0 <= index < M (the caller checks the range; a triangle with an index outside it is skipped by every
+ * entry), vertices (M,3) float32; M, T <= 2^31 - 1.  Two vertices are connected when a triangle names both; degenerate and duplicate
+ * triangles connect like any other.  Every kernel is one bounded pass: none waits for another thread, the rounds are the caller's
+ * loop.  The only atomics are 32-bit integer min / add; every float64 sum has a fixed order: two calls give the same bits.
+ *
+ * mvd_mesh_hook_round: one round of min-label hooking with pointer jumping on label (M) int32.  flags: MVD_MESH_ROUND_FIRST starts a
+ * labelling: label[v] = v and referenced[v] = 0, and the hook pass stores the byte 1 in referenced (M) for every vertex a triangle names.
+ * Hook, per triangle (a,b,c): m = min over x of label[label[x]], lowered with atomicMin into label[label[x]] and label[x].  Shortcut,
+ * per vertex: label[v] = label[label[v]].  Labels only decrease and every value is a vertex of the same component
+ * (csrc/mesh_clean.hip).  changed (device, 4-byte aligned) is zeroed and receives 1 when a word changed.  The caller repeats the
+ * round until changed stays 0, at most 2 ceil(log2(max(M,2))) + 4 times (mesh_clean.py: MAX_ROUNDS); then label[v] is the lowest
+ * vertex index of v's component, a unique fixed point.  T == 0: one call, label[v] = v.  For measurements, the two launches apart:
+ * MVD_MESH_ROUND_NO_SHORTCUT runs the hook alone (changed is zeroed first, as in a whole round), MVD_MESH_ROUND_NO_HOOK the shortcut
+ * alone, which leaves changed as it is and only raises it: the two calls in this order are one round. */
+#define MVD_MESH_ROUND_FIRST 1
+#define MVD_MESH_ROUND_NO_HOOK 2
+#define MVD_MESH_ROUND_NO_SHORTCUT 4
+int mvd_mesh_hook_round(const int* triangles, long long T, long long M, int flags, int* label, unsigned char* referenced, int* changed,
+                        mvd_stream_t stream);
+
+/* From a converged labelling: the roots (referenced, label[v] == v) ranked in ascending vertex order give the component ids
+ * 0 .. C-1; vertex_component (M) int32 = the id of label[v], -1 for an unreferenced vertex; num_components (device, 8-byte aligned)
+ * receives C.  compact.h's ballot counts and two-level scan: no atomic decides an id.
+ * workspace: mvd_mesh_component_rank_workspace_bytes(M), 256-byte aligned. */
+size_t mvd_mesh_component_rank_workspace_bytes(long long M);
+int mvd_mesh_component_rank(const int* label, const unsigned char* referenced, long long M, int* vertex_component,
+                            long long* num_components, void* workspace, size_t workspace_bytes, mvd_stream_t stream);
+
+/* triangle_component (T) int32 = the component of the triangle's first vertex; num_vertices (C) int32 = the vertices of each
+ * component (zeroed here; integer adds, one per wave and distinct component).  C: what mvd_mesh_component_rank gave. */
+int mvd_mesh_component_table(const int* vertex_component, const int* triangles, long long T, long long M, long long C,
+                             int* triangle_component, int* num_vertices, mvd_stream_t stream);
+
+/* The fixed-order sums.  Between mvd_mesh_component_table and this entry the caller sorts triangle_component STABLY and keeps the
+ * permutation: sorted_component (T) int32 ascending, perm (T) int64, perm[p] = the triangle at sorted position p.
+ * num_triangles (C) int32 = the length of each component's segment.  area (C) float64, 8-byte aligned: the sum of the component's
+ * triangle areas.  A triangle's area: e1 = p1 - p0, e2 = p2 - p0 in float64 from the float32 coordinates,
+ * n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), area = 0.5 sqrt((nx nx + ny ny) + nz nz), one rounding per operation,
+ * 0 where that is not finite.  A segment of at most 64 triangles is added in ascending triangle order by one lane.  A longer one by
+ * a wave: the sorted positions are cut at multiples of 2048; a block of 2048 that lies inside the segment enters as its own sum
+ * (256 interleaved partial sums, a xor tree per wave, the four waves in order); lane l adds items l, l + 64, ... of the segment's
+ * head, its blocks and its tail, and the 64 sums meet in a xor tree.  The order depends on the segment's bounds alone.
+ * workspace: mvd_mesh_component_sums_workspace_bytes(T, C), 256-byte aligned. */
+size_t mvd_mesh_component_sums_workspace_bytes(long long T, long long C);
+int mvd_mesh_component_sums_f64(const float* vertices, long long M, const int* triangles, long long T, const int* sorted_component,
+                                const long long* perm, long long C, int* num_triangles, double* area, void* workspace,
+                                size_t workspace_bytes, mvd_stream_t stream);
+
+/* The filter.  A triangle stays when keep_component[triangle_component[t]] != 0 (keep_component (C) bytes; NULL: every triangle
+ * stays, and triangle_component is not read).  A vertex stays when a kept triangle names it, or, with remove_unreferenced == 0,
+ * always.  Kept triangles and kept vertices keep their order: two compact.h compactions with exact sizes, no atomic decides a
+ * position.  One entry, two uses, as mvd_tsdf_extract_f32.  With out_triangles == NULL (then kept_triangles and vertex_remap too) it
+ * counts only.  With them it also writes vertex_remap (M) int32: the new index of a vertex or -1;  kept_triangles: the old index of
+ * each kept triangle;  out_triangles: its indices through the remap; a slot at or past max_triangles is not written.  counts
+ * (device, 16-byte aligned) always receives two int64: the kept vertices and the kept triangles.  counted != 0: the workspace still
+ * holds the counts of an earlier call with these arguments, and they are not formed again.
+ * workspace: mvd_mesh_filter_workspace_bytes(M, T), 256-byte aligned. */
+size_t mvd_mesh_filter_workspace_bytes(long long M, long long T);
+int mvd_mesh_filter(const int* triangles, long long T, long long M, const int* triangle_component, const unsigned char* keep_component,
+                    long long C, int remove_unreferenced, int counted, int* out_triangles, int* kept_triangles, int* vertex_remap,
+                    long long max_triangles, long long* counts, void* workspace, size_t workspace_bytes, mvd_stream_t stream);
+
+/* A per-vertex array through the remap: dst[vertex_remap[v]] = src[v], rows of k float32 (1 <= k <= 65536), bit for bit, for every
+ * v with 0 <= vertex_remap[v] < max_rows.  src (M,k), dst (max_rows,k).  One lane per value: M k <= 2^31 - 1. */
+int mvd_mesh_gather_rows_f32(const float* src, const int* vertex_remap, long long M, int k, long long max_rows, float* dst,
+                             mvd_stream_t stream);
+
+/* Area-weighted vertex normals.  The caller sorts the 3 T corner keys triangles[t][k] STABLY: sorted_vertex (3T) int32 ascending,
+ * perm (3T) int64, perm[p] = the corner 3 t + k at sorted position p.  normals (M,3) float32 = the sum over the vertex's corners, in
+ * ascending (t, k) order, of the un-normalised cross product n of triangle t (mvd_mesh_component_sums_f64's), in float64, divided by
+ * its length sqrt((sx sx + sy sy) + sz sz) and rounded to float32; (0,0,0) where the length is zero or not finite or no triangle
+ * names the vertex.  A triangle that names a vertex twice adds twice.  One lane per vertex: a binary search for its run, then the
+ * run in order.  No atomics.  3 T <= 2^31 - 1. */
+int mvd_mesh_vertex_normals_f32(const float* vertices, long long M, const int* triangles, long long T, const int* sorted_vertex,
+                                const long long* perm, float* normals, mvd_stream_t stream);
+
 /* layout helpers used at the operator-level boundary (reference tensors are NCHW / NCDHW) */
 int mvd_nchw_to_nhwc_f32(const float* src, float* dst, int N, int C, long long HW, mvd_stream_t stream);
 int mvd_nhwc_to_nchw_f32(const float* src, float* dst, int N, int C, long long HW, mvd_stream_t stream);

@@ -31,3 +31,6 @@ from . import tsdf  # noqa: F401,E402
 from .tsdf import TSDFVolume, Mesh, integrate_numpy, extract_numpy, bounds_from_points  # noqa: F401,E402
 from . import render  # noqa: F401,E402
 from .render import render_mesh, render_numpy, RenderResult  # noqa: F401,E402
+from . import mesh_clean  # noqa: F401,E402
+from .mesh_clean import (mesh_components, clean_mesh, vertex_normals, components_numpy, component_table_numpy, clean_numpy,  # noqa: F401,E402
+                         vertex_normals_numpy, MeshComponents, CleanResult)

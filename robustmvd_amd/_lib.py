@@ -183,10 +183,28 @@ SIGNATURES = {
     "mvd_mesh_render_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, _c_float_p, _c_float_p, _i, _i, _i,
                                  ctypes.c_float, _i, _i, _i, _c_float_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p,
                                  ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "mvd_mesh_hook_round": (_i, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, _i] + [ctypes.c_void_p] * 4),
+    "mvd_mesh_component_rank_workspace_bytes": (_sz, [ctypes.c_longlong]),
+    "mvd_mesh_component_rank": (_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "mvd_mesh_component_table": (_i, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_longlong] * 3 + [ctypes.c_void_p] * 3),
+    "mvd_mesh_component_sums_workspace_bytes": (_sz, [ctypes.c_longlong, ctypes.c_longlong]),
+    "mvd_mesh_component_sums_f64": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _sz,
+                                         ctypes.c_void_p]),
+    "mvd_mesh_filter_workspace_bytes": (_sz, [ctypes.c_longlong, ctypes.c_longlong]),
+    "mvd_mesh_filter": (_i, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
+                             ctypes.c_longlong, _i, _i] + [ctypes.c_void_p] * 3 + [ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
+                                                                                   _sz, ctypes.c_void_p]),
+    "mvd_mesh_gather_rows_f32": (_i, [_c_float_p, ctypes.c_void_p, ctypes.c_longlong, _i, ctypes.c_longlong, _c_float_p,
+                                      ctypes.c_void_p]),
+    "mvd_mesh_vertex_normals_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                         ctypes.c_void_p, _c_float_p, ctypes.c_void_p]),
 }
 CULL_NONE, CULL_BACK, CULL_FRONT = 0, 1, 2  # MVD_CULL_*
 RENDER_LOAD_FIRST, RENDER_KEEP_PROJECT, RENDER_KEEP_KEYS, RENDER_NO_RESOLVE = 1, 16, 32, 64  # MVD_RENDER_*
 MESH_RENDER_MAX_SMALL = 64  # ops.mesh_render's default threshold between the lane and the wave path (profiles/mesh_render.txt)
+MESH_ROUND_FIRST, MESH_ROUND_NO_HOOK, MESH_ROUND_NO_SHORTCUT = 1, 2, 4  # MVD_MESH_ROUND_*
 MVD_CLOUD_MAX_THRESHOLDS = 8
 MVD_CLOUD_PAIR_SUMS_PER_WORKGROUP = 2048  # the points one workgroup of mvd_cloud_pair_sums_f32 adds: its tests sit on the edges
 

@@ -1009,6 +1009,155 @@ def mesh_render(vertices, triangles, matrices, size, colors=None, normals=False,
     return out
 
 
+def _mesh_triangles(triangles, M, name="triangles", device=None):
+    t = L.as_dtype(torch.int32, False, triangles, name, device=device)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name} must be (T,3), got {tuple(t.shape)}")
+    if int(M) < 0 or int(M) >= 2 ** 31 or t.shape[0] >= 2 ** 31:
+        raise ValueError(f"{M} vertices and {t.shape[0]} triangles: both must be in 0 .. 2^31 - 1")
+    return t
+
+
+@inference_only
+def mesh_hook_round(triangles, M, label, referenced, changed, first=False, stages=0):
+    """One round of the component labelling IN PLACE (include/mvd.h: mvd_mesh_hook_round): a hook launch over the triangles and a
+    shortcut launch over the vertices.  triangles (T,3) int32, label (M) int32, referenced (M) uint8, changed: one int32 word on the
+    device, zeroed by the call and 1 after it when a label changed.  first: starts a labelling (label[v] = v, referenced = 0).
+    stages: for measurements (tools/bench_mesh_clean.py), L.MESH_ROUND_NO_HOOK or L.MESH_ROUND_NO_SHORTCUT: one launch of the two."""
+    t = _mesh_triangles(triangles, M)
+    dev = t.device
+    M = int(M)
+    lab = L.as_dtype(torch.int32, False, label, "label", (M,), dev)
+    ref = L.as_dtype(torch.uint8, False, referenced, "referenced", (M,), dev)
+    ch = L.as_dtype(torch.int32, False, changed, "changed", device=dev)
+    if ch.numel() != 1 or not (label.is_contiguous() and referenced.is_contiguous()):
+        raise ValueError("changed must hold one word; label and referenced must be contiguous (they are updated in place)")
+    T = int(t.shape[0])
+    call("mvd_mesh_hook_round", dev, t if T else None, T, M, (L.MESH_ROUND_FIRST if first else 0) | int(stages), lab if M else None,
+         ref if M else None, ch)
+
+
+@inference_only
+def mesh_component_rank(label, referenced):
+    """-> (vertex_component (M) int32: the component of every vertex, ids in ascending order of the components' lowest vertex, -1
+    for an unreferenced vertex; num_components: one int64 left on the device) from a converged labelling (mvd_mesh_component_rank)."""
+    lab = L.as_dtype(torch.int32, False, label, "label")
+    dev, M = lab.device, int(lab.numel())
+    ref = L.as_dtype(torch.uint8, False, referenced, "referenced", (M,), dev)
+    vcomp = torch.empty(M, dtype=torch.int32, device=dev)
+    num = torch.empty(1, dtype=torch.int64, device=dev)
+    nbytes = L.load().mvd_mesh_component_rank_workspace_bytes(M)
+    ws = workspace(nbytes, dev)
+    call("mvd_mesh_component_rank", dev, lab if M else None, ref if M else None, M, vcomp if M else None, num, ws, int(nbytes))
+    return vcomp, num
+
+
+@inference_only
+def mesh_component_table(vertex_component, triangles, C):
+    """-> (triangle_component (T) int32: the component of each triangle's first vertex; num_vertices (C) int32)
+    (mvd_mesh_component_table).  C: mesh_component_rank's count, read by the caller."""
+    vc = L.as_dtype(torch.int32, False, vertex_component, "vertex_component")
+    dev, M = vc.device, int(vc.numel())
+    t = _mesh_triangles(triangles, M, device=dev)
+    T, C = int(t.shape[0]), int(C)
+    tcomp = torch.empty(T, dtype=torch.int32, device=dev)
+    nv = torch.empty(C, dtype=torch.int32, device=dev)
+    call("mvd_mesh_component_table", dev, vc if M else None, t if T else None, T, M, C, tcomp if T else None, nv if C else None)
+    return tcomp, nv
+
+
+@inference_only
+def mesh_component_sums(vertices, triangles, sorted_component, perm, C):
+    """-> (num_triangles (C) int32, area (C) float64): the fixed-order sums over the triangles sorted stably by component
+    (mvd_mesh_component_sums_f64).  sorted_component (T) int32 and perm (T) int64: torch.sort(triangle_component, stable=True)."""
+    v = L.as_f32(vertices, "vertices")
+    dev, M = v.device, int(v.shape[0])
+    if v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"vertices must be (M,3), got {tuple(v.shape)}")
+    t = _mesh_triangles(triangles, M, device=dev)
+    T, C = int(t.shape[0]), int(C)
+    key = L.as_dtype(torch.int32, False, sorted_component, "sorted_component", (T,), dev)
+    pm = L.as_dtype(torch.int64, False, perm, "perm", (T,), dev)
+    nt = torch.empty(C, dtype=torch.int32, device=dev)
+    area = torch.empty(C, dtype=torch.float64, device=dev)
+    if C:
+        nbytes = L.load().mvd_mesh_component_sums_workspace_bytes(T, C)
+        ws = workspace(nbytes, dev)
+        call("mvd_mesh_component_sums_f64", dev, v, M, t, T, key, pm, C, nt, area, ws, int(nbytes))
+    return nt, area
+
+
+@inference_only
+def mesh_filter(triangles, M, triangle_component=None, keep_component=None, remove_unreferenced=True):
+    """The kept triangles and vertices of a mesh (include/mvd.h: mvd_mesh_filter; mesh_clean.clean_numpy is the definition).
+    keep_component (C) uint8 / bool with triangle_component (T) int32, or None for every triangle.  Returns (out_triangles (T',3)
+    int32 re-indexed, kept_triangles (T') int32, vertex_remap (M) int32, M') at their exact sizes: the call counts, M' and T' are read
+    (the call's one synchronisation, 16 bytes), and the second call writes from the counts the workspace still holds."""
+    t = _mesh_triangles(triangles, M)
+    dev, T, M = t.device, int(t.shape[0]), int(M)
+    keep, tcomp, C = None, None, 0
+    if keep_component is not None:
+        keep = L.as_dtype(torch.uint8, True, keep_component, "keep_component", device=dev)
+        C = int(keep.numel())
+        if triangle_component is None:
+            raise ValueError("keep_component needs triangle_component")
+        tcomp = L.as_dtype(torch.int32, False, triangle_component, "triangle_component", (T,), dev)
+        if C == 0:  # told by a pointer: one byte nobody reads
+            keep = torch.zeros(1, dtype=torch.uint8, device=dev)
+    nbytes = L.load().mvd_mesh_filter_workspace_bytes(M, T)
+    ws = workspace(nbytes, dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    head = (t if T else None, T, M, tcomp if T else None, keep, C, int(bool(remove_unreferenced)))
+    call("mvd_mesh_filter", dev, *head, 0, None, None, None, 0, counts, ws, int(nbytes))
+    Mk, Tk = (int(n) for n in counts.tolist())
+    out = torch.empty((Tk, 3), dtype=torch.int32, device=dev)
+    kept = torch.empty(Tk, dtype=torch.int32, device=dev)
+    remap = torch.empty(M, dtype=torch.int32, device=dev)
+    # the pointers tell the second use: one word each where the arrays are empty
+    spare = torch.empty(4, dtype=torch.int32, device=dev)
+    call("mvd_mesh_filter", dev, *head, 1, out if Tk else spare, kept if Tk else spare, remap if M else spare, Tk, counts, ws, int(nbytes))
+    return out, kept, remap, Mk
+
+
+@inference_only
+def mesh_gather_rows(src, vertex_remap, rows):
+    """-> (rows,k) float32: dst[vertex_remap[v]] = src[v] for every kept vertex, bit for bit (mvd_mesh_gather_rows_f32)."""
+    remap = L.as_dtype(torch.int32, False, vertex_remap, "vertex_remap")
+    dev, M = remap.device, int(remap.numel())
+    s = L.as_dtype(torch.float32, False, src, "src", device=dev)
+    if s.dim() != 2 or s.shape[0] != M or not 1 <= s.shape[1] <= 65536:
+        raise ValueError(f"src must be ({M},k) with k in 1 .. 65536, got {tuple(s.shape)}")
+    rows, k = int(rows), int(s.shape[1])
+    if not 0 <= rows <= M:
+        raise ValueError(f"{rows} rows out of {M}")
+    if M * k >= 2 ** 31:
+        raise ValueError(f"src holds {M * k} values: M k must be below 2^31")
+    dst = torch.empty((rows, k), dtype=torch.float32, device=dev)
+    if rows:
+        call("mvd_mesh_gather_rows_f32", dev, s, remap, M, k, rows, dst)
+    return dst
+
+
+@inference_only
+def mesh_vertex_normals(vertices, triangles, sorted_vertex, perm):
+    """-> normals (M,3) float32, area-weighted (include/mvd.h: mvd_mesh_vertex_normals_f32; mesh_clean.vertex_normals_numpy is the
+    definition).  sorted_vertex (3T) int32 and perm (3T) int64: torch.sort(triangles.reshape(-1), stable=True)."""
+    v = L.as_f32(vertices, "vertices")
+    if v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"vertices must be (M,3), got {tuple(v.shape)}")
+    dev, M = v.device, int(v.shape[0])
+    t = _mesh_triangles(triangles, M, device=dev)
+    T = int(t.shape[0])
+    if 3 * T >= 2 ** 31:
+        raise ValueError(f"{T} triangles: 3 T must be below 2^31")
+    key = L.as_dtype(torch.int32, False, sorted_vertex, "sorted_vertex", (3 * T,), dev)
+    pm = L.as_dtype(torch.int64, False, perm, "perm", (3 * T,), dev)
+    normals = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    if M:
+        call("mvd_mesh_vertex_normals_f32", dev, v, M, t if T else None, T, key if T else None, pm if T else None, normals)
+    return normals
+
+
 CLOUD_INDEX_LIMIT = (1 << 21) - 1 # a cell or voxel index is in [0, 2^21 - 1): the all-ones key is the invalid points' own
 CLOUD_CELL_MARGIN = 1.0 + 2.0 ** -10  # cell edge = max_dist * margin (csrc/cloud_eval.hip: why 27 cells are enough)
 

@@ -31,8 +31,11 @@ integer: the convention of depth_fusion and tsdf.
      0 where nothing covers;  normals (3,H,W): the winner's unit world-frame winding normal n / |n|, n = (p1-p0) x (p2-p0),
      |n| = sqrt((nx nx + ny ny) + nz nz), or (0,0,0) where |n| is zero or not finite, or the pixel empty.
 
-Left out: near-plane clipping (a triangle with a vertex at or behind the near plane is dropped whole), anti-aliasing, and vertex
-normals (interpolated normals need the vertices' normals, a scatter-add over the triangles).
+  8. Smooth normals (render_mesh(normals="vertex")).  The vertex normals (mesh_clean.py, step 5; a Mesh's own `normals` where it has
+     them) go through step 7's colour interpolation as a per-vertex attribute, and the interpolated vector v is renormalised per pixel:
+     v / sqrt((vx vx + vy vy) + vz vz), (0,0,0) where that length is zero or not finite or the pixel empty.
+
+Left out: near-plane clipping (a triangle with a vertex at or behind the near plane is dropped whole) and anti-aliasing.
 
 Two implementations: render_numpy on the host and the HIP kernels of csrc/mesh_render.hip (ops.mesh_render) for a mesh on a GPU.
 render_mesh picks by where the vertices live.
@@ -271,15 +274,51 @@ def _split_mesh(mesh, triangles, colors):
     return mesh, triangles, colors
 
 
+def _renormalise(m):
+    """(3,H,W) interpolated vectors -> unit vectors, (0,0,0) where the length is zero or not finite: numpy in float64, rounded to
+    float32; a GPU tensor in float32."""
+    if isinstance(m, np.ndarray):
+        v = m.astype(np.float64)
+        with np.errstate(all="ignore"):
+            length = np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+            good = (length > 0) & np.isfinite(length)
+            return np.where(good, v / np.where(good, length, 1.0), 0.0).astype(np.float32)
+    import torch
+    length = torch.sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2])
+    good = (length > 0) & torch.isfinite(length)
+    return torch.where(good, m / torch.where(good, length, torch.ones_like(length)), torch.zeros_like(m))
+
+
+def _render_smooth(mesh, intrinsics, poses, size, triangles, colors, bary, cull, near, max_small):
+    """Step 8: the vertex normals through the colour path, a second rendering when colours are wanted too."""
+    from .mesh_clean import vertex_normals
+    vertices, tri, colors = _split_mesh(mesh, triangles, colors)
+    vn = getattr(mesh, "normals", None)
+    if vn is None:
+        vn = vertex_normals(vertices, tri)
+    kw = dict(cull=cull, near=near, max_small=max_small)
+    smooth = render_mesh(vertices, intrinsics, poses, size, triangles=tri, colors=vn, bary=bary and colors is None, **kw)
+    out = smooth if colors is None else render_mesh(vertices, intrinsics, poses, size, triangles=tri, colors=colors, bary=bary, **kw)
+    out.normals = [_renormalise(m) for m in smooth.colors]
+    if colors is None:
+        out.colors = None
+    return out
+
+
 def render_mesh(mesh, intrinsics, poses, size, triangles=None, colors=None, normals=False, bary=False, cull=None, near=0.0,
                 max_small=None):
-    """Renders a mesh into V views of one size (module docstring) -> RenderResult.
+    """Renders a mesh into V views of one size (module docstring) -> RenderResult.  normals: False, True for the winning triangle's
+    face normal, or "vertex" for interpolated vertex normals (step 8).
 
     mesh: a Mesh (tsdf.extract_mesh's), a pair (vertices, triangles), or the vertices with triangles=.  colors: None, the (M,3)
     vertex colours, or True for a Mesh's own.  intrinsics V x (3,3), poses V x (4,4) world-to-view, size (H,W).  Vertices on a GPU
     run the HIP kernels on that device, in launches of up to 32 views, and the maps are GPU tensors; vertices on the host run
     render_numpy (float64, maps returned as float32).  max_small (device only): csrc/mesh_render.hip's threshold between its two
     rasterisation paths; every value gives the same bits."""
+    if isinstance(normals, str):
+        if normals != "vertex":
+            raise ValueError(f"normals must be False, True or 'vertex', got {normals!r}")
+        return _render_smooth(mesh, intrinsics, poses, size, triangles, colors, bary, cull, near, max_small)
     vertices, triangles, colors = _split_mesh(mesh, triangles, colors)
     places = {_place(a) for a in (vertices, triangles, colors) if a is not None}
     if len(places) != 1:

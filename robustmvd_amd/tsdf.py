@@ -306,16 +306,34 @@ def bounds_from_points(points, voxel, margin=0.0):
 
 @dataclass
 class Mesh:
-    """vertices (M,3) float32, triangles (T,3) int32 into them, colors (M,3) float32 or None; numpy arrays from a volume on the host,
-    GPU tensors from one on a GPU.  write_ply(path, mesh.vertices, mesh.colors, faces=mesh.triangles) saves it."""
+    """vertices (M,3) float32, triangles (T,3) int32 into them, colors (M,3) float32 or None, normals (M,3) float32 or None (nobody
+    fills them in unasked: mesh.normals = mesh.vertex_normals()); numpy arrays from a volume on the host, GPU tensors from one on a
+    GPU.  write_ply(path, mesh.vertices, mesh.colors, faces=mesh.triangles, normals=mesh.normals) saves it."""
     vertices: object
     triangles: object
     colors: object = None
+    normals: object = None
 
     def render(self, intrinsics, poses, size, **kw):
         """-> RenderResult: the mesh seen from V views of one size (render.render_mesh; colors=True renders the mesh's own)."""
         from .render import render_mesh
         return render_mesh(self, intrinsics, poses, size, **kw)
+
+    def components(self):
+        """-> MeshComponents: the connected components with their counts and areas (mesh_clean.mesh_components)."""
+        from .mesh_clean import mesh_components
+        return mesh_components(self)
+
+    def clean(self, **kw):
+        """-> Mesh without the components that fail min_triangles=, min_area= or keep_largest= (mesh_clean.clean_mesh); with
+        attributes= or details=True a CleanResult, whose .mesh is that Mesh."""
+        from .mesh_clean import clean_mesh
+        return clean_mesh(self, **kw)
+
+    def vertex_normals(self):
+        """-> (M,3) float32: the area-weighted vertex normals (mesh_clean.vertex_normals)."""
+        from .mesh_clean import vertex_normals
+        return vertex_normals(self)
 
 
 class TSDFVolume:
@@ -452,14 +470,21 @@ class TSDFVolume:
         the consistency check count."""
         return self.integrate(result.fused_depth, intrinsics, poses, weights=result.mask, images=images)
 
-    def extract_mesh(self, min_weight=1.0):
-        """-> Mesh: the surface between the observed voxels (weight >= min_weight), module docstring."""
+    def extract_mesh(self, min_weight=1.0, clean=None):
+        """-> Mesh: the surface between the observed voxels (weight >= min_weight), module docstring.  clean: None, or a dict of
+        mesh_clean.clean_mesh's keywords min_triangles, min_area, keep_largest and remove_unreferenced, applied to the mesh; any
+        other keyword raises, so that the result is always a Mesh (for attributes or the remaps call mesh.clean yourself)."""
+        extra = set(clean or ()) - {"min_triangles", "min_area", "keep_largest", "remove_unreferenced"}
+        if extra:
+            raise ValueError(f"extract_mesh: clean takes min_triangles, min_area, keep_largest and remove_unreferenced, got {sorted(extra)}")
         if self.device is None:
             v, c, t = extract_numpy(self.tsdf, self.weight, self.color, self.origin, self.voxel, min_weight)
-            return Mesh(v.astype(np.float32), t, None if c is None else c.astype(np.float32))
-        from . import ops
-        v, t, c = ops.tsdf_extract(self.tsdf, self.weight, self.color, self.origin, self.voxel, min_weight)
-        return Mesh(v, t, c)
+            mesh = Mesh(v.astype(np.float32), t, None if c is None else c.astype(np.float32))
+        else:
+            from . import ops
+            v, t, c = ops.tsdf_extract(self.tsdf, self.weight, self.color, self.origin, self.voxel, min_weight)
+            mesh = Mesh(v, t, c)
+        return mesh if clean is None else mesh.clean(**clean)
 
     def render(self, intrinsics, poses, size, min_weight=1.0, **kw):
         """-> RenderResult: extract_mesh(min_weight).render(...), the volume's surface seen from V views: per view the denoised and
