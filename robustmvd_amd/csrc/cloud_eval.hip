@@ -13,16 +13,13 @@
 #include <stdint.h>
 
 #include "compact.h"
+#include "fixed_sums.h"
 
 namespace mvd {
 
 constexpr int CE_BITS = 21;
 constexpr int CE_LIMIT = (1 << CE_BITS) - 1;  // a cell index is in [0, CE_LIMIT): the all-ones key is the invalid points' own
 constexpr long long CE_INVALID_KEY = 0x7fffffffffffffffLL;
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-    return finite_f32(x) && finite_f32(y) && finite_f32(z);
-}
 
 // floor((double(v) - o) * inv), two IEEE double operations and a floor (the library is built without contraction): numpy forms the
 // same bits.  Clamped to [lo, hi] before the conversion, so that a far point cannot overflow the int.
@@ -176,97 +173,46 @@ __global__ void __launch_bounds__(64) cloud_nearest_kernel(const float4* __restr
 }
 
 // ---- scores ------------------------------------------------------------------------------------------------------------------------
-// A workgroup takes 2048 consecutive distances; its ten partials (sum, valid, T counts) are reduced by xor shuffles and then over
-// its four waves in wave order, and one workgroup reduces the workgroups' partials the same way: the order is fixed by n alone.
-constexpr int SC_THREADS = 256;
+// A two-level sum of fixed_sums.h: a workgroup takes 2048 consecutive distances, thread i the distances i, i + 256, ..., and stores
+// one record (the float64 sum, the valid points, the T counts); fixed_final_kernel adds the workgroups' records.
 constexpr int SC_PER_THREAD = 8;
-constexpr int SC_PER_WG = SC_THREADS * SC_PER_THREAD;
-constexpr int SC_SLOTS = 2 + MVD_CLOUD_MAX_THRESHOLDS;  // a double and nine int64, 80 bytes
+constexpr int SC_PER_WG = FS_THREADS * SC_PER_THREAD;
+constexpr int SC_VALID = 1, SC_UNDER = 2;  // the words after the sum: the valid points, then those under threshold t
+using ScoreRecord = FixedRecord<2 + MVD_CLOUD_MAX_THRESHOLDS, 1ull>;  // a double and nine int64, 80 bytes
 
-struct ScoreAcc {
-    double sum;
-    long long cnt[SC_SLOTS - 1];  // [0] the valid points, [1 + t] those under threshold t
-};
-
-__device__ __forceinline__ void score_reduce_store(ScoreAcc a, void* __restrict__ out) {
-    __shared__ double s_sum[SC_THREADS / 64];
-    __shared__ long long s_cnt[SC_THREADS / 64][SC_SLOTS - 1];
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        a.sum += __shfl_xor(a.sum, s);
-#pragma unroll
-        for (int k = 0; k < SC_SLOTS - 1; ++k) a.cnt[k] += __shfl_xor(a.cnt[k], s);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        s_sum[wave] = a.sum;
-#pragma unroll
-        for (int k = 0; k < SC_SLOTS - 1; ++k) s_cnt[wave][k] = a.cnt[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double sum = s_sum[0];
-        for (int w = 1; w < SC_THREADS / 64; ++w) sum += s_sum[w];
-        static_cast<double*>(out)[0] = sum;
-        long long* c = static_cast<long long*>(out) + 1;
-        for (int k = 0; k < SC_SLOTS - 1; ++k) {
-            long long v = s_cnt[0][k];
-            for (int w = 1; w < SC_THREADS / 64; ++w) v += s_cnt[w][k];
-            c[k] = v;
-        }
-    }
-}
-
-__global__ void __launch_bounds__(SC_THREADS) scores_partial_kernel(const float* __restrict__ dist, const int* __restrict__ index,
+__global__ void __launch_bounds__(FS_THREADS) scores_partial_kernel(const float* __restrict__ dist, const int* __restrict__ index,
                                                                     const float* __restrict__ pts, int n,
                                                                     const float* __restrict__ thresholds, int T,
                                                                     unsigned char* __restrict__ partials) {
     float tau[MVD_CLOUD_MAX_THRESHOLDS];
 #pragma unroll
     for (int t = 0; t < MVD_CLOUD_MAX_THRESHOLDS; ++t) tau[t] = t < T ? thresholds[t] : -1.f;  // no distance is under -1
-    ScoreAcc a{};
+    ScoreRecord a{};
     const long long base = (long long)blockIdx.x * SC_PER_WG + threadIdx.x;
 #pragma unroll
     for (int k = 0; k < SC_PER_THREAD; ++k) {
-        const long long i = base + (long long)k * SC_THREADS;
+        const long long i = base + (long long)k * FS_THREADS;
         if (i >= n) break;
         // a query with a neighbour is a valid point; the others are looked up where the points are given
         bool ok = true;
         if (pts && index[i] < 0) ok = finite3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
         if (!ok) continue;
         const float d = dist[i];
-        a.sum += (double)d;
-        a.cnt[0] += 1;
+        a.addf(0, (double)d);
+        a.addi(SC_VALID, 1);
 #pragma unroll
-        for (int t = 0; t < MVD_CLOUD_MAX_THRESHOLDS; ++t) a.cnt[1 + t] += d < tau[t] ? 1 : 0;
+        for (int t = 0; t < MVD_CLOUD_MAX_THRESHOLDS; ++t) a.addi(SC_UNDER + t, d < tau[t] ? 1 : 0);
     }
-    score_reduce_store(a, partials + (size_t)blockIdx.x * SC_SLOTS * 8);
+    fixed_reduce_store(a, partials + (size_t)blockIdx.x * ScoreRecord::block_bytes);
 }
-
-__global__ void __launch_bounds__(SC_THREADS) scores_final_kernel(const unsigned char* __restrict__ partials, int nwg,
-                                                                  void* __restrict__ result) {
-    ScoreAcc a{};
-    for (int w = threadIdx.x; w < nwg; w += SC_THREADS) {
-        const unsigned char* p = partials + (size_t)w * SC_SLOTS * 8;
-        a.sum += reinterpret_cast<const double*>(p)[0];
-#pragma unroll
-        for (int k = 0; k < SC_SLOTS - 1; ++k) a.cnt[k] += reinterpret_cast<const long long*>(p)[1 + k];
-    }
-    score_reduce_store(a, result);
-}
-
-static inline long long score_workgroups(long long n) { return (n + SC_PER_WG - 1) / SC_PER_WG; }
 
 // ---- voxel reduce ------------------------------------------------------------------------------------------------------------------
 // Position i of the sorted keys is the head of a voxel's segment when its key is a valid point's and differs from the key before it.
 // The heads are compacted by compact.h, as the masked pixels of depth_fusion.hip are (ballot counts per 256-key chunk, one
 // workgroup's exclusive scan, rank in the ballot), which numbers the voxels in key order and leaves each voxel's first position in
-// seg[voxel]; seg[number of voxels] is the number of valid points.  Then one lane per voxel adds its points in sorted (= original, the sort
-// is stable) order in float64; a segment of more than 64 points is added by the whole wave instead, lane l taking the points
-// l, l + 64, ... and the 64 sums meeting in an xor-shuffle tree, so a voxel that holds the whole cloud costs n / 64 steps.
-constexpr int VX_THREADS = 256;  // the mean kernel's own geometry: a lane per voxel
-constexpr int VX_WAVES = VX_THREADS / 64;
-constexpr int VX_LONG = 64;  // segments above this length are reduced by the wave
+// seg[voxel]; seg[number of voxels] is the number of valid points.  Then the segment walk of fixed_sums.h adds every voxel's points in
+// sorted (= original, the sort is stable) order in float64: a lane per voxel, the whole wave for a voxel of more than 64 points, so a
+// voxel that holds the whole cloud costs n / 64 steps.
 
 struct VoxelHead {
     const long long* keys;
@@ -289,82 +235,41 @@ __global__ void __launch_bounds__(CP_THREADS) voxel_heads_kernel(const long long
     }
 }
 
-struct VoxelSum {
-    double v[6];
-};
-
 template <bool COLOR>
-__device__ __forceinline__ void voxel_add(VoxelSum& s, const float* __restrict__ pts, const float* __restrict__ col,
-                                          const long long* __restrict__ perm, long long pos, int n) {
-    const long long p = perm[pos];
-    if ((unsigned long long)p >= (unsigned long long)n) return;  // not a permutation of 0..n-1: skipped, never dereferenced
-    s.v[0] += (double)pts[3 * p];
-    s.v[1] += (double)pts[3 * p + 1];
-    s.v[2] += (double)pts[3 * p + 2];
-    if (COLOR) {
-        s.v[3] += (double)col[3 * p];
-        s.v[4] += (double)col[3 * p + 1];
-        s.v[5] += (double)col[3 * p + 2];
-    }
-}
-
-template <bool COLOR>
-__device__ __forceinline__ void voxel_store(const VoxelSum& s, int len, long long vox, float* __restrict__ xyz, float* __restrict__ rgb,
-                                            int* __restrict__ counts) {
-    const double nd = (double)len;
-    xyz[3 * vox] = (float)(s.v[0] / nd);
-    xyz[3 * vox + 1] = (float)(s.v[1] / nd);
-    xyz[3 * vox + 2] = (float)(s.v[2] / nd);
-    if (COLOR) {
-        rgb[3 * vox] = (float)(s.v[3] / nd);
-        rgb[3 * vox + 1] = (float)(s.v[4] / nd);
-        rgb[3 * vox + 2] = (float)(s.v[5] / nd);
-    }
-    counts[vox] = len;
-}
-
-template <bool COLOR>
-__global__ void __launch_bounds__(VX_THREADS) voxel_mean_kernel(const int* __restrict__ seg, const long long* __restrict__ total,
+__global__ void __launch_bounds__(FS_THREADS) voxel_mean_kernel(const int* __restrict__ seg, const long long* __restrict__ total,
                                                                 const long long* __restrict__ perm, const float* __restrict__ pts,
                                                                 const float* __restrict__ col, int n, float* __restrict__ xyz,
                                                                 float* __restrict__ rgb, int* __restrict__ counts) {
-    const int lane = threadIdx.x & 63;
-    const long long nvox = min(total[0], (long long)n);
-    const long long wave_base = ((long long)blockIdx.x * VX_WAVES + (threadIdx.x >> 6)) * 64;
-    if (wave_base >= nvox) return;  // the whole wave
-    const long long vox = wave_base + lane;
-    const bool have = vox < nvox;
-    // seg is ascending and ends at the number of valid points <= n; the clamps keep a corrupted table inside the arrays
-    const int b = have ? min(max(seg[vox], 0), n) : 0, e = have ? min(max(seg[vox + 1], b), n) : 0;
-    const int len = e - b;
-    if (have && len <= VX_LONG) {
-        VoxelSum s{};
-        for (int p = b; p < e; ++p) voxel_add<COLOR>(s, pts, col, perm, p, n);
-        voxel_store<COLOR>(s, len, vox, xyz, rgb, counts);
-    }
-    unsigned long long longs = __ballot(have && len > VX_LONG);
-    while (longs != 0ull) {  // wave-uniform
-        const int owner = __ffsll((long long)longs) - 1;
-        longs &= longs - 1ull;
-        const int lb = __shfl(b, owner), le = __shfl(e, owner);
-        VoxelSum s{};
-        for (int p = lb + lane; p < le; p += 64) voxel_add<COLOR>(s, pts, col, perm, p, n);
+    constexpr int N = COLOR ? 6 : 3;
+    const auto add = [&](FixedSums<N>& s, long long pos) {
+        const long long p = perm[pos];
+        if ((unsigned long long)p >= (unsigned long long)n) return;  // not a permutation of 0..n-1: skipped, never dereferenced
 #pragma unroll
-        for (int k = 0; k < (COLOR ? 6 : 3); ++k)
+        for (int k = 0; k < 3; ++k) {
+            s.v[k] += (double)pts[3 * p + k];
+            if constexpr (COLOR) s.v[3 + k] += (double)col[3 * p + k];
+        }
+    };
+    const auto span = [&](FixedSums<N>& s, long long b, long long e, int lane) { fixed_lane_span(s, b, e, lane, add); };
+    const auto store = [&](const FixedSums<N>& s, int len, long long vox) {
+        const double nd = (double)len;
 #pragma unroll
-            for (int sh = 32; sh >= 1; sh >>= 1) s.v[k] += __shfl_xor(s.v[k], sh);
-        if (lane == 0) voxel_store<COLOR>(s, le - lb, wave_base + owner, xyz, rgb, counts);
-    }
+        for (int k = 0; k < 3; ++k) {
+            xyz[3 * vox + k] = (float)(s.v[k] / nd);
+            if constexpr (COLOR) rgb[3 * vox + k] = (float)(s.v[3 + k] / nd);
+        }
+        counts[vox] = len;
+    };
+    // seg ends at the number of valid points <= n
+    fixed_segment_walk<N>(seg, min(total[0], (long long)n), n, add, span, store);
 }
 
 }  // namespace mvd
 
-#define CE_REQUIRE_COUNT(what, n) MVD_REQUIRE((n) >= 0 && (n) <= 0x7fffffffLL, what ": %lld points, supported 0 .. 2^31 - 1", (long long)(n))
-
 extern "C" int mvd_cloud_cell_keys_f32(const float* points, long long n, double origin_x, double origin_y, double origin_z, double inv,
                                        long long* keys, mvd_stream_t stream) {
     using namespace mvd;
-    CE_REQUIRE_COUNT("cloud_cell_keys", n);
+    MVD_REQUIRE_COUNT("cloud_cell_keys", "points", n);
     if (n == 0) return MVD_OK;
     MVD_REQUIRE(points && keys, "cloud_cell_keys: NULL argument");
     MVD_REQUIRE(isfinite(origin_x) && isfinite(origin_y) && isfinite(origin_z), "cloud_cell_keys: the origin is not finite");
@@ -376,7 +281,7 @@ extern "C" int mvd_cloud_cell_keys_f32(const float* points, long long n, double 
 
 extern "C" int mvd_cloud_grid_build_f32(const float* points, const long long* perm, long long n, float* records, mvd_stream_t stream) {
     using namespace mvd;
-    CE_REQUIRE_COUNT("cloud_grid_build", n);
+    MVD_REQUIRE_COUNT("cloud_grid_build", "points", n);
     if (n == 0) return MVD_OK;
     MVD_REQUIRE(points && perm && records, "cloud_grid_build: NULL argument");
     MVD_REQUIRE(((uintptr_t)records & 15) == 0, "cloud_grid_build: records must be 16-byte aligned");
@@ -389,8 +294,8 @@ extern "C" int mvd_cloud_nearest_f32(const float* query_records, long long n, co
                                      long long m, double origin_x, double origin_y, double origin_z, double inv, float max_dist,
                                      float* dist, int* index, mvd_stream_t stream) {
     using namespace mvd;
-    CE_REQUIRE_COUNT("cloud_nearest", n);
-    CE_REQUIRE_COUNT("cloud_nearest", m);
+    MVD_REQUIRE_COUNT("cloud_nearest", "points", n);
+    MVD_REQUIRE_COUNT("cloud_nearest", "points", m);
     MVD_REQUIRE(max_dist > 0.f && finite_f32(max_dist), "cloud_nearest: max_dist must be finite and > 0, got %g", (double)max_dist);
     MVD_REQUIRE(isfinite(origin_x) && isfinite(origin_y) && isfinite(origin_z), "cloud_nearest: the origin is not finite");
     MVD_REQUIRE(isfinite(inv) && inv > 0.0, "cloud_nearest: inv must be finite and > 0, got %g", inv);
@@ -408,13 +313,13 @@ extern "C" int mvd_cloud_nearest_f32(const float* query_records, long long n, co
 
 extern "C" size_t mvd_cloud_scores_workspace_bytes(long long n) {
     if (n <= 0) return 0;
-    return mvd::align_up((size_t)mvd::score_workgroups(n) * mvd::SC_SLOTS * 8, 256);
+    return mvd::align_up(mvd::fixed_partials_bytes<mvd::ScoreRecord>(n, mvd::SC_PER_WG), 256);
 }
 
 extern "C" int mvd_cloud_scores_f32(const float* dist, const int* index, const float* points, long long n, const float* thresholds, int T,
                                     void* result, void* workspace, size_t workspace_bytes, mvd_stream_t stream) {
     using namespace mvd;
-    CE_REQUIRE_COUNT("cloud_scores", n);
+    MVD_REQUIRE_COUNT("cloud_scores", "points", n);
     MVD_REQUIRE(T >= 1 && T <= MVD_CLOUD_MAX_THRESHOLDS, "cloud_scores: %d thresholds, supported 1..%d", T, MVD_CLOUD_MAX_THRESHOLDS);
     MVD_REQUIRE(thresholds && result, "cloud_scores: NULL argument");
     MVD_REQUIRE(((uintptr_t)result & 7) == 0, "cloud_scores: result must be 8-byte aligned");
@@ -422,12 +327,12 @@ extern "C" int mvd_cloud_scores_f32(const float* dist, const int* index, const f
     MVD_REQUIRE(n == 0 || (workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= mvd_cloud_scores_workspace_bytes(n)),
                 "cloud_scores: workspace too small or not 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    const int nwg = (int)score_workgroups(n);
+    const int nwg = (int)fixed_workgroups(n, SC_PER_WG);
     unsigned char* partials = static_cast<unsigned char*>(workspace);
     if (nwg > 0)
-        hipLaunchKernelGGL(scores_partial_kernel, dim3((unsigned)nwg), dim3(SC_THREADS), 0, st, dist, index, points, (int)n, thresholds, T,
+        hipLaunchKernelGGL(scores_partial_kernel, dim3((unsigned)nwg), dim3(FS_THREADS), 0, st, dist, index, points, (int)n, thresholds, T,
                            partials);
-    hipLaunchKernelGGL(scores_final_kernel, dim3(1), dim3(SC_THREADS), 0, st, partials, nwg, result);  // nwg == 0: zeros
+    fixed_final_launch<ScoreRecord>(partials, nwg, result, st);
     return launch_status("cloud_scores");
 }
 
@@ -440,7 +345,7 @@ extern "C" int mvd_voxel_reduce_f32(const long long* keys, const long long* perm
                                     float* xyz, float* rgb, int* counts, long long* num_voxels, void* workspace, size_t workspace_bytes,
                                     mvd_stream_t stream) {
     using namespace mvd;
-    CE_REQUIRE_COUNT("voxel_reduce", n);
+    MVD_REQUIRE_COUNT("voxel_reduce", "points", n);
     MVD_REQUIRE(num_voxels && ((uintptr_t)num_voxels & 7) == 0, "voxel_reduce: num_voxels must be given and 8-byte aligned");
     MVD_REQUIRE(!colors == !rgb, "voxel_reduce: colors and rgb go together");
     hipStream_t st = (hipStream_t)stream;
@@ -458,12 +363,12 @@ extern "C" int mvd_voxel_reduce_f32(const long long* keys, const long long* perm
     hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(CP_THREADS), 0, st, chunk_counts, compact_chunks(n), num_voxels);
     hipLaunchKernelGGL(voxel_heads_kernel, dim3(nwg), dim3(CP_THREADS), 0, st, keys, (int)n, chunk_counts, num_voxels, seg);
     // one lane per voxel, at most n voxels: the waves past the count leave at once
-    const unsigned mwg = (unsigned)((n + VX_THREADS - 1) / VX_THREADS);
+    const unsigned mwg = (unsigned)((n + FS_THREADS - 1) / FS_THREADS);
     if (colors)
-        hipLaunchKernelGGL(voxel_mean_kernel<true>, dim3(mwg), dim3(VX_THREADS), 0, st, seg, num_voxels, perm, points, colors, (int)n, xyz,
+        hipLaunchKernelGGL(voxel_mean_kernel<true>, dim3(mwg), dim3(FS_THREADS), 0, st, seg, num_voxels, perm, points, colors, (int)n, xyz,
                            rgb, counts);
     else
-        hipLaunchKernelGGL(voxel_mean_kernel<false>, dim3(mwg), dim3(VX_THREADS), 0, st, seg, num_voxels, perm, points, colors, (int)n, xyz,
+        hipLaunchKernelGGL(voxel_mean_kernel<false>, dim3(mwg), dim3(FS_THREADS), 0, st, seg, num_voxels, perm, points, colors, (int)n, xyz,
                            rgb, counts);
     return launch_status("voxel_reduce");
 }

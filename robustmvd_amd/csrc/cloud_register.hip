@@ -11,7 +11,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "mvd_common.h"
+#include "fixed_sums.h"
 
 #pragma STDC FP_CONTRACT OFF
 
@@ -21,8 +21,6 @@ struct RgTransform {
     double m[12];  // the rows of [M | t]
 };
 
-__device__ __forceinline__ bool rg_finite3(float x, float y, float z) { return finite_f32(x) && finite_f32(y) && finite_f32(z); }
-
 // q_a = float32(((M[a,0] x + M[a,1] y) + M[a,2] z) + t[a]) in float64, rounded once.  A row with a non-finite coordinate, before or
 // after, is (NaN, NaN, NaN) with the bits 0x7fc00000: an invalid point stays one, and no NaN's sign or payload is left to the hardware.
 __device__ __forceinline__ bool rg_move(const RgTransform& T, float x, float y, float z, float& qx, float& qy, float& qz) {
@@ -30,7 +28,7 @@ __device__ __forceinline__ bool rg_move(const RgTransform& T, float x, float y, 
     qx = (float)(((T.m[0] * dx + T.m[1] * dy) + T.m[2] * dz) + T.m[3]);
     qy = (float)(((T.m[4] * dx + T.m[5] * dy) + T.m[6] * dz) + T.m[7]);
     qz = (float)(((T.m[8] * dx + T.m[9] * dy) + T.m[10] * dz) + T.m[11]);
-    const bool ok = rg_finite3(x, y, z) && rg_finite3(qx, qy, qz);
+    const bool ok = finite3(x, y, z) && finite3(qx, qy, qz);
     if (!ok) qx = qy = qz = __uint_as_float(0x7fc00000u);
     return ok;
 }
@@ -52,7 +50,7 @@ __global__ void __launch_bounds__(256) transform_kernel(const float* __restrict_
     const double wy = (T.m[4] * vx + T.m[5] * vy) + T.m[6] * vz;
     const double wz = (T.m[8] * vx + T.m[9] * vy) + T.m[10] * vz;
     const double len = sqrt((wx * wx + wy * wy) + wz * wz);
-    const bool ok = rg_finite3(nx, ny, nz) && len > 0.0 && isfinite(len);
+    const bool ok = finite3(nx, ny, nz) && len > 0.0 && isfinite(len);
     out_nrm[3 * i] = ok ? (float)(wx / len) : 0.f;
     out_nrm[3 * i + 1] = ok ? (float)(wy / len) : 0.f;
     out_nrm[3 * i + 2] = ok ? (float)(wz / len) : 0.f;
@@ -72,77 +70,43 @@ __global__ void __launch_bounds__(256) transform_records_kernel(const float* __r
 }
 
 // ---- pair sums ---------------------------------------------------------------------------------------------------------------------
-// A workgroup takes 2048 consecutive source points, a lane eight of them in two batches of four: the four indices and source points
-// are loaded first, then the four gathers of P[j] (and the normal) are issued together, and only then are the terms formed, so that
-// a lane has four dependent gathers in flight instead of one.  The partial sums (a count and 18 or 28 doubles per lane) meet in an
-// xor-shuffle tree, then over the four waves in wave order, and one workgroup reduces the workgroups' 256-byte partials the same way.
-constexpr int RG_THREADS = 256;
+// A two-level sum of fixed_sums.h.  A workgroup takes 2048 consecutive source points, a lane eight of them in two batches of four:
+// the four indices and source points are loaded first, then the four gathers of P[j] (and the normal) are issued together, and only
+// then are the terms formed, so that a lane has four dependent gathers in flight instead of one.  A workgroup's record is a count and
+// 18 or 28 doubles in a 256-byte block; fixed_final_kernel adds the workgroups' records.
 constexpr int RG_BATCH = 4;
 constexpr int RG_PER_THREAD = 8;
-constexpr int RG_PER_WG = RG_THREADS * RG_PER_THREAD;
+constexpr int RG_PER_WG = FS_THREADS * RG_PER_THREAD;
 constexpr int RG_WORDS = 32;  // the result block: an int64 count, the doubles, zeros
 constexpr int RG_POINT = 18, RG_PLANE = 28;
 static_assert(RG_PER_WG == MVD_CLOUD_PAIR_SUMS_PER_WORKGROUP, "include/mvd.h states the points per workgroup");
-static_assert(RG_PER_THREAD % RG_BATCH == 0 && 1 + RG_PLANE <= RG_WORDS, "pair sums geometry");
+static_assert(RG_PER_THREAD % RG_BATCH == 0, "pair sums geometry");
 
-template <int NV>
-struct RgAcc {
-    long long n;
-    double v[NV];
-};
-
-template <int NV>
-__device__ __forceinline__ void rg_reduce_store(RgAcc<NV> a, unsigned char* __restrict__ out) {
-    __shared__ long long s_n[RG_THREADS / 64];
-    __shared__ double s_v[RG_THREADS / 64][NV];
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        a.n += __shfl_xor(a.n, s);
-#pragma unroll
-        for (int k = 0; k < NV; ++k) a.v[k] += __shfl_xor(a.v[k], s);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        s_n[wave] = a.n;
-#pragma unroll
-        for (int k = 0; k < NV; ++k) s_v[wave][k] = a.v[k];
-    }
-    __syncthreads();
-    const int word = threadIdx.x;  // one word of the block per thread, each summed over the waves in wave order
-    if (word == 0) {
-        long long c = s_n[0];
-        for (int w = 1; w < RG_THREADS / 64; ++w) c += s_n[w];
-        reinterpret_cast<long long*>(out)[0] = c;
-    } else if (word <= NV) {
-        double v = s_v[0][word - 1];
-        for (int w = 1; w < RG_THREADS / 64; ++w) v += s_v[w][word - 1];
-        reinterpret_cast<double*>(out)[word] = v;
-    } else if (word < RG_WORDS) {
-        reinterpret_cast<long long*>(out)[word] = 0;
-    }
-}
+template <bool PLANE>
+using PairRecord = FixedRecord<1 + (PLANE ? RG_PLANE : RG_POINT), ((1ull << (PLANE ? RG_PLANE : RG_POINT)) - 1ull) << 1, RG_WORDS>;
 
 // The terms of one pair; the operation order is the docstring's of cloud_register.pair_sums_numpy.
 template <bool PLANE>
-__device__ __forceinline__ void rg_add(RgAcc<PLANE ? RG_PLANE : RG_POINT>& acc, float qx, float qy, float qz, float px, float py,
-                                       float pz, float nx, float ny, float nz, double cx, double cy, double cz) {
+__device__ __forceinline__ void rg_add(PairRecord<PLANE>& acc, float qx, float qy, float qz, float px, float py, float pz, float nx,
+                                       float ny, float nz, double cx, double cy, double cz) {
     const double a[3] = {(double)qx - cx, (double)qy - cy, (double)qz - cz};
     const double b[3] = {(double)px - cx, (double)py - cy, (double)pz - cz};
     const double d[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]};
-    acc.n += 1;
-    if (!PLANE) {
+    acc.addi(0, 1);
+    const auto add = [&](int k, double term) { acc.addf(1 + k, term); };  // sum k of the definition
+    if constexpr (!PLANE) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            acc.v[k] += a[k];
-            acc.v[3 + k] += b[k];
+            add(k, a[k]);
+            add(3 + k, b[k]);
         }
 #pragma unroll
         for (int r = 0; r < 3; ++r)
 #pragma unroll
-            for (int c = 0; c < 3; ++c) acc.v[6 + 3 * r + c] += a[r] * b[c];
-        acc.v[15] += (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2];
-        acc.v[16] += (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2];
-        acc.v[17] += (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+            for (int c = 0; c < 3; ++c) add(6 + 3 * r + c, a[r] * b[c]);
+        add(15, (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
+        add(16, (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2]);
+        add(17, (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
     } else {
         const double u[3] = {(double)nx, (double)ny, (double)nz};
         const double r = (d[0] * u[0] + d[1] * u[1]) + d[2] * u[2];
@@ -151,26 +115,26 @@ __device__ __forceinline__ void rg_add(RgAcc<PLANE ? RG_PLANE : RG_POINT>& acc, 
 #pragma unroll
         for (int i = 0; i < 6; ++i)
 #pragma unroll
-            for (int j = i; j < 6; ++j) acc.v[slot++] += J[i] * J[j];
+            for (int j = i; j < 6; ++j) add(slot++, J[i] * J[j]);
 #pragma unroll
-        for (int k = 0; k < 6; ++k) acc.v[21 + k] += J[k] * r;
-        acc.v[27] += r * r;
+        for (int k = 0; k < 6; ++k) add(21 + k, J[k] * r);
+        add(27, r * r);
     }
 }
 
 template <bool PLANE>
-__global__ void __launch_bounds__(RG_THREADS) pair_sums_partial_kernel(const float* __restrict__ src, int n, RgTransform T,
+__global__ void __launch_bounds__(FS_THREADS) pair_sums_partial_kernel(const float* __restrict__ src, int n, RgTransform T,
                                                                        const int* __restrict__ index, const float* __restrict__ tgt,
                                                                        const float* __restrict__ tnrm, int m, double cx, double cy,
                                                                        double cz, unsigned char* __restrict__ partials) {
-    RgAcc<PLANE ? RG_PLANE : RG_POINT> acc{};
+    PairRecord<PLANE> acc{};
     const long long base = (long long)blockIdx.x * RG_PER_WG + threadIdx.x;
     for (int b0 = 0; b0 < RG_PER_THREAD; b0 += RG_BATCH) {
         int j[RG_BATCH];
         float s[RG_BATCH][3], p[RG_BATCH][3], u[RG_BATCH][3];
 #pragma unroll
         for (int k = 0; k < RG_BATCH; ++k) {
-            const long long i = base + (long long)(b0 + k) * RG_THREADS;
+            const long long i = base + (long long)(b0 + k) * FS_THREADS;
             j[k] = -1;
             s[k][0] = s[k][1] = s[k][2] = 0.f;
             if (i < n) {
@@ -200,28 +164,13 @@ __global__ void __launch_bounds__(RG_THREADS) pair_sums_partial_kernel(const flo
 #pragma unroll
         for (int k = 0; k < RG_BATCH; ++k) {
             float qx, qy, qz;
-            bool pair = rg_move(T, s[k][0], s[k][1], s[k][2], qx, qy, qz) && j[k] >= 0 && rg_finite3(p[k][0], p[k][1], p[k][2]);
-            if (PLANE) pair = pair && rg_finite3(u[k][0], u[k][1], u[k][2]) && !(u[k][0] == 0.f && u[k][1] == 0.f && u[k][2] == 0.f);
+            bool pair = rg_move(T, s[k][0], s[k][1], s[k][2], qx, qy, qz) && j[k] >= 0 && finite3(p[k][0], p[k][1], p[k][2]);
+            if (PLANE) pair = pair && finite3(u[k][0], u[k][1], u[k][2]) && !(u[k][0] == 0.f && u[k][1] == 0.f && u[k][2] == 0.f);
             if (pair) rg_add<PLANE>(acc, qx, qy, qz, p[k][0], p[k][1], p[k][2], u[k][0], u[k][1], u[k][2], cx, cy, cz);
         }
     }
-    rg_reduce_store(acc, partials + (size_t)blockIdx.x * RG_WORDS * 8);
+    fixed_reduce_store(acc, partials + (size_t)blockIdx.x * PairRecord<PLANE>::block_bytes);
 }
-
-template <int NV>
-__global__ void __launch_bounds__(RG_THREADS) pair_sums_final_kernel(const unsigned char* __restrict__ partials, int nwg,
-                                                                     unsigned char* __restrict__ result) {
-    RgAcc<NV> acc{};
-    for (int w = threadIdx.x; w < nwg; w += RG_THREADS) {
-        const unsigned char* p = partials + (size_t)w * RG_WORDS * 8;
-        acc.n += reinterpret_cast<const long long*>(p)[0];
-#pragma unroll
-        for (int k = 0; k < NV; ++k) acc.v[k] += reinterpret_cast<const double*>(p)[1 + k];
-    }
-    rg_reduce_store(acc, result);
-}
-
-static inline long long rg_workgroups(long long n) { return (n + RG_PER_WG - 1) / RG_PER_WG; }
 
 static inline bool rg_load(const double* transform, RgTransform& T) {
     for (int k = 0; k < 12; ++k) {
@@ -233,12 +182,10 @@ static inline bool rg_load(const double* transform, RgTransform& T) {
 
 }  // namespace mvd
 
-#define RG_REQUIRE_COUNT(what, n) MVD_REQUIRE((n) >= 0 && (n) <= 0x7fffffffLL, what ": %lld points, supported 0 .. 2^31 - 1", (long long)(n))
-
 extern "C" int mvd_cloud_transform_f32(const float* points, const float* normals, long long n, const double* transform, float* out_points,
                                        float* out_normals, mvd_stream_t stream) {
     using namespace mvd;
-    RG_REQUIRE_COUNT("cloud_transform", n);
+    MVD_REQUIRE_COUNT("cloud_transform", "points", n);
     RgTransform T;
     MVD_REQUIRE(transform && rg_load(transform, T), "cloud_transform: the transform must be 12 finite doubles");
     MVD_REQUIRE(!normals == !out_normals, "cloud_transform: normals and out_normals go together");
@@ -252,7 +199,7 @@ extern "C" int mvd_cloud_transform_f32(const float* points, const float* normals
 extern "C" int mvd_cloud_transform_records_f32(const float* points, const long long* perm, long long n, const double* transform,
                                                float* records, mvd_stream_t stream) {
     using namespace mvd;
-    RG_REQUIRE_COUNT("cloud_transform_records", n);
+    MVD_REQUIRE_COUNT("cloud_transform_records", "points", n);
     RgTransform T;
     MVD_REQUIRE(transform && rg_load(transform, T), "cloud_transform_records: the transform must be 12 finite doubles");
     if (n == 0) return MVD_OK;
@@ -265,15 +212,15 @@ extern "C" int mvd_cloud_transform_records_f32(const float* points, const long l
 
 extern "C" size_t mvd_cloud_pair_sums_workspace_bytes(long long n) {
     if (n <= 0) return 0;
-    return (size_t)mvd::rg_workgroups(n) * mvd::RG_WORDS * 8;
+    return mvd::fixed_partials_bytes<mvd::PairRecord<true>>(n, mvd::RG_PER_WG);
 }
 
 extern "C" int mvd_cloud_pair_sums_f32(const float* source, long long n, const double* transform, const int* index, const float* target,
                                        const float* target_normals, long long m, double pivot_x, double pivot_y, double pivot_z,
                                        void* result, void* workspace, size_t workspace_bytes, mvd_stream_t stream) {
     using namespace mvd;
-    RG_REQUIRE_COUNT("cloud_pair_sums", n);
-    RG_REQUIRE_COUNT("cloud_pair_sums", m);
+    MVD_REQUIRE_COUNT("cloud_pair_sums", "points", n);
+    MVD_REQUIRE_COUNT("cloud_pair_sums", "points", m);
     RgTransform T;
     MVD_REQUIRE(transform && rg_load(transform, T), "cloud_pair_sums: the transform must be 12 finite doubles");
     MVD_REQUIRE(isfinite(pivot_x) && isfinite(pivot_y) && isfinite(pivot_z), "cloud_pair_sums: the pivot is not finite");
@@ -283,19 +230,18 @@ extern "C" int mvd_cloud_pair_sums_f32(const float* source, long long n, const d
     MVD_REQUIRE(n == 0 || (workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= mvd_cloud_pair_sums_workspace_bytes(n)),
                 "cloud_pair_sums: workspace too small or not 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    const int nwg = (int)rg_workgroups(n);
+    const int nwg = (int)fixed_workgroups(n, RG_PER_WG);
     unsigned char* partials = static_cast<unsigned char*>(workspace);
-    unsigned char* out = static_cast<unsigned char*>(result);
     if (target_normals) {
         if (nwg > 0)
-            hipLaunchKernelGGL(pair_sums_partial_kernel<true>, dim3((unsigned)nwg), dim3(RG_THREADS), 0, st, source, (int)n, T, index, target,
+            hipLaunchKernelGGL(pair_sums_partial_kernel<true>, dim3((unsigned)nwg), dim3(FS_THREADS), 0, st, source, (int)n, T, index, target,
                                target_normals, (int)m, pivot_x, pivot_y, pivot_z, partials);
-        hipLaunchKernelGGL(pair_sums_final_kernel<RG_PLANE>, dim3(1), dim3(RG_THREADS), 0, st, partials, nwg, out);  // nwg == 0: zeros
+        fixed_final_launch<PairRecord<true>>(partials, nwg, result, st);
     } else {
         if (nwg > 0)
-            hipLaunchKernelGGL(pair_sums_partial_kernel<false>, dim3((unsigned)nwg), dim3(RG_THREADS), 0, st, source, (int)n, T, index, target,
+            hipLaunchKernelGGL(pair_sums_partial_kernel<false>, dim3((unsigned)nwg), dim3(FS_THREADS), 0, st, source, (int)n, T, index, target,
                                target_normals, (int)m, pivot_x, pivot_y, pivot_z, partials);
-        hipLaunchKernelGGL(pair_sums_final_kernel<RG_POINT>, dim3(1), dim3(RG_THREADS), 0, st, partials, nwg, out);
+        fixed_final_launch<PairRecord<false>>(partials, nwg, result, st);
     }
     return launch_status("cloud_pair_sums");
 }

@@ -30,6 +30,7 @@
 // the constant L is a vertex of it with label[L] = L, and label[v] <= v makes L its lowest vertex.  That state is unique: whatever
 // order the hooks land in, the result is the same bits.
 #include "compact.h"
+#include "fixed_sums.h"
 
 namespace mvd {
 
@@ -162,18 +163,18 @@ __device__ __forceinline__ double cross_length(const Cross& n) { return sqrt((n.
 __device__ __forceinline__ bool finite_f64(double v) { return fabs(v) <= 1.7976931348623157e308; }  // false for inf and NaN
 
 // Sorted position p holds triangle perm[p] of component key[p].  One workgroup takes MA_BLOCK consecutive positions: it stores each
-// one's area and, for a block that lies inside one component, the block's sum (thread i adds positions i, i + 256, ... in order, a
-// xor tree over the wave, the four waves in order).  seg[c] = the first position of component c, seg[C] = the number of positions
+// one's area and, for a block that lies inside one component, the block's sum (thread i adds positions i, i + 256, ... in order, then
+// fixed_sums.h's sum over the workgroup).  seg[c] = the first position of component c, seg[C] = the number of positions
 // with a component; the keys ascend and every component has a triangle, so every entry is written.
 constexpr int MA_PER = 8;
 constexpr int MA_BLOCK = MC_THREADS * MA_PER;  // 2048
+static_assert(MC_THREADS == FS_THREADS, "the area and sum kernels are launched as fixed_sums.h expects");
 
 __global__ void __launch_bounds__(MC_THREADS) mesh_area_kernel(const float* __restrict__ vtx, const int* __restrict__ tri, int T, int M,
                                                                const int* __restrict__ key, const long long* __restrict__ perm, int C,
                                                                double* __restrict__ area, double* __restrict__ block_sum, int* __restrict__ seg) {
-    __shared__ double wsum[MC_THREADS / 64];
     const long long base = (long long)blockIdx.x * MA_BLOCK;
-    double acc = 0.0;
+    FixedRecord<1, 1ull> acc{};  // one double
 #pragma unroll
     for (int k = 0; k < MA_PER; ++k) {
         const long long p = base + k * MC_THREADS + threadIdx.x;
@@ -188,21 +189,17 @@ __global__ void __launch_bounds__(MC_THREADS) mesh_area_kernel(const float* __re
             }
         }
         area[p] = a;
-        acc += a;
+        acc.addf(0, a);
         const int c = key[p], before = p > 0 ? key[p - 1] : -1;
         if ((unsigned)c < (unsigned)C && c != before) seg[c] = (int)p;
         if (p + 1 == T) seg[C] = T;
     }
-#pragma unroll
-    for (int sh = 32; sh >= 1; sh >>= 1) acc += __shfl_xor(acc, sh);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) block_sum[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+    fixed_reduce_store(acc, block_sum + blockIdx.x);
 }
 
-// One lane per component adds its segment [b,e) of `area` in order.  A segment of more than 64 positions goes to the whole wave: lane l
-// adds items l, l + 64, ... of the segment's head up to the first block boundary, then of its whole blocks (their stored sums), then of
-// its tail, and the 64 sums meet in a xor tree.  The order is fixed by b and e alone.
+// fixed_sums.h's segment walk over `area`, one segment per component.  A segment of more than 64 positions that holds whole blocks is
+// added through their stored sums: lane l adds items l, l + 64, ... of the segment's head up to the first block boundary, of its whole
+// blocks' sums and of its tail, each from zero, and then head + blocks + tail.  The order is fixed by b and e alone.
 __device__ __forceinline__ double area_span(const double* __restrict__ a, long long b, long long e, int lane) {
     double s = 0.0;
     for (long long p = b + lane; p < e; p += 64) s += a[p];
@@ -212,36 +209,21 @@ __device__ __forceinline__ double area_span(const double* __restrict__ a, long l
 __global__ void __launch_bounds__(MC_THREADS) mesh_component_sum_kernel(const int* __restrict__ seg, int C, int T,
                                                                         const double* __restrict__ area, const double* __restrict__ block_sum,
                                                                         int* __restrict__ num_triangles, double* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const long long wave_base = ((long long)blockIdx.x * (MC_THREADS / 64) + (threadIdx.x >> 6)) * 64;
-    if (wave_base >= C) return;  // the whole wave
-    const long long c = wave_base + lane;
-    const bool have = c < C;
-    const int b = have ? min(max(seg[c], 0), T) : 0, e = have ? min(max(seg[c + 1], b), T) : 0;
-    if (have) num_triangles[c] = e - b;
-    if (have && e - b <= 64) {
-        double s = 0.0;
-        for (int p = b; p < e; ++p) s += area[p];
-        out[c] = s;
-    }
-    unsigned long long longs = __ballot(have && e - b > 64);
-    while (longs != 0ull) {  // wave-uniform
-        const int owner = __ffsll((long long)longs) - 1;
-        longs &= longs - 1ull;
-        const long long lb = __shfl(b, owner), le = __shfl(e, owner);
-        const long long first = (lb + MA_BLOCK - 1) / MA_BLOCK, last = le / MA_BLOCK;  // whole blocks [first, last)
-        double s;
+    const auto add = [&](FixedSums<1>& s, long long p) { s.v[0] += area[p]; };
+    const auto span = [&](FixedSums<1>& s, long long b, long long e, int lane) {
+        const long long first = (b + MA_BLOCK - 1) / MA_BLOCK, last = e / MA_BLOCK;  // whole blocks [first, last)
         if (first >= last) {
-            s = area_span(area, lb, le, lane);
+            s.v[0] = area_span(area, b, e, lane);
         } else {
-            s = area_span(area, lb, first * MA_BLOCK, lane);
-            s += area_span(block_sum, first, last, lane);
-            s += area_span(area, last * MA_BLOCK, le, lane);
+            s.v[0] = area_span(area, b, first * MA_BLOCK, lane);
+            s.v[0] += area_span(block_sum, first, last, lane);
+            s.v[0] += area_span(area, last * MA_BLOCK, e, lane);
         }
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) s += __shfl_xor(s, sh);
-        if (lane == 0) out[wave_base + owner] = s;
-    }
+    };
+    fixed_segment_walk<1>(seg, C, T, add, span, [&](const FixedSums<1>& s, int len, long long c) {
+        num_triangles[c] = len;
+        out[c] = s.v[0];
+    });
 }
 
 // ---- filter ----------------------------------------------------------------------------------------------------------------------------
@@ -347,14 +329,11 @@ static inline unsigned mc_blocks(long long n) { return (unsigned)((n + MC_THREAD
 
 }  // namespace mvd
 
-#define MC_REQUIRE_COUNT(what, name, n) \
-    MVD_REQUIRE((n) >= 0 && (n) <= 0x7fffffffLL, what ": %lld " name ", supported 0 .. 2^31 - 1", (long long)(n))
-
 extern "C" int mvd_mesh_hook_round(const int* triangles, long long T, long long M, int flags, int* label, unsigned char* referenced,
                                    int* changed, mvd_stream_t stream) {
     using namespace mvd;
-    MC_REQUIRE_COUNT("mesh_hook_round", "triangles", T);
-    MC_REQUIRE_COUNT("mesh_hook_round", "vertices", M);
+    MVD_REQUIRE_COUNT("mesh_hook_round", "triangles", T);
+    MVD_REQUIRE_COUNT("mesh_hook_round", "vertices", M);
     MVD_REQUIRE(changed && ((uintptr_t)changed & 3) == 0, "mesh_hook_round: changed must be given and 4-byte aligned");
     MVD_REQUIRE(M == 0 || (label && referenced), "mesh_hook_round: NULL argument");
     MVD_REQUIRE(((uintptr_t)label & 3) == 0, "mesh_hook_round: label must be 4-byte aligned");
@@ -380,7 +359,7 @@ extern "C" size_t mvd_mesh_component_rank_workspace_bytes(long long M) {
 extern "C" int mvd_mesh_component_rank(const int* label, const unsigned char* referenced, long long M, int* vertex_component,
                                        long long* num_components, void* workspace, size_t workspace_bytes, mvd_stream_t stream) {
     using namespace mvd;
-    MC_REQUIRE_COUNT("mesh_component_rank", "vertices", M);
+    MVD_REQUIRE_COUNT("mesh_component_rank", "vertices", M);
     MVD_REQUIRE(num_components && ((uintptr_t)num_components & 7) == 0, "mesh_component_rank: num_components must be given and 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     if (M == 0) {
@@ -406,8 +385,8 @@ extern "C" int mvd_mesh_component_rank(const int* label, const unsigned char* re
 extern "C" int mvd_mesh_component_table(const int* vertex_component, const int* triangles, long long T, long long M, long long C,
                                         int* triangle_component, int* num_vertices, mvd_stream_t stream) {
     using namespace mvd;
-    MC_REQUIRE_COUNT("mesh_component_table", "triangles", T);
-    MC_REQUIRE_COUNT("mesh_component_table", "vertices", M);
+    MVD_REQUIRE_COUNT("mesh_component_table", "triangles", T);
+    MVD_REQUIRE_COUNT("mesh_component_table", "vertices", M);
     MVD_REQUIRE(C >= 0 && C <= M, "mesh_component_table: %lld components of %lld vertices", C, M);
     MVD_REQUIRE(M == 0 || vertex_component, "mesh_component_table: NULL argument");
     MVD_REQUIRE(T == 0 || (triangles && triangle_component && M > 0), "mesh_component_table: NULL argument");
@@ -438,8 +417,8 @@ extern "C" int mvd_mesh_component_sums_f64(const float* vertices, long long M, c
                                            const long long* perm, long long C, int* num_triangles, double* area, void* workspace,
                                            size_t workspace_bytes, mvd_stream_t stream) {
     using namespace mvd;
-    MC_REQUIRE_COUNT("mesh_component_sums", "triangles", T);
-    MC_REQUIRE_COUNT("mesh_component_sums", "vertices", M);
+    MVD_REQUIRE_COUNT("mesh_component_sums", "triangles", T);
+    MVD_REQUIRE_COUNT("mesh_component_sums", "vertices", M);
     MVD_REQUIRE(C >= 0 && C <= T, "mesh_component_sums: %lld components of %lld triangles", C, T);
     if (C == 0) return MVD_OK;
     MVD_REQUIRE(vertices && triangles && sorted_component && perm && num_triangles && area, "mesh_component_sums: NULL argument");
@@ -487,8 +466,8 @@ extern "C" int mvd_mesh_filter(const int* triangles, long long T, long long M, c
                                int* kept_triangles, int* vertex_remap, long long max_triangles, long long* counts, void* workspace,
                                size_t workspace_bytes, mvd_stream_t stream) {
     using namespace mvd;
-    MC_REQUIRE_COUNT("mesh_filter", "triangles", T);
-    MC_REQUIRE_COUNT("mesh_filter", "vertices", M);
+    MVD_REQUIRE_COUNT("mesh_filter", "triangles", T);
+    MVD_REQUIRE_COUNT("mesh_filter", "vertices", M);
     MVD_REQUIRE(counts && ((uintptr_t)counts & 15) == 0, "mesh_filter: counts must be given and 16-byte aligned");
     MVD_REQUIRE(!keep_component || (C >= 0 && C <= 0x7fffffffLL && (T == 0 || triangle_component)),
                 "mesh_filter: keep_component needs triangle_component and 0 <= C < 2^31");
@@ -535,7 +514,7 @@ extern "C" int mvd_mesh_filter(const int* triangles, long long T, long long M, c
 extern "C" int mvd_mesh_gather_rows_f32(const float* src, const int* vertex_remap, long long M, int k, long long max_rows, float* dst,
                                         mvd_stream_t stream) {
     using namespace mvd;
-    MC_REQUIRE_COUNT("mesh_gather_rows", "vertices", M);
+    MVD_REQUIRE_COUNT("mesh_gather_rows", "vertices", M);
     MVD_REQUIRE(k >= 1 && k <= 65536, "mesh_gather_rows: %d columns, supported 1 .. 65536", k);
     MVD_REQUIRE(max_rows >= 0 && max_rows <= M, "mesh_gather_rows: %lld rows out of %lld", max_rows, M);
     MVD_REQUIRE(M * k <= 0x7fffffffLL, "mesh_gather_rows: M k = %lld values, supported up to 2^31 - 1 (one lane each)", M * k);
@@ -549,7 +528,7 @@ extern "C" int mvd_mesh_gather_rows_f32(const float* src, const int* vertex_rema
 extern "C" int mvd_mesh_vertex_normals_f32(const float* vertices, long long M, const int* triangles, long long T, const int* sorted_vertex,
                                            const long long* perm, float* normals, mvd_stream_t stream) {
     using namespace mvd;
-    MC_REQUIRE_COUNT("mesh_vertex_normals", "vertices", M);
+    MVD_REQUIRE_COUNT("mesh_vertex_normals", "vertices", M);
     MVD_REQUIRE(T >= 0 && 3 * T <= 0x7fffffffLL, "mesh_vertex_normals: %lld triangles, 3 T must be below 2^31", T);
     if (M == 0) return MVD_OK;
     MVD_REQUIRE(vertices && normals, "mesh_vertex_normals: NULL argument");

@@ -28,6 +28,7 @@ __device__ __forceinline__ void raise_absmax_seen(float* slot, float m, float se
     if (m > seen) raise_absmax(slot, m);
 }
 __host__ __device__ inline bool finite_f32(float v) { return fabsf(v) <= 3.402823466e38f; }  // false for inf and NaN
+__device__ __forceinline__ bool finite3(float x, float y, float z) { return finite_f32(x) && finite_f32(y) && finite_f32(z); }
 __device__ __forceinline__ float finite_abs_or_zero(float v) { return finite_f32(v) ? fabsf(v) : 0.f; }
 // The maximum of every lane's m over a workgroup of 256 threads (four waves): a butterfly inside the wave, one float per wave into
 // wmax (four floats of LDS that nobody else touches until the barrier inside has passed), thread 0 combines the four.  Thread 0
@@ -63,6 +64,9 @@ inline int launch_status(const char* what) {
             return MVD_ERR_INVALID_ARG; \
         }                               \
     } while (0)
+// a count of `name` (points, triangles, vertices) that a kernel indexes with an int
+#define MVD_REQUIRE_COUNT(what, name, n) \
+    MVD_REQUIRE((n) >= 0 && (n) <= 0x7fffffffLL, what ": %lld " name ", supported 0 .. 2^31 - 1", (long long)(n))
 
 // per-view device pointers, passed to kernels by value (kernarg segment)
 struct ViewPtrs {

@@ -1234,12 +1234,9 @@ def cloud_grid(points, origin, cell, check=True):
     return CloudGrid(p, keys, records, origin, cell)
 
 
-@inference_only
-def cloud_nearest(query, grid, max_dist):
-    """The truncated nearest neighbour of every query in the grid's cloud (include/mvd.h: mvd_cloud_nearest_f32).  query: (n,3)
-    points, sorted here by the grid's cells, or a CloudGrid of the same origin and cell (PointCloudEvaluation sorts each cloud once
-    for both directions).  grid.cell must be at least max_dist * (1 + 2^-10).
-    Returns (dist (n) float32, index (n) int32) in the query's original order; index -1 = nothing nearer than max_dist."""
+def _cloud_nearest(query_records, grid, max_dist):
+    """mvd_cloud_nearest_f32 behind cloud_nearest and cloud_nearest_records.  query_records(device) -> the (n,4) records of the
+    queries, asked for once the grid and max_dist have passed their checks -> (dist (n) float32, index (n) int32)."""
     if not isinstance(grid, CloudGrid):
         raise ValueError(f"grid: expected a CloudGrid (ops.cloud_grid), got {type(grid).__name__}")
     dev = grid.points.device
@@ -1248,18 +1245,38 @@ def cloud_nearest(query, grid, max_dist):
         raise ValueError(f"max_dist must be finite and > 0, got {max_dist}")
     if grid.cell < max_dist * CLOUD_CELL_MARGIN * (1 - 1e-12):
         raise ValueError(f"the grid's cell {grid.cell:g} is below max_dist * (1 + 2^-10) = {max_dist * CLOUD_CELL_MARGIN:g}")
-    if isinstance(query, CloudGrid):
-        if query.origin != grid.origin or query.cell != grid.cell or query.points.device != dev:
-            raise ValueError("query and target grids differ in origin, cell or device")
-        q = query
-    else:
-        q = cloud_grid(_cloud_points(query, "query", dev), grid.origin, grid.cell, check=False)
-    n, m = q.points.shape[0], grid.points.shape[0]
+    rec = query_records(dev)
+    n, m = rec.shape[0], grid.points.shape[0]
     dist = torch.empty(n, dtype=torch.float32, device=dev)
     index = torch.empty(n, dtype=torch.int32, device=dev)
-    call("mvd_cloud_nearest_f32", dev, q.records, n, grid.records, grid.keys, m, grid.origin[0], grid.origin[1], grid.origin[2], grid.inv,
+    call("mvd_cloud_nearest_f32", dev, rec, n, grid.records, grid.keys, m, grid.origin[0], grid.origin[1], grid.origin[2], grid.inv,
          max_dist, dist, index)
     return dist, index
+
+
+def _result_block(result, words, dev, owner):
+    """The device block a sum kernel fills: the caller's `result`, checked, or a new one of `words` int64."""
+    if result is None:
+        return torch.empty(words, dtype=torch.int64, device=dev)
+    if result.dtype != torch.int64 or result.device != dev or result.numel() != words or not result.is_contiguous():
+        raise ValueError(f"result must be {words} contiguous int64 on {owner} device")
+    return result
+
+
+@inference_only
+def cloud_nearest(query, grid, max_dist):
+    """The truncated nearest neighbour of every query in the grid's cloud (include/mvd.h: mvd_cloud_nearest_f32).  query: (n,3)
+    points, sorted here by the grid's cells, or a CloudGrid of the same origin and cell (PointCloudEvaluation sorts each cloud once
+    for both directions).  grid.cell must be at least max_dist * (1 + 2^-10).
+    Returns (dist (n) float32, index (n) int32) in the query's original order; index -1 = nothing nearer than max_dist."""
+    def records(dev):
+        if isinstance(query, CloudGrid):
+            if query.origin != grid.origin or query.cell != grid.cell or query.points.device != dev:
+                raise ValueError("query and target grids differ in origin, cell or device")
+            return query.records
+        return cloud_grid(_cloud_points(query, "query", dev), grid.origin, grid.cell, check=False).records
+
+    return _cloud_nearest(records, grid, max_dist)
 
 
 @inference_only
@@ -1280,10 +1297,7 @@ def cloud_scores(dist, index, thresholds, points=None, result=None):
     pts = _cloud_points(points, "points", dev) if points is not None else None
     if pts is not None and pts.shape[0] != n:
         raise ValueError(f"{pts.shape[0]} points for {n} distances")
-    if result is None:
-        result = torch.empty(10, dtype=torch.int64, device=dev)
-    elif result.dtype != torch.int64 or result.device != dev or result.numel() != 10 or not result.is_contiguous():
-        raise ValueError("result must be 10 contiguous int64 on dist's device")
+    result = _result_block(result, 10, dev, "dist's")
     nbytes = L.load().mvd_cloud_scores_workspace_bytes(n)
     ws = workspace(nbytes, dev)
     call("mvd_cloud_scores_f32", dev, d, idx, pts, n, th, th.shape[0], result, ws, int(nbytes))
@@ -1337,23 +1351,13 @@ def cloud_transform_records(points, perm, transform):
 def cloud_nearest_records(records, grid, max_dist):
     """cloud_nearest for query records (n,4) that are already there (cloud_transform_records): -> (dist (n) float32, index (n) int32)
     in the order of the records' original indices."""
-    if not isinstance(grid, CloudGrid):
-        raise ValueError(f"grid: expected a CloudGrid (ops.cloud_grid), got {type(grid).__name__}")
-    dev = grid.points.device
-    max_dist = float(torch.tensor(max_dist, dtype=torch.float32))
-    if not 0.0 < max_dist < float("inf"):
-        raise ValueError(f"max_dist must be finite and > 0, got {max_dist}")
-    if grid.cell < max_dist * CLOUD_CELL_MARGIN * (1 - 1e-12):
-        raise ValueError(f"the grid's cell {grid.cell:g} is below max_dist * (1 + 2^-10) = {max_dist * CLOUD_CELL_MARGIN:g}")
-    rec = L.as_dtype(torch.float32, False, records, "records", device=dev)
-    if rec.dim() != 2 or rec.shape[1] != 4:
-        raise ValueError(f"records must be (n,4), got {tuple(rec.shape)}")
-    n, m = rec.shape[0], grid.points.shape[0]
-    dist = torch.empty(n, dtype=torch.float32, device=dev)
-    index = torch.empty(n, dtype=torch.int32, device=dev)
-    call("mvd_cloud_nearest_f32", dev, rec, n, grid.records, grid.keys, m, grid.origin[0], grid.origin[1], grid.origin[2], grid.inv,
-         max_dist, dist, index)
-    return dist, index
+    def checked(dev):
+        rec = L.as_dtype(torch.float32, False, records, "records", device=dev)
+        if rec.dim() != 2 or rec.shape[1] != 4:
+            raise ValueError(f"records must be (n,4), got {tuple(rec.shape)}")
+        return rec
+
+    return _cloud_nearest(checked, grid, max_dist)
 
 
 @inference_only
@@ -1371,10 +1375,7 @@ def cloud_pair_sums(source, transform, index, target, pivot, target_normals=None
     if nrm is not None and m == 0:
         nrm = torch.zeros((1, 3), dtype=torch.float32, device=dev)  # plane mode is told by a pointer: one row nobody reads
     c = _cloud_origin(pivot, "pivot")
-    if result is None:
-        result = torch.empty(CLOUD_PAIR_SUMS_WORDS, dtype=torch.int64, device=dev)
-    elif result.dtype != torch.int64 or result.device != dev or result.numel() != CLOUD_PAIR_SUMS_WORDS or not result.is_contiguous():
-        raise ValueError(f"result must be {CLOUD_PAIR_SUMS_WORDS} contiguous int64 on the source's device")
+    result = _result_block(result, CLOUD_PAIR_SUMS_WORDS, dev, "the source's")
     nbytes = L.load().mvd_cloud_pair_sums_workspace_bytes(n)
     ws = workspace(nbytes, dev)
     call("mvd_cloud_pair_sums_f32", dev, s, n, _transform12(transform), idx, p if m else None, nrm, m, c[0], c[1], c[2], result, ws,

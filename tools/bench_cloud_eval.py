@@ -9,8 +9,8 @@ Two workloads, in one process on one GPU:
              case in which the grid prunes little and the scan itself is timed
 For each:
   (a) the sort (mvd_cloud_cell_keys_f32, torch.sort, mvd_cloud_grid_build_f32) of each cloud, the nearest kernel per direction, the
-      scores kernel of one direction and the whole PointCloudEvaluation call (with its host reads), each as the median over --repeats
-      HIP-event brackets of --inner calls after --warmup brackets;
+      scores kernel of one direction, mvd_voxel_reduce_f32 on the prediction's sorted voxel keys and the whole PointCloudEvaluation
+      call (with its host reads), each as the median over --repeats HIP-event brackets of --inner calls after --warmup brackets;
   (b) the same definition as chunked torch.cdist(compute_mode="donot_use_mm_for_euclid_dist").min(dim=1) on the same GPU, chunks of
       2^28 distances, one timed pass per direction after one warm-up chunk; the largest difference between its distances and the
       kernel's is printed;
@@ -55,6 +55,7 @@ def main():
             sys.path.insert(0, p)
     from robustmvd_amd import cloud_eval as CE
     from robustmvd_amd import depth_fusion as DF
+    from robustmvd_amd import _lib as L
     from robustmvd_amd import ops
     from bench_depth_fusion import bench_scene
     from bench_vis_mvsnet import event_ms, tree_label
@@ -107,6 +108,15 @@ def main():
         k_ab = event_ms(lambda: nearest(ga, gb, "ab"), args.warmup, args.repeats, args.inner)
         k_ba = event_ms(lambda: nearest(gb, ga, "ba"), args.warmup, args.repeats, args.inner)
         sc = event_ms(lambda: ops.cloud_scores(res["ab"][0], res["ab"][1], th, a), args.warmup, args.repeats, args.inner)
+        # the voxel thinning's own entry on keys sorted beforehand (ops.voxel_downsample's launches without its sort and its read)
+        voxel = float(np.float32(0.006 * 768 / H))
+        vkeys, vperm = ops._cloud_sorted(a, origin, 1.0 / voxel)
+        vout = (torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+                torch.empty(1, dtype=torch.int64, device=dev))
+        vbytes = int(L.load().mvd_voxel_reduce_workspace_bytes(n))
+        vws = ops.workspace(vbytes, dev)
+        vx = event_ms(lambda: ops.call("mvd_voxel_reduce_f32", dev, vkeys, vperm, a, None, n, vout[0], None, vout[1], vout[2], vws, vbytes),
+                      args.warmup, args.repeats, args.inner)
         ev = CE.PointCloudEvaluation(THRESHOLDS, MAX_DIST)
         whole = event_ms(lambda: ev(a, b), args.warmup, args.repeats, 1)
         score = ev(a, b)
@@ -144,6 +154,7 @@ def main():
                 f"  sort (keys, torch.sort, records)   pred {sort_a[0]:8.3f} ms ({sort_a[1]:.3f}, {sort_a[2]:.3f})   gt {sort_b[0]:8.3f} ms ({sort_b[1]:.3f}, {sort_b[2]:.3f})",
                 f"  nearest kernel   pred -> gt {k_ab[0]:9.3f} ms ({k_ab[1]:.3f}, {k_ab[2]:.3f})   gt -> pred {k_ba[0]:9.3f} ms ({k_ba[1]:.3f}, {k_ba[2]:.3f})",
                 f"  scores kernels (one direction, {n} distances) {sc[0]:8.4f} ms ({sc[1]:.4f}, {sc[2]:.4f})",
+                f"  voxel reduce kernels (the predicted cloud at voxel {voxel:.4g}, {int(vout[2].item())} voxels) {vx[0]:8.4f} ms ({vx[1]:.4f}, {vx[2]:.4f})",
                 f"  whole PointCloudEvaluation call (extent reads, two sorts, two searches, two scores, one read) {whole[0]:9.3f} ms ({whole[1]:.3f}, {whole[2]:.3f})",
                 f"  chunked torch.cdist(...).min on the same GPU   pred -> gt {c_ms[0]:10.1f} ms   gt -> pred {c_ms[1]:10.1f} ms   "
                 f"= {c_ms[0] / k_ab[0]:.1f}x and {c_ms[1] / k_ba[0]:.1f}x the nearest kernel (one pass each; {n * m / 1e9:.1f} G distances per direction)",
