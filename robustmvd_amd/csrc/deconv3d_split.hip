@@ -32,6 +32,10 @@
 #ifndef DS_TWO_PHASE
 #define DS_TWO_PHASE 0
 #endif
+// experiments (EXPFLAGS=-DDS_STAGE_PIXMAJOR=1): the persistent form stages its slab pixel-major
+#ifndef DS_STAGE_PIXMAJOR
+#define DS_STAGE_PIXMAJOR 0
+#endif
 
 namespace mvd {
 
@@ -98,6 +102,7 @@ struct DSParams {
     float* yamax;         // YAMAX: raised to max |y| over the finite outputs (zeroed by the caller)
     int B, Di, hi, wi, Cout, relu;
     int tiles_w, tiles_h, ncb;  // ncb: output channel blocks of 16 NT channels, one per workgroup
+    int tiles;                  // the persistent form: ncb tiles_w tiles_h Di B
 };
 
 // NT: 16-channel tiles per workgroup; MT: 16-column tiles per wave (TW = 16 MT input columns); YAMAX: also max |y| (a variant
@@ -343,7 +348,324 @@ __global__ void __launch_bounds__(256) deconv3d_split_kernel(DSParams p) {
     }
 }
 
-template <int CIN, int NT, int MT, bool YAMAX>
+// The persistent, software-pipelined form: the same sums in the same order, bit for bit.  A workgroup walks the tiles t = blockIdx.x,
+// + gridDim.x, ... (a bound from the parameters alone: no ticket, no flag, no wait on another workgroup), decoded as above; with a
+// grid that is a multiple of ncb it keeps its channel block.  Once per workgroup: the activation scale, the per-lane channel
+// constants (again only where the channel block changes), and at the very end ONE workgroup_max
+// and atomic over everything the workgroup wrote: the lane maximum is carried across the tiles, so the epilogue has one phase and
+// no barrier.
+//
+// Loads in flight.  vmcnt retires in order, so what a step waits for is requested ahead of what may stay outstanding:
+//   * weights: LA = 9 (the pair form: 18 fragments, 72 registers) keeps all of them for the life of the workgroup.  LA < 9 streams
+//     them LA (kd, kh) steps ahead in a ring that runs on ACROSS the tiles: step s requests the fragments of step (s + LA) % 9, of
+//     the next tile once that wraps, into the registers step s - 1 has just finished with (all indices are static: a tile is
+//     exactly nine steps);
+//   * the skip values and then the next tile's slab (into registers) go out right behind the last request for THIS tile's weights,
+//     at step 8 - LA (LA = 9: behind the staging): steps 9 - LA .. 8 and the epilogue wait with the slab still in flight, and it
+//     lands under them, the stores and the barrier at the top of the next tile.  SKIP_EARLY = false (conv7, which has no 32
+//     registers left for them) reads the skip values behind the last step instead, as deconv3d_split_kernel does.
+// For the wait counts to be static every load is unconditional: staging items outside the volume load the batch's first voxel and
+// are zeroed when they are split (a neighbour's inf or NaN cannot leak), lanes without an output load the skip of offset 0, a layer
+// without a skip reads y in its place and selects zero, and the last tile prefetches its own slab again.
+// PIXMAJOR: staging item e = (channel group, pixel) with the pixel running fastest, so that consecutive lanes write consecutive
+// 16-byte slots of one plane (no bank conflicts) and read 32 bytes each of consecutive voxels; otherwise the order of
+// deconv3d_split_kernel (consecutive lanes read consecutive bytes and write planes a multiple of 256 bytes apart).
+template <int CIN, int NT, int MT, bool YAMAX, int LA, int WAVES, bool SKIP_EARLY, bool PIXMAJOR>
+__global__ void __launch_bounds__(256, WAVES) deconv3d_split_persist_kernel(DSParams p) {
+    const float amax_seen = absmax_seen(YAMAX ? p.yamax : nullptr);
+    using G = DSGeom<CIN, MT>;
+    constexpr bool PAIR = G::PAIR;
+    constexpr int COLS = G::COLS, NG = G::NG, KS = G::KS, GS = G::GS, TERM = G::TERM, NCLS = G::NCLS, NFRAG = ds_nfrag(CIN);
+    constexpr int NIT = G::NIT, C4 = CIN / 4, NKW = PAIR ? 1 : 3;
+    static_assert(!PAIR || NT == 1, "the pair form has one row tile");
+    static_assert(LA >= 1 && LA <= 9 && (LA < 9 || PAIR), "resident weights: the pair form (one channel block) only");
+    static_assert(NIT <= 32, "one bit per staging item");
+    extern __shared__ __attribute__((aligned(16))) char dslab[];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // a scalar: a tile's output offsets are scalar + lane
+    const int vox = lane & 15, q = lane >> 4;
+    int t = blockIdx.x;
+    if (t >= p.tiles) return;
+
+    float xsc, xsc_inv;
+    split_xscale(p.xamax, xsc, xsc_inv);
+
+    struct Tile { int cb, b, zd, r0, c0; };
+    auto tile_of = [&](int bx) {
+        Tile tl;
+        tl.cb = bx % p.ncb; bx /= p.ncb;
+        tl.c0 = (bx % p.tiles_w) * G::TW; bx /= p.tiles_w;
+        tl.r0 = (bx % p.tiles_h) * DS_TH; bx /= p.tiles_h;
+        tl.zd = bx % p.Di;
+        tl.b = bx / p.Di;
+        return tl;
+    };
+
+    // staging item i of this thread, e = tid + 256 i: where it goes in the slab (-1: beyond the items) and which voxel of a tile it
+    // is.  Worked out again where it is used (tz: a zero the compiler cannot see through), which is cheaper than 2 NIT registers
+    // held for the life of the workgroup.
+    struct Item { int loff, pl, row, col, g; };
+    auto item_of = [&](int i, int tz) {
+        const int e = tid + tz + 256 * i;
+        const int g = PIXMAJOR ? e / G::PIX : e % NG, pix = PIXMAJOR ? e % G::PIX : e / NG;
+        const int col = pix % COLS, r = pix / COLS;
+        const int pl = r / DS_ROWS;
+        return Item{e < G::ITEMS ? g * GS + pix * 16 : -1, pl, r - pl * DS_ROWS, col, g};
+    };
+    // the loads in flight for the next slab, and which of its items lie inside the volume
+    float4 pf[NIT][2];
+    unsigned okm = 0;
+    auto prefetch = [&](const Tile& tl) {
+        const float4* __restrict__ x4 = reinterpret_cast<const float4*>(p.x) + (size_t)tl.b * p.Di * p.hi * p.wi * C4;
+        okm = 0;
+        int tz = 0;
+        asm volatile("" : "+v"(tz));
+#pragma unroll
+        for (int i = 0; i < NIT; ++i) {
+            const Item it = item_of(i, tz);
+            const int plane = tl.zd + it.pl, gr = tl.r0 + it.row, gc = tl.c0 + it.col;
+            const bool ok = it.loff >= 0 && plane < p.Di && gr < p.hi && gc < p.wi;
+            const size_t o = ok ? (((size_t)plane * p.hi + gr) * p.wi + gc) * C4 + 2 * it.g : 0;
+            pf[i][0] = x4[o];
+            pf[i][1] = x4[o + 1];
+            okm |= (ok ? 1u : 0u) << i;
+        }
+    };
+
+    // weight fragments of step `step` of channel block cb
+    dsh8 w[9][NKW][KS][NT][2];
+    auto load_w = [&](int cb, int step) {
+        const char* __restrict__ wl = p.wpk + (size_t)cb * NT * NFRAG * DS_FRAG_BYTES + lane * 16;
+#pragma unroll
+        for (int kw = 0; kw < NKW; ++kw)
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+                for (int n = 0; n < NT; ++n)
+#pragma unroll
+                    for (int tm = 0; tm < 2; ++tm)
+                        w[step][kw][ks][n][tm] = *reinterpret_cast<const dsh8*>(
+                            wl + ((size_t)n * NFRAG + (step * NKW + kw) * KS + ks) * DS_FRAG_BYTES + tm * 1024);
+    };
+
+    // per-lane constants of this lane's 4 output channels (see deconv3d_split_kernel)
+    float emul[NT][4], emul2[NT][4], esc[NT][4], esh[NT][4];
+    auto load_consts = [&](int cb) {
+        const float* __restrict__ eun = reinterpret_cast<const float*>(p.wpk + (size_t)p.ncb * NT * NFRAG * DS_FRAG_BYTES);
+#pragma unroll
+        for (int n = 0; n < NT; ++n)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int row = (cb * NT + n) * 16 + q * 4 + k;
+                const int ch = PAIR ? (row & 7) : row;
+                const int se = (int)((__float_as_uint(eun[row]) >> 23) & 0xffu) + (int)((__float_as_uint(xsc_inv) >> 23) & 0xffu) - 254;
+                emul[n][k] = __uint_as_float((unsigned)(127 + (se >> 1)) << 23);
+                emul2[n][k] = __uint_as_float((unsigned)(127 + se - (se >> 1)) << 23);
+                esc[n][k] = p.scale[ch];
+                esh[n][k] = p.shift[ch];
+            }
+    };
+
+    const char* __restrict__ lbase = dslab + (PAIR ? (q & 1) * GS + (q >> 1) * 16 : q * GS) + (wave * COLS + vox) * 16;
+    const float* __restrict__ skp = p.skip ? p.skip : p.y;
+
+    Tile tl = tile_of(t);
+    load_consts(tl.cb);
+    int cb_have = tl.cb;
+    prefetch(tl);
+#pragma unroll
+    for (int s = 0; s < LA; ++s) load_w(tl.cb, s);
+    [[maybe_unused]] float amax = 0.f;  // max |y| over this lane's finite outputs, all tiles
+
+    for (;;) {
+        const int tn = t + (int)gridDim.x;
+        const bool more = tn < p.tiles;
+        Tile tnext;  // decoded where the requests for it begin (scalar registers)
+        if (tl.cb != cb_have) {
+            load_consts(tl.cb);
+            cb_have = tl.cb;
+        }
+
+        // this lane's outputs: class c, column tile m, channel tile n -> offset of its float4 in y (and skip) = the tile's scalar
+        // base (class 0, m 0, n 0) + an offset of 32 bits (the launcher bounds an output plane): one scalar pair for all of them
+        const int arow = tl.r0 + wave;
+        const bool row_ok = arow < p.hi;  // wave-uniform
+        const size_t obase = ((((size_t)tl.b * 2 * p.Di + 2 * tl.zd) * 2 * p.hi + 2 * arow) * 2 * p.wi + 2 * tl.c0) * p.Cout + (PAIR ? 0 : tl.cb * NT * 16);
+        auto delta = [&](int c, int m, int n) {
+            const int pd = PAIR ? c >> 1 : c >> 2, ph = PAIR ? c & 1 : (c >> 1) & 1, pw = PAIR ? 0 : c & 1;
+            return ((pd * 2 * p.hi + ph) * 2 * p.wi + 32 * m + pw) * p.Cout + 16 * n;
+        };
+        const int lane_off = (2 * vox + (PAIR ? q >> 1 : 0)) * p.Cout + (PAIR ? 4 * (q & 1) : q * 4);
+        bool has[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) has[m] = row_ok && tl.c0 + m * 16 + vox < p.wi;
+
+        __builtin_amdgcn_sched_barrier(0);
+        __syncthreads();  // every wave has finished reading the previous tile's slab
+        int tz = 0;
+        asm volatile("" : "+v"(tz));
+#pragma unroll
+        for (int i = 0; i < NIT; ++i) {
+            const int lo = item_of(i, tz).loff;
+            if (lo < 0) continue;
+            unsigned h[4], l[4];
+            split2(xsc, pf[i][0].x, pf[i][0].y, h[0], l[0]);
+            split2(xsc, pf[i][0].z, pf[i][0].w, h[1], l[1]);
+            split2(xsc, pf[i][1].x, pf[i][1].y, h[2], l[2]);
+            split2(xsc, pf[i][1].z, pf[i][1].w, h[3], l[3]);
+            dsu4 hv = {h[0], h[1], h[2], h[3]}, lv = {l[0], l[1], l[2], l[3]};
+            if (!((okm >> i) & 1u)) { hv = dsu4{0, 0, 0, 0}; lv = dsu4{0, 0, 0, 0}; }
+            *reinterpret_cast<dsu4*>(dslab + lo) = hv;
+            *reinterpret_cast<dsu4*>(dslab + TERM + lo) = lv;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+
+        float4 sk[NCLS][MT][NT];
+        auto request_skip = [&]() {
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c)
+#pragma unroll
+                for (int m = 0; m < MT; ++m)
+#pragma unroll
+                    for (int n = 0; n < NT; ++n) sk[c][m][n] = *reinterpret_cast<const float4*>(
+                            skp + (row_ok ? obase : 0) + (unsigned)(row_ok && tl.c0 + m * 16 < p.wi ? delta(c, m, n) + (has[m] ? lane_off : 0) : 0));
+        };
+        auto request_skip_and_slab = [&]() {
+            if constexpr (SKIP_EARLY) request_skip();
+            tnext = tile_of(more ? tn : t);
+            prefetch(tnext);
+        };
+        if constexpr (LA == 9) {
+            request_skip_and_slab();
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();
+
+        dsf4 acc[NCLS][MT][NT];
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c)
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+#pragma unroll
+                for (int n = 0; n < NT; ++n) acc[c][m][n] = dsf4{0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll
+        for (int step = 0; step < 9; ++step) {
+            const int kd = step / 3, kh = step % 3;
+            if constexpr (LA < 9) {
+                if (step + LA < 9) load_w(tl.cb, step + LA);
+                else load_w(tnext.cb, step + LA - 9);
+                if (step == 8 - LA) request_skip_and_slab();
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            const int rowpix = ((kd == 0 ? DS_ROWS : 0) + (kh == 0)) * COLS;
+#pragma unroll
+            for (int kw = 0; kw < NKW; ++kw) {
+                const int cls = PAIR ? (((kd != 1) << 1) | (kh != 1)) : (((kd != 1) << 2) | ((kh != 1) << 1) | (kw != 1));
+                const int colpix = PAIR ? 0 : (kw == 0);
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    dsh8 xh[MT], xl[MT];
+#pragma unroll
+                    for (int m = 0; m < MT; ++m) {
+                        const char* a = lbase + ks * 4 * GS + (rowpix + colpix + m * 16) * 16;
+                        xh[m] = *reinterpret_cast<const dsh8*>(a);
+                        xl[m] = *reinterpret_cast<const dsh8*>(a + TERM);
+                    }
+#pragma unroll
+                    for (int m = 0; m < MT; ++m)
+#pragma unroll
+                        for (int n = 0; n < NT; ++n) {
+                            acc[cls][m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[step][kw][ks][n][0], xh[m], acc[cls][m][n], 0, 0, 0);
+                            acc[cls][m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[step][kw][ks][n][1], xh[m], acc[cls][m][n], 0, 0, 0);
+                            acc[cls][m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[step][kw][ks][n][0], xl[m], acc[cls][m][n], 0, 0, 0);
+                        }
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (!SKIP_EARLY) request_skip();
+
+        // ---- epilogue, as deconv3d_split_kernel's: y = act(conv 2^(e + k_c) scale + shift) + skip ----
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c)
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+#pragma unroll
+                for (int n = 0; n < NT; ++n) {
+                    float r[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        float val = fmaf(acc[c][m][n][k] * emul[n][k] * emul2[n][k], esc[n][k], esh[n][k]);
+                        if (p.relu) val = fmaxf(val, 0.f);
+                        r[k] = val;
+                    }
+                    const float4 s4 = p.skip ? sk[c][m][n] : make_float4(0.f, 0.f, 0.f, 0.f);
+                    const dsf4 out = {r[0] + s4.x, r[1] + s4.y, r[2] + s4.z, r[3] + s4.w};
+                    if (has[m]) {
+                        if constexpr (YAMAX)
+                            amax = fmaxf(fmaxf(amax, fmaxf(finite_abs_or_zero(out[0]), finite_abs_or_zero(out[1]))),
+                                         fmaxf(finite_abs_or_zero(out[2]), finite_abs_or_zero(out[3])));
+                        *reinterpret_cast<dsf4*>(p.y + obase + (unsigned)(delta(c, m, n) + lane_off)) = out;
+                    }
+                }
+        if (!more) break;
+        t = tn;
+        tl = tnext;
+    }
+    if constexpr (YAMAX) {  // ONE atomic per workgroup, against the slot as it was when the workgroup started
+        const float m = workgroup_max(amax, reinterpret_cast<float*>(dslab + G::LDS), tid);
+        if (tid == 0) {
+            if (m > amax_seen) atomicMax(reinterpret_cast<unsigned*>(p.yamax), __float_as_uint(m));
+        }
+    }
+}
+
+// The layers of the persistent form: the tile each runs at (the entry point's choice below) and, per layer, how far ahead its weights
+// are requested and the waves per SIMD its registers are bounded to.  DS_PERSIST_WGS[layer] = workgroups per CU of its grid where
+// the layer passed the ship rule (in the headline forward its median below the minimum of one tile per workgroup,
+// profiles/deconv_persist_frame.txt); 0 where the layer stays on deconv3d_split_kernel.  The product library builds the instances of
+// the non-zero entries alone; the experiments library builds all of them and reaches them with MVD_DS_PERSIST (0 one tile per
+// workgroup, 1 this rule, n > 1 a grid of exactly n workgroups) and MVD_DS_LA (another look-ahead).
+enum { DS_CONV7 = 0, DS_CONV9 = 1, DS_CONV11 = 2 };
+constexpr int DS_PERSIST_WGS[3] = {2, 2, 2};
+template <int CIN> struct DSPersist;
+// (ALT_LA, ALT_WAVES: the other instance of the experiments library, MVD_DS_LA=<ALT_LA>)
+template <> struct DSPersist<64> { static constexpr int LAYER = DS_CONV7, LA = 1, WAVES = 2, ALT_LA = 1, ALT_WAVES = 2; static constexpr bool SKIP_EARLY = false, ALT_SKIP_EARLY = false; };
+template <> struct DSPersist<32> { static constexpr int LAYER = DS_CONV9, LA = 2, WAVES = 2, ALT_LA = 1, ALT_WAVES = 2; static constexpr bool SKIP_EARLY = true, ALT_SKIP_EARLY = true; };
+template <> struct DSPersist<16> { static constexpr int LAYER = DS_CONV11, LA = 9, WAVES = 2, ALT_LA = 2, ALT_WAVES = 3; static constexpr bool SKIP_EARLY = true, ALT_SKIP_EARLY = false; };
+#ifdef MVD_EXPERIMENTS
+constexpr bool DS_EXP = true;
+#else
+constexpr bool DS_EXP = false;
+#endif
+// grid of the persistent form (0 = not taken): at most 256 CUs x the table's workgroups, a multiple of ncb so that a workgroup
+// keeps its channel block.  (All of them resident beats an even share: conv7's 1152 tiles on 512 workgroups, two or three each,
+// take 39 - 41 us alone, on 384 with three each 45 - 47.)
+static long long ds_persist_grid(int layer, long long tiles, int ncb, long long plane_floats) {
+    if (tiles > 0x3fffffffLL || plane_floats > (1LL << 28)) return 0;  // 32-bit tile indices and in-tile output offsets
+    const int wgs = DS_PERSIST_WGS[layer];
+    if (const char* e = exp_env("MVD_DS_PERSIST")) {
+        const long long v = atoll(e);
+        if (v <= 0) return 0;
+        if (v > 1) return v < tiles ? v : tiles;
+    }
+    if (wgs == 0) return 0;
+    const long long grid = (256LL * wgs + ncb - 1) / ncb * ncb;
+    return grid < tiles ? grid : tiles;
+}
+
+template <int CIN, int NT, int MT, bool YAMAX, int LA, int WAVES, bool SKIP_EARLY>
+static int ds_launch_persist(const DSParams& p, long long grid, hipStream_t st) {
+    using G = DSGeom<CIN, MT>;
+    hipLaunchKernelGGL((deconv3d_split_persist_kernel<CIN, NT, MT, YAMAX, LA, WAVES, SKIP_EARLY, DS_STAGE_PIXMAJOR != 0>), dim3((unsigned)grid), dim3(256),
+                       G::LDS + 16, st, p);
+    return launch_status("deconv3d_split: persistent");
+}
+
+// PERSIST: the tile is the one the layer's persistent form is built for
+template <int CIN, int NT, int MT, bool YAMAX, bool PERSIST>
 static int ds_launch_v(DSParams p, hipStream_t st) {
     using G = DSGeom<CIN, MT>;
     static_assert(G::LDS <= 64 * 1024, "slab exceeds the default LDS limit");
@@ -352,12 +674,24 @@ static int ds_launch_v(DSParams p, hipStream_t st) {
     p.ncb = G::PAIR ? 1 : p.Cout / (16 * NT);
     const long long nblk = (long long)p.ncb * p.tiles_w * p.tiles_h * p.Di * p.B;
     MVD_REQUIRE(nblk <= 0x7fffffffLL, "deconv3d_split: %lld workgroups exceed the grid limit", nblk);
+    if constexpr (PERSIST && (DS_EXP || DS_PERSIST_WGS[DSPersist<CIN>::LAYER] > 0)) {
+        using P = DSPersist<CIN>;
+        if (const long long grid = ds_persist_grid(P::LAYER, nblk, p.ncb, (2LL * p.hi + 2) * 2 * p.wi * p.Cout)) {
+            p.tiles = (int)nblk;
+#ifdef MVD_EXPERIMENTS
+            if (const char* e = exp_env("MVD_DS_LA")) {  // the layer's other instance: another look-ahead of the streamed weights
+                if (P::ALT_LA != P::LA && atoi(e) == P::ALT_LA) return ds_launch_persist<CIN, NT, MT, YAMAX, P::ALT_LA, P::ALT_WAVES, P::ALT_SKIP_EARLY>(p, grid, st);
+            }
+#endif
+            return ds_launch_persist<CIN, NT, MT, YAMAX, P::LA, P::WAVES, P::SKIP_EARLY>(p, grid, st);
+        }
+    }
     hipLaunchKernelGGL((deconv3d_split_kernel<CIN, NT, MT, YAMAX>), dim3((unsigned)nblk), dim3(256), G::LDS + 16, st, p);
     return launch_status("deconv3d_split");
 }
-template <int CIN, int NT, int MT>
+template <int CIN, int NT, int MT, bool PERSIST = false>
 static int ds_launch(const DSParams& p, hipStream_t st) {
-    return p.yamax ? ds_launch_v<CIN, NT, MT, true>(p, st) : ds_launch_v<CIN, NT, MT, false>(p, st);
+    return p.yamax ? ds_launch_v<CIN, NT, MT, true, PERSIST>(p, st) : ds_launch_v<CIN, NT, MT, false, PERSIST>(p, st);
 }
 
 }  // namespace mvd
@@ -402,9 +736,9 @@ int mvd_deconv3d_bn_relu_f32_split(const float* x, const float* x_absmax, const 
     // the experiments library
     int cfg = 0;
     if (const char* e = mvd::exp_env("MVD_DS_CFG")) cfg = atoi(e);
-    if (Cin == 16) return cfg % 10 == 3 ? mvd::ds_launch<16, 1, 3>(p, st) : mvd::ds_launch<16, 1, 2>(p, st);
-    if (Cin == 32) return cfg % 10 == 2 ? mvd::ds_launch<32, 1, 2>(p, st) : mvd::ds_launch<32, 1, 1>(p, st);
+    if (Cin == 16) return cfg % 10 == 3 ? mvd::ds_launch<16, 1, 3>(p, st) : mvd::ds_launch<16, 1, 2, true>(p, st);
+    if (Cin == 32) return cfg % 10 == 2 ? mvd::ds_launch<32, 1, 2>(p, st) : mvd::ds_launch<32, 1, 1, true>(p, st);
     if (cfg / 10 == 2 && Cout % 32 == 0) return mvd::ds_launch<64, 2, 1>(p, st);
-    return mvd::ds_launch<64, 1, 1>(p, st);
+    return mvd::ds_launch<64, 1, 1, true>(p, st);
 }
 }
