@@ -926,6 +926,74 @@ int mvd_mesh_gather_rows_f32(const float* src, const int* vertex_remap, long lon
 int mvd_mesh_vertex_normals_f32(const float* vertices, long long M, const int* triangles, long long T, const int* sorted_vertex,
                                 const long long* perm, float* normals, mvd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Mesh evaluation: the truncated distance from points to a triangle mesh, and deterministic covering samples of its surface.  The
+ * reference has NO counterpart: the definition is robustmvd_amd/mesh_eval.py (mesh_distance_numpy, mesh_grid_pairs_numpy,
+ * sample_mesh_numpy) and DESIGN.md, restated here.
+ *
+ * vertices (M,3) float32, triangles (T,3) int32; M, T and every other count <= 2^31 - 1.  A triangle is INVALID if an index is
+ * outside [0, M) or a vertex has a non-finite coordinate: it matches no query and gets no sample.  A degenerate finite triangle
+ * (zero area) is valid and acts as its segment or point.
+ *
+ * Distance of a query q to a triangle A, B, C, everything relative to the query (the values must survive coordinates of 10^3):
+ *   a = A - q, b = B - q, c = C - q;  E0 = B - A, E1 = C - B, E2 = A - C;  dot(u,v) = (u.x v.x + u.y v.y) + u.z v.z
+ *   seg(p, E): ee = dot(E,E); t = clamp(-dot(p,E) / ee, 0, 1), t = 0 when ee == 0; r = p + t E; the result is dot(r,r)
+ *   d2 = min(seg(a,E0), seg(b,E1), seg(c,E2));  n = E0 x E1, nn = dot(n,n)
+ *   inside iff nn > 0 and dot(n, a x E0) >= 0 and dot(n, b x E1) >= 0 and dot(n, c x E2) >= 0;  inside: d2 = min(d2, dot(n,a)^2 / nn)
+ *   dist(q, triangle) = sqrt(d2)
+ * (The kernel forms the sums as FMAs and the two divisions with a 1-ulp reciprocal.)  Truncated nearest triangle, max_dist > 0:
+ *   dist[i]  = min(max_dist, min over valid triangles)   (max_dist for an invalid query, T = 0 or no valid triangle)
+ *   index[i] = the triangle of that minimum when it is < max_dist (strict), else -1
+ * Among triangles with an equal d2, as the device computed it, the smallest triangle index wins.  No atomic decides a value: two
+ * calls give the same bits.
+ *
+ * The triangle grid.  Cells, keys and inv are mvd_cloud_cell_keys_f32's.  A valid triangle is entered into every cell of its
+ * axis-aligned box, per axis floor((double(min_a) - origin_a) * inv) .. floor((double(max_a) - origin_a) * inv), no dilation (the
+ * caller checks that every index is in [0, 2^21 - 1); the device clamps).
+ * mvd_mesh_cell_counts_f32: counts (T) int64 = the cells of each triangle's box, 0 for an invalid triangle (saturating at 2^31). */
+int mvd_mesh_cell_counts_f32(const float* vertices, long long M, const int* triangles, long long T, double origin_x, double origin_y,
+                             double origin_z, double inv, long long* counts, mvd_stream_t stream);
+
+/* The pair list: ends (T) int64 = the INCLUSIVE prefix sums of the counts (the caller's), P = ends[T-1] <= 2^31 - 1.  keys (P) int64
+ * and pair_triangle (P) int32: one pair per cell of every valid triangle's box, in triangle order, inside a triangle x-major, then
+ * y, then z.  One lane per pair: the triangle by an upper-bound search in ends, the cell from the rank inside the box.  Between
+ * this entry and mvd_mesh_records_f32 the caller sorts the keys STABLY and keeps the permutation. */
+int mvd_mesh_pairs_f32(const float* vertices, long long M, const int* triangles, long long T, const long long* ends, long long P,
+                       double origin_x, double origin_y, double origin_z, double inv, long long* keys, int* pair_triangle,
+                       mvd_stream_t stream);
+
+/* records (P,12) float32, 16-byte aligned, 48 bytes per sorted pair: sorted position i holds the vertices A, B, C (nine floats) of
+ * triangle pair_triangle[perm[i]], that index as the bits of the tenth float, and two zeros. */
+int mvd_mesh_records_f32(const float* vertices, long long M, const int* triangles, long long T, const int* pair_triangle,
+                         const long long* perm, long long P, float* records, mvd_stream_t stream);
+
+/* query_records (n,4): mvd_cloud_grid_build_f32's, keyed with this origin and inv (the queries' order only decides how well a wave's
+ * queries share cells); triangle_records (P,12) and pair_keys (P): the sorted pair list.  The cell edge 1 / inv must be at least
+ * max_dist (1 + 2^-10): then the 3 x 3 x 3 cells around a query's hold every triangle within max_dist (the argument is in
+ * csrc/mesh_eval.hip).  dist (n) and index (n) are written in the queries' ORIGINAL order.  n == 0 writes nothing; P == 0 truncates
+ * every query. */
+int mvd_mesh_nearest_f32(const float* query_records, long long n, const float* triangle_records, const long long* pair_keys,
+                         long long P, double origin_x, double origin_y, double origin_z, double inv, float max_dist, float* dist,
+                         int* index, mvd_stream_t stream);
+
+/* Surface samples at a spacing s > 0, inv_s2 = 1.0 / (double(s) * double(s)) formed by the host.  A valid triangle with longest
+ * squared edge L2 (float64 differences of the float32 coordinates, (dx^2 + dy^2) + dz^2) gets k = the smallest integer >= 1 with
+ * k k >= L2 * inv_s2, found with integer correction steps (independent of how sqrt rounds; capped at 2^26), and k^2 samples: the
+ * centroids of its k^2 congruent sub-triangles.  Rows i = 0 .. k-1; row i holds 2 (k - i) - 1 samples; position t in the row gives
+ * j = t >> 1, down = t & 1 and the weights, each ONE double division,
+ *   on B (3 i + 1 + down) / (3 k),   on C (3 j + 1 + down) / (3 k),   on A (3 (k - i - j) - 2 - 2 down) / (3 k);
+ * the point is (wA A + wB B) + wC C in double, rounded once to float32 (no contraction: numpy forms the same bits); attributes
+ * (M,channels) float32, NULL or with out_attributes, go through the same expression.  Every surface point is within 2 s / 3 of a
+ * sample.  mvd_mesh_sample_counts_f32: counts (T) int64 = k^2, 0 for an invalid triangle (saturating at 2^31).
+ * mvd_mesh_sample_f32: ends (T) = the INCLUSIVE prefix sums of the counts (the caller's), S = ends[T-1]; points (S,3), sample_triangle
+ * (S) int32, out_attributes (S,channels), in triangle order, then sample order.  One lane per sample: the triangle by an upper-bound
+ * search in ends, the row by an integer square root. */
+int mvd_mesh_sample_counts_f32(const float* vertices, long long M, const int* triangles, long long T, double inv_s2, long long* counts,
+                               mvd_stream_t stream);
+int mvd_mesh_sample_f32(const float* vertices, long long M, const int* triangles, long long T, const float* attributes, int channels,
+                        const long long* ends, long long S, double inv_s2, float* points, int* sample_triangle, float* out_attributes,
+                        mvd_stream_t stream);
+
 /* layout helpers used at the operator-level boundary (reference tensors are NCHW / NCDHW) */
 int mvd_nchw_to_nhwc_f32(const float* src, float* dst, int N, int C, long long HW, mvd_stream_t stream);
 int mvd_nhwc_to_nchw_f32(const float* src, float* dst, int N, int C, long long HW, mvd_stream_t stream);

@@ -34,3 +34,6 @@ from .render import render_mesh, render_numpy, RenderResult  # noqa: F401,E402
 from . import mesh_clean  # noqa: F401,E402
 from .mesh_clean import (mesh_components, clean_mesh, vertex_normals, components_numpy, component_table_numpy, clean_numpy,  # noqa: F401,E402
                          vertex_normals_numpy, MeshComponents, CleanResult)
+from . import mesh_eval  # noqa: F401,E402
+from .mesh_eval import (MeshEvaluation, evaluate_mesh, mesh_distance, sample_mesh, mesh_distance_numpy, mesh_grid_pairs_numpy,  # noqa: F401,E402
+                        sample_mesh_numpy)

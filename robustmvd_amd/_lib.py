@@ -200,6 +200,18 @@ SIGNATURES = {
                                       ctypes.c_void_p]),
     "mvd_mesh_vertex_normals_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
                                          ctypes.c_void_p, _c_float_p, ctypes.c_void_p]),
+    "mvd_mesh_cell_counts_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong] + [ctypes.c_double] * 4
+                                 + [ctypes.c_void_p] * 2),
+    "mvd_mesh_pairs_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong]
+                           + [ctypes.c_double] * 4 + [ctypes.c_void_p] * 3),
+    "mvd_mesh_records_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
+                                  ctypes.c_longlong, _c_float_p, ctypes.c_void_p]),
+    "mvd_mesh_nearest_f32": (_i, [_c_float_p, ctypes.c_longlong, _c_float_p, ctypes.c_void_p, ctypes.c_longlong]
+                             + [ctypes.c_double] * 4 + [ctypes.c_float, _c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mvd_mesh_sample_counts_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_double,
+                                        ctypes.c_void_p, ctypes.c_void_p]),
+    "mvd_mesh_sample_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, _c_float_p, _i, ctypes.c_void_p,
+                                 ctypes.c_longlong, ctypes.c_double, _c_float_p, ctypes.c_void_p, _c_float_p, ctypes.c_void_p]),
 }
 CULL_NONE, CULL_BACK, CULL_FRONT = 0, 1, 2  # MVD_CULL_*
 RENDER_LOAD_FIRST, RENDER_KEEP_PROJECT, RENDER_KEEP_KEYS, RENDER_NO_RESOLVE = 1, 16, 32, 64  # MVD_RENDER_*

@@ -12,25 +12,11 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "cloud_grid.h"  // CE_*, cell_index, cell_key, lower_bound: shared with mesh_eval.hip
 #include "compact.h"
 #include "fixed_sums.h"
 
 namespace mvd {
-
-constexpr int CE_BITS = 21;
-constexpr int CE_LIMIT = (1 << CE_BITS) - 1;  // a cell index is in [0, CE_LIMIT): the all-ones key is the invalid points' own
-constexpr long long CE_INVALID_KEY = 0x7fffffffffffffffLL;
-
-// floor((double(v) - o) * inv), two IEEE double operations and a floor (the library is built without contraction): numpy forms the
-// same bits.  Clamped to [lo, hi] before the conversion, so that a far point cannot overflow the int.
-__device__ __forceinline__ int cell_index(float v, double o, double inv, double lo, double hi) {
-    const double t = floor(((double)v - o) * inv);
-    return (int)fmin(fmax(t, lo), hi);
-}
-
-__device__ __forceinline__ long long cell_key(int ix, int iy, int iz) {
-    return ((long long)ix << (2 * CE_BITS)) | ((long long)iy << CE_BITS) | (long long)iz;
-}
 
 // ---- keys and records --------------------------------------------------------------------------------------------------------------
 // The indices are clamped into the key's range: the callers that need exact membership (the target grid, the voxels) have checked
@@ -79,15 +65,6 @@ __global__ void __launch_bounds__(256) grid_build_kernel(const float* __restrict
 // The best candidate is the minimum of (bits of d^2) << 32 | original index as an unsigned 64-bit number: d^2 >= +0, so its bits
 // order like its value, equal d^2 are decided by the smaller index, and a NaN (an invalid target) is above the starting value.
 constexpr int NN_STAGE = 256;
-
-__device__ __forceinline__ int lower_bound(const long long* __restrict__ keys, int m, long long key) {
-    int lo = 0, hi = m;  // the first position whose key is >= key
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 __global__ void __launch_bounds__(64) cloud_nearest_kernel(const float4* __restrict__ qrec, int n, const float4* __restrict__ trec,
                                                            const long long* __restrict__ tkeys, int m, double ox, double oy, double oz,

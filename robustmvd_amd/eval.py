@@ -375,8 +375,9 @@ class MultiViewDepthEvaluation:
 
 
 from .cloud_eval import PointCloudEvaluation  # noqa: E402
+from .mesh_eval import MeshEvaluation  # noqa: E402
 
-_EVALUATIONS = {"mvd": MultiViewDepthEvaluation, "cloud": PointCloudEvaluation}
+_EVALUATIONS = {"mvd": MultiViewDepthEvaluation, "cloud": PointCloudEvaluation, "mesh": MeshEvaluation}
 
 
 def list_evaluations():
@@ -386,7 +387,8 @@ def list_evaluations():
 
 def create_evaluation(evaluation_type, **kwargs):
     """create_evaluation("mvd", out_dir=..., inputs=..., alignment=..., ...) -> MultiViewDepthEvaluation;
-    create_evaluation("cloud", thresholds=..., max_dist=..., voxel=...) -> cloud_eval.PointCloudEvaluation."""
+    create_evaluation("cloud", thresholds=..., max_dist=..., voxel=...) -> cloud_eval.PointCloudEvaluation;
+    create_evaluation("mesh", thresholds=..., max_dist=..., spacing=..., voxel=...) -> mesh_eval.MeshEvaluation."""
     if evaluation_type not in _EVALUATIONS:
         raise ValueError(f"unknown evaluation {evaluation_type!r}; available: {list_evaluations()}")
     return _EVALUATIONS[evaluation_type](**kwargs)

@@ -1419,6 +1419,146 @@ def voxel_downsample(points, voxel, colors=None, origin=None):
     return xyz[:k].clone(), None if rgb is None else rgb[:k].clone(), counts[:k].clone()
 
 
+MESH_MAX_PAIRS = 1 << 28    # mesh_grid's default bound on the (cell, triangle) pairs: 2^28 pairs are 15 GB of keys, permutation and records
+MESH_MAX_SAMPLES = 1 << 28  # mesh_sample's default bound on the samples
+_MESH_HARD_LIMIT = 2 ** 31 - 1
+
+
+def _mesh_arrays(vertices, triangles):
+    v = L.as_f32(vertices, "vertices")
+    if v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"vertices must be (M,3), got {tuple(v.shape)}")
+    return v, _mesh_triangles(triangles, v.shape[0], device=v.device)
+
+
+def _mesh_bound(value, name):
+    value = int(value)
+    if not 1 <= value <= _MESH_HARD_LIMIT:
+        raise ValueError(f"{name} must be in 1 .. 2^31 - 1, got {value}")
+    return value
+
+
+def _mesh_ends(counts):
+    """The inclusive prefix sums of per-triangle int64 counts (torch.cumsum: plumbing), and their total and the largest count in ONE
+    read -> (ends, total, largest)."""
+    if counts.numel() == 0:
+        return counts, 0, 0
+    ends = torch.cumsum(counts, dim=0)
+    total, largest = torch.stack([ends[-1], counts.max()]).tolist()
+    return ends, int(total), int(largest)
+
+
+class MeshGrid:
+    """A mesh's triangles entered into the cells of a uniform grid (mesh_grid): vertices (M,3) and triangles (T,3) as given, keys (P)
+    int64 ascending: the cell of each (cell, triangle) pair, records (P,12): the pairs' triangles in key order (three vertices, the
+    triangle's index as the bits of the tenth float, two zeros), origin (3 floats), cell and inv = 1.0 / cell."""
+    __slots__ = ("vertices", "triangles", "keys", "records", "origin", "cell", "inv")
+
+    def __init__(self, vertices, triangles, keys, records, origin, cell):
+        self.vertices, self.triangles, self.keys, self.records, self.origin, self.cell = vertices, triangles, keys, records, origin, cell
+        self.inv = 1.0 / cell
+
+    @property
+    def pair_triangles(self):
+        """(P) int32: the triangle of each pair, in key order"""
+        return self.records[:, 9].contiguous().view(torch.int32)
+
+
+@inference_only
+def mesh_grid(vertices, triangles, origin, cell, max_pairs=MESH_MAX_PAIRS):
+    """The triangles of a mesh entered into every cell (edge `cell`, from `origin`) of their axis-aligned boxes (include/mvd.h:
+    mvd_mesh_cell_counts_f32, mvd_mesh_pairs_f32, mvd_mesh_records_f32; mesh_eval.mesh_grid_pairs_numpy is the definition) ->
+    MeshGrid.  Every finite vertex's cell indices must be in [0, 2^21 - 1), else ValueError.  The number of pairs P is read once; more
+    than max_pairs (at most 2^31 - 1) raises ValueError: a larger cell gives fewer pairs (and more candidates per query)."""
+    v, t = _mesh_arrays(vertices, triangles)
+    dev, M, T = v.device, int(v.shape[0]), int(t.shape[0])
+    origin, cell, max_pairs = _cloud_origin(origin), float(cell), _mesh_bound(max_pairs, "max_pairs")
+    if not 0.0 < cell < float("inf"):
+        raise ValueError(f"cell must be finite and > 0, got {cell}")
+    inv = 1.0 / cell
+    _check_cloud_indices(_cloud_extent(v), origin, inv, "mesh_grid", cell)
+    counts = torch.empty(T, dtype=torch.int64, device=dev)
+    if T:
+        call("mvd_mesh_cell_counts_f32", dev, v if M else None, M, t, T, origin[0], origin[1], origin[2], inv, counts)
+    ends, P, largest = _mesh_ends(counts)
+    if P > max_pairs:
+        raise ValueError(f"mesh_grid: {P} (cell, triangle) pairs at a cell of {cell:g}, above max_pairs = {max_pairs}; the largest "
+                         f"triangle's box alone covers {largest} cells.  Pass a larger cell= (it may exceed max_dist * (1 + 2^-10): fewer "
+                         "pairs, more candidates per query) or raise max_pairs")
+    keys = torch.empty(P, dtype=torch.int64, device=dev)
+    pair_tri = torch.empty(P, dtype=torch.int32, device=dev)
+    records = torch.empty((P, 12), dtype=torch.float32, device=dev)
+    if P:
+        call("mvd_mesh_pairs_f32", dev, v, M, t, T, ends, P, origin[0], origin[1], origin[2], inv, keys, pair_tri)
+        keys, perm = torch.sort(keys, stable=True)  # torch's sort: plumbing between two kernels, as _cloud_sorted's
+        call("mvd_mesh_records_f32", dev, v, M, t, T, pair_tri, perm, P, records)
+    return MeshGrid(v, t, keys, records, origin, cell)
+
+
+@inference_only
+def mesh_nearest(query, grid, max_dist):
+    """The truncated nearest triangle of every query in the grid's mesh (include/mvd.h: mvd_mesh_nearest_f32).  query: (n,3) points,
+    sorted here by the grid's cells, or a CloudGrid of the same origin and cell (MeshEvaluation sorts a cloud once for both
+    directions).  grid.cell must be at least max_dist * (1 + 2^-10).
+    Returns (dist (n) float32, index (n) int32: the triangle) in the query's original order; index -1 = nothing nearer than max_dist."""
+    if not isinstance(grid, MeshGrid):
+        raise ValueError(f"grid: expected a MeshGrid (ops.mesh_grid), got {type(grid).__name__}")
+    dev = grid.vertices.device
+    max_dist = float(torch.tensor(max_dist, dtype=torch.float32))  # the float32 the kernel compares with
+    if not 0.0 < max_dist < float("inf"):
+        raise ValueError(f"max_dist must be finite and > 0, got {max_dist}")
+    if grid.cell < max_dist * CLOUD_CELL_MARGIN * (1 - 1e-12):
+        raise ValueError(f"the grid's cell {grid.cell:g} is below max_dist * (1 + 2^-10) = {max_dist * CLOUD_CELL_MARGIN:g}")
+    if isinstance(query, CloudGrid):
+        if query.origin != grid.origin or query.cell != grid.cell or query.points.device != dev:
+            raise ValueError("query and mesh grids differ in origin, cell or device")
+        rec = query.records
+    else:
+        rec = cloud_grid(_cloud_points(query, "query", dev), grid.origin, grid.cell, check=False).records
+    n, P = rec.shape[0], grid.keys.shape[0]
+    dist = torch.empty(n, dtype=torch.float32, device=dev)
+    index = torch.empty(n, dtype=torch.int32, device=dev)
+    call("mvd_mesh_nearest_f32", dev, rec if n else None, n, grid.records if P else None, grid.keys if P else None, P, grid.origin[0],
+         grid.origin[1], grid.origin[2], grid.inv, max_dist, dist if n else None, index if n else None)
+    return dist, index
+
+
+@inference_only
+def mesh_sample(vertices, triangles, spacing, attributes=None, max_samples=MESH_MAX_SAMPLES):
+    """Deterministic covering samples of a mesh's surface (include/mvd.h: mvd_mesh_sample_counts_f32, mvd_mesh_sample_f32;
+    mesh_eval.sample_mesh_numpy is the definition, bit for bit): a triangle whose longest edge is L gets k = max(1, ceil(L / spacing))
+    and the centroids of its k^2 congruent sub-triangles, so that every surface point is within 2 spacing / 3 of a sample.
+    attributes (M,c) float32 are interpolated with the points.  The number of samples S is read once; more than max_samples (at most
+    2^31 - 1) raises ValueError.  Returns (points (S,3) float32, triangle (S) int32, attributes (S,c) or None), in triangle order."""
+    v, t = _mesh_arrays(vertices, triangles)
+    dev, M, T = v.device, int(v.shape[0]), int(t.shape[0])
+    spacing, max_samples = float(torch.tensor(float(spacing), dtype=torch.float32)), _mesh_bound(max_samples, "max_samples")
+    if not 0.0 < spacing < float("inf"):
+        raise ValueError(f"spacing must be finite and > 0, got {spacing}")
+    inv_s2 = 1.0 / (spacing * spacing)
+    if not 0.0 < inv_s2 < float("inf"):
+        raise ValueError(f"spacing {spacing:g}: 1 / spacing^2 is not a finite positive double")
+    attr, C = None, 0
+    if attributes is not None:
+        attr = L.as_f32(attributes, "attributes", device=dev)
+        if attr.dim() != 2 or attr.shape[0] != M or not 1 <= attr.shape[1] <= 65536:
+            raise ValueError(f"attributes must be ({M},c) with c in 1 .. 65536, got {tuple(attr.shape)}")
+        C = int(attr.shape[1])
+    counts = torch.empty(T, dtype=torch.int64, device=dev)
+    if T:
+        call("mvd_mesh_sample_counts_f32", dev, v if M else None, M, t, T, inv_s2, counts)
+    ends, S, largest = _mesh_ends(counts)
+    if S > max_samples:
+        raise ValueError(f"mesh_sample: {S} samples at a spacing of {spacing:g}, above max_samples = {max_samples}; the largest triangle "
+                         f"alone gets {largest}.  Pass a larger spacing or raise max_samples")
+    points = torch.empty((S, 3), dtype=torch.float32, device=dev)
+    tri = torch.empty(S, dtype=torch.int32, device=dev)
+    out = torch.empty((S, C), dtype=torch.float32, device=dev) if attr is not None else None
+    if S:
+        call("mvd_mesh_sample_f32", dev, v, M, t, T, attr, C, ends, S, inv_s2, points, tri, out)
+    return points, tri, out
+
+
 class SplitConv2dWeights:
     """Packed split-operand weights of one 2-D layer (pack_conv2d_weights_split) with what conv2d_split needs to call it."""
     __slots__ = ("packed", "bias", "cin", "cin_pad", "cout", "kh", "kw", "stride", "mode")

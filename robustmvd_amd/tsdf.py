@@ -335,6 +335,20 @@ class Mesh:
         from .mesh_clean import vertex_normals
         return vertex_normals(self)
 
+    def distance(self, points, max_dist):
+        """-> (dist (n) float32, index (n) int32): the truncated distance of every point to the surface and its nearest triangle, -1
+        where nothing is nearer than max_dist (mesh_eval.mesh_distance)."""
+        from .mesh_eval import mesh_distance
+        return mesh_distance(points, self, max_dist)
+
+    def sample(self, spacing, colors=False):
+        """-> (points (S,3) float32, triangle (S) int32, colors (S,3) or None): covering samples of the surface, every surface point
+        within 2 spacing / 3 of one (mesh_eval.sample_mesh); colors=True interpolates the mesh's vertex colours."""
+        from .mesh_eval import sample_mesh
+        if colors and self.colors is None:
+            raise ValueError("Mesh.sample(colors=True): the mesh has no colours")
+        return sample_mesh(self, spacing, self.colors if colors else None)
+
 
 class TSDFVolume:
     """A dense TSDF volume (module docstring) on the host (device=None: the numpy forms) or on one GPU (the HIP kernels).
