@@ -30,8 +30,9 @@
 #include <stdlib.h>
 #include <string>
 
-// knock-out builds for tools/ko_conv2d.sh (timing only, WRONG results): 1 stage only a workgroup's first chunk, 2 no MFMAs,
-// 4 weights loaded once, 8 activation fragments read once per step, 16 no stores
+// knock-out builds for tools/ko_conv2d.sh (timing only, WRONG results): 1 stage only a workgroup's first chunk (the persistent form:
+// every tile's first chunk), 2 no MFMAs, 4 weights loaded once, 8 activation fragments read once per step, 16 no stores.  A
+// knock-out build never takes the 3-D march: it times the kernels the knock-outs are written into
 #ifndef C2_KO
 #define C2_KO 0
 #endif
@@ -103,6 +104,7 @@ struct C2Params {
     int Cout, ncp;        // output channels; ncp = Cout padded to the launch's BN
     int tiles_x, tiles_y, nblocks, ksplit, chunks_per_split;
     int tiles;            // the persistent form: tiles of the launch (a workgroup walks blockIdx.x, + gridDim.x, ...)
+    int march_td, march_runs;  // the 3-D march: output planes per run, runs per batch element (ceil(Do / march_td))
     int ncls;             // 1, or 4 = the output parity classes (a, b) of a transposed conv: pad - (a, b), output offset (a, b)
     long long cls_bytes;
     int act;              // 0 none, 1 LeakyReLU(slope), 2 ReLU
@@ -547,24 +549,27 @@ __global__ void __launch_bounds__(256, WAVES) conv2d_split_persist_kernel(C2Para
                     wl[s][q] = *reinterpret_cast<const c2h8*>(wc + s * 2048 + q * nt_stride + 1024);
                 }
             __builtin_amdgcn_sched_barrier(0);
-            __syncthreads();  // every wave has finished reading the previous chunk's patch
+            const bool last = chunk + 1 == p.nchunks;
+            const bool stage = !(C2_KO & 1) || chunk == 0;  // the knock-out: a tile's first chunk only, one patch load per tile
+            if (stage) {
+                __syncthreads();  // every wave has finished reading the previous chunk's patch
 #pragma unroll
-            for (int k = 0; k < G::NIT; ++k) {
-                if (loff[k] < 0) continue;
-                if (goff[k] < 0 || !zlive) v0[k] = v1[k] = c2f4{0, 0, 0, 0};
-                unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-                split2(xsc, v0[k][0], v0[k][1], h0, l0);
-                split2(xsc, v0[k][2], v0[k][3], h1, l1);
-                split2(xsc, v1[k][0], v1[k][1], h2, l2);
-                split2(xsc, v1[k][2], v1[k][3], h3, l3);
-                *reinterpret_cast<c2u4*>(patch + loff[k]) = c2u4{h0, h1, h2, h3};
-                *reinterpret_cast<c2u4*>(patch + loff[k] + PLANE) = c2u4{l0, l1, l2, l3};
+                for (int k = 0; k < G::NIT; ++k) {
+                    if (loff[k] < 0) continue;
+                    if (goff[k] < 0 || !zlive) v0[k] = v1[k] = c2f4{0, 0, 0, 0};
+                    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
+                    split2(xsc, v0[k][0], v0[k][1], h0, l0);
+                    split2(xsc, v0[k][2], v0[k][3], h1, l1);
+                    split2(xsc, v1[k][0], v1[k][1], h2, l2);
+                    split2(xsc, v1[k][2], v1[k][3], h3, l3);
+                    *reinterpret_cast<c2u4*>(patch + loff[k]) = c2u4{h0, h1, h2, h3};
+                    *reinterpret_cast<c2u4*>(patch + loff[k] + PLANE) = c2u4{l0, l1, l2, l3};
+                }
             }
             __builtin_amdgcn_sched_barrier(0);
-            const bool last = chunk + 1 == p.nchunks;
-            prefetch(last ? tnext : tl, last ? 0 : chunk + 1, last);
+            if (!(C2_KO & 1) || last) prefetch(last ? tnext : tl, last ? 0 : chunk + 1, last);
             __builtin_amdgcn_sched_barrier(0);
-            __syncthreads();
+            if (stage) __syncthreads();
 #pragma unroll
             for (int s = 0; s < STEPS; ++s) c2_kstep<G, MTW, NTW>(patch + tapoff[s], wh[s], wl[s], acc);
         }
@@ -592,6 +597,220 @@ __global__ void __launch_bounds__(256, WAVES) conv2d_split_persist_kernel(C2Para
             amax = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
             raise_absmax_seen(p.yamax, amax, amax_seen);
         }
+    }
+}
+
+// The 3-D layers' plane-stationary march (3 x 3 x 3, padding 1, stride SD = 1 or 2, 8-channel chunks, 16-channel tile).  A
+// workgroup owns one 16 x 16 pixel tile, one cout block and a run of up to p.march_td consecutive output planes od0 .. of one batch
+// element, and walks the input planes z0 = SD od0 - 1, z0 + 1, ... that run needs, in order.  Each (plane, 8-channel chunk) is staged
+// ONCE (conv2d_split_kernel stages it once per depth tap it serves: 3 times, 1.5 times for stride 2) and every activation fragment
+// read from LDS meets the weights of every depth tap the plane serves:
+//   stride 1: plane z is kd = 0 of output z + 1, kd = 1 of z, kd = 2 of z - 1: three accumulator sets, output o in set o % 3;
+//   stride 2: plane 2 od + 1 is kd = 2 of od and kd = 0 of od + 1, plane 2 od is kd = 1 of od: two sets, output o in set o % 2.
+// The march is unrolled by the period of those roles (3 planes, 4 planes), so that a set is a fixed block of registers and nothing
+// moves.  An output gets its sums in the order of conv2d_split_kernel - kd outermost (the planes come in that order), then the
+// channel chunk, then the K steps, hi hi, lo hi, hi lo into one accumulator - so y and max |y| are bit-identical; planes outside
+// the volume are staged as the zero patch they are there, and depth taps that belong to a neighbouring run's outputs are skipped.
+// As in the persistent form: grid and work from the parameters alone, every load unconditional, the weights of a chunk requested
+// before the prefetch of the next patch (WRES: one channel chunk, all 27 taps' fragments resident for the whole run), one max-|y|
+// atomic per workgroup.  SLOTS = 2: the patch alternates between two LDS slots and a chunk costs one barrier (conv0_split_kernel).
+template <int R>
+struct C3Rot {
+    static constexpr int value = R;
+};
+template <int SD, int WAVES, int SLOTS, bool WRES>
+__global__ void __launch_bounds__(256, WAVES) conv3d_split_march_kernel(C2Params p) {
+    // max |y| seen so far and its slot wait for the end of the run in vector registers: the scalar file is full
+    float amax_seen = absmax_seen(p.yamax);
+    float* yamax = p.yamax;
+    asm volatile("" : "+v"(amax_seen), "+v"(yamax));
+    using G = C2Geom<3, 3, SD, 1, false>;
+    constexpr int MTW = 4, STEPS = G::STEPS, PB = G::PB, PLANE = G::PLANE, NSETS = SD == 1 ? 3 : 2;
+    extern __shared__ __attribute__((aligned(16))) char patch[];  // SLOTS x [term][patch] | 4 floats
+    float* const wmax = reinterpret_cast<float*>(patch + SLOTS * 2 * PLANE);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int g = lane >> 4, px16 = lane & 15;
+
+    // the work unit: cout block (innermost: neighbours share the patch), tile column and row, run, batch element
+    int bx = blockIdx.x;
+    const int nb = bx % p.nblocks; bx /= p.nblocks;
+    const int tx = bx % p.tiles_x; bx /= p.tiles_x;
+    const int ty = bx % p.tiles_y; bx /= p.tiles_y;
+    const int od0 = (bx % p.march_runs) * p.march_td, bb = bx / p.march_runs;
+    const int nout = min(p.march_td, p.Do - od0);            // output planes of this run
+    const int nplanes = SD == 1 ? nout + 2 : 2 * nout + 1;   // input planes z0 .. z0 + nplanes - 1
+    const int z0 = SD * od0 - 1;
+    const int oy0 = ty * C2_TH, ox0 = tx * C2_TW, iy0 = oy0 * SD - p.pad_y, ix0 = ox0 * SD - p.pad_x;
+    const int ncc = p.nchunks_c;
+
+    float xsc, xsc_inv;
+    split_xscale(p.xamax, xsc, xsc_inv);
+    int loff[G::NIT], goff[G::NIT];  // LDS byte (-1: no item) and offset in the plane (floats, -1 = outside the image)
+#pragma unroll
+    for (int k = 0; k < G::NIT; ++k) {
+        const int it = tid + 256 * k, py = it / G::PW, pxx = it % G::PW;
+        const int iy = iy0 + py, ix = ix0 + pxx;
+        loff[k] = it < G::ITEMS ? ((py * SD + pxx % SD) * G::PWS + pxx / SD) * PB : -1;
+        goff[k] = (it < G::ITEMS && iy >= 0 && iy < p.Hi && ix >= 0 && ix < p.Wi) ? (iy * p.Wi + ix) * p.xs : -1;
+    }
+    int tapoff[STEPS];
+    c2_tapoff<G, 3, SD, 1, STEPS, false>(tapoff, g, px16, wv * MTW);
+    const size_t plane_floats = (size_t)p.Hi * p.Wi * p.xs;  // < 2^31 (launcher)
+    const char* const wlane = p.wpk + (size_t)nb * p.nchunks * STEPS * 2048 + lane * 16;  // chunk kd ncc + c, step s: + (chunk STEPS + s) 2048
+    const int cb = nb * 16 + 4 * g, ox = ox0 + px16;
+    const C2Chan kc = c2_chan(p, cb, xsc_inv);
+    // this lane's outputs of the run's first plane; consecutive planes are p.ys_img apart, rows ostep
+    const size_t out0 = c2_out_offset(p, bb, od0, oy0 + wv * MTW, ox, 0, cb), ostep = c2_row_step(p);
+    const float* const xrun = p.x + (size_t)bb * p.Di * plane_floats;
+
+    c2h8 rh[WRES ? 3 : 1][STEPS], rl[WRES ? 3 : 1][STEPS];
+    if constexpr (WRES) {
+#pragma unroll
+        for (int kd = 0; kd < 3; ++kd)
+#pragma unroll
+            for (int s = 0; s < STEPS; ++s) {
+                rh[kd][s] = *reinterpret_cast<const c2h8*>(wlane + (kd * STEPS + s) * 2048);
+                rl[kd][s] = *reinterpret_cast<const c2h8*>(wlane + (kd * STEPS + s) * 2048 + 1024);
+            }
+    }
+
+    // the loads in flight: the patch of one (plane, chunk)
+    c2f4 v0[G::NIT], v1[G::NIT];
+    int zlive;  // (uniform flags are ints: one scalar register each)
+    auto prefetch = [&](int z, int c) __attribute__((always_inline)) {
+        zlive = z >= 0 && z < p.Di;
+        const float* xim = xrun + (size_t)(zlive ? z : 0) * plane_floats + c * 8;
+#pragma unroll
+        for (int k = 0; k < G::NIT; ++k) {
+            const float* a = xim + max(goff[k], 0);
+            v0[k] = *reinterpret_cast<const c2f4*>(a);
+            v1[k] = *reinterpret_cast<const c2f4*>(a + 4);
+        }
+    };
+    prefetch(z0, 0);
+
+    c2f4 acc[NSETS][MTW];
+#pragma unroll
+    for (int q = 0; q < NSETS; ++q)
+#pragma unroll
+        for (int m = 0; m < MTW; ++m) acc[q][m] = c2f4{0, 0, 0, 0};
+    float amax = 0.f;
+    int item = 0;  // (plane, chunk) pairs staged so far: the LDS slot alternates with it
+
+    // plane j of the run in role R = j % 3 (stride 1), j % 4 (stride 2): which depth taps it serves and in which set their output lives
+    auto plane = [&](auto rot, int j) __attribute__((always_inline)) {
+        constexpr int R = decltype(rot)::value;
+        // set of the output that takes this plane as kd = 0, 1, 2 (-1: the plane is no such tap of any output)
+        constexpr int SET[3] = {SD == 1 ? R : (R % 2 == 0 ? (R / 2) % 2 : -1), SD == 1 ? (R + 2) % 3 : (R % 2 == 1 ? (R / 2) % 2 : -1),
+                                SD == 1 ? (R + 1) % 3 : (R % 2 == 0 ? (R / 2 + 1) % 2 : -1)};
+        // that output's index in the run; taps of a neighbouring run's outputs are left out
+        const int o[3] = {SD == 1 ? j : j / 2, SD == 1 ? j - 1 : (j - 1) / 2, SD == 1 ? j - 2 : j / 2 - 1};
+        int on[3], full = 1;
+#pragma unroll
+        for (int kd = 0; kd < 3; ++kd) {
+            on[kd] = (SET[kd] >= 0 && o[kd] >= 0 && o[kd] < nout) ? 1 : 0;
+            full &= on[kd] | (SET[kd] < 0 ? 1 : 0);
+        }
+        for (int c = 0; c < ncc; ++c) {
+            // the weight fragments of the chunk's served taps, queued behind this chunk's patch and ahead of the next one's
+            c2h8 wh[3][STEPS], wl[3][STEPS];
+#pragma unroll
+            for (int kd = 0; kd < 3; ++kd) {
+                if (SET[kd] < 0) continue;
+#pragma unroll
+                for (int s = 0; s < STEPS; ++s) {
+                    if constexpr (WRES) {
+                        wh[kd][s] = rh[kd][s]; wl[kd][s] = rl[kd][s];
+                    } else {
+                        const char* const wc = wlane + (size_t)((kd * ncc + c) * STEPS + s) * 2048;
+                        wh[kd][s] = *reinterpret_cast<const c2h8*>(wc);
+                        wl[kd][s] = *reinterpret_cast<const c2h8*>(wc + 1024);
+                    }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            char* const slot = patch + (SLOTS == 2 ? (item & 1) * 2 * PLANE : 0);
+            if (SLOTS == 1) __syncthreads();  // every wave has finished reading the previous chunk's patch
+#pragma unroll
+            for (int k = 0; k < G::NIT; ++k) {
+                if (loff[k] < 0) continue;
+                if (goff[k] < 0 || !zlive) v0[k] = v1[k] = c2f4{0, 0, 0, 0};
+                unsigned h0, h1, h2, h3, l0, l1, l2, l3;
+                split2(xsc, v0[k][0], v0[k][1], h0, l0);
+                split2(xsc, v0[k][2], v0[k][3], h1, l1);
+                split2(xsc, v1[k][0], v1[k][1], h2, l2);
+                split2(xsc, v1[k][2], v1[k][3], h3, l3);
+                *reinterpret_cast<c2u4*>(slot + loff[k]) = c2u4{h0, h1, h2, h3};
+                *reinterpret_cast<c2u4*>(slot + loff[k] + PLANE) = c2u4{l0, l1, l2, l3};
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            ++item;
+            {   // the next (plane, chunk); the run's last one asks for itself again
+                const bool lastc = c + 1 == ncc, lastp = j + 1 == nplanes;
+                prefetch(z0 + j + ((lastc && !lastp) ? 1 : 0), lastc ? (lastp ? c : 0) : c + 1);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();
+#pragma unroll
+            for (int s = 0; s < STEPS; ++s) {
+                // one K step: an activation fragment (two pixel rows ahead, as c2_kstep) against the served taps' weights
+                const char* const a = slot + tapoff[s];
+                c2h8 xh = *reinterpret_cast<const c2h8*>(a), xl = *reinterpret_cast<const c2h8*>(a + PLANE);
+                c2h8 yh = *reinterpret_cast<const c2h8*>(a + G::ROWB), yl = *reinterpret_cast<const c2h8*>(a + G::ROWB + PLANE);
+#pragma unroll
+                for (int m = 0; m < MTW; ++m) {
+                    const c2h8 ch = xh, cl = xl;
+                    xh = yh; xl = yl;
+                    if (m + 2 < MTW) {
+                        yh = *reinterpret_cast<const c2h8*>(a + (m + 2) * G::ROWB);
+                        yl = *reinterpret_cast<const c2h8*>(a + (m + 2) * G::ROWB + PLANE);
+                    }
+                    if (full) {  // the sets are independent: their MFMAs interleave, each set in its own order
+#pragma unroll
+                        for (int term = 0; term < 3; ++term)
+#pragma unroll
+                            for (int kd = 0; kd < 3; ++kd)
+                                if (SET[kd] >= 0)
+                                    acc[max(SET[kd], 0)][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(term == 1 ? wl[kd][s] : wh[kd][s], term == 2 ? cl : ch,
+                                                                                                     acc[max(SET[kd], 0)][m], 0, 0, 0);
+                    } else {
+#pragma unroll
+                        for (int kd = 0; kd < 3; ++kd)
+                            if (on[kd]) {  // false for a tap the role does not serve
+                                c2f4& t = acc[max(SET[kd], 0)][m];
+                                t = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[kd][s], ch, t, 0, 0, 0);
+                                t = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[kd][s], ch, t, 0, 0, 0);
+                                t = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[kd][s], cl, t, 0, 0, 0);
+                            }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+        // the output this plane completes (its kd = 2): epilogue, and the set starts over
+        if constexpr (SET[2] >= 0) {
+            if (on[2]) {
+                if (cb < p.Cout && ox < p.Wo) {
+                    const size_t ofs = out0 + (size_t)o[2] * p.ys_img;
+#pragma unroll
+                    for (int m = 0; m < MTW; ++m)
+                        if (oy0 + wv * MTW + m < p.Ho) c2_finish(p, ofs + m * ostep, cb, acc[SET[2]][m], kc, amax);
+                }
+#pragma unroll
+                for (int m = 0; m < MTW; ++m) acc[SET[2]][m] = c2f4{0, 0, 0, 0};
+            }
+        }
+    };
+    for (int j = 0; j < nplanes; j += (SD == 1 ? 3 : 4)) {  // one turn of the roles
+        plane(C3Rot<0>{}, j);
+        if (j + 1 < nplanes) plane(C3Rot<1>{}, j + 1);
+        if (j + 2 < nplanes) plane(C3Rot<2>{}, j + 2);
+        if constexpr (SD == 2)
+            if (j + 3 < nplanes) plane(C3Rot<3>{}, j + 3);
+    }
+    if (yamax) {
+        amax = workgroup_max(amax, wmax, tid);
+        if (tid == 0) raise_absmax_seen(yamax, amax, amax_seen);
     }
 }
 
@@ -758,6 +977,7 @@ struct C2Plan {
     int Ho, Wo, tiles_x, tiles_y, bn, nblocks, ncp, ncls, nchunks, ksplit;
     long long tiles;
     long long persist;  // 0: one tile per workgroup; else the grid of conv2d_split_persist_kernel
+    int march_td;       // 3-D layers: 0, or the output planes per run of conv3d_split_march_kernel (which then replaces both forms)
     size_t part_bytes;
 };
 
@@ -782,6 +1002,37 @@ constexpr int C2_PERSIST_WGS[4][3] = {
     {0, 0, 0},  // 3 x 3 stride 2: the regulariser's conv1 151 -> 155 us, conv5 54 -> 54 in the frame
     {0, 0, 0},  // 5 x 5 stride 2
 };
+// The 3-D layers' march along depth (conv3d_split_march_kernel) replaces both forms above for 3 x 3 x 3 layers with 8-channel
+// chunks, a 16-channel tile and an unsplit reduction whose (tile, run) pairs give every CU a workgroup.  C3_MARCH_TD[stride - 1][one
+// channel chunk, more] = output planes per run where the layer's median in the headline forward is below its minimum on the kernels
+// above (profiles/c3_march_frame.txt), 0 where it stays on them.
+constexpr int C3_MARCH_TD[2][2] = {
+    // stride 1.  The regulariser's conv2 (16 -> 16, two chunks, 128 planes of 6 x 9 tiles): alone 120 - 130 us persistent, 127 - 139 on
+    // runs of 16 (432 workgroups), 123 - 134 on runs of 15, 138 - 205 on runs of 8, 11, 13, 22 and 32: stays
+    {0, 0},
+    // stride 2.  The regulariser's conv1 (8 -> 16, one chunk: the weights stay in registers): 152.8 (min 152.0) -> 128.5 us in the
+    // frame on runs of 16, alone 152 - 165 -> 124 - 133 (runs of 15 the same, 8 135 - 161, 32 178 - 186).  More chunks: not measured
+    // at a shape that fills the device, and that instance spills 6 scalar registers
+    {16, 0},
+};
+constexpr long long C3_MARCH_MIN_WGS = 256;
+// experiments library, MVD_C3_MARCH: 0 off, 1 the rule, n > 1 runs of n planes at any shape (the channel tile narrowed to 16 for it)
+static int c3_march_forced() {
+    const char* e = exp_env("MVD_C3_MARCH");
+    return e ? std::max(atoi(e), 0) : 1;
+}
+static long long c3_march_wgs(const C2Plan& q, int B, int Do, int td) {
+    return (long long)q.tiles_x * q.tiles_y * q.nblocks * B * ((Do + td - 1) / td);
+}
+// B: batch elements, Do: output planes of each
+static int c3_march_td(const C2Shape& s, const C2Plan& q, int B, int Do, int Hi, int Wi, int xs) {
+    if (s.KH != 3 || s.U8 != 1 || q.bn != 16 || q.ksplit != 1 || (long long)Hi * Wi * xs > 0x7fffffffLL) return 0;
+    if (C2_KO) return 0;  // the knock-outs are built into the kernels above
+    const int forced = c3_march_forced();
+    if (forced != 1) return std::min(forced, Do);
+    const int td = std::min(C3_MARCH_TD[s.S - 1][q.nchunks == 3 ? 0 : 1], Do);
+    return (td > 0 && c3_march_wgs(q, B, Do, td) >= C3_MARCH_MIN_WGS) ? td : 0;
+}
 // grid of the persistent form (0 = not taken): at most 256 CUs x the table's workgroups, a multiple of nblocks so that a workgroup
 // keeps its cout block
 static long long c2_persist_grid(const C2Shape& s, const C2Plan& q, int Hi, int Wi, int xs) {
@@ -854,6 +1105,36 @@ static int c2_launch_persist(const C2Params& p, long long grid, hipStream_t st) 
     return launch_status("conv2d_split: persistent");
 }
 
+// the 3-D march on `grid` (tile, cout block, run) workgroups: two LDS slots (one barrier per chunk), two waves per SIMD, and with a
+// single channel chunk (Cin 8) all 27 taps' weight fragments resident
+template <int SD, int SLOTS, bool WRES>
+static int c3_launch_march_as(const C2Params& p, long long grid, hipStream_t st) {
+    using G = C2Geom<3, 3, SD, 1, false>;
+    auto kern = conv3d_split_march_kernel<SD, 2, SLOTS, WRES>;
+    constexpr int lds = SLOTS * 2 * G::PLANE + 16;
+    static_assert(lds <= 80 * 1024, "two workgroups per CU");
+    if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+        return launch_status("conv3d_split_march: LDS attribute");
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, p);
+    return launch_status("conv3d_split_march");
+}
+static int c3_launch_march(const C2Shape& s, const C2Params& p, long long grid, hipStream_t st) {
+    const bool wres = p.nchunks_c == 1;
+#ifdef MVD_EXPERIMENTS  // MVD_C3_SLOTS=1: one LDS slot, two barriers per chunk (measured and not shipped)
+    if (const char* e = exp_env("MVD_C3_SLOTS"); e && atoi(e) == 1) {
+        if (s.S == 2) return wres ? c3_launch_march_as<2, 1, true>(p, grid, st) : c3_launch_march_as<2, 1, false>(p, grid, st);
+        return wres ? c3_launch_march_as<1, 1, true>(p, grid, st) : c3_launch_march_as<1, 1, false>(p, grid, st);
+    }
+#endif
+    if (s.S == 2 && wres) return c3_launch_march_as<2, 2, true>(p, grid, st);
+#ifdef MVD_EXPERIMENTS  // the kinds whose entry of C3_MARCH_TD is 0: reachable through MVD_C3_MARCH only
+    if (s.S == 2) return c3_launch_march_as<2, 2, false>(p, grid, st);
+    return wres ? c3_launch_march_as<1, 2, true>(p, grid, st) : c3_launch_march_as<1, 2, false>(p, grid, st);
+#else
+    return MVD_ERR_INVALID_ARG;
+#endif
+}
+
 // tile of output channels per workgroup: bn = 16 WN NTW
 template <int KH, int KW, int S, int U8, bool NCHW3>
 static int c2_launch_bn(const C2Params& p, int bn, long long nblk, hipStream_t st) {
@@ -910,6 +1191,11 @@ static int c2_run(const char* what, const C2Shape& s, C2Params& p, const C2Plan&
     p.part = ksplit > 1 ? static_cast<float*>(workspace) : nullptr;
     const long long nblk = q.tiles * ksplit;
     MVD_REQUIRE(nblk <= 0x7fffffffLL, "%s: %lld workgroups exceed the grid limit", what, nblk);
+    if (q.march_td > 0) {  // planned for an unsplit reduction only
+        p.march_td = q.march_td;
+        p.march_runs = (p.Do + q.march_td - 1) / q.march_td;
+        return c3_launch_march(s, p, c3_march_wgs(q, p.B / p.Do, p.Do, q.march_td), st);
+    }
     int rc = c2_dispatch(s, p, q.bn, nblk, q.persist, st);
     if (rc != MVD_OK || ksplit == 1) return rc;
     const long long n = (long long)p.B * p.Ho * p.Wo * ((p.Cout + 3) / 4);
@@ -1069,11 +1355,13 @@ static mvd::C2Plan c3_plan(const mvd::C2Shape& s, int B, int Di, int Hi, int Wi,
     // on 16 channels; the stride-2 layers are slower that way).  Smaller grids keep their tile and split K as before.
     if (mode == MVD_CONV3D_STRIDE1 && !mvd::exp_env("MVD_C2_BN") && planes * ((ncout + q.bn - 1) / q.bn) >= 128)
         while (q.bn > 16 && planes * ((ncout + q.bn - 1) / q.bn) < 512) q.bn /= 2;
+    if (mode != MVD_DECONV3D_STRIDE2 && s.U8 == 1 && mvd::c3_march_forced() > 1) q.bn = 16;  // experiments library: the march's tile
     q.nblocks = (ncout + q.bn - 1) / q.bn;
     q.ncp = q.nblocks * q.bn;
     q.nchunks = (mode == MVD_DECONV3D_STRIDE2 ? 2 : 3) * (Cin / (8 * s.U8));
     q.tiles = planes * q.nblocks;
     mvd::c2_plan_finish(s, q, B * *Do, Hi, Wi, Cin);
+    q.march_td = mode == MVD_DECONV3D_STRIDE2 ? 0 : mvd::c3_march_td(s, q, B, *Do, Hi, Wi, Cin);
     return q;
 }
 
