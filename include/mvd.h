@@ -927,6 +927,71 @@ int mvd_mesh_vertex_normals_f32(const float* vertices, long long M, const int* t
                                 const long long* perm, float* normals, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mesh simplification: vertex clustering on a uniform grid with quadric-error placement (Lindstrom 2000).  The reference has NO
+ * counterpart: the definition is robustmvd_amd/mesh_simplify.py (cluster_numpy, cluster_quadrics_numpy, place_numpy,
+ * simplify_numpy) and DESIGN.md, restated here.  No entry uses an atomic.  Every float64 sum is a segment sum in ONE fixed order: a
+ * segment of at most 64 items is added one item after the other from +0.0; a longer one by 64 lanes, lane l the items l, l + 64, ...
+ * in that order from +0.0, and the 64 sums meet in the xor tree v += shuffle_xor(v, s), s = 32 .. 1.  The order depends on the
+ * segment's length alone and the library is built without contraction: two runs give the same bits.
+ * The callers' sorts are STABLE.  After these entries the kept triangles and the referenced clusters are compacted by
+ * mvd_mesh_filter (every triangle its own component, the keep bytes as verdicts) and rows move through mvd_mesh_gather_rows_f32. */
+
+/* Cluster ids.  No counterpart in the reference.  keys (M) int64 ascending: the vertices' cell keys of mvd_cloud_cell_keys_f32
+ * sorted, the invalid vertices' INT64_MAX last;  perm (M) int64: perm[p] = the vertex at sorted position p.  The clusters are the
+ * runs of equal valid keys, numbered in key order (a compact.h compaction of the runs' heads: no atomic decides a number).
+ * vertex_cluster (M) int32: the cluster of every vertex, -1 for an invalid one;  cluster_start (M + 1 entries, K + 1 written): the
+ * first sorted position of each cluster, cluster_start[K] = the number of valid vertices;  cluster_key (M entries, K written);
+ * num_clusters (device, 8-byte aligned): K.  No float sum.
+ * workspace: mvd_mesh_cluster_ids_workspace_bytes(M), 256-byte aligned. */
+size_t mvd_mesh_cluster_ids_workspace_bytes(long long M);
+int mvd_mesh_cluster_ids(const long long* keys, const long long* perm, long long M, int* vertex_cluster, int* cluster_start,
+                         long long* cluster_key, long long* num_clusters, void* workspace, size_t workspace_bytes, mvd_stream_t stream);
+
+/* Segment means.  No counterpart in the reference.  rows (M,k) float32, 1 <= k <= 65536, M k <= 2^31 - 1.  means (K,k) float64:
+ * per column the sum of float64(rows[perm[p]]) over the cluster's sorted positions p in ascending order (= ascending vertex index)
+ * in the segment order above, divided by the number of positions.  One lane per cluster, the wave for a cluster of more than 64. */
+int mvd_mesh_cluster_means_f64(const float* rows, const long long* perm, const int* cluster_start, long long K, long long M, int k,
+                               double* means, mvd_stream_t stream);
+
+/* Triangle triples.  No counterpart in the reference; no sum.  Per triangle: triples (T,3) int32, the clusters of its vertices
+ * rotated so that the smallest comes first, and alive (T) bytes = 1, when the three vertices are valid and the three clusters
+ * pairwise different; otherwise (-1,-1,-1) and 0.  corner_key (T,3) int32: the cluster of each corner, or K for every corner of a
+ * triangle with an invalid vertex (the sentinel sorts last).  3 T <= 2^31 - 1. */
+int mvd_mesh_cluster_triples(const int* triangles, long long T, long long M, const int* vertex_cluster, long long K, int* triples,
+                             unsigned char* alive, int* corner_key, mvd_stream_t stream);
+
+/* Quadrics.  No counterpart in the reference.  The caller sorts the 3 T corner keys stably: sorted_cluster (3T) int32 ascending,
+ * perm (3T) int64, perm[p] = the corner 3 t + j at sorted position p.  Per corner, float64 from the float32 coordinates, one
+ * rounding per operation: e1 = p1 - p0, e2 = p2 - p0, n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x),
+ * q = p0 - ctr with ctr = (idx + 0.5) * cell + origin per axis from the cluster's key, d = -((nx qx + ny qy) + nz qz), and the ten
+ * terms nx nx, nx ny, nx nz, ny ny, ny nz, nz nz, nx d, ny d, nz d, d d.  quadrics (K,10) float64: the sums over each cluster's
+ * corners in ascending sorted position (= ascending (t, j)) in the segment order above; zeros for a cluster without a corner.
+ * The segments come from a binary search per cluster.  3 T <= 2^31 - 1.
+ * workspace: mvd_mesh_cluster_quadrics_workspace_bytes(K), 4-byte aligned. */
+size_t mvd_mesh_cluster_quadrics_workspace_bytes(long long K);
+int mvd_mesh_cluster_quadrics_f64(const float* vertices, long long M, const int* triangles, long long T, const int* sorted_cluster,
+                                  const long long* perm, const long long* cluster_key, long long K, double origin_x, double origin_y,
+                                  double origin_z, double cell, double* quadrics, void* workspace, size_t workspace_bytes,
+                                  mvd_stream_t stream);
+
+/* Placement.  No counterpart in the reference; no sum.  One lane per cluster.  A cluster of one vertex: that vertex's bits,
+ * placed = 2.  Otherwise, with quadrics != NULL: lam = regularisation ((a00 + a11) + a22), A' = A + lam I,
+ * r = -b + lam (mean - ctr), x = adj(A') r / det(A') with the cofactors and the associations of mesh_simplify.py's step 5; the
+ * vertex is float32(ctr + x), placed = 1, when lam > 0, det is finite and > 0, every x_i is finite and |x_i| <= 0.5 cell.
+ * Otherwise, and always with quadrics == NULL: float32(mean), placed = 0.  out_vertices (K,3) float32, placed (K) bytes. */
+int mvd_mesh_cluster_place_f32(const double* quadrics, const double* means, const int* cluster_start, const long long* cluster_key,
+                               const long long* perm, const float* vertices, long long K, long long M, double origin_x, double origin_y,
+                               double origin_z, double cell, double regularisation, float* out_vertices, unsigned char* placed,
+                               mvd_stream_t stream);
+
+/* Duplicates.  No counterpart in the reference; no sum.  perm (T) int64: the triangles ordered so that the alive triples ascend
+ * lexicographically, equal triples in ascending triangle index (two stable sorts: by the third index, then by the 64-bit pair of
+ * the first two).  keep (T) bytes: 1 for an alive triangle whose predecessor in that order is dead or has another triple, 0 for
+ * every other triangle. */
+int mvd_mesh_cluster_mark_first(const int* triples, const unsigned char* alive, const long long* perm, long long T, unsigned char* keep,
+                                mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Mesh evaluation: the truncated distance from points to a triangle mesh, and deterministic covering samples of its surface.  The
  * reference has NO counterpart: the definition is robustmvd_amd/mesh_eval.py (mesh_distance_numpy, mesh_grid_pairs_numpy,
  * sample_mesh_numpy) and DESIGN.md, restated here.

@@ -37,3 +37,5 @@ from .mesh_clean import (mesh_components, clean_mesh, vertex_normals, components
 from . import mesh_eval  # noqa: F401,E402
 from .mesh_eval import (MeshEvaluation, evaluate_mesh, mesh_distance, sample_mesh, mesh_distance_numpy, mesh_grid_pairs_numpy,  # noqa: F401,E402
                         sample_mesh_numpy)
+from . import mesh_simplify  # noqa: F401,E402
+from .mesh_simplify import (simplify_mesh, simplify_numpy, cluster_numpy, cluster_quadrics_numpy, place_numpy, SimplifyResult)  # noqa: F401,E402

@@ -200,6 +200,19 @@ SIGNATURES = {
                                       ctypes.c_void_p]),
     "mvd_mesh_vertex_normals_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
                                          ctypes.c_void_p, _c_float_p, ctypes.c_void_p]),
+    "mvd_mesh_cluster_ids_workspace_bytes": (_sz, [ctypes.c_longlong]),
+    "mvd_mesh_cluster_ids": (_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong] + [ctypes.c_void_p] * 5 + [_sz, ctypes.c_void_p]),
+    "mvd_mesh_cluster_means_f64": (_i, [_c_float_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, _i,
+                                        ctypes.c_void_p, ctypes.c_void_p]),
+    "mvd_mesh_cluster_triples": (_i, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong]
+                                 + [ctypes.c_void_p] * 4),
+    "mvd_mesh_cluster_quadrics_workspace_bytes": (_sz, [ctypes.c_longlong]),
+    "mvd_mesh_cluster_quadrics_f64": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong] + [ctypes.c_double] * 4
+                                      + [ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
+    "mvd_mesh_cluster_place_f32": (_i, [ctypes.c_void_p] * 5 + [_c_float_p, ctypes.c_longlong, ctypes.c_longlong] + [ctypes.c_double] * 5
+                                   + [_c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mvd_mesh_cluster_mark_first": (_i, [ctypes.c_void_p] * 3 + [ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p]),
     "mvd_mesh_cell_counts_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong] + [ctypes.c_double] * 4
                                  + [ctypes.c_void_p] * 2),
     "mvd_mesh_pairs_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong]

@@ -1158,6 +1158,153 @@ def mesh_vertex_normals(vertices, triangles, sorted_vertex, perm):
     return normals
 
 
+class MeshClusters:
+    """The clusters of a mesh's vertices (mesh_cluster_ids): vertex_cluster (M) int32, cluster_start (K+1) int32 into perm,
+    cluster_key (K) int64, perm (M) int64 (the vertices sorted stably by key), origin (3 floats), cell (the float32 edge as a float)."""
+    __slots__ = ("vertex_cluster", "cluster_start", "cluster_key", "perm", "origin", "cell")
+
+    def __init__(self, vertex_cluster, cluster_start, cluster_key, perm, origin, cell):
+        self.vertex_cluster, self.cluster_start, self.cluster_key, self.perm = vertex_cluster, cluster_start, cluster_key, perm
+        self.origin, self.cell = origin, cell
+
+    @property
+    def num_clusters(self):
+        return int(self.cluster_key.shape[0])
+
+    @property
+    def counts(self):
+        return self.cluster_start[1:] - self.cluster_start[:-1]
+
+
+def _mesh_vertices(vertices, device=None):
+    v = L.as_dtype(torch.float32, False, vertices, "vertices", device=device)
+    if v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"vertices must be (M,3), got {tuple(v.shape)}")
+    return v
+
+
+@inference_only
+def mesh_cluster_ids(vertices, cell, origin=None):
+    """The vertices of a mesh sorted into the cells of edge `cell` (taken as float32) and numbered (include/mvd.h:
+    mvd_mesh_cluster_ids; mesh_simplify.cluster_numpy is the definition) -> MeshClusters.  origin defaults to the per-axis minimum
+    over the finite vertices.  Host reads: the extent (6 floats) and K."""
+    v = _mesh_vertices(vertices)
+    dev, M = v.device, int(v.shape[0])
+    cell = float(torch.tensor(float(cell), dtype=torch.float32))
+    if not 0.0 < cell < float("inf"):
+        raise ValueError(f"cell must be finite and > 0, got {cell}")
+    inv = 1.0 / cell
+    extent = _cloud_extent(v)
+    o = _cloud_origin(origin) if origin is not None else ([0.0, 0.0, 0.0] if extent is None else extent[0].tolist())
+    _check_cloud_indices(extent, o, inv, "voxel_downsample", cell)
+    keys, perm = _cloud_sorted(v, o, inv)
+    vc = torch.empty(M, dtype=torch.int32, device=dev)
+    start = torch.empty(M + 1, dtype=torch.int32, device=dev)
+    ckey = torch.empty(M, dtype=torch.int64, device=dev)
+    num = torch.empty(1, dtype=torch.int64, device=dev)
+    nbytes = L.load().mvd_mesh_cluster_ids_workspace_bytes(M)
+    ws = workspace(nbytes, dev)
+    call("mvd_mesh_cluster_ids", dev, keys if M else None, perm if M else None, M, vc if M else None, start, ckey if M else None, num, ws,
+         int(nbytes))
+    K = int(num.item())
+    return MeshClusters(vc, start[:K + 1].clone(), ckey[:K].clone(), perm, o, cell)
+
+
+@inference_only
+def mesh_cluster_means(rows, clusters):
+    """-> (K,k) float64: every cluster's mean of a per-vertex (M,k) float32 array, summed in ascending vertex index in the fixed
+    segment order (mvd_mesh_cluster_means_f64)."""
+    dev, M, K = clusters.perm.device, int(clusters.perm.numel()), clusters.num_clusters
+    r = L.as_dtype(torch.float32, False, rows, "rows", device=dev)
+    if r.dim() != 2 or r.shape[0] != M or not 1 <= r.shape[1] <= 65536:
+        raise ValueError(f"rows must be ({M},k) with k in 1 .. 65536, got {tuple(r.shape)}")
+    k = int(r.shape[1])
+    if M * k >= 2 ** 31:
+        raise ValueError(f"rows holds {M * k} values: M k must be below 2^31")
+    means = torch.empty((K, k), dtype=torch.float64, device=dev)
+    if K:
+        call("mvd_mesh_cluster_means_f64", dev, r, clusters.perm, clusters.cluster_start, K, M, k, means)
+    return means
+
+
+@inference_only
+def mesh_cluster_triples(triangles, clusters):
+    """-> (triples (T,3) int32: the rotated cluster triple or (-1,-1,-1); alive (T) uint8; corner_key (T,3) int32: each corner's
+    cluster, K for a triangle with an invalid vertex) (mvd_mesh_cluster_triples)."""
+    vc = clusters.vertex_cluster
+    dev, M, K = vc.device, int(vc.numel()), clusters.num_clusters
+    t = _mesh_triangles(triangles, M, device=dev)
+    T = int(t.shape[0])
+    if 3 * T >= 2 ** 31:
+        raise ValueError(f"{T} triangles: 3 T must be below 2^31")
+    triples = torch.empty((T, 3), dtype=torch.int32, device=dev)
+    alive = torch.empty(T, dtype=torch.uint8, device=dev)
+    corner = torch.empty((T, 3), dtype=torch.int32, device=dev)
+    if T:
+        call("mvd_mesh_cluster_triples", dev, t, T, M, vc, K, triples, alive, corner)
+    return triples, alive, corner
+
+
+@inference_only
+def mesh_cluster_quadrics(vertices, triangles, sorted_cluster, perm, clusters):
+    """-> (K,10) float64: every cluster's quadric sums over its corners in ascending (triangle, corner) in the fixed segment order
+    (mvd_mesh_cluster_quadrics_f64).  sorted_cluster (3T) int32 and perm (3T) int64: torch.sort(corner_key.reshape(-1), stable=True)."""
+    dev, K = clusters.vertex_cluster.device, clusters.num_clusters
+    v = _mesh_vertices(vertices, dev)
+    M = int(v.shape[0])
+    t = _mesh_triangles(triangles, M, device=dev)
+    T = int(t.shape[0])
+    if 3 * T >= 2 ** 31:
+        raise ValueError(f"{T} triangles: 3 T must be below 2^31")
+    key = L.as_dtype(torch.int32, False, sorted_cluster, "sorted_cluster", (3 * T,), dev)
+    pm = L.as_dtype(torch.int64, False, perm, "perm", (3 * T,), dev)
+    quadrics = torch.empty((K, 10), dtype=torch.float64, device=dev)
+    if K:
+        nbytes = L.load().mvd_mesh_cluster_quadrics_workspace_bytes(K)
+        ws = workspace(nbytes, dev)
+        o = clusters.origin
+        call("mvd_mesh_cluster_quadrics_f64", dev, v, M, t if T else None, T, key if T else None, pm if T else None, clusters.cluster_key, K,
+             o[0], o[1], o[2], clusters.cell, quadrics, ws, int(nbytes))
+    return quadrics
+
+
+@inference_only
+def mesh_cluster_place(vertices, clusters, means, quadrics=None, regularisation=1e-3):
+    """-> (vertices (K,3) float32, placed (K) uint8): per cluster the quadric's regularised minimum (1), the mean (0: quadrics=None,
+    or the minimum is refused) or its single vertex (2) (mvd_mesh_cluster_place_f32; mesh_simplify.place_numpy is the definition)."""
+    dev, K = clusters.vertex_cluster.device, clusters.num_clusters
+    v = _mesh_vertices(vertices, dev)
+    M = int(v.shape[0])
+    mean = L.as_dtype(torch.float64, False, means, "means", (K, 3), dev)
+    q = None if quadrics is None else L.as_dtype(torch.float64, False, quadrics, "quadrics", (K, 10), dev)
+    reg = float(regularisation)
+    if not 0.0 < reg < float("inf"):
+        raise ValueError(f"regularisation must be finite and > 0, got {regularisation}")
+    out = torch.empty((K, 3), dtype=torch.float32, device=dev)
+    placed = torch.empty(K, dtype=torch.uint8, device=dev)
+    if K:
+        o = clusters.origin
+        call("mvd_mesh_cluster_place_f32", dev, q, mean, clusters.cluster_start, clusters.cluster_key, clusters.perm, v, K, M, o[0], o[1], o[2],
+             clusters.cell, reg, out, placed)
+    return out, placed
+
+
+@inference_only
+def mesh_cluster_mark_first(triples, alive, perm):
+    """-> keep (T) uint8: the alive triangles that come first among those of their triple (mvd_mesh_cluster_mark_first).  perm (T)
+    int64 orders the alive triples lexicographically, equal ones by triangle index."""
+    tr = L.as_dtype(torch.int32, False, triples, "triples")
+    dev, T = tr.device, int(tr.shape[0])
+    if tr.dim() != 2 or tr.shape[1] != 3:
+        raise ValueError(f"triples must be (T,3), got {tuple(tr.shape)}")
+    al = L.as_dtype(torch.uint8, False, alive, "alive", (T,), dev)
+    pm = L.as_dtype(torch.int64, False, perm, "perm", (T,), dev)
+    keep = torch.empty(T, dtype=torch.uint8, device=dev)
+    if T:
+        call("mvd_mesh_cluster_mark_first", dev, tr, al, pm, T, keep)
+    return keep
+
+
 CLOUD_INDEX_LIMIT = (1 << 21) - 1 # a cell or voxel index is in [0, 2^21 - 1): the all-ones key is the invalid points' own
 CLOUD_CELL_MARGIN = 1.0 + 2.0 ** -10  # cell edge = max_dist * margin (csrc/cloud_eval.hip: why 27 cells are enough)
 

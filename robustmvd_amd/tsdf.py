@@ -330,6 +330,13 @@ class Mesh:
         from .mesh_clean import clean_mesh
         return clean_mesh(self, **kw)
 
+    def simplify(self, cell, **kw):
+        """-> Mesh with one vertex per occupied cell of edge `cell`, placed by the cell's quadric (mesh_simplify.simplify_mesh:
+        placement=, regularisation=, origin=, unique=, remove_unreferenced=); with attributes= or details=True a SimplifyResult,
+        whose .mesh is that Mesh."""
+        from .mesh_simplify import simplify_mesh
+        return simplify_mesh(self, cell, **kw)
+
     def vertex_normals(self):
         """-> (M,3) float32: the area-weighted vertex normals (mesh_clean.vertex_normals)."""
         from .mesh_clean import vertex_normals
@@ -484,13 +491,20 @@ class TSDFVolume:
         the consistency check count."""
         return self.integrate(result.fused_depth, intrinsics, poses, weights=result.mask, images=images)
 
-    def extract_mesh(self, min_weight=1.0, clean=None):
+    def extract_mesh(self, min_weight=1.0, clean=None, simplify=None):
         """-> Mesh: the surface between the observed voxels (weight >= min_weight), module docstring.  clean: None, or a dict of
         mesh_clean.clean_mesh's keywords min_triangles, min_area, keep_largest and remove_unreferenced, applied to the mesh; any
-        other keyword raises, so that the result is always a Mesh (for attributes or the remaps call mesh.clean yourself)."""
+        other keyword raises, so that the result is always a Mesh (for attributes or the remaps call mesh.clean yourself).
+        simplify: None, or a dict of mesh_simplify.simplify_mesh's keywords cell (required), placement, regularisation, origin,
+        unique and remove_unreferenced, applied after clean."""
         extra = set(clean or ()) - {"min_triangles", "min_area", "keep_largest", "remove_unreferenced"}
         if extra:
             raise ValueError(f"extract_mesh: clean takes min_triangles, min_area, keep_largest and remove_unreferenced, got {sorted(extra)}")
+        if simplify is not None:
+            extra = set(simplify) - {"cell", "placement", "regularisation", "origin", "unique", "remove_unreferenced"}
+            if extra or "cell" not in simplify:
+                raise ValueError("extract_mesh: simplify takes cell (required), placement, regularisation, origin, unique and "
+                                 f"remove_unreferenced, got {sorted(simplify)}")
         if self.device is None:
             v, c, t = extract_numpy(self.tsdf, self.weight, self.color, self.origin, self.voxel, min_weight)
             mesh = Mesh(v.astype(np.float32), t, None if c is None else c.astype(np.float32))
@@ -498,7 +512,9 @@ class TSDFVolume:
             from . import ops
             v, t, c = ops.tsdf_extract(self.tsdf, self.weight, self.color, self.origin, self.voxel, min_weight)
             mesh = Mesh(v, t, c)
-        return mesh if clean is None else mesh.clean(**clean)
+        if clean is not None:
+            mesh = mesh.clean(**clean)
+        return mesh if simplify is None else mesh.simplify(**simplify)
 
     def render(self, intrinsics, poses, size, min_weight=1.0, **kw):
         """-> RenderResult: extract_mesh(min_weight).render(...), the volume's surface seen from V views: per view the denoised and
