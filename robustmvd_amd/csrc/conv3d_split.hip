@@ -11,6 +11,11 @@
 // [w_hi of the 8 couts | w_lo of the 8 couts]: one MFMA with A = a_hi yields both a_hi w_hi and a_hi w_lo (all 16 columns
 // useful), a second with A = a_lo yields a_lo w_hi (half useful).  2 MFMAs of 16 cycles per (tap, 16 voxels) replace 8
 // fp32 MFMAs of 32 cycles: the layer turns from matrix-bound into an LDS / memory pass.
+// The march is plane-stationary (one activation fragment serves the output planes z-1, z, z+1), so the idle half of the a_lo
+// MFMA carries the same product of a SECOND depth tap: the weight fragments pair the depth taps in their column halves
+// (P = [w_hi(kd=2) | w_hi(kd=1)], Q = [w_hi(kd=0) | w_lo(kd=0)], R = [w_lo(kd=2) | w_lo(kd=1)], see the pack kernel), five MFMAs
+// do the work of six (90 per step for 108) and the accumulators' column halves change places between steps with row_ror:8
+// moves.  conv0 of the headline forward: 719 -> 684 us in the frame, every output bit unchanged (profiles/conv0_pack_frame.txt).
 //
 // Range: fp16 spans 2^-24 .. 65504, fp32 operands do not.  Both operands are therefore multiplied by exact powers of two
 // before the split and the result by the inverse afterwards (block floating point, nothing is rounded by the scaling): the
@@ -24,15 +29,21 @@
 //
 // Workgroup (4 waves) = 4 x 32 tile marching through TD + 2 input planes (see the kernel); the fp32 volume is converted to
 // the two fp16 terms while it is staged (global -> registers -> LDS), all 27 weight fragments stay in registers.
+#include <algorithm>
+#include <cstdlib>
+
 #include "mvd_common.h"
 #include "split_operand.h"
 
 // Knock-out / tuning macros for tools/ko_conv0_split.sh (timing only: the results of a knocked-out build are wrong).
 #ifndef SPLIT_KO
-#define SPLIT_KO 0  // 1 no reloads, 2 no stores, 4 no split + LDS writes, 8 no barrier, 16 no MFMAs, 32 no fragment reads
-#endif
+#define SPLIT_KO 0  // 1 no reloads, 2 no stores, 4 no split + LDS writes, 8 no barrier, 16 no MFMAs, 32 no fragment reads,
+#endif              // 64 (six-MFMA schedule only) no lo-term MFMAs of tap kd = 1: the bound of what packing the lo terms can save
 #ifndef SPLIT_DEPTH
 #define SPLIT_DEPTH 4
+#endif
+#ifndef SPLIT_STAGE_AT
+#define SPLIT_STAGE_AT 8  // the slot of the first staging group: 0 .. 8 (inside pass A), or -1 = behind the epilogue groups in pass B
 #endif
 
 namespace mvd {
@@ -60,27 +71,41 @@ struct SplitGeom {
     static constexpr int ITEMS = S_ROWS * COLS * CH8;           // (voxel, 8-channel chunk) items per plane
     static constexpr int NLOAD = (ITEMS + 255) / 256;
     static constexpr int NF = 4 * KWG * 2;                      // fragments per pass: input rows x kw groups x terms
-    static_assert(NF - 8 == 4 * NLOAD, "pass B interleaves 8 epilogue groups and 4 staging groups per item");
+    static_assert(NF - 8 == 4 * NLOAD, "a pass has room for 8 epilogue groups and 4 staging groups per item");
 };
 
-// w (Cout, CIN, 3, 3, 3) fp32 -> [cout block Cout/8][fragment NT][lane 64][8 halves]: lane l = column l%16 (0..7: w_hi of cout
-// 8 cb + l%16, 8..15: w_lo of cout 8 cb + l%16 - 8), K values 8*(l/16) .. +7 of the fragment: CIN = 32: fragment = tap, K = cin;
-// CIN = 16: fragment = (kd, kh, kw pair g), K = 16 * (kw - 2g) + cin, kw = 3 is the zero pad.  Weights divided by the
+// w (Cout, CIN, 3, 3, 3) fp32 -> [cout block Cout/8][fragment NT][lane 64][8 halves]: lane l = column l%16 (cout 8 cb + l%8),
+// K values 8*(l/16) .. +7 of the fragment.  Fragment t = (kh, kw group g, f): three per (kh, g), each with TWO depth taps or
+// terms of the 8 couts in its column halves [0..7 | 8..15]:
+//     f = 0  P = [w_hi(kd = 2) | w_hi(kd = 1)]      f = 1  Q = [w_hi(kd = 0) | w_lo(kd = 0)]      f = 2  R = [w_lo(kd = 2) | w_lo(kd = 1)]
+// CIN = 32: g = kw, K = cin; CIN = 16: g = kw pair, K = 16 * (kw - 2g) + cin, kw = 3 is the zero pad.  Weights divided by the
 // channel's 2^k_c first (exact); wscale (split_wscale_kernel's Cout floats) is appended to the packed buffer.
-template <int CIN>
+// SIX (experiments library): the fragments of the six-MFMA schedule, t = (kd, kh, g) with the columns [w_hi | w_lo] of one tap.
+template <int CIN, bool SIX>
 __global__ void pack_conv0_split_kernel(const float* __restrict__ w, const float* __restrict__ wscale, _Float16* __restrict__ packed, int ncb) {
     using G = SplitGeom<CIN>;
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= ncb * G::NT * 64 * 8) return;
     const int j = e & 7, lane = (e >> 3) & 63, t = (e >> 9) % G::NT, cb = (e >> 9) / G::NT;
     const int col = lane & 15, k = 8 * (lane >> 4) + j, cout = cb * 8 + (col & 7);
+    int kdkh, g;
+    bool lo_term;
+    if constexpr (SIX) {
+        kdkh = t / G::KWG; g = t % G::KWG; lo_term = col >= 8;
+    } else {
+        const int f = t % 3, kh = (t / 3) / G::KWG;
+        g = (t / 3) % G::KWG;
+        const int kd = f == 1 ? 0 : (col < 8 ? 2 : 1);
+        kdkh = kd * 3 + kh;
+        lo_term = f == 2 || (f == 1 && col >= 8);
+    }
     int tap, cin;
-    if constexpr (CIN == 32) { tap = t; cin = k; }
-    else { const int kw = 2 * (t % 2) + k / 16; tap = kw < 3 ? (t / 2) * 3 + kw : -1; cin = k % 16; }
+    if constexpr (CIN == 32) { tap = kdkh * 3 + g; cin = k; }
+    else { const int kw = 2 * g + k / 16; tap = kw < 3 ? kdkh * 3 + kw : -1; cin = k % 16; }
     const float v = tap >= 0 ? w[((size_t)cout * CIN + cin) * 27 + tap] / wscale[cout] : 0.0f;
     _Float16 hi, lo;
     split_weight(v, S_LO_FACTOR, hi, lo);
-    packed[e] = col < 8 ? hi : lo;
+    packed[e] = lo_term ? lo : hi;
 }
 
 struct SplitParams {
@@ -94,6 +119,8 @@ struct SplitParams {
     int B, D, h, w, relu;
     int cout, ncb;        // output channels (a multiple of 8) and Cout / 8: one workgroup computes 8 of them
     int tiles_x, tiles_y, dgroups, td, tiles_per_xcd;
+    int slots;            // > 0 (experiments library): the persistent grid of `slots` workgroups, each an even share of the `total` planes
+    long long total;      // tiles x B x cout blocks x D
 };
 
 __device__ __forceinline__ unsigned pack_h2(_Float16 a, _Float16 b) {
@@ -101,14 +128,39 @@ __device__ __forceinline__ unsigned pack_h2(_Float16 a, _Float16 b) {
     return __builtin_bit_cast(unsigned, v);
 }
 
+// v_mov_b32 with row_ror:8 and a bank mask: the lanes of the masked banks (4 lanes each; 0x3 = columns 0..7 of a row of 16 lanes,
+// 0xc = columns 8..15) take `src` of lane l ^ 8, the others keep `keep`
+template <int BANK_MASK>
+__device__ __forceinline__ float ror8(float keep, float src) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, keep), __builtin_bit_cast(int, src), 0x128, 0xf, BANK_MASK, false));
+}
+
 // Plane-stationary march.  One input plane z is staged per step and every activation fragment read from LDS is used for all
 // the outputs it feeds in d and y: the three output planes z-1, z, z+1 (taps kd = 2, 1, 0) and the wave's two output rows
-// (taps kh = rr - row).  24 fragment reads feed the 108 MFMAs of a step (4.5 per read); with one read per MFMA (the first
-// version, profiles/r02_conv0_split_pmc.txt) the four SIMDs of a CU asked the LDS for 32 clocks of ds_read_b128 per 16
-// clocks of MFMA and the kernel sat on the LDS port at 35 % matrix utilisation.  Three output planes of accumulators are in
-// flight per wave (48 VGPRs); the LDS holds two plane slots (the one being read, the one being written).
+// (taps kh = rr - row).  48 fragment reads (24 fragments, once per pass) feed the 90 MFMAs of a step; with one read per MFMA
+// (the first version, profiles/r02_conv0_split_pmc.txt) the four SIMDs of a CU asked the LDS for 32 clocks of ds_read_b128 per
+// 16 clocks of MFMA and the kernel sat on the LDS port at 35 % matrix utilisation.  Three output planes of accumulators are in
+// flight per wave (40 VGPRs); the LDS holds two plane slots (the one being read, the one being written).
 // wave wv: columns 16 (wv & 1) .. +15, output rows 2 (wv >> 1), +1 of the 4 x 32 tile.
-template <int CIN, bool YAMAX = false>  // YAMAX: also max |y| (a variant of its own: the extra epilogue work costs the plain one 7 %)
+//
+// Five MFMAs per (tap pair, 16 voxels, row, kh) where the first version issued six.  The idle column half of its a_lo MFMA
+// (a_lo w_lo, never read) carries a second depth tap of the same product: with the fragments P, Q, R of the pack kernel
+//     X  += a_hi P   hi*hi of plane z-1 | hi*hi of plane z          Y  += a_hi Q   hi*hi of plane z+1 | hi*lo of plane z+1
+//     Z  += a_hi R   hi*lo of plane z-1 | hi*lo of plane z          LB += a_lo Q   lo*hi of plane z+1 | unused
+//     LA += a_lo P   lo*hi of plane z-1 | lo*hi of plane z
+// (columns 0..7 | 8..15), ten accumulators and 90 MFMAs per step.  After X, Z, LA (pass A) the three terms of plane z-1 sit in
+// columns 0..7 of the same lanes; between steps the column HALVES change places instead of the plane slots (a lane holds column
+// l%16, so each move is v_mov_b32 with row_ror:8 and a bank mask):
+//     X' = (X 8..15 -> 0..7,  Y 0..7 -> 8..15)      Z' = (Z 8..15 -> 0..7,  Y 8..15 stay)      LA' = (LA 8..15 -> 0..7,  LB 0..7 -> 8..15)
+// Every accumulation chain (plane, row, product, column) takes its terms in the first version's order — the kd = 0 taps at step
+// p-1, kd = 1 at p, kd = 2 at p+1, each in the fragment loop's order — and the columns of an MFMA are independent: the same bits.
+// SIX (experiments library, MVD_CONV0_LEGACY): that first version, acc[plane slot][row][term] with one tap [w_hi | w_lo] per MFMA.
+//
+// A workgroup marches one or more SEGMENTS (tile, batch, cout block, planes d0 .. d1-1) of the work in the order (tile, batch,
+// cout block, plane): the ordinary grid gives each workgroup one segment of td planes, the persistent grid (p.slots; measured
+// and not shipped, the experiments library's MVD_CONV0_SLOTS) an even share of all planes (+-1), cut wherever the share ends.
+// A plane's chains are the same three steps wherever a segment starts.
+template <int CIN, bool YAMAX = false, bool SIX = false>  // YAMAX: also max |y| (a variant of its own: the extra epilogue work costs the plain one 7 %)
 __global__ void __launch_bounds__(256, 2) conv0_split_kernel(SplitParams p) {
     using G = SplitGeom<CIN>;
     constexpr int S_COLS = G::COLS, S_HALF_BYTES = G::HALF_BYTES, S_PLANE_BYTES = G::PLANE_BYTES, S_ITEMS = G::ITEMS, S_NLOAD = G::NLOAD;
@@ -117,31 +169,91 @@ __global__ void __launch_bounds__(256, 2) conv0_split_kernel(SplitParams p) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int D = p.D, h = p.h, w = p.w;
 
-    // XCD-aware decode (blocks b and b + 8 share an XCD and its L2): each XCD owns a contiguous run of (row-major) tiles, so
+    // XCD-aware order (blocks b and b + 8 share an XCD and its L2): each XCD owns a contiguous run of (row-major) tiles, so
     // the halo rows and columns that neighbouring tiles share are re-read from ONE L2 instead of from HBM by eight
     const int xcd = blockIdx.x & 7;
-    int j = blockIdx.x >> 3;
-    const int cb = j % p.ncb; j /= p.ncb;  // the cout blocks of a tile run next to each other: they read the same input through one L2
-    const int t_in = j % p.tiles_per_xcd; j /= p.tiles_per_xcd;
-    const int dg = j % p.dgroups;
-    const int b = j / p.dgroups;
-    const int tile = xcd * p.tiles_per_xcd + t_in;
-    if (tile >= p.tiles_x * p.tiles_y) return;  // block-uniform
-    const int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
-    const int x0 = tx * S_TW, y0 = ty * S_TH;
-    const int dz0 = dg * p.td, dz1 = min(dz0 + p.td, D);
-
-    h16x8 wf[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) wf[t] = *reinterpret_cast<const h16x8*>(p.wpk + (((size_t)cb * NT + t) * 64 + lane) * 16);
+    long long lin, lin_end;  // this workgroup's planes in the order (tile, batch, cout block, plane)
+    if (p.slots > 0) {       // persistent: workgroups ranked by (XCD, index inside it), equal contiguous shares
+        const int q = p.slots >> 3, rem = p.slots & 7;
+        const int rank = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (int)(blockIdx.x >> 3);
+        lin = p.total * rank / p.slots;
+        lin_end = p.total * (rank + 1) / p.slots;
+    } else {
+        int j = blockIdx.x >> 3;
+        const int cb = j % p.ncb; j /= p.ncb;  // the cout blocks of a tile run next to each other: they read the same input through one L2
+        const int t_in = j % p.tiles_per_xcd; j /= p.tiles_per_xcd;
+        const int dg = j % p.dgroups;
+        const int b = j / p.dgroups;
+        const int tile = xcd * p.tiles_per_xcd + t_in;
+        if (tile >= p.tiles_x * p.tiles_y) return;  // block-uniform
+        lin = (((long long)tile * p.B + b) * p.ncb + cb) * D + dg * p.td;
+        lin_end = lin + min(p.td, D - dg * p.td);
+    }
 
     // staging map: item e = tid + 256 k -> (row, col, 8-channel chunk).  Everything below is branch-free: a voxel outside the
     // plane (or a plane outside the volume) is an out-of-range buffer offset (reads 0), the 208 idle items of the last round
     // write to a dump row behind the two slots.  With branches the compiler cannot count what is outstanding and falls back to
     // vmcnt(0), which also waits for the stores.
     constexpr unsigned OOB = 0x80000000u;
-    unsigned gob[S_NLOAD];
     int loff[S_NLOAD];
+#pragma unroll
+    for (int k = 0; k < S_NLOAD; ++k) {
+        const int e = tid + 256 * k;
+        const int vox = e / G::CH8, ch = e % G::CH8;
+        const int c = vox % S_COLS;
+        if constexpr (CIN == 32) loff[k] = e < S_ITEMS ? (vox * 64 + ((ch ^ ((c >> 1) & 3)) * 16)) : -1;  // swizzled as in conv0_f16
+        else loff[k] = e < S_ITEMS ? e * 16 : -1;  // 32 bytes per voxel: fragment reads are conflict-free as they stand
+    }
+    const size_t plane_f = (size_t)h * w * CIN;
+    char* const dump = ring + 2 * S_PLANE_BYTES + tid * 16;
+    float xs, xs_inv;
+    split_xscale(p.absmax, xs, xs_inv);
+    // two fp32 values -> the packed fp16 pairs (hi, lo * 2^11)
+    auto split2 = [xs](float a0, float a1, unsigned& hi, unsigned& lo) { mvd::split2(xs, a0, a1, hi, lo, S_LO_FACTOR); };
+    const int col = lane & 15;
+    const float floor_ = p.relu ? 0.f : -__builtin_inff();
+    const int xh = wv & 1, rp = wv >> 1;
+
+    int fragk[KWG];
+#pragma unroll
+    for (int kw = 0; kw < KWG; ++kw) {
+        if constexpr (CIN == 32) {
+            const int c = 16 * xh + (lane & 15) + kw;
+            fragk[kw] = (2 * rp * S_COLS + c) * 64 + (((lane >> 4) ^ ((c >> 1) & 3)) * 16);
+        } else {  // kw pair: K slices 0,1 = voxel c, slices 2,3 = voxel c + 1 (32 bytes further)
+            const int c = 16 * xh + (lane & 15) + 2 * kw;
+            fragk[kw] = (2 * rp * S_COLS + c) * 32 + (lane >> 4) * 16;
+        }
+    }
+    const size_t yplane_f = (size_t)h * w * p.cout;
+    const unsigned vox_b = (unsigned)p.cout * 4u;  // bytes from one output voxel to the next
+
+    h16x8 wf[NT];
+    float esc_ = 0.f, esh_ = 0.f, eun_ = 0.f;  // epilogue constants of the lanes that end up with a result: column (cout) l%16 < 8
+    int cb_resident = -1;
+    [[maybe_unused]] float amax_ = 0.f;  // max |y| of this lane's stored values (YAMAX)
+
+  while (lin < lin_end) {  // one segment per turn (block-uniform)
+    const int dz0 = (int)(lin % D);
+    long long sj = lin / D;
+    const int cb = (int)(sj % p.ncb); sj /= p.ncb;
+    const int b = (int)(sj % p.B);
+    const int tile = (int)(sj / p.B);
+    const int dz1 = (int)min((long long)D, dz0 + (lin_end - lin));
+    lin += dz1 - dz0;
+    const int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
+    const int x0 = tx * S_TW, y0 = ty * S_TH;
+
+    if (cb != cb_resident) {  // the weight fragments stay across the segments of one cout block
+        cb_resident = cb;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) wf[t] = *reinterpret_cast<const h16x8*>(p.wpk + (((size_t)cb * NT + t) * 64 + lane) * 16);
+        esc_ = p.scale[cb * 8 + (col & 7)];
+        esh_ = p.shift[cb * 8 + (col & 7)];
+        eun_ = reinterpret_cast<const float*>(p.wpk + (size_t)p.ncb * NT * 64 * 16)[cb * 8 + (col & 7)] * xs_inv;  // 2^(k_c + e): undoes both scalings
+    }
+
+    unsigned gob[S_NLOAD];
 #pragma unroll
     for (int k = 0; k < S_NLOAD; ++k) {
         const int e = tid + 256 * k;
@@ -150,10 +262,7 @@ __global__ void __launch_bounds__(256, 2) conv0_split_kernel(SplitParams p) {
         const int gy = y0 - 1 + r, gx = x0 - 1 + c;
         const bool in = e < S_ITEMS && c < S_TW + 2 && gy >= 0 && gy < h && gx >= 0 && gx < w;  // (the 35th column of CIN = 16 stays zero)
         gob[k] = in ? (unsigned)(((gy * w + gx) * CIN + ch * 8) * 4) : OOB;                 // bytes inside a plane
-        if constexpr (CIN == 32) loff[k] = e < S_ITEMS ? (vox * 64 + ((ch ^ ((c >> 1) & 3)) * 16)) : -1;  // swizzled as in conv0_f16
-        else loff[k] = e < S_ITEMS ? e * 16 : -1;  // 32 bytes per voxel: fragment reads are conflict-free as they stand
     }
-    const size_t plane_f = (size_t)h * w * CIN;
     const float* xb = p.x + (size_t)b * D * plane_f;
     su32x4 pre[S_NLOAD][2];
     auto fetch = [&](int d) {
@@ -166,11 +275,6 @@ __global__ void __launch_bounds__(256, 2) conv0_split_kernel(SplitParams p) {
             pre[k][1] = __builtin_amdgcn_raw_buffer_load_b128(rs, gob[k] + 16u, 0, 0);
         }
     };
-    char* const dump = ring + 2 * S_PLANE_BYTES + tid * 16;
-    // two fp32 values -> the packed fp16 pairs (hi, lo * 2^11)
-    float xs, xs_inv;
-    split_xscale(p.absmax, xs, xs_inv);
-    auto split2 = [xs](float a0, float a1, unsigned& hi, unsigned& lo) { mvd::split2(xs, a0, a1, hi, lo, S_LO_FACTOR); };
     auto stash = [&](int d) {  // prologue only: the loop below stages inside the MFMA stream
         char* slot = ring + (d & 1) * S_PLANE_BYTES;
 #pragma unroll
@@ -189,31 +293,15 @@ __global__ void __launch_bounds__(256, 2) conv0_split_kernel(SplitParams p) {
         }
     };
 
-    // epilogue constants of the lanes that end up with a result: column (cout) l%16 < 8
-    const int col = lane & 15;
-    float esc_ = p.scale[cb * 8 + (col & 7)], esh_ = p.shift[cb * 8 + (col & 7)];
-    float eun_ = reinterpret_cast<const float*>(p.wpk + (size_t)p.ncb * NT * 64 * 16)[cb * 8 + (col & 7)] * xs_inv;  // 2^(k_c + e): undoes both scalings
-    const float floor_ = p.relu ? 0.f : -__builtin_inff();
-    const int xh = wv & 1, rp = wv >> 1;
-
-    int fragk[KWG];
-#pragma unroll
-    for (int kw = 0; kw < KWG; ++kw) {
-        if constexpr (CIN == 32) {
-            const int c = 16 * xh + (lane & 15) + kw;
-            fragk[kw] = (2 * rp * S_COLS + c) * 64 + (((lane >> 4) ^ ((c >> 1) & 3)) * 16);
-        } else {  // kw pair: K slices 0,1 = voxel c, slices 2,3 = voxel c + 1 (32 bytes further)
-            const int c = 16 * xh + (lane & 15) + 2 * kw;
-            fragk[kw] = (2 * rp * S_COLS + c) * 32 + (lane >> 4) * 16;
-        }
-    }
-
-    // acc[plane slot][row][term]: slot 0 = output plane z-1 (finishes in this step), 1 = plane z, 2 = plane z+1 (starts)
-    sf32x4 acc[3][2][2];
+    // X, Z, LA, Y, LB [row]: the ten accumulators of the table above (40 VGPRs); a segment starts them from zero.
+    // SIX: acc[plane slot][row][term]: slot 0 = output plane z-1 (finishes in this step), 1 = plane z, 2 = plane z+1 (starts)
+    constexpr sf32x4 ZERO4 = {0, 0, 0, 0};
+    [[maybe_unused]] sf32x4 X[2] = {ZERO4, ZERO4}, Z[2] = {ZERO4, ZERO4}, LA[2] = {ZERO4, ZERO4}, Y[2] = {ZERO4, ZERO4}, LB[2] = {ZERO4, ZERO4};
+    [[maybe_unused]] sf32x4 acc[3][2][2];
 #pragma unroll
     for (int s = 0; s < 3; ++s)
 #pragma unroll
-        for (int r = 0; r < 2; ++r) { acc[s][r][0] = sf32x4{0, 0, 0, 0}; acc[s][r][1] = sf32x4{0, 0, 0, 0}; }
+        for (int r = 0; r < 2; ++r) { acc[s][r][0] = ZERO4; acc[s][r][1] = ZERO4; }
 
     // store offsets inside one output plane (bytes); OOB = dropped by the buffer store
     unsigned yoff[2];
@@ -223,28 +311,29 @@ __global__ void __launch_bounds__(256, 2) conv0_split_kernel(SplitParams p) {
         yoff[row] = (col < 8 && oy < h) ? (unsigned)((((size_t)oy * w + x0 + 16 * xh + 4 * (lane >> 4)) * p.cout + cb * 8 + col) * 4) : OOB;
     }
     const int oxb = x0 + 16 * xh + 4 * (lane >> 4);
-    const size_t yplane_f = (size_t)h * w * p.cout;
-    const unsigned vox_b = (unsigned)p.cout * 4u;  // bytes from one output voxel to the next
 
     fetch(dz0 - 1);
     asm volatile("" : "+v"(esc_), "+v"(esh_), "+v"(eun_));  // the per-lane epilogue constants have landed: no vmcnt wait inside the loop
     stash(dz0 - 1);
     fetch(dz0);
 
-    // One step = one input plane z (outputs dz0 .. dz1-1 need z = dz0-1 .. dz1), ONE stream of 108 MFMAs in two passes over the
+    // One step = one input plane z (outputs dz0 .. dz1-1 need z = dz0-1 .. dz1), ONE stream of 90 MFMAs in two passes over the
     // plane's 24 fragments (fragment = input row rr, kw, term; rows 1 and 2, which feed both output rows, first):
-    //   pass A  tap kd = 2 only: finishes output plane z-1 (36 MFMAs)
-    //   pass B  taps kd = 1, 0 for planes z and z+1 (72 MFMAs); everything else rides between these MFMAs of the same wave,
-    //           where about two vector instructions per MFMA issue for free (tools/micro/coissue3.hip):
-    //           groups 0..7   epilogue + store of plane z-1 (one of the lane's 8 values per group)
-    //           groups 8..23  split item k = (g-8)/4 of plane z+1 (loaded a step ago), a pair of floats per group, write it to
-    //                         the other LDS slot, reload the item's registers with plane z+2
-    // so there is no staging phase, no copy of the finished accumulators and one barrier per step.  In a phase-separated
-    // version (stage, barrier, MFMAs, stores) the two workgroups of a CU ran in lockstep and the matrix pipe idled through
-    // every staging phase (50 % busy).
+    //   pass A  X, Z, LA: finishes output plane z-1 (54 MFMAs)                                 [SIX: tap kd = 2, 36 MFMAs]
+    //   pass B  Y, LB: starts plane z+1 (36 MFMAs)                                             [SIX: taps kd = 1, 0, 72 MFMAs]
+    // Everything else rides between these MFMAs of the same wave, where about two vector instructions per MFMA issue for free
+    // (tools/micro/coissue3.hip), one group per fragment (slot = pass * 24 + fragment):
+    //   slots 24..31            epilogue + store of plane z-1 (one of the lane's 8 values per group)
+    //   slots STAGE_AT .. +15   split item k of plane z+1 (loaded a step ago), a pair of floats per group, write it to the other
+    //                           LDS slot (free from the barrier on), reload the item's registers with plane z+2
+    // so there is no staging phase and one barrier per step.  In a phase-separated version (stage, barrier, MFMAs, stores) the two
+    // workgroups of a CU ran in lockstep and the matrix pipe idled through every staging phase (50 % busy).
     // With loads AND stores outstanding the compiler has to treat vmcnt as unordered: the first use of a prefetched register
-    // (pass B, group 8) becomes a full flush.  By then the youngest load is two thirds of a step old and the stores a full one.
-    [[maybe_unused]] float amax_ = 0.f;  // max |y| of this lane's stored values (YAMAX)
+    // (the first staging group) becomes a full flush.  By then the youngest load is two thirds of a step old; the stores are a
+    // full step old where the staging follows the epilogue (SIX) and half a step where it rides in pass A.
+    constexpr int STAGE_AT = SIX || SPLIT_STAGE_AT < 0 ? G::NF + 8 : SPLIT_STAGE_AT;
+    static_assert(STAGE_AT >= 0 && STAGE_AT + 4 * S_NLOAD <= 2 * G::NF && (STAGE_AT >= G::NF + 8 || STAGE_AT + 4 * S_NLOAD <= G::NF),
+                  "the staging groups fit into one step, clear of the epilogue groups");
     for (int z = dz0 - 1; z <= dz1; ++z) {
         if (!(SPLIT_KO & 8)) __syncthreads();  // plane z is staged; the other slot (plane z-1) has been read by every wave
         const char* slot = ring + (z & 1) * S_PLANE_BYTES;
@@ -269,51 +358,29 @@ __global__ void __launch_bounds__(256, 2) conv0_split_kernel(SplitParams p) {
         };
 #pragma unroll
         for (int i = 0; i < DEPTH; ++i) fr[i] = frag(i);
-        // ---- pass A
-#pragma unroll
-        for (int g = 0; g < NF; ++g) {
-            const int term = g & 1, kw = (g >> 1) % KWG, rr = rr_of(g / (2 * KWG));
-            const h16x8 f = fr[g % DEPTH];
-#pragma unroll
-            for (int row = 0; row < 2; ++row) {
-                const int kh = rr - row;
-                if (kh < 0 || kh > 2) continue;
-                if (SPLIT_KO & 16) acc[0][row][term][0] += f[0] * wf[(6 + kh) * KWG + kw][0];
-                else acc[0][row][term] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f, wf[(6 + kh) * KWG + kw], acc[0][row][term], 0, 0, 0);
-            }
-            fr[g % DEPTH] = frag(g + DEPTH);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // ---- pass B.  lane l holds voxels 4*(l/16) .. +3 of column l%16: columns 0..7 = hi*hi for cout c, columns 8..15 = hi*lo;
-        // result(c) = acc_hi[c] + 2^-11 (acc_hi[c + 8] + acc_lo[c])
-        float hl = __shfl_down(acc[0][0][0][0], 8, 16);
+        // the ride-along group of slot si.  lane l holds voxels 4*(l/16) .. +3 of column l%16; after pass A the lanes of columns
+        // 0..7 have result(c) = hi*hi + 2^-11 (hi*lo + lo*hi) of cout c in X, Z, LA.  [SIX: hi*lo sits in column c + 8 of acc_hi]
+        [[maybe_unused]] float hl = 0.f;
         unsigned hq0 = 0, lq0 = 0;
-#pragma unroll
-        for (int g = 0; g < NF; ++g) {
-            const int term = g & 1, kw = (g >> 1) % KWG, rr = rr_of(g / (2 * KWG));
-            const h16x8 f = fr[(NF + g) % DEPTH];
-#pragma unroll
-            for (int row = 0; row < 2; ++row) {
-                const int kh = rr - row;
-                if (kh < 0 || kh > 2) continue;
-#pragma unroll
-                for (int s = 1; s < 3; ++s)  // plane slot s takes tap kd = 2 - s
-                    if (SPLIT_KO & 16) acc[s][row][term][0] += f[0] * wf[((2 - s) * 3 + kh) * KWG + kw][0];
-                    else acc[s][row][term] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f, wf[((2 - s) * 3 + kh) * KWG + kw], acc[s][row][term], 0, 0, 0);
-            }
-            if (NF + g + DEPTH < NR) fr[(NF + g) % DEPTH] = frag(NF + g + DEPTH);
-            if (g < 8) {  // epilogue value g of the finished plane
-                const int row = g >> 2, i = g & 3;
-                const float cur = hl;
-                if (g + 1 < 8) hl = __shfl_down(acc[0][(g + 1) >> 2][0][(g + 1) & 3], 8, 16);
-                float r = __builtin_fmaf(cur + acc[0][row][1][i], 1.0f / 2048.0f, acc[0][row][0][i]);
+        auto ride = [&](int si) {
+            if (si >= NF && si < NF + 8) {  // epilogue value g of the finished plane
+                const int g = si - NF, row = g >> 2, i = g & 3;
+                float r;
+                if constexpr (SIX) {
+                    const float cur = hl;
+                    if (g + 1 < 8) hl = __shfl_down(acc[0][(g + 1) >> 2][0][(g + 1) & 3], 8, 16);
+                    r = __builtin_fmaf(cur + acc[0][row][1][i], 1.0f / 2048.0f, acc[0][row][0][i]);
+                } else {
+                    r = __builtin_fmaf(Z[row][i] + LA[row][i], 1.0f / 2048.0f, X[row][i]);
+                }
                 r = fmaxf(__builtin_fmaf(r * eun_, esc_, esh_), floor_);
                 if constexpr (YAMAX)
                     if (out_ok && yoff[row] != OOB && ox + i < w) amax_ = fmaxf(amax_, finite_abs_or_zero(r));
                 if (!(SPLIT_KO & 2) || r == 12345.678f)
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r), rs_out, ox + i < w ? yoff[row] + vox_b * i : OOB, 0, 0);
-            } else if (!(SPLIT_KO & 4)) {  // staging of plane z+1 / reload with plane z+2: item k, float pair q of its 4
-                const int k = (g - 8) >> 2, q = (g - 8) & 3;
+            } else if (si >= STAGE_AT && si < STAGE_AT + 4 * S_NLOAD && !(SPLIT_KO & 4)) {
+                // staging of plane z+1 / reload with plane z+2: item k, float pair q of its 4
+                const int k = (si - STAGE_AT) >> 2, q = (si - STAGE_AT) & 3;
                 const sf32x4 v = __builtin_bit_cast(sf32x4, pre[k][q >> 1]);
                 unsigned hq1, lq1;
                 split2(v[(q & 1) * 2], v[(q & 1) * 2 + 1], hq1, lq1);
@@ -329,17 +396,82 @@ __global__ void __launch_bounds__(256, 2) conv0_split_kernel(SplitParams p) {
                     pre[k][1] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, gob[k] + 16u, 0, 0);
                 }
             }
+        };
+        auto mma = [](const h16x8& a, const h16x8& b, sf32x4& c) {
+            if (SPLIT_KO & 16) c[0] += a[0] * b[0];
+            else c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+        };
+        // ---- pass A
+#pragma unroll
+        for (int g = 0; g < NF; ++g) {
+            const int term = g & 1, kw = (g >> 1) % KWG, rr = rr_of(g / (2 * KWG));
+            const h16x8 f = fr[g % DEPTH];
+#pragma unroll
+            for (int row = 0; row < 2; ++row) {
+                const int kh = rr - row;
+                if (kh < 0 || kh > 2) continue;
+                if constexpr (SIX) {
+                    mma(f, wf[(6 + kh) * KWG + kw], acc[0][row][term]);
+                } else if (term == 0) {
+                    mma(f, wf[(kh * KWG + kw) * 3 + 0], X[row]);
+                    mma(f, wf[(kh * KWG + kw) * 3 + 2], Z[row]);
+                } else {
+                    mma(f, wf[(kh * KWG + kw) * 3 + 0], LA[row]);
+                }
+            }
+            fr[g % DEPTH] = frag(g + DEPTH);
+            ride(g);
             __builtin_amdgcn_sched_barrier(0);
         }
+        // ---- pass B
+        if constexpr (SIX) hl = __shfl_down(acc[0][0][0][0], 8, 16);
 #pragma unroll
-        for (int r = 0; r < 2; ++r)
+        for (int g = 0; g < NF; ++g) {
+            const int term = g & 1, kw = (g >> 1) % KWG, rr = rr_of(g / (2 * KWG));
+            const h16x8 f = fr[(NF + g) % DEPTH];
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                acc[0][r][t] = acc[1][r][t];
-                acc[1][r][t] = acc[2][r][t];
-                acc[2][r][t] = sf32x4{0, 0, 0, 0};
+            for (int row = 0; row < 2; ++row) {
+                const int kh = rr - row;
+                if (kh < 0 || kh > 2) continue;
+                if constexpr (SIX) {
+#pragma unroll
+                    for (int s = 1; s < 3; ++s) {  // plane slot s takes tap kd = 2 - s
+                        if ((SPLIT_KO & 64) && s == 1 && term == 1) continue;
+                        mma(f, wf[((2 - s) * 3 + kh) * KWG + kw], acc[s][row][term]);
+                    }
+                } else {
+                    mma(f, wf[(kh * KWG + kw) * 3 + 1], term == 0 ? Y[row] : LB[row]);
+                }
             }
+            if (NF + g + DEPTH < NR) fr[(NF + g) % DEPTH] = frag(NF + g + DEPTH);
+            ride(NF + g);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (SIX) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    acc[0][r][t] = acc[1][r][t];
+                    acc[1][r][t] = acc[2][r][t];
+                    acc[2][r][t] = ZERO4;
+                }
+        } else {  // the column halves change places: plane z -> columns 0..7, plane z+1 -> columns 8..15
+            constexpr int LOW = 0x3, HIGH = 0xc;  // bank masks: columns 0..7, 8..15
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    X[r][i] = ror8<HIGH>(ror8<LOW>(X[r][i], X[r][i]), Y[r][i]);
+                    Z[r][i] = ror8<LOW>(Y[r][i], Z[r][i]);
+                    LA[r][i] = ror8<HIGH>(ror8<LOW>(LA[r][i], LA[r][i]), LB[r][i]);
+                    Y[r][i] = 0.f;
+                    LB[r][i] = 0.f;
+                }
+        }
     }
+    if (lin < lin_end) __syncthreads();  // the next segment's prologue writes a slot that this one's last step reads
+  }
     if constexpr (YAMAX) {  // what a following split-operand layer scales its activations by: ONE atomic per workgroup
         for (int o = 32; o > 0; o >>= 1) amax_ = fmaxf(amax_, __shfl_xor(amax_, o));
         __syncthreads();  // the ring is free
@@ -358,12 +490,22 @@ __global__ void __launch_bounds__(256, 2) conv0_split_kernel(SplitParams p) {
 static bool split_shape_ok(int Cin, int Cout) { return (Cin == 32 || Cin == 16) && Cout >= 8 && Cout <= 64 && Cout % 8 == 0; }
 static size_t split_frag_bytes(int Cin, int Cout) { return (size_t)(Cout / 8) * (Cin == 32 ? 27 : 18) * 64 * 16; }
 
+// the six-MFMA schedule with its own fragment layout: experiments library only (pack and launch read the same switch)
+static bool split_six() { return mvd::exp_env("MVD_CONV0_LEGACY") != nullptr; }
+
+template <int CIN, bool YAMAX, bool SIX>
+static int launch_split_k(const mvd::SplitParams& p, long long nblk, hipStream_t st) {
+    const size_t lds = 2 * (size_t)mvd::SplitGeom<CIN>::PLANE_BYTES + 256 * 16;  // two slots + the dump row
+    (void)hipFuncSetAttribute((const void*)mvd::conv0_split_kernel<CIN, YAMAX, SIX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((mvd::conv0_split_kernel<CIN, YAMAX, SIX>), dim3((unsigned)nblk), dim3(256), lds, st, p);
+    return mvd::launch_status("conv3d_split");
+}
 template <int CIN, bool YAMAX>
 static int launch_split_v(const mvd::SplitParams& p, long long nblk, hipStream_t st) {
-    const size_t lds = 2 * (size_t)mvd::SplitGeom<CIN>::PLANE_BYTES + 256 * 16;  // two slots + the dump row
-    (void)hipFuncSetAttribute((const void*)mvd::conv0_split_kernel<CIN, YAMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((mvd::conv0_split_kernel<CIN, YAMAX>), dim3((unsigned)nblk), dim3(256), lds, st, p);
-    return mvd::launch_status("conv3d_split");
+#ifdef MVD_EXPERIMENTS
+    if (split_six()) return launch_split_k<CIN, YAMAX, true>(p, nblk, st);
+#endif
+    return launch_split_k<CIN, YAMAX, false>(p, nblk, st);
 }
 template <int CIN>
 static int launch_split(const mvd::SplitParams& p, long long nblk, hipStream_t st) {
@@ -382,9 +524,17 @@ int mvd_pack_conv3d_weights_split(const float* w, int Cin, int Cout, void* packe
     const int ncb = Cout / 8;
     float* wscale = reinterpret_cast<float*>(static_cast<char*>(packed) + split_frag_bytes(Cin, Cout));
     mvd::split_wscale_launch(w, wscale, Cin, Cout, 27, false, Cout, Cout, (hipStream_t)stream);
-    const unsigned nb = (unsigned)((split_frag_bytes(Cin, Cout) / 2 + 255) / 256);
-    if (Cin == 32) hipLaunchKernelGGL(mvd::pack_conv0_split_kernel<32>, dim3(nb), dim3(256), 0, (hipStream_t)stream, w, wscale, (_Float16*)packed, ncb);
-    else hipLaunchKernelGGL(mvd::pack_conv0_split_kernel<16>, dim3(nb), dim3(256), 0, (hipStream_t)stream, w, wscale, (_Float16*)packed, ncb);
+    const dim3 nb((unsigned)((split_frag_bytes(Cin, Cout) / 2 + 255) / 256));
+    _Float16* out = (_Float16*)packed;
+#ifdef MVD_EXPERIMENTS
+    if (split_six()) {
+        if (Cin == 32) hipLaunchKernelGGL((mvd::pack_conv0_split_kernel<32, true>), nb, dim3(256), 0, (hipStream_t)stream, w, wscale, out, ncb);
+        else hipLaunchKernelGGL((mvd::pack_conv0_split_kernel<16, true>), nb, dim3(256), 0, (hipStream_t)stream, w, wscale, out, ncb);
+        return mvd::launch_status("pack_conv3d_weights_split");
+    }
+#endif
+    if (Cin == 32) hipLaunchKernelGGL((mvd::pack_conv0_split_kernel<32, false>), nb, dim3(256), 0, (hipStream_t)stream, w, wscale, out, ncb);
+    else hipLaunchKernelGGL((mvd::pack_conv0_split_kernel<16, false>), nb, dim3(256), 0, (hipStream_t)stream, w, wscale, out, ncb);
     return mvd::launch_status("pack_conv3d_weights_split");
 }
 
@@ -419,10 +569,24 @@ static int conv3d_split_entry(const float* x, const float* x_absmax, const void*
     p.tiles_y = (h + mvd::S_TH - 1) / mvd::S_TH;
     const long long tiles = (long long)p.tiles_x * p.tiles_y;
     p.tiles_per_xcd = (int)((tiles + 7) / 8);
+    p.total = tiles * B * p.ncb * D;
+    MVD_REQUIRE(p.total < (1LL << 44), "conv3d_split: %lld planes of tiles exceed the supported range", p.total);
     int td = 32;
     while (td > 8 && tiles * B * p.ncb * ((D + td - 1) / td) < 2048) td /= 2;
+    if (const char* e = mvd::exp_env("MVD_CONV0_TD")) {  // experiments library: forced march length of the ordinary grid
+        if (atoi(e) > 0) td = atoi(e);
+    }
     p.td = td;
     p.dgroups = (D + td - 1) / td;
+    // The persistent grid (two workgroups per CU, each an even run of planes: no partial last round, one depth halo per run) is
+    // built and tested but not taken: neighbouring tiles are then marched at different depths, their shared halo rows and
+    // columns miss the L2, and conv0 of the headline forward takes 756 us against 684 (profiles/conv0_pack_frame.txt).
+    int slots = 0;
+    if (const char* e = mvd::exp_env("MVD_CONV0_SLOTS")) slots = atoi(e);  // experiments library: n > 0 forces n workgroups, 0 the ordinary grid
+    if (slots > 0) {
+        p.slots = (int)std::min<long long>(slots, p.total);
+        return Cin == 32 ? launch_split<32>(p, p.slots, (hipStream_t)stream) : launch_split<16>(p, p.slots, (hipStream_t)stream);
+    }
     const long long nblk = 8LL * p.ncb * p.tiles_per_xcd * p.dgroups * B;
     MVD_REQUIRE(nblk <= 0x7fffffffLL, "conv3d_split: %lld workgroups exceed the grid limit", nblk);
     return Cin == 32 ? launch_split<32>(p, nblk, (hipStream_t)stream) : launch_split<16>(p, nblk, (hipStream_t)stream);
