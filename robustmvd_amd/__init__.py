@@ -28,7 +28,8 @@ from .cloud_eval import (PointCloudEvaluation, CloudScore, evaluate_scene, read_
 from . import cloud_register  # noqa: F401,E402
 from .cloud_register import register_clouds, register_numpy, Registration  # noqa: F401,E402
 from . import tsdf  # noqa: F401,E402
-from .tsdf import TSDFVolume, Mesh, integrate_numpy, extract_numpy, bounds_from_points  # noqa: F401,E402
+from .mesh import Mesh  # noqa: F401,E402
+from .tsdf import TSDFVolume, integrate_numpy, extract_numpy, bounds_from_points  # noqa: F401,E402
 from . import render  # noqa: F401,E402
 from .render import render_mesh, render_numpy, RenderResult  # noqa: F401,E402
 from . import mesh_clean  # noqa: F401,E402

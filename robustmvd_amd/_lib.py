@@ -1,10 +1,11 @@
-"""ctypes binding of libmvd_hip.so (include/mvd.h).  PyTorch tensors are only used for device
-memory and the current stream; the library sees raw device pointers.
+"""ctypes binding of libmvd_hip.so: the signatures and constants are read from include/mvd.h at import.
+PyTorch tensors are only used for device memory and the current stream; the library sees raw device pointers.
 
 There is NO CPU fallback: if the library is missing or cannot be loaded the import of any op raises.
 """
 import ctypes
 import os
+import re
 
 import torch
 
@@ -14,224 +15,56 @@ LIB_PATH = os.path.join(_HERE, "lib", "libmvd_hip.so")
 # Never loaded by the product path; tools/ and the variants test route calls through it with use_experiments_library().
 EXP_LIB_PATH = os.path.join(_HERE, "lib_exp", "libmvd_hip_exp.so")
 
-MVD_MAX_VIEWS = 32
-LAYOUT_NCDHW = 0
-LAYOUT_NDHWC = 1
-GRID_EXACT = 0x100
-FEAT_NHWC_BORDER = 0x200
-CONV3D_STRIDE1 = 0
-CONV2D, DECONV2D, CONV2D_IMAGE = 0, 1, 2  # mvd_conv2d_split_f32 modes
-CONV3D_STRIDE2 = 1
-DECONV3D_STRIDE2 = 2
-LAYOUT_NCHW = 0
-LAYOUT_NHWC = 1
-LAYOUT_NHWC_BORDER = 2
-INVDEPTH_SHARED, INVDEPTH_BATCHED, INVDEPTH_PER_PIXEL = 0, 1, 2
-REDUCE_VARIANCE = 0
-REDUCE_VARIANCE_KEYSQ = 1
-REDUCE_GROUPCORR = 2
-ALIGN_NONE, ALIGN_MEDIAN, ALIGN_LSQ = 0, 1, 2  # MVD_ALIGN_*
-K3_GATHER_RADIUS = 3  # MVD_K3_GATHER_RADIUS: the gather backward's window is (2 * 3 + 1)^2 key pixels per plane
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mvd.h")
 
-_c_float_p = ctypes.c_void_p
 _pp = ctypes.POINTER(ctypes.c_void_p)
-_i = ctypes.c_int
-_sz = ctypes.c_size_t
+_SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t, "float": ctypes.c_float,
+            "double": ctypes.c_double, "mvd_stream_t": ctypes.c_void_p}
 
-# name -> (restype, argtypes); mirrors include/mvd.h one to one
-SIGNATURES = {
-    "mvd_version": (_i, []),
-    "mvd_last_error": (ctypes.c_char_p, []),
-    "mvd_sweep_corr_workspace_bytes": (_sz, [_i] * 7),
-    "mvd_sweep_corr_f32": (_i, [_c_float_p, _pp, _c_float_p, _pp, _pp, _c_float_p, _i] + [_i] * 8
-                           + [_pp, _pp, ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_sweep_corr_ex_f32": (_i, [_c_float_p, _pp, _c_float_p, _pp, _pp, _c_float_p, _i, ctypes.c_float] + [_i] * 8
-                              + [_pp, _pp, ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_sweep_corr_nhwc_f32": (_i, [_c_float_p, _pp, _c_float_p, _pp, _pp, _c_float_p, _i, ctypes.c_float] + [_i] * 8
-                                + [_pp, _pp, _i, _c_float_p, ctypes.c_void_p]),
-    "mvd_fuse_views_nhwc_f32": (_i, [_pp, _pp, _pp] + [_i] * 6 + [_c_float_p, _c_float_p, _i, _c_float_p, ctypes.c_void_p]),
-    "mvd_upsample2x_nhwc_f32": (_i, [_c_float_p, _c_float_p, _c_float_p] + [_i] * 5 + [ctypes.c_void_p]),
-    "mvd_sweep_warp_f32": (_i, [_pp, _c_float_p, _pp, _pp, _c_float_p] + [_i] * 10 + [_pp, _pp, ctypes.c_void_p]),
-    "mvd_fuse_views_f32": (_i, [_pp, _pp, _pp, _i, _i, _i, _i, _i, _c_float_p, _c_float_p, ctypes.c_void_p]),
-    "mvd_warp_variance_workspace_bytes": (_sz, [_i] * 5),
-    "mvd_warp_variance_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _c_float_p] + [_i] * 6
-                              + [_c_float_p, _i, ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_warp_variance_absmax_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _c_float_p] + [_i] * 6
-                                     + [_c_float_p, _c_float_p, _i, ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_absmax_f32": (_i, [_c_float_p, ctypes.c_longlong, _c_float_p, ctypes.c_void_p]),
-    "mvd_warp_variance_f16_workspace_bytes": (_sz, [_i]),
-    "mvd_warp_variance_f16": (_i, [ctypes.c_void_p, _pp, _pp, _c_float_p, _c_float_p] + [_i] * 5
-                              + [ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_convert_f32_to_f16": (_i, [_c_float_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]),
-    "mvd_convert_f16_to_f32": (_i, [ctypes.c_void_p, _c_float_p, ctypes.c_longlong, ctypes.c_void_p]),
-    "mvd_homo_warp_f32": (_i, [_c_float_p] * 4 + [_i] * 5 + [_c_float_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_conv3d_packed_weight_floats": (_sz, [_i, _i]),
-    "mvd_pack_conv3d_weights_f32": (_i, [_c_float_p, _i, _i, _i, _c_float_p, ctypes.c_void_p]),
-    "mvd_conv3d_bn_relu_f32": (_i, [_c_float_p] * 6 + [_i] * 8 + [ctypes.c_void_p]),
-    "mvd_conv3d_bn_relu_absmax_f32": (_i, [_c_float_p] * 7 + [_i] * 8 + [ctypes.c_void_p]),
-    "mvd_conv3d_weight_grad_workspace_bytes": (_sz, [_i] * 7),
-    "mvd_conv3d_weight_grad_f32": (_i, [_c_float_p] * 3 + [_i] * 7 + [ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_conv3d_f16_packed_weight_bytes": (_sz, [_i, _i]),
-    "mvd_pack_conv3d_weights_f16": (_i, [_c_float_p, _i, _i, ctypes.c_void_p, ctypes.c_void_p]),
-    "mvd_conv3d_bn_relu_f16in": (_i, [ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p] + [_i] * 7
-                                 + [ctypes.c_void_p]),
-    "mvd_conv3d_split_packed_weight_bytes": (_sz, [_i, _i]),
-    "mvd_conv3d_bn_relu_absmax_f32_split": (_i, [_c_float_p, _c_float_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p]
-                                            + [_i] * 7 + [ctypes.c_void_p]),
-    "mvd_conv3d_igemm_packed_weight_bytes": (_sz, [_i] * 3),
-    "mvd_pack_conv3d_weights_igemm": (_i, [_c_float_p, _i, _i, _i, ctypes.c_void_p, ctypes.c_void_p]),
-    "mvd_conv3d_igemm_workspace_bytes": (_sz, [_i] * 7),
-    "mvd_conv3d_bn_relu_igemm_f32": (_i, [_c_float_p, _c_float_p, ctypes.c_void_p] + [_c_float_p] * 5 + [_i] * 8
-                                     + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "mvd_conv2d_split_packed_weight_bytes": (_sz, [_i] * 6),
-    "mvd_pack_conv2d_weights_split": (_i, [_c_float_p] + [_i] * 7 + [ctypes.c_void_p, ctypes.c_void_p]),
-    "mvd_conv2d_split_workspace_bytes": (_sz, [_i] * 9),
-    "mvd_conv2d_split_f32": (_i, [_c_float_p, _c_float_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p] + [_i] * 7
-                             + [ctypes.c_longlong] * 3 + [_i] * 5 + [ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    "mvd_pack_conv3d_weights_split": (_i, [_c_float_p, _i, _i, ctypes.c_void_p, ctypes.c_void_p]),
-    "mvd_conv3d_bn_relu_f32_split": (_i, [_c_float_p, _c_float_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p] + [_i] * 7
-                                     + [ctypes.c_void_p]),
-    "mvd_deconv3d_split_packed_weight_bytes": (_sz, [_i, _i]),
-    "mvd_pack_deconv3d_weights_split": (_i, [_c_float_p, _i, _i, ctypes.c_void_p, ctypes.c_void_p]),
-    "mvd_deconv3d_bn_relu_f32_split": (_i, [_c_float_p, _c_float_p, ctypes.c_void_p] + [_c_float_p] * 5 + [_i] * 7 + [ctypes.c_void_p]),
-    "mvd_conv2d_packed_weight_floats": (_sz, [_i, _i, _i]),
-    "mvd_pack_conv2d_weights_f32": (_i, [_c_float_p, _i, _i, _i, _c_float_p, ctypes.c_void_p]),
-    "mvd_conv2d_bn_relu_f32": (_i, [_c_float_p, _i, _c_float_p, _c_float_p, _c_float_p, _c_float_p, _i] + [_i] * 8
-                               + [ctypes.c_void_p]),
-    "mvd_conv2d_head_tile_count": (_sz, [_i] * 3),
-    "mvd_conv2d_head_f32": (_i, [_c_float_p] * 9 + [_i] * 3 + [ctypes.c_void_p]),
-    "mvd_conv2d_head_split_packed_bytes": (_sz, []),
-    "mvd_pack_conv2d_head_split_weights": (_i, [_c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "mvd_conv2d_head_split_f32": (_i, [_c_float_p] * 4 + [ctypes.c_void_p] + [_c_float_p] * 4 + [_i] * 3 + [ctypes.c_void_p]),
-    "mvd_conv2d_bn_relu_absmax_f32": (_i, [_c_float_p, _i, _c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, _i] + [_i] * 8
-                                      + [ctypes.c_void_p]),
-    "mvd_softmax_regress_f32": (_i, [_c_float_p, _c_float_p, _i, _i, _i, _i, _c_float_p, _c_float_p, ctypes.c_void_p]),
-    "mvd_softmax_regress_stats_f32": (_i, [_c_float_p, _c_float_p, _i, _i, _i, _i, _c_float_p, _c_float_p, _c_float_p,
-                                           ctypes.c_void_p]),
-    "mvd_softmax_regress_backward_f32": (_i, [_c_float_p] * 5 + [_i] * 4 + [_c_float_p, ctypes.c_void_p]),
-    "mvd_bias_leaky_relu_f32": (_i, [_c_float_p, _c_float_p, _i, _i, ctypes.c_longlong, ctypes.c_float, ctypes.c_void_p]),
-    "mvd_dispnet_head_f32": (_i, [_c_float_p, _c_float_p, _c_float_p, _i, ctypes.c_longlong, ctypes.c_void_p]),
-    "mvd_arm_kernel_timing": (_i, [ctypes.c_void_p, ctypes.c_void_p]),
-    "mvd_stream_fill_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_float, ctypes.c_void_p]),
-    "mvd_warp_variance_backward_workspace_bytes": (_sz, [_i]),
-    "mvd_warp_variance_backward_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _c_float_p, _c_float_p] + [_i] * 6
-                                       + [_c_float_p, _pp, ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_warp_variance_backward_gather_workspace_bytes": (_sz, [_i] * 6),
-    "mvd_warp_variance_backward_gather_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _c_float_p, _c_float_p] + [_i] * 6
-                                              + [_c_float_p, _pp, ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_sweep_corr_backward_f32": (_i, [_c_float_p, _pp, _c_float_p, _pp, _pp, _c_float_p, _i, ctypes.c_float, _pp] + [_i] * 8
-                                    + [_c_float_p, _pp, ctypes.c_void_p]),
-    "mvd_fuse_views_backward_f32": (_i, [_pp, _pp, _pp, _c_float_p] + [_i] * 5 + [_pp, _pp, ctypes.c_void_p]),
-    "mvd_sweep_reduce_workspace_bytes": (_sz, [_i] * 5),
-    "mvd_sweep_reduce_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _i] + [ctypes.c_float] * 4 + [_i] * 8
-                             + [_pp, ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_sweep_reduce_nhwc_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _i] + [ctypes.c_float] * 4 + [_i] * 7
-                                  + [_c_float_p, ctypes.c_void_p]),
-    "mvd_softmax_regress_pp_f32": (_i, [_c_float_p, _c_float_p, _i, _i, _i, _i, _c_float_p, _c_float_p, ctypes.c_void_p]),
-    "mvd_sweep_groupcorr_nhwc_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _i] + [ctypes.c_float] * 5 + [_i] * 7 + [_pp, ctypes.c_void_p]),
-    "mvd_soft_argmin_f32": (_i, [_c_float_p, _c_float_p, _i, _c_float_p, ctypes.c_float] + [_i] * 4 + [_c_float_p] * 3 + [ctypes.c_void_p]),
-    "mvd_vis_fuse_f32": (_i, [_pp, _pp] + [_i] * 6 + [_c_float_p, ctypes.c_void_p]),
-    "mvd_sweep_reduce_backward_workspace_bytes": (_sz, [_i] * 5),
-    "mvd_sweep_reduce_backward_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _i] + [ctypes.c_float] * 4 + [_i, _i, _pp] + [_i] * 6
-                                      + [_c_float_p, _pp, ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_sweep_warp_backward_f32": (_i, [_c_float_p, _pp, _pp, _c_float_p, _i, _pp] + [_i] * 8 + [_pp, ctypes.c_void_p]),
-    "mvd_resize_order1_f32": (_i, [_c_float_p, _c_float_p, ctypes.c_longlong, _i, _i, _i, _i, ctypes.c_void_p]),
-    "mvd_nchw_to_nhwc_f32": (_i, [_c_float_p, _c_float_p, _i, _i, ctypes.c_longlong, ctypes.c_void_p]),
-    "mvd_nhwc_to_nchw_f32": (_i, [_c_float_p, _c_float_p, _i, _i, ctypes.c_longlong, ctypes.c_void_p]),
-    "mvd_zero_border_nhwc_f32": (_i, [_c_float_p, _i, _i, _i, _i, ctypes.c_void_p]),
-    "mvd_depth_eval_workspace_bytes": (_sz, [_i, _i]),
-    "mvd_depth_align_stats_f32": (_i, [_c_float_p] * 3 + [ctypes.c_void_p] * 2 + [_i] * 6 + [_c_float_p, ctypes.c_void_p,
-                                                                                            ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_depth_score_f32": (_i, [_c_float_p] * 3 + [ctypes.c_void_p] * 2 + [_i] * 7 + [ctypes.c_float] * 4
-                            + [_c_float_p, ctypes.c_void_p] + [_c_float_p] * 4 + [ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_rank_keys_f32": (_i, [_c_float_p] * 4 + [_i, ctypes.c_longlong, _c_float_p, ctypes.c_void_p]),
-    "mvd_ranked_step_sums_f64": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _sz,
-                                      ctypes.c_void_p]),
-    "mvd_geo_consistency_f32": (_i, [_c_float_p, _pp, _c_float_p, _c_float_p, _i, _i, _i, ctypes.c_float, ctypes.c_float, _i,
-                                     ctypes.c_float] + [ctypes.c_void_p] * 5),
-    "mvd_compact_points_workspace_bytes": (_sz, [_i, _i]),
-    "mvd_compact_points_f32": (_i, [ctypes.c_void_p] + [_c_float_p] * 3 + [_i, _i, _c_float_p, _c_float_p, ctypes.c_void_p,
-                                                                          ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_compact_points_attr_f32": (_i, [ctypes.c_void_p] + [_c_float_p] * 4 + [_i, _i] + [_c_float_p] * 3
-                                    + [ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_depth_normals_f32": (_i, [_c_float_p, _c_float_p, _i, _i, _c_float_p, ctypes.c_void_p]),
-    "mvd_geo_merge_f32": (_i, [_c_float_p, _pp, _c_float_p, _c_float_p, _i, _i, _i, ctypes.c_float, ctypes.c_float, _i, ctypes.c_float,
-                               ctypes.c_void_p, _pp, _c_float_p, _pp, _c_float_p, _pp] + [ctypes.c_void_p] * 7),
-    "mvd_cloud_cell_keys_f32": (_i, [_c_float_p, ctypes.c_longlong] + [ctypes.c_double] * 4 + [ctypes.c_void_p] * 2),
-    "mvd_cloud_grid_build_f32": (_i, [_c_float_p, ctypes.c_void_p, ctypes.c_longlong, _c_float_p, ctypes.c_void_p]),
-    "mvd_cloud_nearest_f32": (_i, [_c_float_p, ctypes.c_longlong, _c_float_p, ctypes.c_void_p, ctypes.c_longlong]
-                              + [ctypes.c_double] * 4 + [ctypes.c_float, _c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "mvd_cloud_scores_workspace_bytes": (_sz, [ctypes.c_longlong]),
-    "mvd_cloud_scores_f32": (_i, [_c_float_p, ctypes.c_void_p, _c_float_p, ctypes.c_longlong, _c_float_p, _i, ctypes.c_void_p,
-                                  ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_voxel_reduce_workspace_bytes": (_sz, [ctypes.c_longlong]),
-    "mvd_voxel_reduce_f32": (_i, [ctypes.c_void_p] * 2 + [_c_float_p] * 2 + [ctypes.c_longlong, _c_float_p, _c_float_p]
-                             + [ctypes.c_void_p] * 3 + [_sz, ctypes.c_void_p]),
-    "mvd_cloud_transform_f32": (_i, [_c_float_p, _c_float_p, ctypes.c_longlong, ctypes.c_void_p, _c_float_p, _c_float_p, ctypes.c_void_p]),
-    "mvd_cloud_transform_records_f32": (_i, [_c_float_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, _c_float_p, ctypes.c_void_p]),
-    "mvd_cloud_pair_sums_workspace_bytes": (_sz, [ctypes.c_longlong]),
-    "mvd_cloud_pair_sums_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p,
-                                     ctypes.c_longlong] + [ctypes.c_double] * 3 + [ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_tsdf_integrate_f32": (_i, [_c_float_p] * 3 + [_i] * 3 + [_pp] * 3 + [_c_float_p, _i, _i, _i, ctypes.c_float, ctypes.c_float,
-                                                                            ctypes.c_void_p]),
-    "mvd_tsdf_extract_workspace_bytes": (_sz, [_i] * 3),
-    "mvd_tsdf_extract_f32": (_i, [_c_float_p] * 3 + [_i] * 3 + [ctypes.c_float] * 5 + [_i, _c_float_p, _c_float_p, ctypes.c_void_p,
-                                                                                      ctypes.c_longlong, ctypes.c_longlong,
-                                                                                      ctypes.c_void_p, ctypes.c_void_p, _sz,
-                                                                                      ctypes.c_void_p]),
-    "mvd_mesh_render_workspace_bytes": (_sz, [ctypes.c_longlong, ctypes.c_longlong, _i, _i, _i]),
-    "mvd_mesh_render_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, _c_float_p, _c_float_p, _i, _i, _i,
-                                 ctypes.c_float, _i, _i, _i, _c_float_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p,
-                                 ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_mesh_hook_round": (_i, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, _i] + [ctypes.c_void_p] * 4),
-    "mvd_mesh_component_rank_workspace_bytes": (_sz, [ctypes.c_longlong]),
-    "mvd_mesh_component_rank": (_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
-                                     ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_mesh_component_table": (_i, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_longlong] * 3 + [ctypes.c_void_p] * 3),
-    "mvd_mesh_component_sums_workspace_bytes": (_sz, [ctypes.c_longlong, ctypes.c_longlong]),
-    "mvd_mesh_component_sums_f64": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
-                                         ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _sz,
-                                         ctypes.c_void_p]),
-    "mvd_mesh_filter_workspace_bytes": (_sz, [ctypes.c_longlong, ctypes.c_longlong]),
-    "mvd_mesh_filter": (_i, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
-                             ctypes.c_longlong, _i, _i] + [ctypes.c_void_p] * 3 + [ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
-                                                                                   _sz, ctypes.c_void_p]),
-    "mvd_mesh_gather_rows_f32": (_i, [_c_float_p, ctypes.c_void_p, ctypes.c_longlong, _i, ctypes.c_longlong, _c_float_p,
-                                      ctypes.c_void_p]),
-    "mvd_mesh_vertex_normals_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
-                                         ctypes.c_void_p, _c_float_p, ctypes.c_void_p]),
-    "mvd_mesh_cluster_ids_workspace_bytes": (_sz, [ctypes.c_longlong]),
-    "mvd_mesh_cluster_ids": (_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong] + [ctypes.c_void_p] * 5 + [_sz, ctypes.c_void_p]),
-    "mvd_mesh_cluster_means_f64": (_i, [_c_float_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, _i,
-                                        ctypes.c_void_p, ctypes.c_void_p]),
-    "mvd_mesh_cluster_triples": (_i, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong]
-                                 + [ctypes.c_void_p] * 4),
-    "mvd_mesh_cluster_quadrics_workspace_bytes": (_sz, [ctypes.c_longlong]),
-    "mvd_mesh_cluster_quadrics_f64": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
-                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong] + [ctypes.c_double] * 4
-                                      + [ctypes.c_void_p, ctypes.c_void_p, _sz, ctypes.c_void_p]),
-    "mvd_mesh_cluster_place_f32": (_i, [ctypes.c_void_p] * 5 + [_c_float_p, ctypes.c_longlong, ctypes.c_longlong] + [ctypes.c_double] * 5
-                                   + [_c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "mvd_mesh_cluster_mark_first": (_i, [ctypes.c_void_p] * 3 + [ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p]),
-    "mvd_mesh_cell_counts_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong] + [ctypes.c_double] * 4
-                                 + [ctypes.c_void_p] * 2),
-    "mvd_mesh_pairs_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong]
-                           + [ctypes.c_double] * 4 + [ctypes.c_void_p] * 3),
-    "mvd_mesh_records_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
-                                  ctypes.c_longlong, _c_float_p, ctypes.c_void_p]),
-    "mvd_mesh_nearest_f32": (_i, [_c_float_p, ctypes.c_longlong, _c_float_p, ctypes.c_void_p, ctypes.c_longlong]
-                             + [ctypes.c_double] * 4 + [ctypes.c_float, _c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "mvd_mesh_sample_counts_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_double,
-                                        ctypes.c_void_p, ctypes.c_void_p]),
-    "mvd_mesh_sample_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, _c_float_p, _i, ctypes.c_void_p,
-                                 ctypes.c_longlong, ctypes.c_double, _c_float_p, ctypes.c_void_p, _c_float_p, ctypes.c_void_p]),
-}
-CULL_NONE, CULL_BACK, CULL_FRONT = 0, 1, 2  # MVD_CULL_*
-RENDER_LOAD_FIRST, RENDER_KEEP_PROJECT, RENDER_KEEP_KEYS, RENDER_NO_RESOLVE = 1, 16, 32, 64  # MVD_RENDER_*
+
+def _ctype(decl, fn, is_return=False):
+    """The ctypes class of one parameter (or return) declaration of `fn`.  A type outside the header's vocabulary raises: a
+    guessed type would be a wrong call into the GPU library."""
+    decl = " ".join(decl.replace("*", " * ").split())
+    if is_return:
+        if decl == "const char *":
+            return ctypes.c_char_p
+    elif re.fullmatch(r"[\w ]+ \* const \*( \w+)?", decl):  # a host array of device pointers
+        return _pp
+    elif "*" in decl:
+        return ctypes.c_void_p
+    for name, ctype in _SCALARS.items():
+        if re.fullmatch(name if is_return else rf"{name}( \w+)?", decl):
+            return ctype
+    raise RuntimeError(f"include/mvd.h: {fn}: no ctypes mapping for '{decl}'")
+
+
+def parse_header(text):
+    """(signatures, constants) of a C header in include/mvd.h's style: every `ret mvd_name(args);` as
+    name -> (restype, argtypes), and every `#define MVD_<NAME> <integer literal>` as NAME -> value."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {name: int(value, 0) for name, value in
+                 re.findall(r"^[ \t]*#[ \t]*define[ \t]+MVD_(\w+)[ \t]+(0[xX][0-9a-fA-F]+|\d+)[ \t]*$", text, flags=re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    signatures = {}
+    for ret, fn, args in re.findall(r"([\w \t*]+?)\b(mvd_\w+)\s*\(([^()]*)\)\s*;", text):
+        args = [] if args.strip() in ("", "void") else args.split(",")
+        signatures[fn] = (_ctype(ret, fn, True), [_ctype(a, fn) for a in args])
+    unparsed = sorted(set(re.findall(r"\b(mvd_\w+)\s*\(", text)) - set(signatures))
+    if unparsed:
+        raise RuntimeError(f"include/mvd.h: {unparsed[0]}: not a plain `ret name(args);` declaration")
+    return signatures, constants
+
+
+if not os.path.exists(HEADER_PATH):
+    raise RuntimeError(f"{HEADER_PATH} not found: the binding takes every signature and constant from it")
+with open(HEADER_PATH) as _f:
+    # name -> (restype, argtypes), and the header's MVD_<NAME> integers as module attributes <NAME>
+    SIGNATURES, _constants = parse_header(_f.read())
+globals().update(_constants)
+MVD_MAX_VIEWS, MVD_CLOUD_MAX_THRESHOLDS = _constants["MAX_VIEWS"], _constants["CLOUD_MAX_THRESHOLDS"]
+MVD_CLOUD_PAIR_SUMS_PER_WORKGROUP = _constants["CLOUD_PAIR_SUMS_PER_WORKGROUP"]
 MESH_RENDER_MAX_SMALL = 64  # ops.mesh_render's default threshold between the lane and the wave path (profiles/mesh_render.txt)
-MESH_ROUND_FIRST, MESH_ROUND_NO_HOOK, MESH_ROUND_NO_SHORTCUT = 1, 2, 4  # MVD_MESH_ROUND_*
-MVD_CLOUD_MAX_THRESHOLDS = 8
-MVD_CLOUD_PAIR_SUMS_PER_WORKGROUP = 2048  # the points one workgroup of mvd_cloud_pair_sums_f32 adds: its tests sit on the edges
 
 # built into the product library only (csrc/Makefile PRODSRCS): the experiments library has no variants of these
 PRODUCT_ONLY = ("mvd_sweep_reduce_backward_workspace_bytes", "mvd_sweep_reduce_backward_f32")

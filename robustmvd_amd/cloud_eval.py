@@ -36,20 +36,21 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .depth_fusion import DepthFusion, _is_tensor, _place, _to_numpy
+from .depth_fusion import DepthFusion
+from .mesh import is_tensor, one_place, place, to_numpy
 
 MAX_THRESHOLDS = 8
 INDEX_LIMIT = (1 << 21) - 1
 
 
-def _points(a, name):
-    p = np.asarray(_to_numpy(a), dtype=np.float32)
+def host_points(a, name):
+    p = np.asarray(to_numpy(a), dtype=np.float32)
     if p.ndim != 2 or p.shape[1] != 3:
         raise ValueError(f"{name} must be (n,3), got {p.shape}")
     return p
 
 
-def _thresholds(thresholds, max_dist):
+def check_thresholds(thresholds, max_dist):
     """-> (thresholds (T,) float32, max_dist float32), validated; max_dist None = 4 x the largest threshold."""
     th = np.atleast_1d(np.asarray(thresholds, dtype=np.float32))
     if th.ndim != 1 or not 1 <= len(th) <= MAX_THRESHOLDS:
@@ -69,7 +70,7 @@ def nearest_numpy(query, target, max_dist, dtype=np.float64):
     (differences, (dx^2 + dy^2) + dz^2, sqrt) in float32: the gap between the two is what tests/test_hip_cloud_eval.py derives its
     band from.  max_dist=np.inf gives the untruncated distance (inf without a valid target)."""
     ft = np.dtype(dtype).type
-    q, p = _points(query, "query").astype(ft), _points(target, "target").astype(ft)
+    q, p = host_points(query, "query").astype(ft), host_points(target, "target").astype(ft)
     md = ft(np.float32(max_dist))
     if not md > 0:
         raise ValueError(f"max_dist must be > 0, got {max_dist}")
@@ -118,7 +119,7 @@ class CloudScore:
     registration: object = None
 
 
-def _combine(sum_p, n_p, cnt_p, sum_g, n_g, cnt_g, **fields):
+def combine_scores(sum_p, n_p, cnt_p, sum_g, n_g, cnt_g, **fields):
     """Definition 2 from the two directions' float64 sums, valid counts and per-threshold counts."""
     with np.errstate(all="ignore"):
         acc = np.float64(sum_p) / np.float64(n_p)
@@ -139,18 +140,18 @@ def _direction_numpy(q, p, th, md, ft):
 def cloud_scores_numpy(pred, gt, thresholds, max_dist, dtype=np.float64):
     """Definition 2 -> CloudScore, with the distances of nearest_numpy(dtype=dtype) (dist_pred / dist_gt are returned in float32)."""
     ft = np.dtype(dtype).type
-    th, md = _thresholds(thresholds, max_dist)
-    pred, gt = _points(pred, "pred"), _points(gt, "gt")
+    th, md = check_thresholds(thresholds, max_dist)
+    pred, gt = host_points(pred, "pred"), host_points(gt, "gt")
     dp, sp, np_, cp = _direction_numpy(pred, gt, th, md, ft)
     dg, sg, ng, cg = _direction_numpy(gt, pred, th, md, ft)
-    return _combine(sp, np_, cp, sg, ng, cg, dist_pred=dp.astype(np.float32), dist_gt=dg.astype(np.float32), thresholds=th,
+    return combine_scores(sp, np_, cp, sg, ng, cg, dist_pred=dp.astype(np.float32), dist_gt=dg.astype(np.float32), thresholds=th,
                     max_dist=float(md), pred_points=pred)
 
 
 def voxel_keys_numpy(points, voxel, origin=None):
     """Definition 3's keys -> (keys (n,) int64 with INT64_MAX for invalid points, origin (3,) float64).  ValueError when an index
     leaves [0, 2^21 - 1)."""
-    p = _points(points, "points")
+    p = host_points(points, "points")
     voxel = np.float32(voxel)
     if not (voxel > 0 and np.isfinite(voxel)):
         raise ValueError(f"voxel must be finite and > 0, got {voxel}")
@@ -175,10 +176,10 @@ def voxel_keys_numpy(points, voxel, origin=None):
 
 def voxel_downsample_numpy(points, voxel, colors=None, origin=None):
     """Definition 3 -> (xyz (k,3) float32, rgb (k,3) float32 or None, counts (k,) int32), voxels in ascending key order."""
-    p = _points(points, "points")
+    p = host_points(points, "points")
     col = None
     if colors is not None:
-        col = np.asarray(_to_numpy(colors), dtype=np.float32)
+        col = np.asarray(to_numpy(colors), dtype=np.float32)
         if col.shape != p.shape:
             raise ValueError(f"colors: shape {col.shape}, expected {p.shape}")
     keys, _ = voxel_keys_numpy(p, voxel, origin)
@@ -206,16 +207,16 @@ class PointCloudEvaluation:
     here or per call) and the ALIGNED prediction is scored; the score's `registration` tells how it went."""
 
     def __init__(self, thresholds, max_dist=None, voxel=None, align=None, align_max_dist=None, gt_normals=None):
-        self.thresholds, self.max_dist = _thresholds(thresholds, max_dist)
+        self.thresholds, self.max_dist = check_thresholds(thresholds, max_dist)
         if voxel is not None and not (np.float32(voxel) > 0 and np.isfinite(np.float32(voxel))):
             raise ValueError(f"voxel must be finite and > 0, got {voxel}")
         self.voxel = None if voxel is None else float(np.float32(voxel))
         self.align, self.align_max_dist, self.gt_normals = align, None, gt_normals
         if align is not None:
-            from .cloud_register import MODES, _radii
+            from .cloud_register import MODES, check_radii
             if align not in MODES:
                 raise ValueError(f"align must be None or one of {MODES}, got {align!r}")
-            self.align_max_dist = _radii([4.0 * self.max_dist, 2.0 * self.max_dist, self.max_dist] if align_max_dist is None
+            self.align_max_dist = check_radii([4.0 * self.max_dist, 2.0 * self.max_dist, self.max_dist] if align_max_dist is None
                                          else align_max_dist)
         elif align_max_dist is not None or gt_normals is not None:
             raise ValueError("align_max_dist and gt_normals belong to align=...")
@@ -230,12 +231,12 @@ class PointCloudEvaluation:
         normals = self.gt_normals if gt_normals is None else gt_normals
         if self.align == "plane" and normals is None:
             raise ValueError("align='plane' needs gt_normals")
-        if normals is not None and _place(normals) != _place(gt):
-            if _place(gt) == "host":
-                normals = _to_numpy(normals)
+        if normals is not None and place(normals) != place(gt):
+            if place(gt) == "host":
+                normals = to_numpy(normals)
             else:
                 import torch
-                normals = torch.as_tensor(_to_numpy(normals), dtype=torch.float32).to(gt.device)
+                normals = torch.as_tensor(to_numpy(normals), dtype=torch.float32).to(gt.device)
         reg = register_clouds(pred, gt, self.align_max_dist, mode=self.align, target_normals=normals if self.align == "plane" else None)
         return reg.apply(pred), reg
 
@@ -243,13 +244,11 @@ class PointCloudEvaluation:
         """pred_points (n,3), gt_points (m,3), pred_colors (n,3) or None: numpy arrays or torch tensors.  Clouds on the GPU run the HIP
         kernels and the result's dist_pred / dist_gt / pred_points are GPU tensors; clouds on the host run the numpy specification.
         Both clouds must be in the same place: a mixed pair raises instead of being moved silently (colours follow the points)."""
-        places = {_place(pred_points), _place(gt_points)}
-        if len(places) != 1:
-            raise ValueError(f"the predicted and the ground-truth cloud are in different places ({sorted(places)}): move them to one first")
-        return (self._run_host if places == {"host"} else self._run_device)(pred_points, gt_points, pred_colors, gt_normals)
+        host = one_place(pred_points, gt_points, what="predicted and the ground-truth cloud") == "host"
+        return (self._run_host if host else self._run_device)(pred_points, gt_points, pred_colors, gt_normals)
 
     def _run_host(self, pred, gt, colors, gt_normals=None):
-        pred, gt = _points(pred, "pred_points"), _points(gt, "gt_points")
+        pred, gt = host_points(pred, "pred_points"), host_points(gt, "gt_points")
         if self.voxel is not None:
             pred, colors, _ = voxel_downsample_numpy(pred, self.voxel, colors)
         pred, reg = self._register(pred, gt, gt_normals)
@@ -265,15 +264,15 @@ class PointCloudEvaluation:
             if a.dim() != 2 or a.shape[1] != 3:
                 raise ValueError(f"{name} must be (n,3), got {tuple(a.shape)}")
         if colors is not None:
-            colors = colors.to(dev) if _is_tensor(colors) else torch.from_numpy(np.ascontiguousarray(colors, dtype=np.float32)).to(dev)
+            colors = colors.to(dev) if is_tensor(colors) else torch.from_numpy(np.ascontiguousarray(colors, dtype=np.float32)).to(dev)
         if self.voxel is not None:
             pred, colors, _ = ops.voxel_downsample(pred, self.voxel, colors)
-        pred, gt = ops._cloud_points(pred, "pred_points"), ops._cloud_points(gt, "gt_points", dev)
+        pred, gt = ops.cloud_points(pred, "pred_points"), ops.cloud_points(gt, "gt_points", dev)
         pred, reg = self._register(pred, gt, gt_normals)
         md, T = float(self.max_dist), len(self.thresholds)
         cell = md * ops.CLOUD_CELL_MARGIN
         # one grid for both clouds: each is sorted once and serves as the queries of one direction and the targets of the other
-        extents = [e for e in (ops._cloud_extent(pred), ops._cloud_extent(gt)) if e is not None]
+        extents = [e for e in (ops.cloud_extent(pred), ops.cloud_extent(gt)) if e is not None]
         origin = np.min([e[0] for e in extents], axis=0).tolist() if extents else [0.0, 0.0, 0.0]
         gp, gg = ops.cloud_grid(pred, origin, cell), ops.cloud_grid(gt, origin, cell)
         th = torch.from_numpy(self.thresholds).to(dev)
@@ -285,7 +284,7 @@ class PointCloudEvaluation:
         blocks = blocks.cpu()  # the one read of the evaluation
         sp, np_, cp = ops.cloud_scores_read(blocks[0], T)
         sg, ng, cg = ops.cloud_scores_read(blocks[1], T)
-        return _combine(sp, np_, cp, sg, ng, cg, dist_pred=dp, dist_gt=dg, thresholds=self.thresholds, max_dist=md, pred_points=pred,
+        return combine_scores(sp, np_, cp, sg, ng, cg, dist_pred=dp, dist_gt=dg, thresholds=self.thresholds, max_dist=md, pred_points=pred,
                         pred_colors=colors, registration=reg)
 
 
@@ -304,13 +303,13 @@ def evaluate_scene(model, images, intrinsics, poses, gt_points, fusion=None, num
     elif evaluation_args:
         raise ValueError(f"evaluation is given: unexpected {sorted(evaluation_args)}")
     fusion = DepthFusion() if fusion is None else fusion
-    device = gt_points.device if _place(gt_points) != "host" else None
+    device = gt_points.device if place(gt_points) != "host" else None
     out = fusion.reconstruct(model, images, intrinsics, poses, num_sources=num_sources, device=device)
-    if _place(out.points) == "host":
-        gt_points = _to_numpy(gt_points)
-    elif _place(gt_points) != _place(out.points):
+    if place(out.points) == "host":
+        gt_points = to_numpy(gt_points)
+    elif place(gt_points) != place(out.points):
         import torch
-        gt_points = torch.as_tensor(_to_numpy(gt_points), dtype=torch.float32).to(out.points.device)
+        gt_points = torch.as_tensor(to_numpy(gt_points), dtype=torch.float32).to(out.points.device)
     return evaluation(out.points, gt_points, out.colors, gt_normals=gt_normals)
 
 

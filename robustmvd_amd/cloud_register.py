@@ -52,8 +52,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .cloud_eval import _points, nearest_numpy
-from .depth_fusion import _is_tensor, _place, _to_numpy
+from .cloud_eval import host_points, nearest_numpy
+from .mesh import is_tensor, one_place, place, to_numpy
 
 MODES = ("rigid", "similarity", "plane")
 POINT_SUMS, PLANE_SUMS = 18, 28
@@ -61,9 +61,9 @@ MIN_PAIRS = {"rigid": 3, "similarity": 3, "plane": 6}
 EIGEN_CUT = 1e-9
 
 
-def _affine(transform):
+def affine_parts(transform):
     """(4,4) or (3,4) -> (M (3,3), t (3,)) float64, finite; a (4,4) must end in the row 0 0 0 1."""
-    T = np.asarray(_to_numpy(transform), dtype=np.float64)
+    T = np.asarray(to_numpy(transform), dtype=np.float64)
     if T.shape == (4, 4):
         if not np.array_equal(T[3], [0.0, 0.0, 0.0, 1.0]):
             raise ValueError(f"transform: the last row must be 0 0 0 1, got {T[3].tolist()}")
@@ -81,7 +81,7 @@ def _matrix(M, t):
 
 
 def _normals(a, n, name="normals"):
-    v = np.asarray(_to_numpy(a), dtype=np.float32)
+    v = np.asarray(to_numpy(a), dtype=np.float32)
     if v.shape != (n, 3):
         raise ValueError(f"{name}: shape {v.shape}, expected {(n, 3)}")
     return v
@@ -98,8 +98,8 @@ def _through(M, x, t=None):
 
 def transform_numpy(points, transform, normals=None):
     """Definition 1 -> q (n,3) float32, or (q, normals (n,3) float32) when normals are given."""
-    p = _points(points, "points")
-    M, t = _affine(transform)
+    p = host_points(points, "points")
+    M, t = affine_parts(transform)
     with np.errstate(all="ignore"):
         q = _through(M, p.astype(np.float64), t).astype(np.float32)
         bad = ~(np.isfinite(p).all(axis=1) & np.isfinite(q).all(axis=1))
@@ -117,8 +117,8 @@ def transform_numpy(points, transform, normals=None):
 
 def pair_terms_numpy(source, transform, index, target, pivot, target_normals=None):
     """Definition 3's terms, one row per pair in the source's order -> (N, 18) or (N, 28) float64 (plane mode: with target_normals)."""
-    s, p = _points(source, "source"), _points(target, "target")
-    j = np.asarray(_to_numpy(index)).astype(np.int64).reshape(-1)
+    s, p = host_points(source, "source"), host_points(target, "target")
+    j = np.asarray(to_numpy(index)).astype(np.int64).reshape(-1)
     if j.shape != (len(s),):
         raise ValueError(f"index: shape {j.shape}, expected {(len(s),)}")
     c = np.asarray(pivot, dtype=np.float64).reshape(-1)
@@ -218,13 +218,13 @@ class Registration:
 
     def apply(self, points, normals=None):
         """points (n,3) (and normals) through the transform: numpy arrays by transform_numpy, GPU tensors by ops.cloud_transform."""
-        if _place(points) == "host":
+        if place(points) == "host":
             return transform_numpy(points, self.transform, normals)
         from . import ops
         return ops.cloud_transform(points, self.transform, normals)
 
 
-def _radii(max_dist):
+def check_radii(max_dist):
     r = np.atleast_1d(np.asarray(max_dist, dtype=np.float32))
     if r.ndim != 1 or len(r) == 0 or not (np.isfinite(r).all() and (r > 0).all()):
         raise ValueError(f"max_dist must be one or more finite radii > 0, got {max_dist}")
@@ -292,10 +292,10 @@ def _check_mode(mode, target_normals):
 def register_numpy(source, target, max_dist, mode="rigid", init=None, target_normals=None, iterations=50, tol=None):
     """The definition on host arrays -> Registration; the pairs are nearest_numpy's in float64."""
     _check_mode(mode, target_normals)
-    s, p = _points(source, "source"), _points(target, "target")
+    s, p = host_points(source, "source"), host_points(target, "target")
     nrm = _normals(target_normals, len(p), "target_normals") if mode == "plane" else None
-    radii = _radii(max_dist)
-    M0, t0 = _affine(np.eye(4) if init is None else init)
+    radii = check_radii(max_dist)
+    M0, t0 = affine_parts(np.eye(4) if init is None else init)
 
     def pair_sums(M, t, radius, pivot):
         T = _matrix(M, t)
@@ -314,23 +314,23 @@ def _register_device(source, target, max_dist, mode, init, target_normals, itera
     import torch
     from . import ops
     _check_mode(mode, target_normals)
-    s = ops._cloud_points(source, "source")
+    s = ops.cloud_points(source, "source")
     dev = s.device
-    p = ops._cloud_points(target, "target", dev)
+    p = ops.cloud_points(target, "target", dev)
     nrm = None
     if mode == "plane":
-        nrm = target_normals if _is_tensor(target_normals) else torch.from_numpy(np.ascontiguousarray(target_normals, dtype=np.float32)).to(dev)
+        nrm = target_normals if is_tensor(target_normals) else torch.from_numpy(np.ascontiguousarray(target_normals, dtype=np.float32)).to(dev)
         nrm = ops.L.as_f32(nrm, "target_normals", (p.shape[0], 3), dev)
-    radii = _radii(max_dist)
-    M0, t0 = _affine(np.eye(4) if init is None else init)
-    source_box, target_box = ops._cloud_extent(s), ops._cloud_extent(p)
+    radii = check_radii(max_dist)
+    M0, t0 = affine_parts(np.eye(4) if init is None else init)
+    source_box, target_box = ops.cloud_extent(s), ops.cloud_extent(p)
     origin = [0.0, 0.0, 0.0] if target_box is None else target_box[0].tolist()
     grid = ops.cloud_grid(p, origin, radii[0] * ops.CLOUD_CELL_MARGIN)
     state = {}
 
     def sort(M, t):
         moved = ops.cloud_transform(s, _matrix(M, t))
-        state["perm"] = ops._cloud_sorted(moved, grid.origin, grid.inv)[1]
+        state["perm"] = ops.cloud_sorted(moved, grid.origin, grid.inv)[1]
 
     def pair_sums(M, t, radius, pivot):
         T = _matrix(M, t)
@@ -357,10 +357,7 @@ def register_clouds(source, target, max_dist, mode="rigid", init=None, target_no
     for name, a in (("source", source), ("target", target)):
         if len(getattr(a, "shape", ())) == 2 and a.shape[0] >= 2 ** 31:  # before anything is copied or made contiguous
             raise ValueError(f"{name}: {a.shape[0]} points, supported below 2^31")
-    places = {_place(source), _place(target)}
-    if len(places) != 1:
-        raise ValueError(f"the source and the target cloud are in different places ({sorted(places)}): move them to one first")
-    if places == {"host"}:
+    if one_place(source, target, what="source and the target cloud") == "host":
         return register_numpy(source, target, max_dist, mode, init, target_normals, iterations, tol)
     return _register_device(source, target, max_dist, mode, init, target_normals, iterations, tol)
 

@@ -45,6 +45,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from .mesh import is_tensor, one_place, to_numpy
+
 MAX_SOURCES = 32
 
 
@@ -56,7 +58,7 @@ def _inv_pose(T):
     return out
 
 
-def _pinhole(K, name):
+def pinhole(K, name):
     K = np.asarray(K, dtype=np.float64)
     if K.shape != (3, 3) or K[1, 0] != 0 or K[2, 0] != 0 or K[2, 1] != 0 or K[2, 2] != 1 or K[0, 0] == 0 or K[1, 1] == 0:
         raise ValueError(f"{name}: expected pinhole intrinsics [[fx, s, cx], [0, fy, cy], [0, 0, 1]], got {K.tolist()}")
@@ -87,10 +89,10 @@ def _project_into(Ka, Ta, Kb, Tb):
 
 def compose_matrices(key_K, key_T, src_Ks, src_Ts):
     """-> (V,24) float64: per source A (9, row-major), b (3), A' (9), b' (3).  The device takes them rounded to float32."""
-    Kk, Tk = _pinhole(key_K, "key intrinsics"), np.asarray(key_T, dtype=np.float64)
+    Kk, Tk = pinhole(key_K, "key intrinsics"), np.asarray(key_T, dtype=np.float64)
     rows = []
     for i, (Ks, Ts) in enumerate(zip(src_Ks, src_Ts)):
-        Ks, Ts = _pinhole(Ks, f"source intrinsics {i}"), np.asarray(Ts, dtype=np.float64)
+        Ks, Ts = pinhole(Ks, f"source intrinsics {i}"), np.asarray(Ts, dtype=np.float64)
         A, b = _project_into(Ks, Ts, Kk, Tk)
         A2, b2 = _project_into(Kk, Tk, Ks, Ts)
         rows.append(np.concatenate([A.ravel(), b, A2.ravel(), b2]))
@@ -100,7 +102,7 @@ def compose_matrices(key_K, key_T, src_Ks, src_Ts):
 def compose_backprojection(key_K, key_T):
     """-> 12 float64: B = Rk^T Kk^-1 (9, row-major) and c = -Rk^T tk, so that X = depth * B (x,y,1) + c."""
     Tk_inv = _inv_pose(np.asarray(key_T, dtype=np.float64))
-    return np.concatenate([(Tk_inv[:3, :3] @ _pinhole_inv(_pinhole(key_K, "key intrinsics"))).ravel(), Tk_inv[:3, 3]])
+    return np.concatenate([(Tk_inv[:3, :3] @ _pinhole_inv(pinhole(key_K, "key intrinsics"))).ravel(), Tk_inv[:3, 3]])
 
 
 def _check_views(depth, src_depths):
@@ -282,15 +284,15 @@ def write_ply(path, points, colors=None, normals=None, faces=None):
     """Binary little-endian PLY: float32 x y z, with normals float32 nx ny nz, and with colors uchar red green blue.  colors: (M,3)
     in 0..255 (rounded and clipped).  faces: (T,3) vertex indices (a Mesh's triangles), written as `element face` with
     `property list uchar int vertex_indices`."""
-    pts = np.asarray(_to_numpy(points), dtype="<f4").reshape(-1, 3)
+    pts = np.asarray(to_numpy(points), dtype="<f4").reshape(-1, 3)
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     if normals is not None:
-        nrm = np.asarray(_to_numpy(normals), dtype="<f4").reshape(-1, 3)
+        nrm = np.asarray(to_numpy(normals), dtype="<f4").reshape(-1, 3)
         if len(nrm) != len(pts):
             raise ValueError(f"{len(nrm)} normals for {len(pts)} points")
         fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
     if colors is not None:
-        col = np.clip(np.rint(np.asarray(_to_numpy(colors), dtype=np.float64).reshape(-1, 3)), 0, 255).astype(np.uint8)
+        col = np.clip(np.rint(np.asarray(to_numpy(colors), dtype=np.float64).reshape(-1, 3)), 0, 255).astype(np.uint8)
         if len(col) != len(pts):
             raise ValueError(f"{len(col)} colours for {len(pts)} points")
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
@@ -307,7 +309,7 @@ def write_ply(path, points, colors=None, normals=None, faces=None):
     if colors is not None:
         header += ["property uchar red", "property uchar green", "property uchar blue"]
     if faces is not None:
-        tri = np.asarray(_to_numpy(faces)).reshape(-1, 3)
+        tri = np.asarray(to_numpy(faces)).reshape(-1, 3)
         if len(tri) and (tri.min() < 0 or tri.max() >= len(pts)):
             raise ValueError(f"faces index outside the {len(pts)} points")
         frec = np.empty(len(tri), dtype=[("n", "u1"), ("v", "<i4", (3,))])
@@ -321,19 +323,7 @@ def write_ply(path, points, colors=None, normals=None, faces=None):
             f.write(frec.tobytes())
 
 
-def _is_tensor(a):
-    return type(a).__module__.split(".")[0] == "torch"
-
-
-def _place(a):
-    return str(a.device) if _is_tensor(a) and a.is_cuda else "host"
-
-
-def _to_numpy(a):
-    return a.detach().cpu().numpy() if _is_tensor(a) else np.asarray(a)
-
-
-def _map2d(a, name):
+def map2d(a, name):
     """One (H,W) map from (H,W), (1,H,W) or (1,1,H,W), numpy or torch."""
     if a.ndim < 2 or int(np.prod(a.shape[:-2])) != 1:
         raise ValueError(f"{name}: expected one (H,W) map, got {tuple(a.shape)}")
@@ -403,20 +393,18 @@ class DepthFusion:
                 raise ValueError(f"view {i}: source index out of range in {s}")
             if self.merge and i in s:
                 raise ValueError(f"view {i} is among its own sources {s}: merge mode cannot claim pixels of the view it is emitting")
-        Ks = [_to_numpy(K).astype(np.float64).reshape(3, 3) for K in intrinsics]
-        Ts = [_to_numpy(T).astype(np.float64).reshape(4, 4) for T in poses]
-        places = {_place(m) for m in list(depths) + list(uncertainties or [])}
-        if len(places) != 1:
-            raise ValueError(f"depth and uncertainty maps are in different places ({sorted(places)}): move them to one first")
-        run = self._run_host if places == {"host"} else self._run_device
-        return run([_map2d(d, f"depths[{i}]") for i, d in enumerate(depths)], Ks, Ts,
-                   None if uncertainties is None else [_map2d(u, f"uncertainties[{i}]") for i, u in enumerate(uncertainties)],
+        Ks = [to_numpy(K).astype(np.float64).reshape(3, 3) for K in intrinsics]
+        Ts = [to_numpy(T).astype(np.float64).reshape(4, 4) for T in poses]
+        host = one_place(*depths, *(uncertainties or []), what="depth and uncertainty maps") == "host"
+        run = self._run_host if host else self._run_device
+        return run([map2d(d, f"depths[{i}]") for i, d in enumerate(depths)], Ks, Ts,
+                   None if uncertainties is None else [map2d(u, f"uncertainties[{i}]") for i, u in enumerate(uncertainties)],
                    images, sources)
 
     def _run_host(self, depths, Ks, Ts, uncs, images, sources):
-        depths = [_to_numpy(d) for d in depths]
-        uncs = None if uncs is None else [_to_numpy(u) for u in uncs]
-        images = None if images is None else [_to_numpy(im) for im in images]
+        depths = [to_numpy(d) for d in depths]
+        uncs = None if uncs is None else [to_numpy(u) for u in uncs]
+        images = None if images is None else [to_numpy(im) for im in images]
         for i, im in enumerate(images or []):
             if im.shape != (3,) + depths[i].shape:
                 raise ValueError(f"images[{i}]: shape {im.shape}, expected {(3,) + depths[i].shape}")
@@ -453,7 +441,7 @@ class DepthFusion:
         from . import ops
         dev = depths[0].device
         N = len(depths)
-        up = lambda a: a.to(dev) if _is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        up = lambda a: a.to(dev) if is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         depths = [up(d) for d in depths]
         uncs = None if uncs is None or self.max_uncertainty is None else [up(u) for u in uncs]
         images = None if images is None else [up(im) for im in images]
@@ -516,8 +504,8 @@ class DepthFusion:
         N = len(images)
         if not (len(intrinsics) == len(poses) == N) or N < 2:
             raise ValueError(f"{N} images, {len(intrinsics)} intrinsics, {len(poses)} poses; at least 2 views are needed")
-        Ks = [_to_numpy(K).astype(np.float64).reshape(3, 3) for K in intrinsics]
-        Ts = [_to_numpy(T).astype(np.float64).reshape(4, 4) for T in poses]
+        Ks = [to_numpy(K).astype(np.float64).reshape(3, 3) for K in intrinsics]
+        Ts = [to_numpy(T).astype(np.float64).reshape(4, 4) for T in poses]
         depths, uncs, Ks_pred, colours = [], [], [], []
         for k in range(N):
             others = sorted((j for j in range(N) if j != k), key=lambda j: (abs(j - k), j))
@@ -526,11 +514,11 @@ class DepthFusion:
             pred, aux = model.run(images=[images[j] for j in order], keyview_idx=0,
                                   poses=[(Ts[j] @ Tk_inv).astype(np.float32) for j in order],
                                   intrinsics=[Ks[j].astype(np.float32) for j in order])
-            depth = _map2d(pred["depth"], "pred['depth']")
+            depth = map2d(pred["depth"], "pred['depth']")
             depths.append(depth)
             unc = (aux or {}).get("depth_uncertainty")
-            uncs.append(None if unc is None else _map2d(unc, "aux['depth_uncertainty']"))
-            img = _to_numpy(images[k]).astype(np.float32)
+            uncs.append(None if unc is None else map2d(unc, "aux['depth_uncertainty']"))
+            img = to_numpy(images[k]).astype(np.float32)
             img = img.reshape(img.shape[-3:])
             (hp, wp), (hi, wi) = depth.shape, img.shape[-2:]
             K = Ks[k].copy()
@@ -543,7 +531,7 @@ class DepthFusion:
         if device is not None:
             import torch
             device = torch.device(device)
-            move = ((lambda a: torch.as_tensor(a).to(device)) if device.type == "cuda" else _to_numpy)
+            move = ((lambda a: torch.as_tensor(a).to(device)) if device.type == "cuda" else to_numpy)
             depths = [move(d) for d in depths]
             uncs = None if uncs is None else [move(u) for u in uncs]
         return self(depths, Ks_pred, Ts, uncs, colours, **fusion_inputs)

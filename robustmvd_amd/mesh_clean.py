@@ -35,8 +35,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .depth_fusion import _is_tensor, _place, _to_numpy
-from .render import check_index_range
+from .mesh import Mesh, check_mesh, check_triangles, int32_triangles, is_mesh, one_place, split_mesh, to_numpy
 
 
 def max_rounds(M):
@@ -71,60 +70,6 @@ class CleanResult:
 
 
 # ---- argument checks -----------------------------------------------------------------------------------------------------------------
-def _split(mesh, triangles):
-    if hasattr(mesh, "vertices") and hasattr(mesh, "triangles"):
-        if triangles is not None:
-            raise ValueError("a Mesh brings its own triangles")
-        return mesh.vertices, mesh.triangles
-    if isinstance(mesh, (tuple, list)) and len(mesh) == 2 and triangles is None:
-        mesh, triangles = mesh
-    if triangles is None:
-        raise ValueError("expected a Mesh, (vertices, triangles) or vertices with triangles=")
-    return mesh, triangles
-
-
-def _dtype_name(a):
-    return str(a.dtype).replace("torch.", "")
-
-
-def _check_arrays(vertices, triangles, extra=()):
-    """-> (place, M, T).  vertices (M,3) float32, triangles (T,3) of an integer dtype, every array in one place."""
-    for name, a in (("vertices", vertices), ("triangles", triangles)) + tuple(extra):
-        if not (_is_tensor(a) or isinstance(a, np.ndarray)):
-            raise ValueError(f"{name}: expected a numpy array or a torch tensor, got {type(a).__name__}")
-    places = {_place(a) for a in (vertices, triangles) + tuple(a for _, a in extra)}
-    if len(places) != 1:
-        raise ValueError(f"the mesh arrays are in different places ({sorted(places)})")
-    if vertices.ndim != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"vertices must be (M,3), got {tuple(vertices.shape)}")
-    if _dtype_name(vertices) != "float32":
-        raise ValueError(f"vertices: dtype {_dtype_name(vertices)}, expected float32")
-    M = int(vertices.shape[0])
-    T = _check_triangles(triangles, M)
-    for name, a in extra:
-        if a.ndim != 2 or a.shape[0] != M or a.shape[1] < 1 or _dtype_name(a) != "float32":
-            raise ValueError(f"{name}: expected ({M},k) float32, got {tuple(a.shape)} {_dtype_name(a)}")
-    return places.pop(), M, T
-
-
-def _check_triangles(triangles, M):
-    if triangles.ndim != 2 or triangles.shape[1] != 3:
-        raise ValueError(f"triangles must be (T,3), got {tuple(triangles.shape)}")
-    if _dtype_name(triangles) not in ("int32", "int64", "int16", "uint8", "int8", "uint16", "uint32", "uint64"):
-        raise ValueError(f"triangles: dtype {_dtype_name(triangles)}, expected an integer dtype (int32)")
-    T = int(triangles.shape[0])
-    if T >= 2 ** 31 or M >= 2 ** 31 or M < 0:
-        raise ValueError(f"{M} vertices and {T} triangles: both must be below 2^31")
-    if T:
-        if _is_tensor(triangles):
-            import torch
-            lo, hi = torch.aminmax(triangles)
-        else:
-            lo, hi = triangles.min(), triangles.max()
-        check_index_range(int(lo), int(hi), M)
-    return T
-
-
 def _check_criteria(min_triangles, min_area, keep_largest):
     if min_triangles is not None and (int(min_triangles) != min_triangles or min_triangles < 0):
         raise ValueError(f"min_triangles must be a non-negative integer, got {min_triangles}")
@@ -141,8 +86,8 @@ def components_numpy(triangles, M, details=False):
     synchronous form of the rounds: every hook of a round reads the labels the round started with, the shortcut reads the hooked
     ones.  details=True -> (label, referenced (M) bool, rounds)."""
     M = int(M)
-    tri = np.asarray(_to_numpy(triangles))
-    T = _check_triangles(tri, M)
+    tri = np.asarray(to_numpy(triangles))
+    T = check_triangles(tri, M)
     tri = tri.astype(np.int64)
     label = np.arange(M, dtype=np.int64)
     referenced = np.zeros(M, dtype=bool)
@@ -192,8 +137,8 @@ def triangle_areas_numpy(vertices, triangles):
 
 def component_table_numpy(vertices, triangles):
     """Steps 1 to 3 -> MeshComponents of numpy arrays."""
-    vertices, tri = np.asarray(_to_numpy(vertices)), np.asarray(_to_numpy(triangles))
-    _, M, T = _check_arrays(vertices, tri)
+    vertices, tri = np.asarray(to_numpy(vertices)), np.asarray(to_numpy(triangles))
+    M, T = check_mesh(vertices, tri)
     label, referenced, rounds = components_numpy(tri, M, details=True)
     roots = np.nonzero(referenced & (label == np.arange(M)))[0]  # ascending: the ids
     C = len(roots)
@@ -226,9 +171,9 @@ def keep_components(num_triangles, area, min_triangles=None, min_area=None, keep
 def clean_numpy(vertices, triangles, min_triangles=None, min_area=None, keep_largest=None, remove_unreferenced=True, attributes=()):
     """Step 4 -> (vertices (M',3) float32, triangles (T',3) int32, the attributes' kept rows (list), vertex_remap (M) int32,
     kept_triangles (T') int32)."""
-    vertices, tri = np.asarray(_to_numpy(vertices)), np.asarray(_to_numpy(triangles))
-    attributes = [np.asarray(_to_numpy(a)) for a in attributes]
-    _, M, T = _check_arrays(vertices, tri, tuple((f"attributes[{i}]", a) for i, a in enumerate(attributes)))
+    vertices, tri = np.asarray(to_numpy(vertices)), np.asarray(to_numpy(triangles))
+    attributes = [np.asarray(to_numpy(a)) for a in attributes]
+    M, T = check_mesh(vertices, tri, tuple((f"attributes[{i}]", a) for i, a in enumerate(attributes)))
     keep_t = np.ones(T, dtype=bool)
     if _check_criteria(min_triangles, min_area, keep_largest):
         table = component_table_numpy(vertices, tri)
@@ -244,8 +189,8 @@ def clean_numpy(vertices, triangles, min_triangles=None, min_area=None, keep_lar
 
 def vertex_normals_numpy(vertices, triangles):
     """Step 5 in float64 -> (M,3) float64 (the public form rounds to float32)."""
-    vertices, tri = np.asarray(_to_numpy(vertices)), np.asarray(_to_numpy(triangles))
-    _, M, T = _check_arrays(vertices, tri)
+    vertices, tri = np.asarray(to_numpy(vertices)), np.asarray(to_numpy(triangles))
+    M, T = check_mesh(vertices, tri)
     n = cross_numpy(vertices, tri)
     corner = tri.astype(np.int64).ravel()  # corner 3 t + k names vertex triangles[t][k]: ascending (t, k)
     # bincount adds in the order of the list: per vertex in ascending (triangle, corner)
@@ -257,11 +202,6 @@ def vertex_normals_numpy(vertices, triangles):
 
 
 # ---- the device path ---------------------------------------------------------------------------------------------------------------------
-def _device_triangles(triangles):
-    import torch
-    return triangles.to(torch.int32).contiguous()
-
-
 def _labels_device(tri, M):
     """The host-driven rounds -> (label, referenced, rounds).  The changed word is read after every round (one 4-byte copy): reading
     it every second round instead was not worth an extra round (profiles/mesh_clean.txt)."""
@@ -296,11 +236,12 @@ def _components_device(vertices, tri):
 def mesh_components(mesh, triangles=None):
     """-> MeshComponents (steps 1 to 3).  mesh: a Mesh, a pair (vertices, triangles), or the vertices with triangles=.  Arrays on the
     host run the numpy forms; GPU tensors run the kernels and give GPU tensors."""
-    vertices, triangles = _split(mesh, triangles)
-    place, _, _ = _check_arrays(vertices, triangles)
+    vertices, triangles, _ = split_mesh(mesh, triangles)
+    place = one_place(vertices, triangles, what="mesh arrays")
+    check_mesh(vertices, triangles)
     if place == "host":
         return component_table_numpy(vertices, triangles)
-    return _components_device(vertices.contiguous(), _device_triangles(triangles))
+    return _components_device(vertices.contiguous(), int32_triangles(triangles))
 
 
 def clean_mesh(mesh, min_triangles=None, min_area=None, keep_largest=None, remove_unreferenced=True, attributes=None, details=False):
@@ -308,23 +249,22 @@ def clean_mesh(mesh, min_triangles=None, min_area=None, keep_largest=None, remov
     dict of them.  With attributes or details=True the result is a CleanResult: the mesh, the attributes' kept rows in the same
     container, vertex_remap and kept_triangles.  Arrays on the host run clean_numpy; GPU tensors run the kernels: the table's counts
     and areas (C values each) are read for the verdicts, the two output sizes for the allocation."""
-    from .tsdf import Mesh
-    if not (hasattr(mesh, "vertices") and hasattr(mesh, "triangles")):
-        vertices, triangles = _split(mesh, None)
-        mesh = Mesh(vertices, triangles)
+    if not is_mesh(mesh):
+        mesh = Mesh(*split_mesh(mesh)[:2])
     has_criteria = _check_criteria(min_triangles, min_area, keep_largest)
     names = list(attributes) if isinstance(attributes, dict) else None
     given = [] if attributes is None else list(attributes.values() if names is not None else attributes)
     own = [(n, getattr(mesh, n, None)) for n in ("colors", "normals")]
     rows = [a for _, a in own if a is not None] + given
     labels = [f"mesh.{n}" for n, a in own if a is not None] + [f"attributes[{i if names is None else repr(names[i])}]" for i in range(len(given))]
-    place, M, T = _check_arrays(mesh.vertices, mesh.triangles, tuple(zip(labels, rows)))
+    place = one_place(mesh.vertices, mesh.triangles, *rows, what="mesh arrays")
+    M, T = check_mesh(mesh.vertices, mesh.triangles, tuple(zip(labels, rows)))
     if place == "host":
         v, t, out, remap, kept = clean_numpy(mesh.vertices, mesh.triangles, min_triangles, min_area, keep_largest, remove_unreferenced, rows)
     else:
         import torch
         from . import ops
-        vertices, tri = mesh.vertices.contiguous(), _device_triangles(mesh.triangles)
+        vertices, tri = mesh.vertices.contiguous(), int32_triangles(mesh.triangles)
         tcomp = keep = None
         if has_criteria:
             table = _components_device(vertices, tri)
@@ -346,12 +286,13 @@ def clean_mesh(mesh, min_triangles=None, min_area=None, keep_largest=None, remov
 
 def vertex_normals(mesh, triangles=None):
     """Step 5 -> (M,3) float32: numpy on the host, the kernel (and a GPU tensor) for a mesh on a GPU."""
-    vertices, triangles = _split(mesh, triangles)
-    place, _, _ = _check_arrays(vertices, triangles)
+    vertices, triangles, _ = split_mesh(mesh, triangles)
+    place = one_place(vertices, triangles, what="mesh arrays")
+    check_mesh(vertices, triangles)
     if place == "host":
         return vertex_normals_numpy(vertices, triangles).astype(np.float32)
     import torch
     from . import ops
-    tri = _device_triangles(triangles)
+    tri = int32_triangles(triangles)
     key, perm = torch.sort(tri.reshape(-1), stable=True)
     return ops.mesh_vertex_normals(vertices.contiguous(), tri, key, perm)

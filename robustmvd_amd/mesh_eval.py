@@ -51,8 +51,9 @@ matches no query and gets no sample.  A degenerate but finite triangle (zero are
 """
 import numpy as np
 
-from .cloud_eval import INDEX_LIMIT, CloudScore, _combine, _points, _thresholds, nearest_numpy, voxel_downsample_numpy  # noqa: F401
-from .depth_fusion import _is_tensor, _place, _to_numpy
+from .cloud_eval import (INDEX_LIMIT, CloudScore, check_thresholds, combine_scores, host_points, nearest_numpy,  # noqa: F401
+                         voxel_downsample_numpy)
+from .mesh import check_mesh, one_place, place, split_mesh, to_numpy
 
 MAX_PAIRS = 1 << 28
 MAX_SAMPLES = 1 << 28
@@ -61,14 +62,13 @@ K_CAP = 1 << 26
 
 
 def _mesh_numpy(vertices, triangles):
-    v = np.asarray(_to_numpy(vertices), dtype=np.float32)
-    t = np.asarray(_to_numpy(triangles))
-    if v.ndim != 2 or v.shape[1] != 3:
-        raise ValueError(f"vertices must be (M,3), got {v.shape}")
+    """The numpy forms' mesh: vertices converted to float32, an empty triangle array of any shape taken as (0,3), and no index
+    range: a triangle with an index outside 0 .. M-1 is invalid (valid_triangles_numpy), not an error."""
+    v = np.asarray(to_numpy(vertices), dtype=np.float32)
+    t = np.asarray(to_numpy(triangles))
     if t.size == 0:
         t = t.reshape(-1, 3)
-    if t.ndim != 2 or t.shape[1] != 3 or not np.issubdtype(t.dtype, np.integer):
-        raise ValueError(f"triangles must be (T,3) integers, got {t.shape} {t.dtype}")
+    check_mesh(v, t, index_range=False)
     return v, t.astype(np.int64)
 
 
@@ -117,7 +117,7 @@ def triangle_distance_numpy(query, vertices, triangles, index, dtype=np.float64)
     """dist(query[i], triangle index[i]) per query -> (n,) of dtype: what a returned index is worth."""
     ft = np.dtype(dtype).type
     v, t = _mesh_numpy(vertices, triangles)
-    q = _points(query, "query").astype(ft)
+    q = host_points(query, "query").astype(ft)
     tri = t[np.asarray(index, dtype=np.int64)]
     with np.errstate(all="ignore"):
         return np.sqrt(triangle_d2_numpy(q, v[tri[:, 0]].astype(ft), v[tri[:, 1]].astype(ft), v[tri[:, 2]].astype(ft)))
@@ -129,7 +129,7 @@ def mesh_distance_numpy(query, vertices, triangles, max_dist, dtype=np.float64):
     distance (inf without a valid triangle)."""
     ft = np.dtype(dtype).type
     v, t = _mesh_numpy(vertices, triangles)
-    q = _points(query, "query").astype(ft)
+    q = host_points(query, "query").astype(ft)
     md = ft(np.float32(max_dist))
     if not md > 0:
         raise ValueError(f"max_dist must be > 0, got {max_dist}")
@@ -220,7 +220,7 @@ def sample_mesh_numpy(vertices, triangles, spacing, attributes=None, max_samples
     v, t = _mesh_numpy(vertices, triangles)
     attr = None
     if attributes is not None:
-        attr = np.asarray(_to_numpy(attributes), dtype=np.float32)
+        attr = np.asarray(to_numpy(attributes), dtype=np.float32)
         if attr.ndim != 2 or attr.shape[0] != len(v) or attr.shape[1] < 1:
             raise ValueError(f"attributes must be ({len(v)},c), got {attr.shape}")
     max_samples = int(max_samples)
@@ -253,31 +253,8 @@ def sample_mesh_numpy(vertices, triangles, spacing, attributes=None, max_samples
 
 # ---- front ends: the host or the device, by where the inputs are -------------------------------------------------------------------
 
-def _as_mesh(obj):
-    """A Mesh (anything with .vertices and .triangles) or (vertices, triangles) -> (vertices, triangles, colors); a cloud -> None"""
-    if hasattr(obj, "vertices") and hasattr(obj, "triangles"):
-        return obj.vertices, obj.triangles, getattr(obj, "colors", None)
-    if isinstance(obj, (tuple, list)) and len(obj) == 2:
-        return obj[0], obj[1], None
-    return None
-
-
-def _need_mesh(mesh):
-    parts = _as_mesh(mesh)
-    if parts is None:
-        raise ValueError(f"mesh: expected a Mesh or (vertices, triangles), got {type(mesh).__name__}")
-    return parts
-
-
-def _one_place(*arrays):
-    places = {_place(a) for a in arrays}
-    if len(places) != 1:
-        raise ValueError(f"the inputs are in different places ({sorted(places)}): move them to one first")
-    return places.pop()
-
-
 def _device_origin(ops, clouds):
-    extents = [e for e in (ops._cloud_extent(c) for c in clouds) if e is not None]
+    extents = [e for e in (ops.cloud_extent(c) for c in clouds) if e is not None]
     return np.min([e[0] for e in extents], axis=0).tolist() if extents else [0.0, 0.0, 0.0]
 
 
@@ -285,13 +262,13 @@ def mesh_distance(points, mesh, max_dist, max_pairs=MAX_PAIRS):
     """The truncated distance of every point to the mesh's surface (definition 1) -> (dist (n) float32, index (n) int32: the nearest
     triangle, or -1 where nothing is nearer than max_dist).  mesh: a Mesh or (vertices, triangles).  GPU tensors run the HIP
     kernels (ops.mesh_grid at a cell of max_dist (1 + 2^-10), ops.mesh_nearest), numpy arrays the numpy specification."""
-    vertices, triangles, _ = _need_mesh(mesh)
-    if _one_place(points, vertices, triangles) == "host":
+    vertices, triangles, _ = split_mesh(mesh)
+    if one_place(points, vertices, triangles) == "host":
         d, i = mesh_distance_numpy(points, vertices, triangles, max_dist)
         return d.astype(np.float32), i
     from . import ops
     md = float(np.float32(max_dist))
-    v = ops._cloud_points(vertices, "vertices")
+    v = ops.cloud_points(vertices, "vertices")
     grid = ops.mesh_grid(v, triangles, _device_origin(ops, [v]), md * ops.CLOUD_CELL_MARGIN, max_pairs=max_pairs)
     return ops.mesh_nearest(points, grid, md)
 
@@ -299,8 +276,8 @@ def mesh_distance(points, mesh, max_dist, max_pairs=MAX_PAIRS):
 def sample_mesh(mesh, spacing, attributes=None, max_samples=MAX_SAMPLES):
     """Deterministic covering samples of the mesh's surface (definition 3) -> (points (S,3) float32, triangle (S) int32, attributes
     (S,c) or None); GPU tensors run the HIP kernels (ops.mesh_sample), numpy arrays the numpy specification: the same bits."""
-    vertices, triangles, _ = _need_mesh(mesh)
-    if _one_place(vertices, triangles, *([] if attributes is None else [attributes])) == "host":
+    vertices, triangles, _ = split_mesh(mesh)
+    if one_place(vertices, triangles, *([] if attributes is None else [attributes])) == "host":
         return sample_mesh_numpy(vertices, triangles, spacing, attributes, max_samples)
     from . import ops
     return ops.mesh_sample(vertices, triangles, spacing, attributes, max_samples=max_samples)
@@ -323,7 +300,7 @@ class MeshEvaluation:
     samples).  Inputs on the GPU run the HIP kernels, inputs on the host the numpy specification; a mixed pair raises."""
 
     def __init__(self, thresholds, max_dist=None, spacing=None, voxel=None, max_pairs=MAX_PAIRS, max_samples=MAX_SAMPLES):
-        self.thresholds, self.max_dist = _thresholds(thresholds, max_dist)
+        self.thresholds, self.max_dist = check_thresholds(thresholds, max_dist)
         spacing = self.thresholds.min() if spacing is None else np.float32(spacing)
         for name, value in (("spacing", spacing), ("voxel", voxel)):
             if value is not None and not (np.float32(value) > 0 and np.isfinite(np.float32(value))):
@@ -333,11 +310,11 @@ class MeshEvaluation:
         self.max_pairs, self.max_samples = max_pairs, max_samples
 
     def __call__(self, pred, gt):
-        sides = [_as_mesh(pred), _as_mesh(gt)]
+        sides = [split_mesh(pred, required=False), split_mesh(gt, required=False)]
         if sides[0] is None and sides[1] is None:
             raise ValueError("MeshEvaluation needs a mesh on at least one side; two clouds are PointCloudEvaluation's")
         arrays = [a for side, raw in zip(sides, (pred, gt)) for a in (side[:2] if side is not None else (raw,))]
-        run = self._run_host if _one_place(*arrays) == "host" else self._run_device
+        run = self._run_host if one_place(*arrays) == "host" else self._run_device
         return run(sides, pred, gt)
 
     def _run_host(self, sides, pred, gt):
@@ -345,7 +322,7 @@ class MeshEvaluation:
         asks, answers = [], []
         for k, (side, raw) in enumerate(zip(sides, (pred, gt))):
             if side is None:
-                p = _points(raw, ("pred", "gt")[k])
+                p = host_points(raw, ("pred", "gt")[k])
                 if self.voxel is not None and k == 0:
                     p = voxel_downsample_numpy(p, self.voxel)[0]
                 asks.append(p)
@@ -365,7 +342,7 @@ class MeshEvaluation:
 
         dp, sp, np_, cp = direction(asks[0], answers[1])
         dg, sg, ng, cg = direction(asks[1], answers[0])
-        return _combine(sp, np_, cp, sg, ng, cg, dist_pred=dp, dist_gt=dg, thresholds=th, max_dist=float(md), pred_points=asks[0])
+        return combine_scores(sp, np_, cp, sg, ng, cg, dist_pred=dp, dist_gt=dg, thresholds=th, max_dist=float(md), pred_points=asks[0])
 
     def _run_device(self, sides, pred, gt):
         import torch
@@ -375,12 +352,12 @@ class MeshEvaluation:
         asks, meshes = [], []
         for k, (side, raw) in enumerate(zip(sides, (pred, gt))):
             if side is None:
-                p = ops._cloud_points(raw, ("pred", "gt")[k])
+                p = ops.cloud_points(raw, ("pred", "gt")[k])
                 if self.voxel is not None and k == 0:
                     p = ops.voxel_downsample(p, self.voxel)[0]
                 meshes.append(None)
             else:
-                v = ops._cloud_points(side[0], "vertices")
+                v = ops.cloud_points(side[0], "vertices")
                 p = ops.mesh_sample(v, side[1], self.spacing, max_samples=self.max_samples)[0]
                 if self.voxel is not None:
                     p = ops.voxel_downsample(p, self.voxel)[0]
@@ -404,20 +381,20 @@ class MeshEvaluation:
         blocks = blocks.cpu()  # the one read of the scores
         sp, np_, cp = ops.cloud_scores_read(blocks[0], T)
         sg, ng, cg = ops.cloud_scores_read(blocks[1], T)
-        return _combine(sp, np_, cp, sg, ng, cg, dist_pred=dp, dist_gt=dg, thresholds=self.thresholds, max_dist=md, pred_points=asks[0])
+        return combine_scores(sp, np_, cp, sg, ng, cg, dist_pred=dp, dist_gt=dg, thresholds=self.thresholds, max_dist=md, pred_points=asks[0])
 
 
 def evaluate_mesh(mesh, gt, thresholds, **evaluation_args):
     """MeshEvaluation(thresholds, **evaluation_args)(mesh, gt) -> CloudScore: a reconstructed mesh against a ground-truth cloud or mesh.
     A ground truth on the host follows a mesh on the GPU (and the other way round)."""
-    vertices, triangles, _ = _need_mesh(mesh)
-    other = _as_mesh(gt)
-    place = _place(vertices)
-    if _place(gt if other is None else other[0]) != place:
+    vertices, triangles, _ = split_mesh(mesh)
+    other = split_mesh(gt, required=False)
+    where = place(vertices)
+    if place(gt if other is None else other[0]) != where:
         def move(a):
-            if place == "host":
-                return _to_numpy(a)
+            if where == "host":
+                return to_numpy(a)
             import torch
-            return torch.as_tensor(_to_numpy(a)).to(vertices.device)
+            return torch.as_tensor(to_numpy(a)).to(vertices.device)
         gt = move(gt) if other is None else (move(other[0]), move(other[1]))
     return MeshEvaluation(thresholds, **evaluation_args)(mesh, gt)

@@ -62,8 +62,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from .cloud_eval import voxel_keys_numpy
-from .depth_fusion import _to_numpy
-from .mesh_clean import _check_arrays, clean_numpy, cross_numpy
+from .mesh import Mesh, check_mesh, int32_triangles, is_mesh, one_place, split_mesh, to_numpy
+from .mesh_clean import clean_numpy, cross_numpy, vertex_normals
 
 INVALID_KEY = np.iinfo(np.int64).max
 _MASK = (1 << 21) - 1
@@ -149,7 +149,7 @@ def cluster_numpy(vertices, cell, origin=None):
 
 def cluster_means_numpy(rows, clusters):
     """Step 3 -> (K,k) float64: the means of a per-vertex (M,k) float32 array, every sum in ascending vertex index."""
-    r = np.asarray(_to_numpy(rows), dtype=np.float32)[clusters.order].astype(np.float64)
+    r = np.asarray(to_numpy(rows), dtype=np.float32)[clusters.order].astype(np.float64)
     lab, K = clusters.vertex_cluster[clusters.order], clusters.num_clusters
     if K == 0:
         return np.zeros((0, r.shape[1]))
@@ -162,8 +162,8 @@ def cluster_means_numpy(rows, clusters):
 def corner_terms_numpy(vertices, triangles, clusters):
     """Step 4's terms -> (corner_cluster (3T) int32, terms (3T,10) float64) in (t, j) order; a corner of a dropped triangle has the
     cluster K (the sentinel the device sorts last) and its terms are not to be read."""
-    v = np.asarray(_to_numpy(vertices), dtype=np.float32)
-    tri = np.asarray(_to_numpy(triangles)).astype(np.int64).reshape(-1, 3)
+    v = np.asarray(to_numpy(vertices), dtype=np.float32)
+    tri = np.asarray(to_numpy(triangles)).astype(np.int64).reshape(-1, 3)
     K = clusters.num_clusters
     tc = clusters.vertex_cluster[tri]
     valid = (tc >= 0).all(axis=1)
@@ -196,7 +196,7 @@ def place_numpy(vertices, triangles, clusters, placement="quadric", regularisati
     (the tests hand in the device's).  details=True -> also a dict of lam, det (K) and x (K,3) float64 as the quadric branch formed
     them (placement="mean": None)."""
     reg = _check_settings(placement, regularisation)
-    v = np.asarray(_to_numpy(vertices), dtype=np.float32)
+    v = np.asarray(to_numpy(vertices), dtype=np.float32)
     K, c = clusters.num_clusters, np.float64(clusters.c)
     mean = cluster_means_numpy(v, clusters) if means is None else np.asarray(means, dtype=np.float64).reshape(K, 3)
     out = mean.astype(np.float32)
@@ -227,7 +227,7 @@ def place_numpy(vertices, triangles, clusters, placement="quadric", regularisati
 
 def triples_numpy(triangles, vertex_cluster):
     """Step 6's first half -> (triples (T,3) int32, alive (T) bool)."""
-    tri = np.asarray(_to_numpy(triangles)).astype(np.int64).reshape(-1, 3)
+    tri = np.asarray(to_numpy(triangles)).astype(np.int64).reshape(-1, 3)
     tc = np.asarray(vertex_cluster)[tri]
     alive = (tc >= 0).all(axis=1) & (tc[:, 0] != tc[:, 1]) & (tc[:, 1] != tc[:, 2]) & (tc[:, 0] != tc[:, 2])
     first = np.argmin(tc, axis=1) if len(tc) else np.zeros(0, dtype=np.int64)
@@ -246,12 +246,11 @@ def kept_numpy(triples, alive, unique=True):
 
 def simplify_numpy(vertices, triangles, cell, placement="quadric", regularisation=1e-3, origin=None, unique=True,
                    remove_unreferenced=True, attributes=(), quadrics=None, means=None):
-    """Steps 1 to 7 -> SimplifyResult of numpy arrays (mesh: a tsdf.Mesh without colours or normals; attributes: the list of the
+    """Steps 1 to 7 -> SimplifyResult of numpy arrays (mesh: a Mesh without colours or normals; attributes: the list of the
     attributes' means (M',k) float32).  quadrics / means: place_numpy's overrides."""
-    from .tsdf import Mesh
-    vertices, tri = np.asarray(_to_numpy(vertices)), np.asarray(_to_numpy(triangles))
-    attributes = [np.asarray(_to_numpy(a)) for a in attributes]
-    _check_arrays(vertices, tri, tuple((f"attributes[{i}]", a) for i, a in enumerate(attributes)))
+    vertices, tri = np.asarray(to_numpy(vertices)), np.asarray(to_numpy(triangles))
+    attributes = [np.asarray(to_numpy(a)) for a in attributes]
+    check_mesh(vertices, tri, tuple((f"attributes[{i}]", a) for i, a in enumerate(attributes)))
     _check_settings(placement, regularisation)
     clusters = cluster_numpy(vertices, cell, origin)
     pos, placed = place_numpy(vertices, tri, clusters, placement, regularisation, quadrics, means)
@@ -314,11 +313,8 @@ def simplify_mesh(mesh, cell, placement="quadric", regularisation=1e-3, origin=N
     normals (if the input had them) are recomputed.  mesh: a Mesh or a pair (vertices, triangles).  attributes: per-vertex (M,k)
     float32 arrays, a list or a dict of them.  With attributes or details=True the result is a SimplifyResult.  Arrays on the host
     run simplify_numpy; GPU tensors run the kernels and give GPU tensors."""
-    from .mesh_clean import _device_triangles, _split, vertex_normals
-    from .tsdf import Mesh
-    if not (hasattr(mesh, "vertices") and hasattr(mesh, "triangles")):
-        vertices, triangles = _split(mesh, None)
-        mesh = Mesh(vertices, triangles)
+    if not is_mesh(mesh):
+        mesh = Mesh(*split_mesh(mesh)[:2])
     cell = float(_check_cell(cell))
     reg = _check_settings(placement, regularisation)
     names = list(attributes) if isinstance(attributes, dict) else None
@@ -327,12 +323,13 @@ def simplify_mesh(mesh, cell, placement="quadric", regularisation=1e-3, origin=N
     rows = ([colors] if colors is not None else []) + given
     labels = (["mesh.colors"] if colors is not None else []) + [f"attributes[{i if names is None else repr(names[i])}]" for i in range(len(given))]
     extra = tuple(zip(labels, rows)) + ((("mesh.normals", mesh.normals),) if had_normals else ())
-    place, M, T = _check_arrays(mesh.vertices, mesh.triangles, extra)
+    place = one_place(mesh.vertices, mesh.triangles, *(a for _, a in extra), what="mesh arrays")
+    check_mesh(mesh.vertices, mesh.triangles, extra)
     if place == "host":
         r = simplify_numpy(mesh.vertices, mesh.triangles, cell, placement, reg, origin, unique, remove_unreferenced, rows)
         new, out, vertex_map, kept, placed, counts = r.mesh, list(r.attributes), r.vertex_map, r.kept_triangles, r.placed, r.cluster_counts
     else:
-        v, t, out, vertex_map, kept, placed, counts, _ = _simplify_device(mesh.vertices.contiguous(), _device_triangles(mesh.triangles), cell,
+        v, t, out, vertex_map, kept, placed, counts, _ = _simplify_device(mesh.vertices.contiguous(), int32_triangles(mesh.triangles), cell,
                                                                            placement, reg, origin, unique, remove_unreferenced,
                                                                            [a.contiguous() for a in rows])
         new = Mesh(v, t)

@@ -13,6 +13,7 @@ import itertools
 import torch
 
 from . import _lib as L
+from .mesh import check_triangles
 
 
 def _tensors(obj):
@@ -975,11 +976,12 @@ def mesh_render(vertices, triangles, matrices, size, colors=None, normals=False,
     outside 0 .. M - 1 (the kernels skip such a triangle).  stages, workspace_, out: for measurements (tools/bench_render.py), the
     MVD_RENDER_KEEP_* / NO_RESOLVE bits with the workspace and the result of an earlier call on the same arguments."""
     from . import render as R
-    v = L.as_f32(vertices, "vertices")
-    dev = v.device
-    t = L.as_dtype(torch.int32, True, triangles, "triangles", device=dev)
+    v = _device_vertices(vertices, convert=True)
+    dev, M = v.device, int(v.shape[0])
+    t = _device_triangles(triangles, M, dev, convert=True, index_range=check_indices)
+    T = int(t.shape[0])
     c = None if colors is None else L.as_f32(colors, "colors", device=dev)
-    M, T = R.check_mesh(v, t, c)
+    R.check_colors(c, M)
     mats = L.as_f32(matrices, "matrices", device=dev)
     if mats.dim() != 2 or mats.shape[1] != 12 or not 1 <= mats.shape[0] <= L.MVD_MAX_VIEWS:
         raise ValueError(f"matrices must be (V,12) with V in 1..{L.MVD_MAX_VIEWS}, got {tuple(mats.shape)}")
@@ -991,9 +993,6 @@ def mesh_render(vertices, triangles, matrices, size, colors=None, normals=False,
     max_small = L.MESH_RENDER_MAX_SMALL if max_small is None else int(max_small)
     if not 0 <= max_small < 2 ** 31:
         raise ValueError(f"max_small must be in 0 .. 2^31 - 1, got {max_small}")
-    if check_indices and T:
-        lo, hi = torch.aminmax(t)
-        R.check_index_range(int(lo), int(hi), M)
     if out is None:
         maps = lambda on: torch.empty((V, 3, H, W), dtype=torch.float32, device=dev) if on else None
         out = {"depth": torch.empty((V, H, W), dtype=torch.float32, device=dev),
@@ -1009,12 +1008,19 @@ def mesh_render(vertices, triangles, matrices, size, colors=None, normals=False,
     return out
 
 
-def _mesh_triangles(triangles, M, name="triangles", device=None):
-    t = L.as_dtype(torch.int32, False, triangles, name, device=device)
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError(f"{name} must be (T,3), got {tuple(t.shape)}")
-    if int(M) < 0 or int(M) >= 2 ** 31 or t.shape[0] >= 2 ** 31:
-        raise ValueError(f"{M} vertices and {t.shape[0]} triangles: both must be in 0 .. 2^31 - 1")
+def _device_vertices(vertices, device=None, convert=False):
+    """A mesh's vertices (M,3) as the kernels take them: float32, contiguous, on a GPU; another dtype is converted or refused."""
+    v = L.as_dtype(torch.float32, convert, vertices, "vertices", device=device)
+    if v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"vertices must be (M,3), got {tuple(v.shape)}")
+    return v
+
+
+def _device_triangles(triangles, M, device=None, convert=False, index_range=False):
+    """A mesh's triangles (T,3) as the kernels take them: int32, contiguous, on a GPU, M and T below 2^31; another dtype is converted
+    or refused.  index_range: mesh.check_triangles' reduction and read, which only mesh_render asks for."""
+    t = L.as_dtype(torch.int32, convert, triangles, "triangles", device=device)
+    check_triangles(t, M, dtypes=False, index_range=index_range)
     return t
 
 
@@ -1024,7 +1030,7 @@ def mesh_hook_round(triangles, M, label, referenced, changed, first=False, stage
     shortcut launch over the vertices.  triangles (T,3) int32, label (M) int32, referenced (M) uint8, changed: one int32 word on the
     device, zeroed by the call and 1 after it when a label changed.  first: starts a labelling (label[v] = v, referenced = 0).
     stages: for measurements (tools/bench_mesh_clean.py), L.MESH_ROUND_NO_HOOK or L.MESH_ROUND_NO_SHORTCUT: one launch of the two."""
-    t = _mesh_triangles(triangles, M)
+    t = _device_triangles(triangles, M)
     dev = t.device
     M = int(M)
     lab = L.as_dtype(torch.int32, False, label, "label", (M,), dev)
@@ -1058,7 +1064,7 @@ def mesh_component_table(vertex_component, triangles, C):
     (mvd_mesh_component_table).  C: mesh_component_rank's count, read by the caller."""
     vc = L.as_dtype(torch.int32, False, vertex_component, "vertex_component")
     dev, M = vc.device, int(vc.numel())
-    t = _mesh_triangles(triangles, M, device=dev)
+    t = _device_triangles(triangles, M, dev)
     T, C = int(t.shape[0]), int(C)
     tcomp = torch.empty(T, dtype=torch.int32, device=dev)
     nv = torch.empty(C, dtype=torch.int32, device=dev)
@@ -1074,7 +1080,7 @@ def mesh_component_sums(vertices, triangles, sorted_component, perm, C):
     dev, M = v.device, int(v.shape[0])
     if v.dim() != 2 or v.shape[1] != 3:
         raise ValueError(f"vertices must be (M,3), got {tuple(v.shape)}")
-    t = _mesh_triangles(triangles, M, device=dev)
+    t = _device_triangles(triangles, M, dev)
     T, C = int(t.shape[0]), int(C)
     key = L.as_dtype(torch.int32, False, sorted_component, "sorted_component", (T,), dev)
     pm = L.as_dtype(torch.int64, False, perm, "perm", (T,), dev)
@@ -1093,7 +1099,7 @@ def mesh_filter(triangles, M, triangle_component=None, keep_component=None, remo
     keep_component (C) uint8 / bool with triangle_component (T) int32, or None for every triangle.  Returns (out_triangles (T',3)
     int32 re-indexed, kept_triangles (T') int32, vertex_remap (M) int32, M') at their exact sizes: the call counts, M' and T' are read
     (the call's one synchronisation, 16 bytes), and the second call writes from the counts the workspace still holds."""
-    t = _mesh_triangles(triangles, M)
+    t = _device_triangles(triangles, M)
     dev, T, M = t.device, int(t.shape[0]), int(M)
     keep, tcomp, C = None, None, 0
     if keep_component is not None:
@@ -1146,7 +1152,7 @@ def mesh_vertex_normals(vertices, triangles, sorted_vertex, perm):
     if v.dim() != 2 or v.shape[1] != 3:
         raise ValueError(f"vertices must be (M,3), got {tuple(v.shape)}")
     dev, M = v.device, int(v.shape[0])
-    t = _mesh_triangles(triangles, M, device=dev)
+    t = _device_triangles(triangles, M, dev)
     T = int(t.shape[0])
     if 3 * T >= 2 ** 31:
         raise ValueError(f"{T} triangles: 3 T must be below 2^31")
@@ -1176,28 +1182,21 @@ class MeshClusters:
         return self.cluster_start[1:] - self.cluster_start[:-1]
 
 
-def _mesh_vertices(vertices, device=None):
-    v = L.as_dtype(torch.float32, False, vertices, "vertices", device=device)
-    if v.dim() != 2 or v.shape[1] != 3:
-        raise ValueError(f"vertices must be (M,3), got {tuple(v.shape)}")
-    return v
-
-
 @inference_only
 def mesh_cluster_ids(vertices, cell, origin=None):
     """The vertices of a mesh sorted into the cells of edge `cell` (taken as float32) and numbered (include/mvd.h:
     mvd_mesh_cluster_ids; mesh_simplify.cluster_numpy is the definition) -> MeshClusters.  origin defaults to the per-axis minimum
     over the finite vertices.  Host reads: the extent (6 floats) and K."""
-    v = _mesh_vertices(vertices)
+    v = _device_vertices(vertices)
     dev, M = v.device, int(v.shape[0])
     cell = float(torch.tensor(float(cell), dtype=torch.float32))
     if not 0.0 < cell < float("inf"):
         raise ValueError(f"cell must be finite and > 0, got {cell}")
     inv = 1.0 / cell
-    extent = _cloud_extent(v)
+    extent = cloud_extent(v)
     o = _cloud_origin(origin) if origin is not None else ([0.0, 0.0, 0.0] if extent is None else extent[0].tolist())
     _check_cloud_indices(extent, o, inv, "voxel_downsample", cell)
-    keys, perm = _cloud_sorted(v, o, inv)
+    keys, perm = cloud_sorted(v, o, inv)
     vc = torch.empty(M, dtype=torch.int32, device=dev)
     start = torch.empty(M + 1, dtype=torch.int32, device=dev)
     ckey = torch.empty(M, dtype=torch.int64, device=dev)
@@ -1233,7 +1232,7 @@ def mesh_cluster_triples(triangles, clusters):
     cluster, K for a triangle with an invalid vertex) (mvd_mesh_cluster_triples)."""
     vc = clusters.vertex_cluster
     dev, M, K = vc.device, int(vc.numel()), clusters.num_clusters
-    t = _mesh_triangles(triangles, M, device=dev)
+    t = _device_triangles(triangles, M, dev)
     T = int(t.shape[0])
     if 3 * T >= 2 ** 31:
         raise ValueError(f"{T} triangles: 3 T must be below 2^31")
@@ -1250,9 +1249,9 @@ def mesh_cluster_quadrics(vertices, triangles, sorted_cluster, perm, clusters):
     """-> (K,10) float64: every cluster's quadric sums over its corners in ascending (triangle, corner) in the fixed segment order
     (mvd_mesh_cluster_quadrics_f64).  sorted_cluster (3T) int32 and perm (3T) int64: torch.sort(corner_key.reshape(-1), stable=True)."""
     dev, K = clusters.vertex_cluster.device, clusters.num_clusters
-    v = _mesh_vertices(vertices, dev)
+    v = _device_vertices(vertices, dev)
     M = int(v.shape[0])
-    t = _mesh_triangles(triangles, M, device=dev)
+    t = _device_triangles(triangles, M, dev)
     T = int(t.shape[0])
     if 3 * T >= 2 ** 31:
         raise ValueError(f"{T} triangles: 3 T must be below 2^31")
@@ -1273,7 +1272,7 @@ def mesh_cluster_place(vertices, clusters, means, quadrics=None, regularisation=
     """-> (vertices (K,3) float32, placed (K) uint8): per cluster the quadric's regularised minimum (1), the mean (0: quadrics=None,
     or the minimum is refused) or its single vertex (2) (mvd_mesh_cluster_place_f32; mesh_simplify.place_numpy is the definition)."""
     dev, K = clusters.vertex_cluster.device, clusters.num_clusters
-    v = _mesh_vertices(vertices, dev)
+    v = _device_vertices(vertices, dev)
     M = int(v.shape[0])
     mean = L.as_dtype(torch.float64, False, means, "means", (K, 3), dev)
     q = None if quadrics is None else L.as_dtype(torch.float64, False, quadrics, "quadrics", (K, 10), dev)
@@ -1309,7 +1308,7 @@ CLOUD_INDEX_LIMIT = (1 << 21) - 1 # a cell or voxel index is in [0, 2^21 - 1): t
 CLOUD_CELL_MARGIN = 1.0 + 2.0 ** -10  # cell edge = max_dist * margin (csrc/cloud_eval.hip: why 27 cells are enough)
 
 
-def _cloud_points(points, name, device=None):
+def cloud_points(points, name, device=None):
     p = L.as_f32(points, name, device=device)
     if p.dim() != 2 or p.shape[1] != 3:
         raise ValueError(f"{name} must be (n,3), got {tuple(p.shape)}")
@@ -1318,7 +1317,7 @@ def _cloud_points(points, name, device=None):
     return p
 
 
-def _cloud_extent(p):
+def cloud_extent(p):
     """Per-axis min and max over the valid points of p (n,3) as float64 numpy, or None when there is none: one read of 6 floats."""
     if p.shape[0] == 0:
         return None
@@ -1346,7 +1345,7 @@ def _check_cloud_indices(extent, origin, inv, what, edge):
                          f"{edge:g} gives indices {min(lo):.0f} .. {max(hi):.0f}; each must be in [0, {CLOUD_INDEX_LIMIT})")
 
 
-def _cloud_sorted(p, origin, inv):
+def cloud_sorted(p, origin, inv):
     """Keys of p's cells, sorted stably, and the permutation -> (keys, perm).  The sort is torch's: plumbing between two kernels."""
     n = p.shape[0]
     keys = torch.empty(n, dtype=torch.int64, device=p.device)
@@ -1368,14 +1367,14 @@ def cloud_grid(points, origin, cell, check=True):
     """points (n,3) sorted into the cells of edge `cell` from `origin` (include/mvd.h: mvd_cloud_cell_keys_f32,
     mvd_cloud_grid_build_f32) -> CloudGrid.  check: every valid point's cell indices must be in [0, 2^21 - 1), else ValueError
     (a target grid needs it; check=False clamps instead, for a cloud that is only queried)."""
-    p = _cloud_points(points, "points")
+    p = cloud_points(points, "points")
     origin, cell = _cloud_origin(origin), float(cell)
     if not 0.0 < cell < float("inf"):
         raise ValueError(f"cell must be finite and > 0, got {cell}")
     inv = 1.0 / cell
     if check:
-        _check_cloud_indices(_cloud_extent(p), origin, inv, "cloud_grid", cell)
-    keys, perm = _cloud_sorted(p, origin, inv)
+        _check_cloud_indices(cloud_extent(p), origin, inv, "cloud_grid", cell)
+    keys, perm = cloud_sorted(p, origin, inv)
     records = torch.empty((p.shape[0], 4), dtype=torch.float32, device=p.device)
     call("mvd_cloud_grid_build_f32", p.device, p, perm, p.shape[0], records)
     return CloudGrid(p, keys, records, origin, cell)
@@ -1421,7 +1420,7 @@ def cloud_nearest(query, grid, max_dist):
             if query.origin != grid.origin or query.cell != grid.cell or query.points.device != dev:
                 raise ValueError("query and target grids differ in origin, cell or device")
             return query.records
-        return cloud_grid(_cloud_points(query, "query", dev), grid.origin, grid.cell, check=False).records
+        return cloud_grid(cloud_points(query, "query", dev), grid.origin, grid.cell, check=False).records
 
     return _cloud_nearest(records, grid, max_dist)
 
@@ -1441,7 +1440,7 @@ def cloud_scores(dist, index, thresholds, points=None, result=None):
     if th.dim() != 1 or not 1 <= th.shape[0] <= L.MVD_CLOUD_MAX_THRESHOLDS:
         raise ValueError(f"{th.numel()} thresholds, supported 1..{L.MVD_CLOUD_MAX_THRESHOLDS}")
     th = L.as_f32(th.to(dev), "thresholds")
-    pts = _cloud_points(points, "points", dev) if points is not None else None
+    pts = cloud_points(points, "points", dev) if points is not None else None
     if pts is not None and pts.shape[0] != n:
         raise ValueError(f"{pts.shape[0]} points for {n} distances")
     result = _result_block(result, 10, dev, "dist's")
@@ -1463,8 +1462,8 @@ CLOUD_PAIR_SUMS_WORDS = 32  # cloud_pair_sums' block: 256 bytes
 
 def _transform12(transform):
     """A (4,4) or (3,4) transform [M | t] (cloud_register.py) -> the 12 finite doubles the C entries take, as a ctypes array."""
-    from .cloud_register import _affine
-    M, t = _affine(transform)
+    from .cloud_register import affine_parts
+    M, t = affine_parts(transform)
     return (ctypes.c_double * 12)(*[float(v) for a in range(3) for v in (M[a, 0], M[a, 1], M[a, 2], t[a])])
 
 
@@ -1472,7 +1471,7 @@ def _transform12(transform):
 def cloud_transform(points, transform, normals=None):
     """points (n,3) through x -> M x + t in float64, rounded once (include/mvd.h: mvd_cloud_transform_f32; bit for bit
     cloud_register.transform_numpy) -> (n,3) float32, or (points, normals) with the normals (n,3) through M and re-normalised."""
-    p = _cloud_points(points, "points")
+    p = cloud_points(points, "points")
     n, dev = p.shape[0], p.device
     T = _transform12(transform)
     nrm = L.as_f32(normals, "normals", (n, 3), dev) if normals is not None else None
@@ -1486,7 +1485,7 @@ def cloud_transform(points, transform, normals=None):
 def cloud_transform_records(points, perm, transform):
     """cloud_grid's records of the MOVED points (include/mvd.h: mvd_cloud_transform_records_f32): sorted position i holds
     T(points[perm[i]]) and perm[i].  perm (n) int64: the permutation of a stable sort of the cell keys -> records (n,4) float32."""
-    p = _cloud_points(points, "points")
+    p = cloud_points(points, "points")
     n, dev = p.shape[0], p.device
     perm = L.as_dtype(torch.int64, False, perm, "perm", (n,), dev)
     records = torch.empty((n, 4), dtype=torch.float32, device=dev)
@@ -1513,10 +1512,10 @@ def cloud_pair_sums(source, transform, index, target, pivot, target_normals=None
     (n) int32 from cloud_nearest of the moved source, target (m,3), pivot: 3 numbers, target_normals (m,3): plane mode.  Returns a
     device int64 tensor of 32 words, left on the device: the count of pairs, then the bits of the float64 sums (read it with
     cloud_pair_sums_read)."""
-    s = _cloud_points(source, "source")
+    s = cloud_points(source, "source")
     n, dev = s.shape[0], s.device
     idx = L.as_dtype(torch.int32, False, index, "index", (n,), dev)
-    p = _cloud_points(target, "target", dev)
+    p = cloud_points(target, "target", dev)
     m = p.shape[0]
     nrm = L.as_f32(target_normals, "target_normals", (m, 3), dev) if target_normals is not None else None
     if nrm is not None and m == 0:
@@ -1542,7 +1541,7 @@ def voxel_downsample(points, voxel, colors=None, origin=None):
     """One point per occupied voxel of edge `voxel` (include/mvd.h: mvd_voxel_reduce_f32): the float64 mean of the voxel's valid
     points (and colours), in ascending order of the key floor((x - o) / voxel) per axis; origin defaults to the per-axis minimum
     over the valid points.  Returns (xyz (k,3) float32, rgb (k,3) or None, counts (k,) int32)."""
-    p = _cloud_points(points, "points")
+    p = cloud_points(points, "points")
     n, dev = p.shape[0], p.device
     voxel = float(torch.tensor(float(voxel), dtype=torch.float32))  # the definition takes the voxel as float32: inv = 1 / float64(float32)
     if not 0.0 < voxel < float("inf"):
@@ -1551,10 +1550,10 @@ def voxel_downsample(points, voxel, colors=None, origin=None):
     if colors is not None:
         col = L.as_f32(colors, "colors", (n, 3), dev)
     inv = 1.0 / voxel
-    extent = _cloud_extent(p)
+    extent = cloud_extent(p)
     o = _cloud_origin(origin) if origin is not None else ([0.0, 0.0, 0.0] if extent is None else extent[0].tolist())
     _check_cloud_indices(extent, o, inv, "voxel_downsample", voxel)
-    keys, perm = _cloud_sorted(p, o, inv)
+    keys, perm = cloud_sorted(p, o, inv)
     xyz = torch.empty((n, 3), dtype=torch.float32, device=dev)
     rgb = torch.empty((n, 3), dtype=torch.float32, device=dev) if col is not None else None
     counts = torch.empty(n, dtype=torch.int32, device=dev)
@@ -1569,13 +1568,6 @@ def voxel_downsample(points, voxel, colors=None, origin=None):
 MESH_MAX_PAIRS = 1 << 28    # mesh_grid's default bound on the (cell, triangle) pairs: 2^28 pairs are 15 GB of keys, permutation and records
 MESH_MAX_SAMPLES = 1 << 28  # mesh_sample's default bound on the samples
 _MESH_HARD_LIMIT = 2 ** 31 - 1
-
-
-def _mesh_arrays(vertices, triangles):
-    v = L.as_f32(vertices, "vertices")
-    if v.dim() != 2 or v.shape[1] != 3:
-        raise ValueError(f"vertices must be (M,3), got {tuple(v.shape)}")
-    return v, _mesh_triangles(triangles, v.shape[0], device=v.device)
 
 
 def _mesh_bound(value, name):
@@ -1617,13 +1609,14 @@ def mesh_grid(vertices, triangles, origin, cell, max_pairs=MESH_MAX_PAIRS):
     mvd_mesh_cell_counts_f32, mvd_mesh_pairs_f32, mvd_mesh_records_f32; mesh_eval.mesh_grid_pairs_numpy is the definition) ->
     MeshGrid.  Every finite vertex's cell indices must be in [0, 2^21 - 1), else ValueError.  The number of pairs P is read once; more
     than max_pairs (at most 2^31 - 1) raises ValueError: a larger cell gives fewer pairs (and more candidates per query)."""
-    v, t = _mesh_arrays(vertices, triangles)
+    v = _device_vertices(vertices, convert=True)
+    t = _device_triangles(triangles, v.shape[0], v.device)
     dev, M, T = v.device, int(v.shape[0]), int(t.shape[0])
     origin, cell, max_pairs = _cloud_origin(origin), float(cell), _mesh_bound(max_pairs, "max_pairs")
     if not 0.0 < cell < float("inf"):
         raise ValueError(f"cell must be finite and > 0, got {cell}")
     inv = 1.0 / cell
-    _check_cloud_indices(_cloud_extent(v), origin, inv, "mesh_grid", cell)
+    _check_cloud_indices(cloud_extent(v), origin, inv, "mesh_grid", cell)
     counts = torch.empty(T, dtype=torch.int64, device=dev)
     if T:
         call("mvd_mesh_cell_counts_f32", dev, v if M else None, M, t, T, origin[0], origin[1], origin[2], inv, counts)
@@ -1637,7 +1630,7 @@ def mesh_grid(vertices, triangles, origin, cell, max_pairs=MESH_MAX_PAIRS):
     records = torch.empty((P, 12), dtype=torch.float32, device=dev)
     if P:
         call("mvd_mesh_pairs_f32", dev, v, M, t, T, ends, P, origin[0], origin[1], origin[2], inv, keys, pair_tri)
-        keys, perm = torch.sort(keys, stable=True)  # torch's sort: plumbing between two kernels, as _cloud_sorted's
+        keys, perm = torch.sort(keys, stable=True)  # torch's sort: plumbing between two kernels, as cloud_sorted's
         call("mvd_mesh_records_f32", dev, v, M, t, T, pair_tri, perm, P, records)
     return MeshGrid(v, t, keys, records, origin, cell)
 
@@ -1661,7 +1654,7 @@ def mesh_nearest(query, grid, max_dist):
             raise ValueError("query and mesh grids differ in origin, cell or device")
         rec = query.records
     else:
-        rec = cloud_grid(_cloud_points(query, "query", dev), grid.origin, grid.cell, check=False).records
+        rec = cloud_grid(cloud_points(query, "query", dev), grid.origin, grid.cell, check=False).records
     n, P = rec.shape[0], grid.keys.shape[0]
     dist = torch.empty(n, dtype=torch.float32, device=dev)
     index = torch.empty(n, dtype=torch.int32, device=dev)
@@ -1677,7 +1670,8 @@ def mesh_sample(vertices, triangles, spacing, attributes=None, max_samples=MESH_
     and the centroids of its k^2 congruent sub-triangles, so that every surface point is within 2 spacing / 3 of a sample.
     attributes (M,c) float32 are interpolated with the points.  The number of samples S is read once; more than max_samples (at most
     2^31 - 1) raises ValueError.  Returns (points (S,3) float32, triangle (S) int32, attributes (S,c) or None), in triangle order."""
-    v, t = _mesh_arrays(vertices, triangles)
+    v = _device_vertices(vertices, convert=True)
+    t = _device_triangles(triangles, v.shape[0], v.device)
     dev, M, T = v.device, int(v.shape[0]), int(t.shape[0])
     spacing, max_samples = float(torch.tensor(float(spacing), dtype=torch.float32)), _mesh_bound(max_samples, "max_samples")
     if not 0.0 < spacing < float("inf"):

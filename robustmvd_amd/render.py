@@ -44,7 +44,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .depth_fusion import _pinhole, _place, _to_numpy
+from .depth_fusion import pinhole
+from .mesh import check_mesh, one_place, split_mesh, to_numpy
 
 MAX_VIEWS = 32  # views per launch (MVD_MAX_VIEWS)
 CULL = {None: 0, "none": 0, "back": 1, "front": 2}
@@ -53,23 +54,14 @@ _PAIR_BUDGET = 1 << 22  # (triangle, pixel) pairs evaluated at a time by render_
 
 def compose_projection(K, T):
     """-> 12 float64, row-major 3x4: P = K T[:3], which takes (X,1) to (qx,qy,qz)."""
-    K, T = _pinhole(K, "intrinsics"), np.asarray(T, dtype=np.float64).reshape(4, 4)
+    K, T = pinhole(K, "intrinsics"), np.asarray(T, dtype=np.float64).reshape(4, 4)
     return (K @ T[:3]).ravel()
 
 
-def check_mesh(vertices, triangles, colors=None):
-    """The host-side argument checks both paths share -> (M, T).  The index range is the caller's to check where the triangles
-    live on a GPU (render_mesh does it with one reduction)."""
-    if vertices.ndim != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"vertices must be (M,3), got {tuple(vertices.shape)}")
-    if triangles.ndim != 2 or triangles.shape[1] != 3:
-        raise ValueError(f"triangles must be (T,3), got {tuple(triangles.shape)}")
-    M, T = int(vertices.shape[0]), int(triangles.shape[0])
-    if T >= 2 ** 31 or M >= 2 ** 31:
-        raise ValueError(f"{M} vertices and {T} triangles: both must be below 2^31")
+def check_colors(colors, M):
+    """The renderer takes exactly three channels, of any dtype (both paths convert)."""
     if colors is not None and tuple(colors.shape) != (M, 3):
         raise ValueError(f"colors: shape {tuple(colors.shape)}, expected {(M, 3)}")
-    return M, T
 
 
 def check_views(intrinsics, poses, size):
@@ -89,11 +81,6 @@ def check_cull(cull):
     if cull not in CULL:
         raise ValueError(f"cull must be None, 'back' or 'front', got {cull!r}")
     return CULL[cull]
-
-
-def check_index_range(lo, hi, M):
-    if lo < 0 or hi >= M:
-        raise ValueError(f"triangles: vertex indices must be in 0 .. {M - 1}, found {lo if lo < 0 else hi}")
 
 
 def edge_value(xa, ya, xb, yb, px, py):
@@ -197,15 +184,14 @@ def render_numpy(vertices, triangles, intrinsics, poses, size, colors=None, norm
     two is what tests/render_cases.py derives its bands from.  details=True adds a second result, a dict of per-view arrays: x, y, z
     (M,) and valid (M,), the screen vertices."""
     ft = np.dtype(dtype).type
-    vertices = np.asarray(_to_numpy(vertices), dtype=np.float32)
-    tri = np.asarray(_to_numpy(triangles))
-    colors = None if colors is None else np.asarray(_to_numpy(colors), dtype=np.float32)
-    M, T = check_mesh(vertices, tri, colors)
+    vertices = np.asarray(to_numpy(vertices), dtype=np.float32)
+    tri = np.asarray(to_numpy(triangles))
+    colors = None if colors is None else np.asarray(to_numpy(colors), dtype=np.float32)
+    M, T = check_mesh(vertices, tri, dtypes=False)
+    check_colors(colors, M)
     V, H, W = check_views(intrinsics, poses, size)
     cull = check_cull(cull)
     tri = tri.astype(np.int64)
-    if T:
-        check_index_range(int(tri.min()), int(tri.max()), M)
     out = RenderResult([], [], [], [] if bary else None, [] if colors is not None else None, [] if normals else None)
     det = {n: [] for n in ("x", "y", "z", "valid")}
     for v in range(V):
@@ -258,22 +244,6 @@ def render_numpy(vertices, triangles, intrinsics, poses, size, colors=None, norm
     return (out, det) if details else out
 
 
-def _split_mesh(mesh, triangles, colors):
-    if hasattr(mesh, "vertices") and hasattr(mesh, "triangles"):
-        if triangles is not None:
-            raise ValueError("render_mesh: a Mesh brings its own triangles")
-        return mesh.vertices, mesh.triangles, mesh.colors if colors is True else (None if colors is None or colors is False else colors)
-    if isinstance(mesh, (tuple, list)) and len(mesh) == 2 and triangles is None:
-        mesh, triangles = mesh
-    if triangles is None:
-        raise ValueError("render_mesh: expected a Mesh, (vertices, triangles) or vertices with triangles=")
-    if colors is True or colors is False:
-        if colors:
-            raise ValueError("render_mesh: colors=True needs a Mesh with colours; pass the (M,3) array instead")
-        colors = None
-    return mesh, triangles, colors
-
-
 def _renormalise(m):
     """(3,H,W) interpolated vectors -> unit vectors, (0,0,0) where the length is zero or not finite: numpy in float64, rounded to
     float32; a GPU tensor in float32."""
@@ -292,7 +262,7 @@ def _renormalise(m):
 def _render_smooth(mesh, intrinsics, poses, size, triangles, colors, bary, cull, near, max_small):
     """Step 8: the vertex normals through the colour path, a second rendering when colours are wanted too."""
     from .mesh_clean import vertex_normals
-    vertices, tri, colors = _split_mesh(mesh, triangles, colors)
+    vertices, tri, colors = split_mesh(mesh, triangles, colors)
     vn = getattr(mesh, "normals", None)
     if vn is None:
         vn = vertex_normals(vertices, tri)
@@ -319,24 +289,18 @@ def render_mesh(mesh, intrinsics, poses, size, triangles=None, colors=None, norm
         if normals != "vertex":
             raise ValueError(f"normals must be False, True or 'vertex', got {normals!r}")
         return _render_smooth(mesh, intrinsics, poses, size, triangles, colors, bary, cull, near, max_small)
-    vertices, triangles, colors = _split_mesh(mesh, triangles, colors)
-    places = {_place(a) for a in (vertices, triangles, colors) if a is not None}
-    if len(places) != 1:
-        raise ValueError(f"the mesh arrays are in different places ({sorted(places)})")
-    place = places.pop()
-    if place == "host":
+    vertices, triangles, colors = split_mesh(mesh, triangles, colors)
+    if one_place(*(a for a in (vertices, triangles, colors) if a is not None), what="mesh arrays") == "host":
         r = render_numpy(vertices, triangles, intrinsics, poses, size, colors, normals, bary, cull, near)
         f32 = lambda maps: None if maps is None else [m.astype(np.float32) for m in maps]
         return RenderResult(f32(r.depth), r.triangle, r.mask, f32(r.bary), f32(r.colors), f32(r.normals))
     import torch
     from . import ops
-    M, T = check_mesh(vertices, triangles, colors)
+    M, T = check_mesh(vertices, triangles, dtypes=False)  # the index range: one reduction for all the launches
+    check_colors(colors, M)
     V, H, W = check_views(intrinsics, poses, size)
     check_cull(cull)
-    if T:
-        lo, hi = torch.aminmax(triangles)
-        check_index_range(int(lo), int(hi), M)
-    table = torch.from_numpy(np.stack([compose_projection(_to_numpy(K), _to_numpy(P)) for K, P in zip(intrinsics, poses)])
+    table = torch.from_numpy(np.stack([compose_projection(to_numpy(K), to_numpy(P)) for K, P in zip(intrinsics, poses)])
                              .astype(np.float32).reshape(V, 12)).to(vertices.device) if V else None
     out = RenderResult([], [], [], [] if bary else None, [] if colors is not None else None, [] if normals else None)
     per = max(1, min(MAX_VIEWS, (2 ** 32 - 1) // max(T, 1)))  # views per launch: views x triangles stays below 2^32

@@ -45,11 +45,11 @@ ops.tsdf_extract) for a volume on a GPU.  TSDFVolume picks by its `device`.
 """
 import functools
 import itertools
-from dataclasses import dataclass
 
 import numpy as np
 
-from .depth_fusion import _is_tensor, _map2d, _pinhole, _place, _to_numpy
+from .depth_fusion import map2d, pinhole
+from .mesh import Mesh, is_tensor, one_place, place, to_numpy  # noqa: F401  (tsdf.Mesh stays importable)
 
 MAX_VIEWS = 32  # views per launch (MVD_MAX_VIEWS)
 EDGE_KINDS = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))
@@ -140,7 +140,7 @@ def kernel_tables_header():
 
 def compose_matrix(K, T, origin, voxel):
     """-> 12 float64, row-major 3x4: M = K T[:3] [[s I, origin], [0, 1]], which takes (i,j,k,1) to (Qx,Qy,Qz)."""
-    K, T = _pinhole(K, "intrinsics"), np.asarray(T, dtype=np.float64).reshape(4, 4)
+    K, T = pinhole(K, "intrinsics"), np.asarray(T, dtype=np.float64).reshape(4, 4)
     G = np.eye(4)
     G[:3, :3] *= float(voxel)
     G[:3, 3] = np.asarray(origin, dtype=np.float64).reshape(3)
@@ -183,16 +183,16 @@ def integrate_numpy(tsdf, weight, color, depths, intrinsics, poses, origin, voxe
     det = {n: [] for n in ("u", "v", "qz", "sdf", "px", "py", "inb", "updated")}
     one = ft(1)
     for n in range(V):
-        d = np.asarray(_to_numpy(depths[n])).astype(ft)
+        d = np.asarray(to_numpy(depths[n])).astype(ft)
         if d.ndim != 2:
             raise ValueError(f"depths[{n}] must be (H,W), got {d.shape}")
         H, W = d.shape
-        w = np.ones((H, W), dtype=ft) if weights is None else np.asarray(_to_numpy(weights[n])).astype(ft)
+        w = np.ones((H, W), dtype=ft) if weights is None else np.asarray(to_numpy(weights[n])).astype(ft)
         if w.shape != d.shape:
             raise ValueError(f"weights[{n}]: shape {w.shape}, expected {d.shape}")
         img = None
         if images is not None and C is not None:
-            img = np.asarray(_to_numpy(images[n])).astype(ft)
+            img = np.asarray(to_numpy(images[n])).astype(ft)
             if img.shape != (3, H, W):
                 raise ValueError(f"images[{n}]: shape {img.shape}, expected {(3, H, W)}")
         m = compose_matrix(intrinsics[n], poses[n], origin, s)
@@ -229,8 +229,8 @@ def extract_numpy(tsdf, weight, color=None, origin=(0.0, 0.0, 0.0), voxel=1.0, m
     The observed and inside verdicts are taken on the float32 state as it is; t, the positions and the colours are formed in `dtype`
     (float32: on the float32-rounded origin and voxel, what the device is handed)."""
     ft = np.dtype(dtype).type
-    F32, W32 = np.asarray(_to_numpy(tsdf), dtype=np.float32), np.asarray(_to_numpy(weight), dtype=np.float32)
-    C = None if color is None else np.asarray(_to_numpy(color), dtype=np.float32).astype(ft)
+    F32, W32 = np.asarray(to_numpy(tsdf), dtype=np.float32), np.asarray(to_numpy(weight), dtype=np.float32)
+    C = None if color is None else np.asarray(to_numpy(color), dtype=np.float32).astype(ft)
     _check_state(F32, W32, C)
     nz, ny, nx = F32.shape
     N = nx * ny * nz
@@ -293,7 +293,7 @@ def extract_numpy(tsdf, weight, color=None, origin=(0.0, 0.0, 0.0), voxel=1.0, m
 def bounds_from_points(points, voxel, margin=0.0):
     """-> (origin (3,) float64, dims (nx,ny,nz)) of the smallest volume of edge `voxel`, its origin on the voxel lattice through 0,
     that holds every finite point of the (M,3) cloud (DepthFusion's, for one) with `margin` around it."""
-    p = np.asarray(_to_numpy(points), dtype=np.float64).reshape(-1, 3)
+    p = np.asarray(to_numpy(points), dtype=np.float64).reshape(-1, 3)
     p = p[np.isfinite(p).all(axis=1)]
     if not len(p):
         raise ValueError("bounds_from_points: no finite point")
@@ -302,59 +302,6 @@ def bounds_from_points(points, voxel, margin=0.0):
     lo = np.floor((p.min(axis=0) - margin) / voxel)
     hi = np.ceil((p.max(axis=0) + margin) / voxel)
     return lo * voxel, tuple(int(n) for n in (hi - lo + 1))
-
-
-@dataclass
-class Mesh:
-    """vertices (M,3) float32, triangles (T,3) int32 into them, colors (M,3) float32 or None, normals (M,3) float32 or None (nobody
-    fills them in unasked: mesh.normals = mesh.vertex_normals()); numpy arrays from a volume on the host, GPU tensors from one on a
-    GPU.  write_ply(path, mesh.vertices, mesh.colors, faces=mesh.triangles, normals=mesh.normals) saves it."""
-    vertices: object
-    triangles: object
-    colors: object = None
-    normals: object = None
-
-    def render(self, intrinsics, poses, size, **kw):
-        """-> RenderResult: the mesh seen from V views of one size (render.render_mesh; colors=True renders the mesh's own)."""
-        from .render import render_mesh
-        return render_mesh(self, intrinsics, poses, size, **kw)
-
-    def components(self):
-        """-> MeshComponents: the connected components with their counts and areas (mesh_clean.mesh_components)."""
-        from .mesh_clean import mesh_components
-        return mesh_components(self)
-
-    def clean(self, **kw):
-        """-> Mesh without the components that fail min_triangles=, min_area= or keep_largest= (mesh_clean.clean_mesh); with
-        attributes= or details=True a CleanResult, whose .mesh is that Mesh."""
-        from .mesh_clean import clean_mesh
-        return clean_mesh(self, **kw)
-
-    def simplify(self, cell, **kw):
-        """-> Mesh with one vertex per occupied cell of edge `cell`, placed by the cell's quadric (mesh_simplify.simplify_mesh:
-        placement=, regularisation=, origin=, unique=, remove_unreferenced=); with attributes= or details=True a SimplifyResult,
-        whose .mesh is that Mesh."""
-        from .mesh_simplify import simplify_mesh
-        return simplify_mesh(self, cell, **kw)
-
-    def vertex_normals(self):
-        """-> (M,3) float32: the area-weighted vertex normals (mesh_clean.vertex_normals)."""
-        from .mesh_clean import vertex_normals
-        return vertex_normals(self)
-
-    def distance(self, points, max_dist):
-        """-> (dist (n) float32, index (n) int32): the truncated distance of every point to the surface and its nearest triangle, -1
-        where nothing is nearer than max_dist (mesh_eval.mesh_distance)."""
-        from .mesh_eval import mesh_distance
-        return mesh_distance(points, self, max_dist)
-
-    def sample(self, spacing, colors=False):
-        """-> (points (S,3) float32, triangle (S) int32, colors (S,3) or None): covering samples of the surface, every surface point
-        within 2 spacing / 3 of one (mesh_eval.sample_mesh); colors=True interpolates the mesh's vertex colours."""
-        from .mesh_eval import sample_mesh
-        if colors and self.colors is None:
-            raise ValueError("Mesh.sample(colors=True): the mesh has no colours")
-        return sample_mesh(self, spacing, self.colors if colors else None)
 
 
 class TSDFVolume:
@@ -410,15 +357,12 @@ class TSDFVolume:
         """A volume around existing state: numpy arrays give a host volume (float32 copies), GPU tensors one on their device (taken
         as they are where they are contiguous float32)."""
         arrays = [a for a in (tsdf, weight, color) if a is not None]
-        places = {_place(a) for a in arrays}
-        if len(places) != 1:
-            raise ValueError(f"the state arrays are in different places ({sorted(places)})")
+        where = one_place(*arrays, what="state arrays")
         self = cls.__new__(cls)
-        place = places.pop()
-        self._setup(origin, voxel, trunc, max_weight, None if place == "host" else place)
+        self._setup(origin, voxel, trunc, max_weight, None if where == "host" else where)
         _check_state(tsdf, weight, color)
         if self.device is None:
-            take = lambda a: np.array(_to_numpy(a), dtype=np.float32)
+            take = lambda a: np.array(to_numpy(a), dtype=np.float32)
         else:
             import torch
             take = lambda a: a.to(torch.float32).contiguous()
@@ -445,15 +389,15 @@ class TSDFVolume:
                 raise ValueError(f"{len(opt)} {name} for {N} views")
         if N == 0:
             return self
-        Ks = [_to_numpy(K).astype(np.float64).reshape(3, 3) for K in intrinsics]
-        Ts = [_to_numpy(T).astype(np.float64).reshape(4, 4) for T in poses]
-        depths = [_map2d(d, f"depths[{i}]") for i, d in enumerate(depths)]
-        weights = None if weights is None else [_map2d(w, f"weights[{i}]") for i, w in enumerate(weights)]
+        Ks = [to_numpy(K).astype(np.float64).reshape(3, 3) for K in intrinsics]
+        Ts = [to_numpy(T).astype(np.float64).reshape(4, 4) for T in poses]
+        depths = [map2d(d, f"depths[{i}]") for i, d in enumerate(depths)]
+        weights = None if weights is None else [map2d(w, f"weights[{i}]") for i, w in enumerate(weights)]
         mine = "host" if self.device is None else str(self.device)
         for name, maps in (("depths", depths), ("weights", weights), ("images", images)):
             for i, a in enumerate(maps or []):
-                if _place(a) not in ("host", mine):
-                    raise ValueError(f"{name}[{i}] is on {_place(a)}, the volume on {mine}: move the maps to the volume's device first")
+                if place(a) not in ("host", mine):
+                    raise ValueError(f"{name}[{i}] is on {place(a)}, the volume on {mine}: move the maps to the volume's device first")
         for i, d in enumerate(depths):
             if weights is not None and tuple(weights[i].shape) != tuple(d.shape):
                 raise ValueError(f"weights[{i}]: shape {tuple(weights[i].shape)}, expected {tuple(d.shape)}")
@@ -470,7 +414,7 @@ class TSDFVolume:
             return self
         import torch
         from . import ops
-        up = lambda a: (a if _is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(self.device)
+        up = lambda a: (a if is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(self.device)
         table = torch.from_numpy(np.stack([compose_matrix(Ks[i], Ts[i], self.origin, self.voxel) for i in range(N)])
                                  .astype(np.float32)).to(self.device)
         use_images = images is not None and self.color is not None

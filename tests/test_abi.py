@@ -75,3 +75,50 @@ def test_product_library_never_reads_the_environment():
     for f in os.listdir(os.path.join(ROOT, "robustmvd_amd", "csrc")):
         if f.endswith((".hip", ".h")) and f != "mvd_api.hip":
             assert "getenv" not in open(os.path.join(ROOT, "robustmvd_amd", "csrc", f)).read(), f
+
+
+SYNTHETIC_HEADER = """
+#define MVD_ANSWER 42
+#define MVD_FLAG 0x10 /* hexadecimal */
+#define MVD_NOT_AN_INTEGER 1.5f
+typedef void* mvd_stream_t;
+const char* mvd_every_type(const float* a, float* const* b, const unsigned char* const* c, void* d, int e, long long f,
+                           size_t g, float h, double i, mvd_stream_t stream);
+size_t mvd_two_lines(int first, /* a comment, with a comma (and brackets) */
+                     const void* second);  // trailing
+int mvd_no_arguments(void);
+"""
+
+
+def test_signatures_are_derived_from_the_header_text():
+    from robustmvd_amd import _lib
+    sigs, consts = _lib.parse_header(SYNTHETIC_HEADER)
+    pp = ctypes.POINTER(ctypes.c_void_p)
+    assert sigs == {
+        "mvd_every_type": (ctypes.c_char_p, [ctypes.c_void_p, pp, pp, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong,
+                                             ctypes.c_size_t, ctypes.c_float, ctypes.c_double, ctypes.c_void_p]),
+        "mvd_two_lines": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_void_p]),
+        "mvd_no_arguments": (ctypes.c_int, []),
+    }
+    assert consts == {"ANSWER": 42, "FLAG": 16}
+
+
+@pytest.mark.parametrize("declaration", ["int mvd_takes_short(int n, short flag);", "short mvd_takes_short(int n);",
+                                         "int mvd_takes_short(const int n);", "int mvd_takes_short(unsigned n);",
+                                         "int mvd_takes_short(void (*callback)(int), int n);"])
+def test_an_unmapped_type_is_refused_by_name(declaration):
+    from robustmvd_amd import _lib
+    with pytest.raises(RuntimeError, match="mvd_takes_short"):
+        _lib.parse_header("int mvd_fine(int n);\n" + declaration)
+
+
+def test_every_integer_define_of_the_header_is_exposed():
+    from robustmvd_amd import _lib
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mvd.h")).read(), flags=re.S)
+    defines = re.findall(r"^#define MVD_(\w+)\s+(0x[0-9a-fA-F]+|\d+)\s*$", text, flags=re.M)
+    assert len(defines) >= 37
+    for name, value in defines:
+        assert getattr(_lib, name) == int(value, 0), name
+    for name in ("MVD_MAX_VIEWS", "MVD_CLOUD_MAX_THRESHOLDS", "MVD_CLOUD_PAIR_SUMS_PER_WORKGROUP"):
+        assert getattr(_lib, name) == getattr(_lib, name[4:])
+    assert _lib.VERSION == 100 and _lib.MESH_RENDER_MAX_SMALL == 64

@@ -110,7 +110,7 @@ def main():
         sc = event_ms(lambda: ops.cloud_scores(res["ab"][0], res["ab"][1], th, a), args.warmup, args.repeats, args.inner)
         # the voxel thinning's own entry on keys sorted beforehand (ops.voxel_downsample's launches without its sort and its read)
         voxel = float(np.float32(0.006 * 768 / H))
-        vkeys, vperm = ops._cloud_sorted(a, origin, 1.0 / voxel)
+        vkeys, vperm = ops.cloud_sorted(a, origin, 1.0 / voxel)
         vout = (torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
                 torch.empty(1, dtype=torch.int64, device=dev))
         vbytes = int(L.load().mvd_voxel_reduce_workspace_bytes(n))

@@ -138,9 +138,9 @@ def main():
     for mult in args.cells:
         cell = float(np.float32(mult * voxel))
         inv = 1.0 / cell
-        extent = ops._cloud_extent(v)
+        extent = ops.cloud_extent(v)
         o = extent[0].tolist()
-        t_keys = timed(lambda: ops._cloud_sorted(v, o, inv))
+        t_keys = timed(lambda: ops.cloud_sorted(v, o, inv))
         t_ids = host_ms(lambda: ops.mesh_cluster_ids(v, cell), args.warmup, args.repeats)
         cl = ops.mesh_cluster_ids(v, cell)
         K = cl.num_clusters

@@ -121,16 +121,16 @@ def main():
            f"--warmup {args.warmup} --repeats {args.repeats} --inner {args.inner}" + (" --small (REHEARSAL: not a measurement)" if args.small else ""),
            f"{n} source points onto {m} target points, radii {RADII}; ms = median (min, max) per call over HIP-event brackets", ""]
 
-    box = ops._cloud_extent(target)
+    box = ops.cloud_extent(target)
     pivot = 0.5 * (box[0] + box[1])
     grid = ops.cloud_grid(target, box[0].tolist(), float(np.float32(RADII[0])) * ops.CLOUD_CELL_MARGIN)
     for label, T in (("first iteration (identity, radius %g)" % RADII[0], np.eye(4)), ("last radius (T*, radius %g)" % RADII[-1], star)):
         radius = RADII[0] if T is not star else RADII[-1]
         moved = ops.cloud_transform(source, T)
-        perm = ops._cloud_sorted(moved, grid.origin, grid.inv)[1]
+        perm = ops.cloud_sorted(moved, grid.origin, grid.inv)[1]
         records = ops.cloud_transform_records(source, perm, T)
         index = ops.cloud_nearest_records(records, grid, radius)[1]
-        sort = event_ms(lambda: ops._cloud_sorted(ops.cloud_transform(source, T), grid.origin, grid.inv), args.warmup, args.repeats, args.inner)
+        sort = event_ms(lambda: ops.cloud_sorted(ops.cloud_transform(source, T), grid.origin, grid.inv), args.warmup, args.repeats, args.inner)
         move = event_ms(lambda: ops.cloud_transform_records(source, perm, T), args.warmup, args.repeats, args.inner)
         near = event_ms(lambda: ops.cloud_nearest_records(records, grid, radius), args.warmup, args.repeats, args.inner)
         s_pt = event_ms(lambda: ops.cloud_pair_sums(source, T, index, target, pivot), args.warmup, args.repeats, args.inner)
