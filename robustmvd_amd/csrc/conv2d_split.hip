@@ -63,6 +63,20 @@ struct C2Geom {
     static constexpr int ITEMS = PH * PW * U8;                 // staging items (pixel, 8-channel group)
     static constexpr int NIT = (ITEMS + 255) / 256;
     static_assert(2 * PLANE <= 80 * 1024, "patch exceeds half the LDS (two workgroups per CU)");
+    // THE patch layout, [8-channel group][row][column parity][column / S][PB]: LDS byte of patch pixel (py, px), group c8, in one
+    // term's plane.  Every staging store (item_loff, conv2d_split_kernel's own item loop) and the fragment reads (c2_tapoff) go through it.
+    static __device__ __forceinline__ int lds_byte(int py, int px, int c8) { return ((py * S + px % S) * PWS + px / S) * PB + c8 * C8S; }
+    // The persistent kernels' staging item it = (patch pixel it / U8, group it % U8), pixels row by row: its LDS byte, -1 past the patch ...
+    static __device__ __forceinline__ int item_loff(int it) {
+        const int pix = it / U8;
+        return it < ITEMS ? lds_byte(pix / PW, pix % PW, it % U8) : -1;
+    }
+    // ... and its offset (floats) in an Hi x Wi input plane with pixels xs floats apart whose pixel (iy0, ix0) is the patch's first:
+    // -1 past the patch or outside the image (= the padding).  The plane and the chunk's channel offset are the caller's.
+    static __device__ __forceinline__ long long item_goff(int it, int iy0, int ix0, int Hi, int Wi, int xs) {
+        const int pix = it / U8, iy = iy0 + pix / PW, ix = ix0 + pix % PW;
+        return (it < ITEMS && iy >= 0 && iy < Hi && ix >= 0 && ix < Wi) ? ((long long)iy * Wi + ix) * xs + it % U8 * 8 : -1;
+    }
 };
 // The first layer on a planar 3-channel image (7 x 7, stride 2): a pixel is 4 halves (r, g, b, 0) = 8 bytes, rows are stored as
 // they are (no parity planes), so the 16 bytes a lane reads are the TWO x-adjacent pixels of taps kx = 2g, 2g + 1 and a K step is
@@ -245,15 +259,50 @@ __device__ __forceinline__ void c2_tapoff(int (&tapoff)[STEPS], int g, int px16,
         } else {
             int unit = 4 * s + g;
             if (unit >= G::UNITS) unit = 0;  // meets zero weights
-            const int tap = unit / U8, c8 = unit % U8, ky = tap / KW, kx = tap % KW;
-            tapoff[s] = ((ky * S + kx % S) * G::PWS + kx / S + px16) * G::PB + c8 * G::C8S + row0 * G::ROWB;
+            // output pixel (row0, px16) reads patch pixel (ky + row0 S, kx + px16 S).  row0 is added outside lds_byte: inside it, the steps
+            // of each kernel row get a base register of their own, where now ONE lane-dependent base serves every step through the
+            // reads' offset fields (8 - 10 vector registers on the 9-step chunks)
+            const int tap = unit / U8, ky = tap / KW, kx = tap % KW;
+            tapoff[s] = G::lds_byte(ky, kx + px16 * S, unit % U8) + row0 * G::ROWB;
         }
     }
 }
-// one K step of a wave: its MTW pixel rows against its NTW weight fragments; activation fragments TWO pixel rows ahead (one row =
-// 3 NTW MFMAs = 48 .. 96 clocks: less than a conflicted LDS read)
-template <class G, int MTW, int NTW>
-__device__ __forceinline__ void c2_kstep(const char* a, const c2h8 (&wh)[NTW], const c2h8 (&wl)[NTW], c2f4 (&acc)[MTW][NTW]) {
+// the two fp16 terms of eight floats -> the same 16 bytes of the patch's hi and lo plane (`plane` bytes apart)
+__device__ __forceinline__ void c2_split_store(char* dst, int plane, float xsc, c2f4 v0, c2f4 v1) {
+    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
+    split2(xsc, v0[0], v0[1], h0, l0);
+    split2(xsc, v0[2], v0[3], h1, l1);
+    split2(xsc, v1[0], v1[1], h2, l2);
+    split2(xsc, v1[2], v1[3], h3, l3);
+    *reinterpret_cast<c2u4*>(dst) = c2u4{h0, h1, h2, h3};
+    *reinterpret_cast<c2u4*>(dst + plane) = c2u4{l0, l1, l2, l3};
+}
+// The persistent kernels' patch loads of one chunk (8 U8 channels at `chan`) of input plane z of the Di planes that start at plane
+// `img0` of x: EVERY staging item loads, so that the vmcnt counts are static - an item outside the image reads the plane's first
+// pixel, a plane outside the volume reads plane 0; both are zeroed when they are split.  Returns whether the plane exists.
+template <int NIT>
+__device__ __forceinline__ int c2_prefetch(const float* x, size_t img0, int z, int Di, size_t plane_floats, int chan, const int (&goff)[NIT],
+                                           c2f4 (&v0)[NIT], c2f4 (&v1)[NIT]) {
+    const int zlive = z >= 0 && z < Di;
+    const float* xim = x + (img0 + (zlive ? z : 0)) * plane_floats + chan;
+#pragma unroll
+    for (int k = 0; k < NIT; ++k) {
+        const float* a = xim + max(goff[k], 0);
+        v0[k] = *reinterpret_cast<const c2f4*>(a);
+        v1[k] = *reinterpret_cast<const c2f4*>(a + 4);
+    }
+    return zlive;
+}
+// the hi and lo fragment of one (cout tile, chunk, step) of the packed weights, w = the lane's 16 bytes of the hi fragment
+__device__ __forceinline__ void c2_wpair(const char* w, c2h8& hi, c2h8& lo) {
+    hi = *reinterpret_cast<const c2h8*>(w);
+    lo = *reinterpret_cast<const c2h8*>(w + 1024);
+}
+// The row pipeline of one K step: the wave's MTW pixel rows in turn, body(m, hi fragment, lo fragment) per row with the activation
+// fragments read TWO pixel rows ahead (one row = 3 NTW MFMAs = 48 .. 96 clocks: less than a conflicted LDS read).  a = the lane's
+// fragment of row 0 (patch + tapoff[s]).
+template <class G, int MTW, class Body>
+__device__ __forceinline__ void c2_rows(const char* a, Body&& body) {
     constexpr int PLANE = G::PLANE;
     c2h8 xh = *reinterpret_cast<const c2h8*>(a), xl = *reinterpret_cast<const c2h8*>(a + PLANE);
     c2h8 yh = xh, yl = xl;
@@ -269,6 +318,14 @@ __device__ __forceinline__ void c2_kstep(const char* a, const c2h8 (&wh)[NTW], c
             yh = *reinterpret_cast<const c2h8*>(a + (m + 2) * G::ROWB);
             yl = *reinterpret_cast<const c2h8*>(a + (m + 2) * G::ROWB + PLANE);
         }
+        body(m, ch, cl);
+        __builtin_amdgcn_sched_barrier(0);  // keeps the compiler from hoisting every row's reads to the top (registers)
+    }
+}
+// one K step of a wave: its MTW pixel rows against its NTW weight fragments
+template <class G, int MTW, int NTW>
+__device__ __forceinline__ void c2_kstep(const char* a, const c2h8 (&wh)[NTW], const c2h8 (&wl)[NTW], c2f4 (&acc)[MTW][NTW]) {
+    c2_rows<G, MTW>(a, [&](int m, c2h8 ch, c2h8 cl) __attribute__((always_inline)) {
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
             if (C2_KO & 2) {
@@ -279,8 +336,18 @@ __device__ __forceinline__ void c2_kstep(const char* a, const c2h8 (&wh)[NTW], c
             acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[t], ch, acc[m][t], 0, 0, 0);
             acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t], cl, acc[m][t], 0, 0, 0);
         }
-        __builtin_amdgcn_sched_barrier(0);  // keeps the compiler from hoisting every row's reads to the top (registers)
-    }
+    });
+}
+// the epilogue of cout tile `t` of a wave's MTW output rows in the persistent kernels: the first nrows of them are inside the image,
+// row m goes to o0 + m ostep.  (conv2d_split_kernel keeps its own loop: through this helper - either form of the row bound, forced
+// inline or not - the compiler computes its row conditions ahead of the chunk loop and keeps them as 64-bit masks, and the 16-row
+// tiles spill 13 - 31 scalar registers that they do not spill now.)
+template <int MTW, int NT>
+__device__ __forceinline__ void c2_finish_rows(const C2Params& p, size_t o0, size_t ostep, int nrows, int cb, const c2f4 (&acc)[MTW][NT], int t,
+                                               const C2Chan& k, float& amax) {
+#pragma unroll
+    for (int m = 0; m < MTW; ++m)
+        if (m < nrows) c2_finish(p, o0 + m * ostep, cb, acc[m][t], k, amax);
 }
 
 template <int KH, int KW, int S, int U8, int WM, int NTW, bool NCHW3>
@@ -303,7 +370,10 @@ __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
     float xsc, xsc_inv;
     split_xscale(p.xamax, xsc, xsc_inv);
 
-    // staging items of this thread: global offset (floats, without the chunk's channel offset; -1 = outside the image) and LDS byte
+    // staging items of this thread: global offset (floats, without the chunk's channel offset; -1 = outside the image) and LDS byte.
+    // (C2Geom::item_goff / item_loff say the same for the persistent kernels.  Called here, the compiler moves part of this arithmetic
+    // into the chunk loop ahead of the patch loads; with the loop written out, 28 of the 32 instances compile to the instructions they
+    // had before the shared helpers existed, profiles/c2_one_copy_resources.txt.)
     long long goff[G::NIT];
     int loff[G::NIT];
 #pragma unroll
@@ -319,7 +389,7 @@ __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
             loff[k] = live ? pix * PB : -1;
         } else {  // inside its input image; the image (plane) is the chunk's
             goff[k] = inside ? ((long long)iy * p.Wi + ix) * p.xs + c8 * 8 : -1;
-            loff[k] = live ? ((py * S + pxx % S) * G::PWS + pxx / S) * PB + c8 * G::C8S : -1;
+            loff[k] = live ? G::lds_byte(py, pxx, c8) : -1;
         }
     }
     int tapoff[STEPS];
@@ -344,10 +414,7 @@ __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
     const char* const wlast = wlane + ((size_t)max(c_end, c_begin + 1) * STEPS - 1) * 2048;
     if (c_begin < c_end) {
 #pragma unroll
-        for (int t = 0; t < NTW; ++t) {
-            wh[t] = *reinterpret_cast<const c2h8*>(wc + t * nt_stride);
-            wl[t] = *reinterpret_cast<const c2h8*>(wc + t * nt_stride + 1024);
-        }
+        for (int t = 0; t < NTW; ++t) c2_wpair(wc + t * nt_stride, wh[t], wl[t]);
     }
 
     for (int chunk = c_begin; chunk < c_end; ++chunk) {
@@ -375,18 +442,15 @@ __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
 #pragma unroll
             for (int k = 0; k < G::NIT; ++k) {
                 if (loff[k] < 0) continue;
-                unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-                split2(xsc, v0[k][0], v0[k][1], h0, l0);
-                split2(xsc, v0[k][2], v0[k][3], h1, l1);
-                if constexpr (NCHW3) {
+                if constexpr (NCHW3) {  // (r, g, b, 0): 8 bytes per term
+                    unsigned h0, h1, l0, l1;
+                    split2(xsc, v0[k][0], v0[k][1], h0, l0);
+                    split2(xsc, v0[k][2], v0[k][3], h1, l1);
                     *reinterpret_cast<unsigned long long*>(patch + loff[k]) = (unsigned long long)h0 | ((unsigned long long)h1 << 32);
                     *reinterpret_cast<unsigned long long*>(patch + loff[k] + PLANE) = (unsigned long long)l0 | ((unsigned long long)l1 << 32);
-                    continue;
+                } else {
+                    c2_split_store(patch + loff[k], PLANE, xsc, v0[k], v1[k]);
                 }
-                split2(xsc, v1[k][0], v1[k][1], h2, l2);
-                split2(xsc, v1[k][2], v1[k][3], h3, l3);
-                *reinterpret_cast<c2u4*>(patch + loff[k]) = c2u4{h0, h1, h2, h3};
-                *reinterpret_cast<c2u4*>(patch + loff[k] + PLANE) = c2u4{l0, l1, l2, l3};
             }
             __syncthreads();
         }
@@ -402,10 +466,7 @@ __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
                 const char* wn = wc + 2048;
                 wn = wn > wlast ? wlast : wn;
 #pragma unroll
-                for (int t = 0; t < NTW; ++t) {
-                    nh[t] = *reinterpret_cast<const c2h8*>(wn + t * nt_stride);
-                    nl[t] = *reinterpret_cast<const c2h8*>(wn + t * nt_stride + 1024);
-                }
+                for (int t = 0; t < NTW; ++t) c2_wpair(wn + t * nt_stride, nh[t], nl[t]);
                 wc += 2048;
             }
             c2_kstep<G, MTW, NTW>(patch + tapoff[s], wh, wl, acc);
@@ -440,7 +501,7 @@ __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
                 if (oy0 + wm * MTW + m < p.Ho) c2_finish(p, o0 + m * ostep, cb, acc[m][t], kc, amax);
         }
     }
-    if (p.yamax && !p.part) {
+    if (p.yamax && !p.part) {  // workgroup_max, spelled out: the call costs <3, 3, 2, 1, 4, 1> its 97th vector register (5 -> 4 waves)
         for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
         if (lane == 0) wmax[wv] = amax;
         __syncthreads();
@@ -467,7 +528,7 @@ template <int KH, int KW, int S, int U8, int WM, int NTW, int WAVES>
 __global__ void __launch_bounds__(256, WAVES) conv2d_split_persist_kernel(C2Params p) {
     const float amax_seen = absmax_seen(p.yamax);
     using G = C2Geom<KH, KW, S, U8, false>;
-    constexpr int WN = 4 / WM, MTW = 16 / WM, STEPS = G::STEPS, PB = G::PB, PLANE = G::PLANE;
+    constexpr int WN = 4 / WM, MTW = 16 / WM, STEPS = G::STEPS, PLANE = G::PLANE;
     extern __shared__ __attribute__((aligned(16))) char patch[];
     float* const wmax = reinterpret_cast<float*>(patch + 2 * PLANE);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -480,38 +541,23 @@ __global__ void __launch_bounds__(256, WAVES) conv2d_split_persist_kernel(C2Para
     split_xscale(p.xamax, xsc, xsc_inv);
     int loff[G::NIT];
 #pragma unroll
-    for (int k = 0; k < G::NIT; ++k) {
-        const int it = tid + 256 * k, pix = it / U8, c8 = it % U8, py = pix / G::PW, pxx = pix % G::PW;
-        loff[k] = it < G::ITEMS ? ((py * S + pxx % S) * G::PWS + pxx / S) * PB + c8 * G::C8S : -1;
-    }
+    for (int k = 0; k < G::NIT; ++k) loff[k] = G::item_loff(tid + 256 * k);
     int tapoff[STEPS];
     c2_tapoff<G, KW, S, U8, STEPS, false>(tapoff, g, px16, wm * MTW);
     const size_t nt_stride = (size_t)p.nchunks * STEPS * 2048;
     const size_t plane_floats = (size_t)p.Hi * p.Wi * p.xs;  // < 2^31 (launcher)
 
-    // the loads in flight: the patch of one chunk of one tile.  goff: offset in the plane (floats, -1 = outside the image)
+    // the loads in flight: the patch of one chunk of one tile.  goff: offset in the plane (floats, -1 = outside the image; 32 bits)
     int goff[G::NIT];
     c2f4 v0[G::NIT], v1[G::NIT];
     bool zlive;
     auto prefetch = [&](const C2Tile& tl, int chunk, bool new_tile) {
         if (new_tile) {
 #pragma unroll
-            for (int k = 0; k < G::NIT; ++k) {
-                const int it = tid + 256 * k, pix = it / U8, c8 = it % U8, py = pix / G::PW, pxx = pix % G::PW;
-                const int iy = tl.iy0 + py, ix = tl.ix0 + pxx;
-                const bool inside = it < G::ITEMS && iy >= 0 && iy < p.Hi && ix >= 0 && ix < p.Wi;
-                goff[k] = inside ? (iy * p.Wi + ix) * p.xs + c8 * 8 : -1;
-            }
+            for (int k = 0; k < G::NIT; ++k) goff[k] = (int)G::item_goff(tid + 256 * k, tl.iy0, tl.ix0, p.Hi, p.Wi, p.xs);
         }
         const int kd = chunk / p.nchunks_c, zi = tl.od * p.SD - p.pad_d + kd;  // the input plane of this chunk (0 for a 2-D layer)
-        zlive = zi >= 0 && zi < p.Di;
-        const float* xim = p.x + ((size_t)tl.bb * p.Di + (zlive ? zi : 0)) * plane_floats + (size_t)(chunk - kd * p.nchunks_c) * G::CC;
-#pragma unroll
-        for (int k = 0; k < G::NIT; ++k) {
-            const float* a = xim + max(goff[k], 0);
-            v0[k] = *reinterpret_cast<const c2f4*>(a);
-            v1[k] = *reinterpret_cast<const c2f4*>(a + 4);
-        }
+        zlive = c2_prefetch(p.x, (size_t)tl.bb * p.Di, zi, p.Di, plane_floats, (chunk - kd * p.nchunks_c) * G::CC, goff, v0, v1);
     };
 
     C2Tile tl = c2_tile<S>(p, t);
@@ -544,10 +590,7 @@ __global__ void __launch_bounds__(256, WAVES) conv2d_split_persist_kernel(C2Para
 #pragma unroll
             for (int s = 0; s < STEPS; ++s)
 #pragma unroll
-                for (int q = 0; q < NTW; ++q) {
-                    wh[s][q] = *reinterpret_cast<const c2h8*>(wc + s * 2048 + q * nt_stride);
-                    wl[s][q] = *reinterpret_cast<const c2h8*>(wc + s * 2048 + q * nt_stride + 1024);
-                }
+                for (int q = 0; q < NTW; ++q) c2_wpair(wc + s * 2048 + q * nt_stride, wh[s][q], wl[s][q]);
             __builtin_amdgcn_sched_barrier(0);
             const bool last = chunk + 1 == p.nchunks;
             const bool stage = !(C2_KO & 1) || chunk == 0;  // the knock-out: a tile's first chunk only, one patch load per tile
@@ -557,13 +600,7 @@ __global__ void __launch_bounds__(256, WAVES) conv2d_split_persist_kernel(C2Para
                 for (int k = 0; k < G::NIT; ++k) {
                     if (loff[k] < 0) continue;
                     if (goff[k] < 0 || !zlive) v0[k] = v1[k] = c2f4{0, 0, 0, 0};
-                    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-                    split2(xsc, v0[k][0], v0[k][1], h0, l0);
-                    split2(xsc, v0[k][2], v0[k][3], h1, l1);
-                    split2(xsc, v1[k][0], v1[k][1], h2, l2);
-                    split2(xsc, v1[k][2], v1[k][3], h3, l3);
-                    *reinterpret_cast<c2u4*>(patch + loff[k]) = c2u4{h0, h1, h2, h3};
-                    *reinterpret_cast<c2u4*>(patch + loff[k] + PLANE) = c2u4{l0, l1, l2, l3};
+                    c2_split_store(patch + loff[k], PLANE, xsc, v0[k], v1[k]);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -580,23 +617,16 @@ __global__ void __launch_bounds__(256, WAVES) conv2d_split_persist_kernel(C2Para
         for (int q = 0; q < NTW; ++q) {
             const int cb = (nt0 + q) * 16 + 4 * g;
             if (cb >= p.Cout || ox >= p.Wo) continue;
-            const size_t o0 = c2_out_offset(p, tl.bb, tl.od, tl.oy0 + wm * MTW, ox, tl.cls, cb), ostep = c2_row_step(p);
-#pragma unroll
-            for (int m = 0; m < MTW; ++m)
-                if (tl.oy0 + wm * MTW + m < p.Ho) c2_finish(p, o0 + m * ostep, cb, acc[m][q], kc[q], amax);
+            const int oy = tl.oy0 + wm * MTW;
+            c2_finish_rows(p, c2_out_offset(p, tl.bb, tl.od, oy, ox, tl.cls, cb), c2_row_step(p), p.Ho - oy, cb, acc, q, kc[q], amax);
         }
         if (!more) break;
         t = tn;
         tl = tnext;
     }
     if (p.yamax) {
-        for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-        if (lane == 0) wmax[wv] = amax;
-        __syncthreads();
-        if (tid == 0) {
-            amax = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-            raise_absmax_seen(p.yamax, amax, amax_seen);
-        }
+        amax = workgroup_max(amax, wmax, tid);
+        if (tid == 0) raise_absmax_seen(p.yamax, amax, amax_seen);
     }
 }
 
@@ -625,7 +655,7 @@ __global__ void __launch_bounds__(256, WAVES) conv3d_split_march_kernel(C2Params
     float* yamax = p.yamax;
     asm volatile("" : "+v"(amax_seen), "+v"(yamax));
     using G = C2Geom<3, 3, SD, 1, false>;
-    constexpr int MTW = 4, STEPS = G::STEPS, PB = G::PB, PLANE = G::PLANE, NSETS = SD == 1 ? 3 : 2;
+    constexpr int MTW = 4, STEPS = G::STEPS, PLANE = G::PLANE, NSETS = SD == 1 ? 3 : 2;
     extern __shared__ __attribute__((aligned(16))) char patch[];  // SLOTS x [term][patch] | 4 floats
     float* const wmax = reinterpret_cast<float*>(patch + SLOTS * 2 * PLANE);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -648,10 +678,8 @@ __global__ void __launch_bounds__(256, WAVES) conv3d_split_march_kernel(C2Params
     int loff[G::NIT], goff[G::NIT];  // LDS byte (-1: no item) and offset in the plane (floats, -1 = outside the image)
 #pragma unroll
     for (int k = 0; k < G::NIT; ++k) {
-        const int it = tid + 256 * k, py = it / G::PW, pxx = it % G::PW;
-        const int iy = iy0 + py, ix = ix0 + pxx;
-        loff[k] = it < G::ITEMS ? ((py * SD + pxx % SD) * G::PWS + pxx / SD) * PB : -1;
-        goff[k] = (it < G::ITEMS && iy >= 0 && iy < p.Hi && ix >= 0 && ix < p.Wi) ? (iy * p.Wi + ix) * p.xs : -1;
+        loff[k] = G::item_loff(tid + 256 * k);
+        goff[k] = (int)G::item_goff(tid + 256 * k, iy0, ix0, p.Hi, p.Wi, p.xs);
     }
     int tapoff[STEPS];
     c2_tapoff<G, 3, SD, 1, STEPS, false>(tapoff, g, px16, wv * MTW);
@@ -661,6 +689,7 @@ __global__ void __launch_bounds__(256, WAVES) conv3d_split_march_kernel(C2Params
     const C2Chan kc = c2_chan(p, cb, xsc_inv);
     // this lane's outputs of the run's first plane; consecutive planes are p.ys_img apart, rows ostep
     const size_t out0 = c2_out_offset(p, bb, od0, oy0 + wv * MTW, ox, 0, cb), ostep = c2_row_step(p);
+    const int nrows = p.Ho - (oy0 + wv * MTW);
     const float* const xrun = p.x + (size_t)bb * p.Di * plane_floats;
 
     c2h8 rh[WRES ? 3 : 1][STEPS], rl[WRES ? 3 : 1][STEPS];
@@ -668,32 +697,20 @@ __global__ void __launch_bounds__(256, WAVES) conv3d_split_march_kernel(C2Params
 #pragma unroll
         for (int kd = 0; kd < 3; ++kd)
 #pragma unroll
-            for (int s = 0; s < STEPS; ++s) {
-                rh[kd][s] = *reinterpret_cast<const c2h8*>(wlane + (kd * STEPS + s) * 2048);
-                rl[kd][s] = *reinterpret_cast<const c2h8*>(wlane + (kd * STEPS + s) * 2048 + 1024);
-            }
+            for (int s = 0; s < STEPS; ++s) c2_wpair(wlane + (kd * STEPS + s) * 2048, rh[kd][s], rl[kd][s]);
     }
 
     // the loads in flight: the patch of one (plane, chunk)
     c2f4 v0[G::NIT], v1[G::NIT];
     int zlive;  // (uniform flags are ints: one scalar register each)
-    auto prefetch = [&](int z, int c) __attribute__((always_inline)) {
-        zlive = z >= 0 && z < p.Di;
-        const float* xim = xrun + (size_t)(zlive ? z : 0) * plane_floats + c * 8;
-#pragma unroll
-        for (int k = 0; k < G::NIT; ++k) {
-            const float* a = xim + max(goff[k], 0);
-            v0[k] = *reinterpret_cast<const c2f4*>(a);
-            v1[k] = *reinterpret_cast<const c2f4*>(a + 4);
-        }
-    };
+    auto prefetch = [&](int z, int c) __attribute__((always_inline)) { zlive = c2_prefetch(xrun, 0, z, p.Di, plane_floats, c * 8, goff, v0, v1); };
     prefetch(z0, 0);
 
-    c2f4 acc[NSETS][MTW];
+    c2f4 acc[MTW][NSETS];  // [pixel row][set]
 #pragma unroll
-    for (int q = 0; q < NSETS; ++q)
+    for (int m = 0; m < MTW; ++m)
 #pragma unroll
-        for (int m = 0; m < MTW; ++m) acc[q][m] = c2f4{0, 0, 0, 0};
+        for (int q = 0; q < NSETS; ++q) acc[m][q] = c2f4{0, 0, 0, 0};
     float amax = 0.f;
     int item = 0;  // (plane, chunk) pairs staged so far: the LDS slot alternates with it
 
@@ -722,9 +739,7 @@ __global__ void __launch_bounds__(256, WAVES) conv3d_split_march_kernel(C2Params
                     if constexpr (WRES) {
                         wh[kd][s] = rh[kd][s]; wl[kd][s] = rl[kd][s];
                     } else {
-                        const char* const wc = wlane + (size_t)((kd * ncc + c) * STEPS + s) * 2048;
-                        wh[kd][s] = *reinterpret_cast<const c2h8*>(wc);
-                        wl[kd][s] = *reinterpret_cast<const c2h8*>(wc + 1024);
+                        c2_wpair(wlane + (size_t)((kd * ncc + c) * STEPS + s) * 2048, wh[kd][s], wl[kd][s]);
                     }
                 }
             }
@@ -735,13 +750,7 @@ __global__ void __launch_bounds__(256, WAVES) conv3d_split_march_kernel(C2Params
             for (int k = 0; k < G::NIT; ++k) {
                 if (loff[k] < 0) continue;
                 if (goff[k] < 0 || !zlive) v0[k] = v1[k] = c2f4{0, 0, 0, 0};
-                unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-                split2(xsc, v0[k][0], v0[k][1], h0, l0);
-                split2(xsc, v0[k][2], v0[k][3], h1, l1);
-                split2(xsc, v1[k][0], v1[k][1], h2, l2);
-                split2(xsc, v1[k][2], v1[k][3], h3, l3);
-                *reinterpret_cast<c2u4*>(slot + loff[k]) = c2u4{h0, h1, h2, h3};
-                *reinterpret_cast<c2u4*>(slot + loff[k] + PLANE) = c2u4{l0, l1, l2, l3};
+                c2_split_store(slot + loff[k], PLANE, xsc, v0[k], v1[k]);
             }
             __builtin_amdgcn_sched_barrier(0);
             ++item;
@@ -753,51 +762,35 @@ __global__ void __launch_bounds__(256, WAVES) conv3d_split_march_kernel(C2Params
             __syncthreads();
 #pragma unroll
             for (int s = 0; s < STEPS; ++s) {
-                // one K step: an activation fragment (two pixel rows ahead, as c2_kstep) against the served taps' weights
-                const char* const a = slot + tapoff[s];
-                c2h8 xh = *reinterpret_cast<const c2h8*>(a), xl = *reinterpret_cast<const c2h8*>(a + PLANE);
-                c2h8 yh = *reinterpret_cast<const c2h8*>(a + G::ROWB), yl = *reinterpret_cast<const c2h8*>(a + G::ROWB + PLANE);
-#pragma unroll
-                for (int m = 0; m < MTW; ++m) {
-                    const c2h8 ch = xh, cl = xl;
-                    xh = yh; xl = yl;
-                    if (m + 2 < MTW) {
-                        yh = *reinterpret_cast<const c2h8*>(a + (m + 2) * G::ROWB);
-                        yl = *reinterpret_cast<const c2h8*>(a + (m + 2) * G::ROWB + PLANE);
-                    }
+                // one K step: an activation fragment per pixel row against the served taps' weights
+                c2_rows<G, MTW>(slot + tapoff[s], [&](int m, c2h8 ch, c2h8 cl) __attribute__((always_inline)) {
                     if (full) {  // the sets are independent: their MFMAs interleave, each set in its own order
 #pragma unroll
                         for (int term = 0; term < 3; ++term)
 #pragma unroll
                             for (int kd = 0; kd < 3; ++kd)
                                 if (SET[kd] >= 0)
-                                    acc[max(SET[kd], 0)][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(term == 1 ? wl[kd][s] : wh[kd][s], term == 2 ? cl : ch,
-                                                                                                     acc[max(SET[kd], 0)][m], 0, 0, 0);
+                                    acc[m][max(SET[kd], 0)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(term == 1 ? wl[kd][s] : wh[kd][s], term == 2 ? cl : ch,
+                                                                                                     acc[m][max(SET[kd], 0)], 0, 0, 0);
                     } else {
 #pragma unroll
                         for (int kd = 0; kd < 3; ++kd)
                             if (on[kd]) {  // false for a tap the role does not serve
-                                c2f4& t = acc[max(SET[kd], 0)][m];
+                                c2f4& t = acc[m][max(SET[kd], 0)];
                                 t = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[kd][s], ch, t, 0, 0, 0);
                                 t = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[kd][s], ch, t, 0, 0, 0);
                                 t = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[kd][s], cl, t, 0, 0, 0);
                             }
                     }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                });
             }
         }
         // the output this plane completes (its kd = 2): epilogue, and the set starts over
         if constexpr (SET[2] >= 0) {
             if (on[2]) {
-                if (cb < p.Cout && ox < p.Wo) {
-                    const size_t ofs = out0 + (size_t)o[2] * p.ys_img;
+                if (cb < p.Cout && ox < p.Wo) c2_finish_rows(p, out0 + (size_t)o[2] * p.ys_img, ostep, nrows, cb, acc, SET[2], kc, amax);
 #pragma unroll
-                    for (int m = 0; m < MTW; ++m)
-                        if (oy0 + wv * MTW + m < p.Ho) c2_finish(p, ofs + m * ostep, cb, acc[SET[2]][m], kc, amax);
-                }
-#pragma unroll
-                for (int m = 0; m < MTW; ++m) acc[SET[2]][m] = c2f4{0, 0, 0, 0};
+                for (int m = 0; m < MTW; ++m) acc[m][SET[2]] = c2f4{0, 0, 0, 0};
             }
         }
     };
@@ -1064,31 +1057,39 @@ static void c2_plan_finish(const C2Shape& s, C2Plan& q, int B, int Hi, int Wi, i
     q.part_bytes = q.ksplit > 1 ? (size_t)q.ksplit * q.ncls * B * q.Ho * q.Wo * q.ncp * sizeof(float) : 0;
     q.persist = c2_persist_grid(s, q, Hi, Wi, xs);
 }
+// what both plans start with: the tiles of `images` Ho x Wo output images (planes and parity classes count as images) with `bn`
+// output channels per workgroup
+static void c2_plan_tiles(C2Plan& q, int Ho, int Wo, long long images, int cout, int bn) {
+    q.Ho = Ho; q.Wo = Wo; q.bn = bn;
+    q.tiles_y = (Ho + C2_TH - 1) / C2_TH;
+    q.tiles_x = (Wo + C2_TW - 1) / C2_TW;
+    q.nblocks = (cout + bn - 1) / bn;
+    q.ncp = q.nblocks * bn;
+    q.tiles = (long long)q.tiles_x * q.tiles_y * images * q.nblocks;
+}
 static C2Plan c2_plan(const C2Shape& s, int B, int Hi, int Wi, int cin_pad, int xs, int cout, int KH, int KW, int stride) {
     C2Plan q{};
-    if (s.transposed) { q.Ho = Hi; q.Wo = Wi; q.ncls = 4; }
-    else { q.Ho = (Hi + 2 * (KH / 2) - KH) / stride + 1; q.Wo = (Wi + 2 * (KW / 2) - KW) / stride + 1; q.ncls = 1; }
-    q.tiles_y = (q.Ho + C2_TH - 1) / C2_TH;
-    q.tiles_x = (q.Wo + C2_TW - 1) / C2_TW;
-    q.bn = c2_bn(cout);
-    q.nblocks = (cout + q.bn - 1) / q.bn;
-    q.ncp = q.nblocks * q.bn;
+    q.ncls = s.transposed ? 4 : 1;
+    if (s.transposed) c2_plan_tiles(q, Hi, Wi, 4LL * B, cout, c2_bn(cout));
+    else c2_plan_tiles(q, (Hi + 2 * (KH / 2) - KH) / stride + 1, (Wi + 2 * (KW / 2) - KW) / stride + 1, B, cout, c2_bn(cout));
     q.nchunks = cin_pad / (8 * s.U8);
-    q.tiles = (long long)q.tiles_x * q.tiles_y * B * q.nblocks * q.ncls;
     c2_plan_finish(s, q, B, Hi, Wi, xs);
     return q;
 }
 
+// every launch of the three main kernels: `lds` bytes of dynamic LDS (above 48 KiB the kernel has to be told), 256 threads
+template <class K>
+static int c2_launch_lds(K kern, int lds, long long grid, const C2Params& p, hipStream_t st, const char* what) {
+    if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+        return launch_status((std::string(what) + ": LDS attribute").c_str());
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, p);
+    return launch_status(what);
+}
 template <int KH, int KW, int S, int U8, int WM, int NTW, bool NCHW3>
 static int c2_launch(const C2Params& p, long long nblk, hipStream_t st) {
-    using G = C2Geom<KH, KW, S, U8, NCHW3>;
-    auto kern = conv2d_split_kernel<KH, KW, S, U8, WM, NTW, NCHW3>;
-    constexpr int lds = 2 * G::PLANE + 16;
+    constexpr int lds = 2 * C2Geom<KH, KW, S, U8, NCHW3>::PLANE + 16;
     static_assert(lds <= 80 * 1024, "two workgroups per CU");
-    if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-        return launch_status("conv2d_split: LDS attribute");
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), lds, st, p);
-    return launch_status("conv2d_split");
+    return c2_launch_lds(conv2d_split_kernel<KH, KW, S, U8, WM, NTW, NCHW3>, lds, nblk, p, st, "conv2d_split");
 }
 // the persistent form on a grid of `grid` workgroups; bounded to three waves per SIMD (168 registers) where a chunk's weight
 // fragments (8 STEPS registers), the prefetched patch (8 NIT) and the accumulators (64 / WM) fit that without spilling: the
@@ -1098,25 +1099,18 @@ template <int KH, int KW, int S, int U8, int WM>
 static int c2_launch_persist(const C2Params& p, long long grid, hipStream_t st) {
     using G = C2Geom<KH, KW, S, U8, false>;
     constexpr int WAVES = (G::STEPS == 3 && (G::NIT <= 2 || WM == 4)) ? 3 : 2;
-    auto kern = conv2d_split_persist_kernel<KH, KW, S, U8, WM, 1, WAVES>;
     constexpr int lds = 2 * G::PLANE + 16;
     static_assert(lds <= 48 * 1024, "the persistent form: three workgroups per CU, no LDS attribute");
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, p);
-    return launch_status("conv2d_split: persistent");
+    return c2_launch_lds(conv2d_split_persist_kernel<KH, KW, S, U8, WM, 1, WAVES>, lds, grid, p, st, "conv2d_split: persistent");
 }
 
 // the 3-D march on `grid` (tile, cout block, run) workgroups: two LDS slots (one barrier per chunk), two waves per SIMD, and with a
 // single channel chunk (Cin 8) all 27 taps' weight fragments resident
 template <int SD, int SLOTS, bool WRES>
 static int c3_launch_march_as(const C2Params& p, long long grid, hipStream_t st) {
-    using G = C2Geom<3, 3, SD, 1, false>;
-    auto kern = conv3d_split_march_kernel<SD, 2, SLOTS, WRES>;
-    constexpr int lds = SLOTS * 2 * G::PLANE + 16;
+    constexpr int lds = SLOTS * 2 * C2Geom<3, 3, SD, 1, false>::PLANE + 16;
     static_assert(lds <= 80 * 1024, "two workgroups per CU");
-    if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-        return launch_status("conv3d_split_march: LDS attribute");
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, p);
-    return launch_status("conv3d_split_march");
+    return c2_launch_lds(conv3d_split_march_kernel<SD, 2, SLOTS, WRES>, lds, grid, p, st, "conv3d_split_march");
 }
 static int c3_launch_march(const C2Shape& s, const C2Params& p, long long grid, hipStream_t st) {
     const bool wres = p.nchunks_c == 1;
@@ -1181,9 +1175,11 @@ static int c2_dispatch(const C2Shape& s, C2Params& p, int bn, long long nblk, lo
     return c2_launch_bn<3, 3, 1, 1, false>(p, bn, nblk, st);
 }
 
-// the tail of both entry points (`what`: the entry's name in messages; p.B, p.Ho, p.Wo, p.Cout, p.ncls, p.nchunks set): K split
-// only with a workspace for it, the grid limit, the main kernel, and the reduce kernel behind a split
+// the tail of both entry points (`what`: the entry's name in messages; p.B, p.Cout, p.nchunks set): the plan's grid goes into the
+// parameters, K split only with a workspace for it, the grid limit, the main kernel, and the reduce kernel behind a split
 static int c2_run(const char* what, const C2Shape& s, C2Params& p, const C2Plan& q, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    p.Ho = q.Ho; p.Wo = q.Wo; p.ncls = q.ncls;
+    p.tiles_x = q.tiles_x; p.tiles_y = q.tiles_y; p.nblocks = q.nblocks; p.ncp = q.ncp;
     int ksplit = q.ksplit;
     if (ksplit > 1 && (!workspace || workspace_bytes < q.part_bytes)) ksplit = 1;  // no workspace: the plain grid
     p.ksplit = ksplit;
@@ -1262,11 +1258,10 @@ int mvd_conv2d_split_f32(const float* x, const float* x_absmax, const void* pack
     const size_t fb = mvd::c2_frag_bytes(s, Cin_pad, Cout);
     p.eun = reinterpret_cast<const float*>(static_cast<const char*>(packed_w) + fb);
     const mvd::C2Plan q = mvd::c2_plan(s, B, Hi, Wi, Cin_pad, x_pixel_stride, Cout, KH, KW, stride);
-    p.Ho = q.Ho; p.Wo = q.Wo; p.ncls = q.ncls;
     if (s.transposed) {
         p.Hy = 2 * Hi; p.Wy = 2 * Wi; p.oy_mul = p.ox_mul = 2; p.pad_y = p.pad_x = 1;
     } else {
-        p.Hy = p.Ho; p.Wy = p.Wo; p.oy_mul = p.ox_mul = 1; p.pad_y = KH / 2; p.pad_x = KW / 2;
+        p.Hy = q.Ho; p.Wy = q.Wo; p.oy_mul = p.ox_mul = 1; p.pad_y = KH / 2; p.pad_x = KW / 2;
     }
     MVD_REQUIRE(y_channel_stride != 1 || Cout < 4 || (y_pixel_stride % 4 == 0 && y_row_stride % 4 == 0 && y_image_stride % 4 == 0),
                 "conv2d_split: channel-last output strides must be multiples of 4 floats");
@@ -1274,10 +1269,7 @@ int mvd_conv2d_split_f32(const float* x, const float* x_absmax, const void* pack
     p.ys_row = y_row_stride > 0 ? y_row_stride : (long long)p.Wy * y_pixel_stride;
     p.ys_img = y_image_stride > 0 ? y_image_stride : (long long)p.Hy * p.ys_row;
     p.wpk = static_cast<const char*>(packed_w);
-    p.cls_bytes = (long long)(fb / p.ncls);
-    p.tiles_y = q.tiles_y; p.tiles_x = q.tiles_x;
-    p.nblocks = q.nblocks;
-    p.ncp = q.ncp;
+    p.cls_bytes = (long long)(fb / q.ncls);
     return mvd::c2_run("conv2d_split", s, p, q, workspace, workspace_bytes, st);
 }
 
@@ -1345,21 +1337,18 @@ int mvd_pack_conv3d_weights_igemm(const float* w, int Cin, int Cout, int mode, v
 static mvd::C2Plan c3_plan(const mvd::C2Shape& s, int B, int Di, int Hi, int Wi, int Cin, int ncout, int mode, int* Do) {
     mvd::C2Plan q{};
     const int sd = mode == MVD_CONV3D_STRIDE2 ? 2 : 1;
-    *Do = Di / sd; q.Ho = Hi / sd; q.Wo = Wi / sd; q.ncls = 1;
-    q.tiles_y = (q.Ho + mvd::C2_TH - 1) / mvd::C2_TH;
-    q.tiles_x = (q.Wo + mvd::C2_TW - 1) / mvd::C2_TW;
-    q.bn = mvd::c2_bn(ncout);  // the packing rule's tile: any narrower one reads the same 16-channel fragments
-    const long long planes = (long long)q.tiles_x * q.tiles_y * B * *Do;
+    *Do = Di / sd; q.ncls = 1;
+    int bn = mvd::c2_bn(ncout);  // the packing rule's tile: any narrower one reads the same 16-channel fragments
+    mvd::c2_plan_tiles(q, Hi / sd, Wi / sd, (long long)B * *Do, ncout, bn);
+    const long long planes = q.tiles / q.nblocks;
     // a stride-1 level with too many tiles for a split of K (128+) and fewer than two per CU (conv6 of a 256-plane volume: 192):
     // narrower channel tiles, more workgroups, each with a shorter chain of MFMAs per staged chunk (conv6 45 -> 43 us in the frame
     // on 16 channels; the stride-2 layers are slower that way).  Smaller grids keep their tile and split K as before.
-    if (mode == MVD_CONV3D_STRIDE1 && !mvd::exp_env("MVD_C2_BN") && planes * ((ncout + q.bn - 1) / q.bn) >= 128)
-        while (q.bn > 16 && planes * ((ncout + q.bn - 1) / q.bn) < 512) q.bn /= 2;
-    if (mode != MVD_DECONV3D_STRIDE2 && s.U8 == 1 && mvd::c3_march_forced() > 1) q.bn = 16;  // experiments library: the march's tile
-    q.nblocks = (ncout + q.bn - 1) / q.bn;
-    q.ncp = q.nblocks * q.bn;
+    if (mode == MVD_CONV3D_STRIDE1 && !mvd::exp_env("MVD_C2_BN") && q.tiles >= 128)
+        while (bn > 16 && planes * ((ncout + bn - 1) / bn) < 512) bn /= 2;
+    if (mode != MVD_DECONV3D_STRIDE2 && s.U8 == 1 && mvd::c3_march_forced() > 1) bn = 16;  // experiments library: the march's tile
+    if (bn != q.bn) mvd::c2_plan_tiles(q, q.Ho, q.Wo, (long long)B * *Do, ncout, bn);
     q.nchunks = (mode == MVD_DECONV3D_STRIDE2 ? 2 : 3) * (Cin / (8 * s.U8));
-    q.tiles = planes * q.nblocks;
     mvd::c2_plan_finish(s, q, B * *Do, Hi, Wi, Cin);
     q.march_td = mode == MVD_DECONV3D_STRIDE2 ? 0 : mvd::c3_march_td(s, q, B, *Do, Hi, Wi, Cin);
     return q;
@@ -1393,11 +1382,11 @@ int mvd_conv3d_bn_relu_igemm_f32(const float* x, const float* x_absmax, const vo
     p.B = B * Do; p.Hi = Hi; p.Wi = Wi; p.xs = Cin; p.nchunks = q.nchunks;
     p.Di = Di; p.Do = Do; p.KD = tr ? 2 : 3; p.SD = mode == MVD_CONV3D_STRIDE2 ? 2 : 1; p.pad_d = tr ? 0 : 1; p.nchunks_c = Cin / (8 * s.U8);
     p.sub3d = tr ? 1 : 0; p.Cr = Cout; p.Dy = tr ? 2 * Di : Do;
-    p.Ho = q.Ho; p.Wo = q.Wo; p.Hy = tr ? 2 * Hi : q.Ho; p.Wy = tr ? 2 * Wi : q.Wo;
+    p.Hy = tr ? 2 * Hi : q.Ho; p.Wy = tr ? 2 * Wi : q.Wo;
     p.oy_mul = p.ox_mul = 1; p.pad_y = p.pad_x = tr ? 0 : 1;
-    p.Cout = ncout; p.ncp = q.ncp; p.ys = Cout; p.ycs = 1;
+    p.Cout = ncout; p.ys = Cout; p.ycs = 1;
     p.ys_row = (long long)p.Wy * Cout; p.ys_img = (long long)p.Hy * p.ys_row;
-    p.tiles_x = q.tiles_x; p.tiles_y = q.tiles_y; p.nblocks = q.nblocks; p.ncls = 1; p.cls_bytes = 0;
+    p.cls_bytes = 0;
     p.act = relu ? 2 : 0; p.slope = 0.f;
     MVD_REQUIRE(q.nblocks * (q.bn / 16) <= mvd::c2_ntiles(ncout), "conv3d_igemm: channel tile %d reads past the %d packed fragments", q.bn,
                 mvd::c2_ntiles(ncout));
