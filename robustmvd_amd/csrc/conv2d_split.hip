@@ -39,9 +39,6 @@
 
 namespace mvd {
 
-typedef _Float16 c2h8 __attribute__((ext_vector_type(8)));
-typedef float c2f4 __attribute__((ext_vector_type(4)));
-typedef unsigned int c2u4 __attribute__((ext_vector_type(4)));
 constexpr int C2_TH = 16, C2_TW = 16;  // output pixels per workgroup tile
 
 template <int KH, int KW, int S, int U8, bool IMG = false>
@@ -206,7 +203,7 @@ __device__ __forceinline__ size_t c2_out_offset(const C2Params& p, int b, int od
 }
 __device__ __forceinline__ size_t c2_row_step(const C2Params& p) { return (size_t)(p.sub3d ? 2 : p.oy_mul) * p.ys_row; }
 // epilogue of 4 consecutive output channels cb .. cb + 3 at output offset o (main kernel and split-K reduce)
-__device__ __forceinline__ void c2_finish(const C2Params& p, size_t o, int cb, c2f4 a, const C2Chan& k, float& amax) {
+__device__ __forceinline__ void c2_finish(const C2Params& p, size_t o, int cb, spf4 a, const C2Chan& k, float& amax) {
     float r4[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -222,7 +219,7 @@ __device__ __forceinline__ void c2_finish(const C2Params& p, size_t o, int cb, c
         r4[r] = v;
     }
     if (cb + 3 < p.Cout && p.ycs == 1) {
-        *reinterpret_cast<c2f4*>(p.y + o) = c2f4{r4[0], r4[1], r4[2], r4[3]};
+        *reinterpret_cast<spf4*>(p.y + o) = spf4{r4[0], r4[1], r4[2], r4[3]};
     } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
@@ -267,36 +264,21 @@ __device__ __forceinline__ void c2_tapoff(int (&tapoff)[STEPS], int g, int px16,
         }
     }
 }
-// the two fp16 terms of eight floats -> the same 16 bytes of the patch's hi and lo plane (`plane` bytes apart)
-__device__ __forceinline__ void c2_split_store(char* dst, int plane, float xsc, c2f4 v0, c2f4 v1) {
-    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-    split2(xsc, v0[0], v0[1], h0, l0);
-    split2(xsc, v0[2], v0[3], h1, l1);
-    split2(xsc, v1[0], v1[1], h2, l2);
-    split2(xsc, v1[2], v1[3], h3, l3);
-    *reinterpret_cast<c2u4*>(dst) = c2u4{h0, h1, h2, h3};
-    *reinterpret_cast<c2u4*>(dst + plane) = c2u4{l0, l1, l2, l3};
-}
 // The persistent kernels' patch loads of one chunk (8 U8 channels at `chan`) of input plane z of the Di planes that start at plane
 // `img0` of x: EVERY staging item loads, so that the vmcnt counts are static - an item outside the image reads the plane's first
 // pixel, a plane outside the volume reads plane 0; both are zeroed when they are split.  Returns whether the plane exists.
 template <int NIT>
 __device__ __forceinline__ int c2_prefetch(const float* x, size_t img0, int z, int Di, size_t plane_floats, int chan, const int (&goff)[NIT],
-                                           c2f4 (&v0)[NIT], c2f4 (&v1)[NIT]) {
+                                           spf4 (&v0)[NIT], spf4 (&v1)[NIT]) {
     const int zlive = z >= 0 && z < Di;
     const float* xim = x + (img0 + (zlive ? z : 0)) * plane_floats + chan;
 #pragma unroll
     for (int k = 0; k < NIT; ++k) {
         const float* a = xim + max(goff[k], 0);
-        v0[k] = *reinterpret_cast<const c2f4*>(a);
-        v1[k] = *reinterpret_cast<const c2f4*>(a + 4);
+        v0[k] = *reinterpret_cast<const spf4*>(a);
+        v1[k] = *reinterpret_cast<const spf4*>(a + 4);
     }
     return zlive;
-}
-// the hi and lo fragment of one (cout tile, chunk, step) of the packed weights, w = the lane's 16 bytes of the hi fragment
-__device__ __forceinline__ void c2_wpair(const char* w, c2h8& hi, c2h8& lo) {
-    hi = *reinterpret_cast<const c2h8*>(w);
-    lo = *reinterpret_cast<const c2h8*>(w + 1024);
 }
 // The row pipeline of one K step: the wave's MTW pixel rows in turn, body(m, hi fragment, lo fragment) per row with the activation
 // fragments read TWO pixel rows ahead (one row = 3 NTW MFMAs = 48 .. 96 clocks: less than a conflicted LDS read).  a = the lane's
@@ -304,19 +286,19 @@ __device__ __forceinline__ void c2_wpair(const char* w, c2h8& hi, c2h8& lo) {
 template <class G, int MTW, class Body>
 __device__ __forceinline__ void c2_rows(const char* a, Body&& body) {
     constexpr int PLANE = G::PLANE;
-    c2h8 xh = *reinterpret_cast<const c2h8*>(a), xl = *reinterpret_cast<const c2h8*>(a + PLANE);
-    c2h8 yh = xh, yl = xl;
+    sph8 xh = *reinterpret_cast<const sph8*>(a), xl = *reinterpret_cast<const sph8*>(a + PLANE);
+    sph8 yh = xh, yl = xl;
     if (MTW > 1) {
-        yh = *reinterpret_cast<const c2h8*>(a + G::ROWB);
-        yl = *reinterpret_cast<const c2h8*>(a + G::ROWB + PLANE);
+        yh = *reinterpret_cast<const sph8*>(a + G::ROWB);
+        yl = *reinterpret_cast<const sph8*>(a + G::ROWB + PLANE);
     }
 #pragma unroll
     for (int m = 0; m < MTW; ++m) {
-        const c2h8 ch = xh, cl = xl;
+        const sph8 ch = xh, cl = xl;
         xh = yh; xl = yl;
         if (m + 2 < MTW && !(C2_KO & 8)) {
-            yh = *reinterpret_cast<const c2h8*>(a + (m + 2) * G::ROWB);
-            yl = *reinterpret_cast<const c2h8*>(a + (m + 2) * G::ROWB + PLANE);
+            yh = *reinterpret_cast<const sph8*>(a + (m + 2) * G::ROWB);
+            yl = *reinterpret_cast<const sph8*>(a + (m + 2) * G::ROWB + PLANE);
         }
         body(m, ch, cl);
         __builtin_amdgcn_sched_barrier(0);  // keeps the compiler from hoisting every row's reads to the top (registers)
@@ -324,17 +306,15 @@ __device__ __forceinline__ void c2_rows(const char* a, Body&& body) {
 }
 // one K step of a wave: its MTW pixel rows against its NTW weight fragments
 template <class G, int MTW, int NTW>
-__device__ __forceinline__ void c2_kstep(const char* a, const c2h8 (&wh)[NTW], const c2h8 (&wl)[NTW], c2f4 (&acc)[MTW][NTW]) {
-    c2_rows<G, MTW>(a, [&](int m, c2h8 ch, c2h8 cl) __attribute__((always_inline)) {
+__device__ __forceinline__ void c2_kstep(const char* a, const sph8 (&wh)[NTW], const sph8 (&wl)[NTW], spf4 (&acc)[MTW][NTW]) {
+    c2_rows<G, MTW>(a, [&](int m, sph8 ch, sph8 cl) __attribute__((always_inline)) {
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
             if (C2_KO & 2) {
                 acc[m][t][0] += (float)ch[0] * (float)wh[t][0] + (float)cl[1] * (float)wl[t][1];
                 continue;
             }
-            acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t], ch, acc[m][t], 0, 0, 0);
-            acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[t], ch, acc[m][t], 0, 0, 0);
-            acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t], cl, acc[m][t], 0, 0, 0);
+            acc[m][t] = split_mfma3(wh[t], wl[t], ch, cl, acc[m][t]);
         }
     });
 }
@@ -343,7 +323,7 @@ __device__ __forceinline__ void c2_kstep(const char* a, const c2h8 (&wh)[NTW], c
 // inline or not - the compiler computes its row conditions ahead of the chunk loop and keeps them as 64-bit masks, and the 16-row
 // tiles spill 13 - 31 scalar registers that they do not spill now.)
 template <int MTW, int NT>
-__device__ __forceinline__ void c2_finish_rows(const C2Params& p, size_t o0, size_t ostep, int nrows, int cb, const c2f4 (&acc)[MTW][NT], int t,
+__device__ __forceinline__ void c2_finish_rows(const C2Params& p, size_t o0, size_t ostep, int nrows, int cb, const spf4 (&acc)[MTW][NT], int t,
                                                const C2Chan& k, float& amax) {
 #pragma unroll
     for (int m = 0; m < MTW; ++m)
@@ -400,41 +380,41 @@ __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
     const size_t nt_stride = (size_t)p.nchunks * STEPS * 2048;
     const char* wlane = p.wpk + (size_t)cls * p.cls_bytes + (size_t)nt0 * nt_stride + lane * 16;
 
-    c2f4 acc[MTW][NTW];
+    spf4 acc[MTW][NTW];
 #pragma unroll
     for (int m = 0; m < MTW; ++m)
 #pragma unroll
-        for (int t = 0; t < NTW; ++t) acc[m][t] = c2f4{0, 0, 0, 0};
+        for (int t = 0; t < NTW; ++t) acc[m][t] = spf4{0, 0, 0, 0};
 
     const int c_begin = ks * p.chunks_per_split, c_end = min(p.nchunks, c_begin + p.chunks_per_split);
 
     // weight fragments one K step ahead (steps and chunks are consecutive in the packed buffer); the last prefetch re-reads
-    c2h8 wh[NTW], wl[NTW];
+    sph8 wh[NTW], wl[NTW];
     const char* wc = wlane + (size_t)c_begin * STEPS * 2048;
     const char* const wlast = wlane + ((size_t)max(c_end, c_begin + 1) * STEPS - 1) * 2048;
     if (c_begin < c_end) {
 #pragma unroll
-        for (int t = 0; t < NTW; ++t) c2_wpair(wc + t * nt_stride, wh[t], wl[t]);
+        for (int t = 0; t < NTW; ++t) split_wpair(wc + t * nt_stride, wh[t], wl[t]);
     }
 
     for (int chunk = c_begin; chunk < c_end; ++chunk) {
         // ---- stage the chunk's patch: global fp32 -> two fp16 terms -> LDS -------------------------------------------------------
         if (!(C2_KO & 1) || chunk == c_begin) {
-            c2f4 v0[G::NIT], v1[G::NIT];
+            spf4 v0[G::NIT], v1[G::NIT];
             const int kd = chunk / p.nchunks_c, zi = od * p.SD - p.pad_d + kd;  // the input plane of this chunk (0 for a 2-D layer)
             const bool zlive = zi >= 0 && zi < p.Di;
             const float* xim = p.x + ((size_t)bb * p.Di + (zlive ? zi : 0)) * p.Hi * p.Wi * p.xs + (size_t)(chunk - kd * p.nchunks_c) * G::CC;
 #pragma unroll
             for (int k = 0; k < G::NIT; ++k) {
-                v0[k] = c2f4{0, 0, 0, 0};
-                v1[k] = c2f4{0, 0, 0, 0};
+                v0[k] = spf4{0, 0, 0, 0};
+                v1[k] = spf4{0, 0, 0, 0};
                 if (goff[k] >= 0 && zlive) {
                     if constexpr (NCHW3) {
                         const size_t pl = (size_t)p.Hi * p.Wi;
                         v0[k][0] = p.x[goff[k]]; v0[k][1] = p.x[goff[k] + pl]; v0[k][2] = p.x[goff[k] + 2 * pl];
                     } else {
-                        v0[k] = *reinterpret_cast<const c2f4*>(xim + goff[k]);
-                        v1[k] = *reinterpret_cast<const c2f4*>(xim + goff[k] + 4);
+                        v0[k] = *reinterpret_cast<const spf4*>(xim + goff[k]);
+                        v1[k] = *reinterpret_cast<const spf4*>(xim + goff[k] + 4);
                     }
                 }
             }
@@ -449,7 +429,7 @@ __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
                     *reinterpret_cast<unsigned long long*>(patch + loff[k]) = (unsigned long long)h0 | ((unsigned long long)h1 << 32);
                     *reinterpret_cast<unsigned long long*>(patch + loff[k] + PLANE) = (unsigned long long)l0 | ((unsigned long long)l1 << 32);
                 } else {
-                    c2_split_store(patch + loff[k], PLANE, xsc, v0[k], v1[k]);
+                    split8_store(patch + loff[k], PLANE, xsc, v0[k], v1[k]);
                 }
             }
             __syncthreads();
@@ -458,7 +438,7 @@ __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
         // ---- K steps: activation fragments one pixel row ahead, weights one step ahead ---------------------------------------------
 #pragma unroll
         for (int s = 0; s < STEPS; ++s) {
-            c2h8 nh[NTW], nl[NTW];
+            sph8 nh[NTW], nl[NTW];
             if (C2_KO & 4) {
 #pragma unroll
                 for (int t = 0; t < NTW; ++t) { nh[t] = wh[t]; nl[t] = wl[t]; }
@@ -466,7 +446,7 @@ __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
                 const char* wn = wc + 2048;
                 wn = wn > wlast ? wlast : wn;
 #pragma unroll
-                for (int t = 0; t < NTW; ++t) c2_wpair(wn + t * nt_stride, nh[t], nl[t]);
+                for (int t = 0; t < NTW; ++t) split_wpair(wn + t * nt_stride, nh[t], nl[t]);
                 wc += 2048;
             }
             c2_kstep<G, MTW, NTW>(patch + tapoff[s], wh, wl, acc);
@@ -488,7 +468,7 @@ __global__ void __launch_bounds__(256, 2) conv2d_split_kernel(C2Params p) {
                     const int oy = oy0 + wm * MTW + m;
                     if (oy >= p.Ho) continue;
                     const size_t pl = ((size_t)b * p.Ho + oy) * p.Wo + ox;
-                    *reinterpret_cast<c2f4*>(p.part + (((size_t)cls * p.ksplit + ks) * p.B * p.Ho * p.Wo + pl) * p.ncp + cb) = acc[m][t];
+                    *reinterpret_cast<spf4*>(p.part + (((size_t)cls * p.ksplit + ks) * p.B * p.Ho * p.Wo + pl) * p.ncp + cb) = acc[m][t];
                 }
             continue;
         }
@@ -549,7 +529,7 @@ __global__ void __launch_bounds__(256, WAVES) conv2d_split_persist_kernel(C2Para
 
     // the loads in flight: the patch of one chunk of one tile.  goff: offset in the plane (floats, -1 = outside the image; 32 bits)
     int goff[G::NIT];
-    c2f4 v0[G::NIT], v1[G::NIT];
+    spf4 v0[G::NIT], v1[G::NIT];
     bool zlive;
     auto prefetch = [&](const C2Tile& tl, int chunk, bool new_tile) {
         if (new_tile) {
@@ -577,20 +557,20 @@ __global__ void __launch_bounds__(256, WAVES) conv2d_split_persist_kernel(C2Para
         const bool more = tn < p.tiles;
         const C2Tile tnext = c2_tile<S>(p, more ? tn : t);
 
-        c2f4 acc[MTW][NTW];
+        spf4 acc[MTW][NTW];
 #pragma unroll
         for (int m = 0; m < MTW; ++m)
 #pragma unroll
-            for (int q = 0; q < NTW; ++q) acc[m][q] = c2f4{0, 0, 0, 0};
+            for (int q = 0; q < NTW; ++q) acc[m][q] = spf4{0, 0, 0, 0};
 
         for (int chunk = 0; chunk < p.nchunks; ++chunk) {
             // every weight fragment of the chunk, queued behind this chunk's patch (already in flight) and ahead of the next one's
-            c2h8 wh[STEPS][NTW], wl[STEPS][NTW];
+            sph8 wh[STEPS][NTW], wl[STEPS][NTW];
             const char* const wc = wlane + (size_t)chunk * STEPS * 2048;
 #pragma unroll
             for (int s = 0; s < STEPS; ++s)
 #pragma unroll
-                for (int q = 0; q < NTW; ++q) c2_wpair(wc + s * 2048 + q * nt_stride, wh[s][q], wl[s][q]);
+                for (int q = 0; q < NTW; ++q) split_wpair(wc + s * 2048 + q * nt_stride, wh[s][q], wl[s][q]);
             __builtin_amdgcn_sched_barrier(0);
             const bool last = chunk + 1 == p.nchunks;
             const bool stage = !(C2_KO & 1) || chunk == 0;  // the knock-out: a tile's first chunk only, one patch load per tile
@@ -599,8 +579,8 @@ __global__ void __launch_bounds__(256, WAVES) conv2d_split_persist_kernel(C2Para
 #pragma unroll
                 for (int k = 0; k < G::NIT; ++k) {
                     if (loff[k] < 0) continue;
-                    if (goff[k] < 0 || !zlive) v0[k] = v1[k] = c2f4{0, 0, 0, 0};
-                    c2_split_store(patch + loff[k], PLANE, xsc, v0[k], v1[k]);
+                    if (goff[k] < 0 || !zlive) v0[k] = v1[k] = spf4{0, 0, 0, 0};
+                    split8_store(patch + loff[k], PLANE, xsc, v0[k], v1[k]);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -692,25 +672,25 @@ __global__ void __launch_bounds__(256, WAVES) conv3d_split_march_kernel(C2Params
     const int nrows = p.Ho - (oy0 + wv * MTW);
     const float* const xrun = p.x + (size_t)bb * p.Di * plane_floats;
 
-    c2h8 rh[WRES ? 3 : 1][STEPS], rl[WRES ? 3 : 1][STEPS];
+    sph8 rh[WRES ? 3 : 1][STEPS], rl[WRES ? 3 : 1][STEPS];
     if constexpr (WRES) {
 #pragma unroll
         for (int kd = 0; kd < 3; ++kd)
 #pragma unroll
-            for (int s = 0; s < STEPS; ++s) c2_wpair(wlane + (kd * STEPS + s) * 2048, rh[kd][s], rl[kd][s]);
+            for (int s = 0; s < STEPS; ++s) split_wpair(wlane + (kd * STEPS + s) * 2048, rh[kd][s], rl[kd][s]);
     }
 
     // the loads in flight: the patch of one (plane, chunk)
-    c2f4 v0[G::NIT], v1[G::NIT];
+    spf4 v0[G::NIT], v1[G::NIT];
     int zlive;  // (uniform flags are ints: one scalar register each)
     auto prefetch = [&](int z, int c) __attribute__((always_inline)) { zlive = c2_prefetch(xrun, 0, z, p.Di, plane_floats, c * 8, goff, v0, v1); };
     prefetch(z0, 0);
 
-    c2f4 acc[MTW][NSETS];  // [pixel row][set]
+    spf4 acc[MTW][NSETS];  // [pixel row][set]
 #pragma unroll
     for (int m = 0; m < MTW; ++m)
 #pragma unroll
-        for (int q = 0; q < NSETS; ++q) acc[m][q] = c2f4{0, 0, 0, 0};
+        for (int q = 0; q < NSETS; ++q) acc[m][q] = spf4{0, 0, 0, 0};
     float amax = 0.f;
     int item = 0;  // (plane, chunk) pairs staged so far: the LDS slot alternates with it
 
@@ -730,7 +710,7 @@ __global__ void __launch_bounds__(256, WAVES) conv3d_split_march_kernel(C2Params
         }
         for (int c = 0; c < ncc; ++c) {
             // the weight fragments of the chunk's served taps, queued behind this chunk's patch and ahead of the next one's
-            c2h8 wh[3][STEPS], wl[3][STEPS];
+            sph8 wh[3][STEPS], wl[3][STEPS];
 #pragma unroll
             for (int kd = 0; kd < 3; ++kd) {
                 if (SET[kd] < 0) continue;
@@ -739,7 +719,7 @@ __global__ void __launch_bounds__(256, WAVES) conv3d_split_march_kernel(C2Params
                     if constexpr (WRES) {
                         wh[kd][s] = rh[kd][s]; wl[kd][s] = rl[kd][s];
                     } else {
-                        c2_wpair(wlane + (size_t)((kd * ncc + c) * STEPS + s) * 2048, wh[kd][s], wl[kd][s]);
+                        split_wpair(wlane + (size_t)((kd * ncc + c) * STEPS + s) * 2048, wh[kd][s], wl[kd][s]);
                     }
                 }
             }
@@ -749,8 +729,8 @@ __global__ void __launch_bounds__(256, WAVES) conv3d_split_march_kernel(C2Params
 #pragma unroll
             for (int k = 0; k < G::NIT; ++k) {
                 if (loff[k] < 0) continue;
-                if (goff[k] < 0 || !zlive) v0[k] = v1[k] = c2f4{0, 0, 0, 0};
-                c2_split_store(slot + loff[k], PLANE, xsc, v0[k], v1[k]);
+                if (goff[k] < 0 || !zlive) v0[k] = v1[k] = spf4{0, 0, 0, 0};
+                split8_store(slot + loff[k], PLANE, xsc, v0[k], v1[k]);
             }
             __builtin_amdgcn_sched_barrier(0);
             ++item;
@@ -763,7 +743,7 @@ __global__ void __launch_bounds__(256, WAVES) conv3d_split_march_kernel(C2Params
 #pragma unroll
             for (int s = 0; s < STEPS; ++s) {
                 // one K step: an activation fragment per pixel row against the served taps' weights
-                c2_rows<G, MTW>(slot + tapoff[s], [&](int m, c2h8 ch, c2h8 cl) __attribute__((always_inline)) {
+                c2_rows<G, MTW>(slot + tapoff[s], [&](int m, sph8 ch, sph8 cl) __attribute__((always_inline)) {
                     if (full) {  // the sets are independent: their MFMAs interleave, each set in its own order
 #pragma unroll
                         for (int term = 0; term < 3; ++term)
@@ -776,10 +756,8 @@ __global__ void __launch_bounds__(256, WAVES) conv3d_split_march_kernel(C2Params
 #pragma unroll
                         for (int kd = 0; kd < 3; ++kd)
                             if (on[kd]) {  // false for a tap the role does not serve
-                                c2f4& t = acc[m][max(SET[kd], 0)];
-                                t = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[kd][s], ch, t, 0, 0, 0);
-                                t = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[kd][s], ch, t, 0, 0, 0);
-                                t = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[kd][s], cl, t, 0, 0, 0);
+                                spf4& t = acc[m][max(SET[kd], 0)];
+                                t = split_mfma3(wh[kd][s], wl[kd][s], ch, cl, t);
                             }
                     }
                 });
@@ -790,7 +768,7 @@ __global__ void __launch_bounds__(256, WAVES) conv3d_split_march_kernel(C2Params
             if (on[2]) {
                 if (cb < p.Cout && ox < p.Wo) c2_finish_rows(p, out0 + (size_t)o[2] * p.ys_img, ostep, nrows, cb, acc, SET[2], kc, amax);
 #pragma unroll
-                for (int m = 0; m < MTW; ++m) acc[m][SET[2]] = c2f4{0, 0, 0, 0};
+                for (int m = 0; m < MTW; ++m) acc[m][SET[2]] = spf4{0, 0, 0, 0};
             }
         }
     };
@@ -827,17 +805,17 @@ __global__ void __launch_bounds__(256) c2_reduce_kernel(C2Params p) {
         // ksplit is a power of two >= 2: eight loads in flight, added in the fixed order ks = 0, 1, ...
         const float* pp = p.part + ((size_t)cls * p.ksplit * npix + pl) * p.ncp + cb;
         const size_t kstr = (size_t)npix * p.ncp;
-        c2f4 s = c2f4{0, 0, 0, 0};
+        spf4 s = spf4{0, 0, 0, 0};
         int ks = 0;
         for (; ks + 8 <= p.ksplit; ks += 8) {
-            c2f4 v[8];
+            spf4 v[8];
 #pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = *reinterpret_cast<const c2f4*>(pp + (size_t)(ks + q) * kstr);
+            for (int q = 0; q < 8; ++q) v[q] = *reinterpret_cast<const spf4*>(pp + (size_t)(ks + q) * kstr);
 #pragma unroll
             for (int q = 0; q < 8; ++q) s += v[q];
         }
         for (; ks + 2 <= p.ksplit; ks += 2) {
-            const c2f4 v0 = *reinterpret_cast<const c2f4*>(pp + (size_t)ks * kstr), v1 = *reinterpret_cast<const c2f4*>(pp + (size_t)(ks + 1) * kstr);
+            const spf4 v0 = *reinterpret_cast<const spf4*>(pp + (size_t)ks * kstr), v1 = *reinterpret_cast<const spf4*>(pp + (size_t)(ks + 1) * kstr);
             s += v0;
             s += v1;
         }

@@ -24,33 +24,36 @@
 // LDS: per term and 8-channel group a plane of 16-byte pixels, the planes a whole number of 256-byte bank rows apart: the 16
 // voxels of a fragment read 256 contiguous bytes per K group, which is the conflict-free case of ds_read_b128 (DESIGN.md, K4:
 // tools/micro/ldsbank.hip; the same layout as conv2d_split.hip's C8S planes).
+//
+// Two kernels, one tile per workgroup (deconv3d_split_kernel) and persistent (deconv3d_split_persist_kernel), that differ in their
+// SCHEDULE alone: what is requested when, which barriers, which waits, and how an output's offset is formed.  What they compute
+// has one definition each, above them: the tile decode (ds_tile), the per-lane channel constants (ds_chan), the weight fragments of
+// a (kd, kh) step (ds_load_w), a staging item, its place in the volume and its split-and-store (ds_item, ds_item_goff,
+// ds_stage_store), the (kd, kh) step (ds_kstep), the parities of an accumulator class (ds_class), the epilogue value and the lane's
+// max |y| (ds_finish, ds_lane_max) and the workgroup's one atomic (ds_raise); split8_store, split_wpair and split_mfma3 under them
+// are the family's (split_operand.h).
 #include "mvd_common.h"
 #include "split_operand.h"
 #include <stdlib.h>
 
-// experiments (EXPFLAGS=-DDS_TWO_PHASE=1): the two-phase epilogue of the max |y| variant in the plain variant too
-#ifndef DS_TWO_PHASE
-#define DS_TWO_PHASE 0
-#endif
-// experiments (EXPFLAGS=-DDS_STAGE_PIXMAJOR=1): the persistent form stages its slab pixel-major
-#ifndef DS_STAGE_PIXMAJOR
-#define DS_STAGE_PIXMAJOR 0
-#endif
-
 namespace mvd {
-
-typedef _Float16 dsh8 __attribute__((ext_vector_type(8)));
-typedef float dsf4 __attribute__((ext_vector_type(4)));
-typedef unsigned int dsu4 __attribute__((ext_vector_type(4)));
 
 constexpr int DS_TH = 4, DS_ROWS = DS_TH + 1;
 
-template <int CIN, int MT>
+// weight fragments (each a hi and a lo term of 64 lanes x 16 bytes) per tile of 16 GEMM rows
+static constexpr int ds_nfrag(int cin) { return cin == 16 ? 9 : 27 * (cin / 32); }
+static constexpr size_t DS_FRAG_BYTES = 2 * 64 * 16;
+
+// MT: 16-column tiles per wave (TW = 16 MT input columns)
+template <int CIN_, int MT_>
 struct DSGeom {
+    static constexpr int CIN = CIN_, MT = MT_;
     static constexpr bool PAIR = CIN == 16;
     static constexpr int TW = 16 * MT, COLS = TW + 1;
-    static constexpr int NG = CIN / 8;                       // 8-channel groups per voxel
+    static constexpr int NG = CIN / 8, C4 = CIN / 4;         // 8-channel groups, float4s per voxel
     static constexpr int KS = PAIR ? 1 : CIN / 32;           // K steps per tap
+    static constexpr int NKW = PAIR ? 1 : 3;                 // kw taps per (kd, kh) step (the pair form has them inside K)
+    static constexpr int NFRAG = ds_nfrag(CIN);
     static constexpr int PIX = 2 * DS_ROWS * COLS;           // staged pixels: [plane 2][row][col]
     static constexpr int GS = (PIX * 16 + 255) / 256 * 256;  // bytes between the planes of consecutive channel groups
     static constexpr int TERM = NG * GS;                     // the hi (or lo) part of the slab
@@ -58,9 +61,6 @@ struct DSGeom {
     static constexpr int ITEMS = PIX * NG, NIT = (ITEMS + 255) / 256;  // staging items (pixel, 8-channel group)
     static constexpr int NCLS = PAIR ? 4 : 8;                // accumulator classes: (d, h) parities, times w parities
 };
-// weight fragments (each a hi and a lo term of 64 lanes x 16 bytes) per tile of 16 GEMM rows
-static constexpr int ds_nfrag(int cin) { return cin == 16 ? 9 : 27 * (cin / 32); }
-static constexpr size_t DS_FRAG_BYTES = 2 * 64 * 16;
 
 // w (Cin, Cout, 3, 3, 3) -> [row tile][fragment][term hi, lo][lane 64][8 halves]; lane l = GEMM row l % 16, K values 8 (l / 16) .. + 7.
 // CIN = 32 / 64: row = output channel 16 nt + l % 16, fragment = (tap, K step ks), K = input channel - 32 ks.
@@ -105,153 +105,214 @@ struct DSParams {
     int tiles;                  // the persistent form: ncb tiles_w tiles_h Di B
 };
 
-// NT: 16-channel tiles per workgroup; MT: 16-column tiles per wave (TW = 16 MT input columns); YAMAX: also max |y| (a variant
-// of its own, as conv0_split_kernel's)
+// ---- what both kernels compute: G = DSGeom<CIN, MT>, NT = 16-channel tiles per workgroup ----
+
+// tile bx of the launch: channel block cb (innermost: the channel blocks of a tile run next to each other, one input through one
+// L2), input columns c0 .. + TW, rows r0 .. + 4, planes zd and zd + 1 of batch element b
+struct DSTile { int cb, b, zd, r0, c0; };
+template <class G>
+__device__ __forceinline__ DSTile ds_tile(const DSParams& p, int bx) {
+    DSTile tl;
+    tl.cb = bx % p.ncb; bx /= p.ncb;
+    tl.c0 = (bx % p.tiles_w) * G::TW; bx /= p.tiles_w;
+    tl.r0 = (bx % p.tiles_h) * DS_TH; bx /= p.tiles_h;
+    tl.zd = bx % p.Di;
+    tl.b = bx / p.Di;
+    return tl;
+}
+
+// per-lane constants of the lane's 4 output channels (4 q .. + 3 of each 16-channel tile of channel block cb): 2^(e + k_c) as TWO
+// factors 2^floor(s/2) 2^(s - floor(s/2)) (e + k_c alone can leave fp32's exponent range, 2^-157 for activations of 1e-30 and
+// weights of 1e-10, where the result does not), batch-norm scale and shift
+template <int NT>
+struct DSChan { float mul[NT][4], mul2[NT][4], sc[NT][4], sh[NT][4]; };
+template <class G, int NT>
+__device__ __forceinline__ void ds_chan(const DSParams& p, int cb, int q, float xsc_inv, DSChan<NT>& c) {
+    const float* __restrict__ eun = reinterpret_cast<const float*>(p.wpk + (size_t)p.ncb * NT * G::NFRAG * DS_FRAG_BYTES);
+#pragma unroll
+    for (int n = 0; n < NT; ++n)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int row = (cb * NT + n) * 16 + q * 4 + k;
+            const int ch = G::PAIR ? (row & 7) : row;
+            const int se = (int)((__float_as_uint(eun[row]) >> 23) & 0xffu) + (int)((__float_as_uint(xsc_inv) >> 23) & 0xffu) - 254;
+            c.mul[n][k] = __uint_as_float((unsigned)(127 + (se >> 1)) << 23);
+            c.mul2[n][k] = __uint_as_float((unsigned)(127 + se - (se >> 1)) << 23);
+            c.sc[n][k] = p.scale[ch];
+            c.sh[n][k] = p.shift[ch];
+        }
+}
+
+// the weight fragments of (kd, kh) step `step` of channel block cb, in one batch: [kw][K step][16-channel tile][hi, lo]
+template <class G, int NT>
+__device__ __forceinline__ void ds_load_w(const DSParams& p, int cb, int lane, int step, sph8 (&dst)[G::NKW][G::KS][NT][2]) {
+    const char* __restrict__ wl = p.wpk + (size_t)cb * NT * G::NFRAG * DS_FRAG_BYTES + lane * 16;
+#pragma unroll
+    for (int kw = 0; kw < G::NKW; ++kw)
+#pragma unroll
+        for (int ks = 0; ks < G::KS; ++ks)
+#pragma unroll
+            for (int n = 0; n < NT; ++n)
+                split_wpair(wl + ((size_t)n * G::NFRAG + (step * G::NKW + kw) * G::KS + ks) * DS_FRAG_BYTES, dst[kw][ks][n][0], dst[kw][ks][n][1]);
+}
+
+// staging item e = (pixel e / NG, 8-channel group e % NG) (consecutive lanes read consecutive bytes and write planes a multiple of
+// 256 bytes apart), the pixels [plane 2][row][col]: where it goes in one term's half of the slab (-1: beyond the items) and which
+// voxel of a tile it is
+struct DSItem { int loff, pl, row, col, g; };
+template <class G>
+__device__ __forceinline__ DSItem ds_item(int e) {
+    const int g = e % G::NG, pix = e / G::NG;
+    const int col = pix % G::COLS, r = pix / G::COLS;
+    const int pl = r / DS_ROWS;
+    return DSItem{e < G::ITEMS ? g * G::GS + pix * 16 : -1, pl, r - pl * DS_ROWS, col, g};
+}
+// ... and its offset in float4s in its batch element's volume; live = it is an item and lies inside the volume, otherwise the
+// offset is 0 (both kernels load all the same and zero it when they split it)
+template <class G>
+__device__ __forceinline__ size_t ds_item_goff(const DSParams& p, const DSTile& tl, const DSItem& it, bool& live) {
+    const int plane = tl.zd + it.pl, gr = tl.r0 + it.row, gc = tl.c0 + it.col;
+    live = it.loff >= 0 && plane < p.Di && gr < p.hi && gc < p.wi;
+    return live ? (((size_t)plane * p.hi + gr) * p.wi + gc) * G::C4 + 2 * it.g : 0;
+}
+// ... and its eight floats into the slab as their two fp16 terms, zeros for an item outside the volume
+template <class G>
+__device__ __forceinline__ void ds_stage_store(char* slab, int loff, float xsc, spf4 v0, spf4 v1, bool live) {
+    if (loff >= 0) split8_store(slab + loff, G::TERM, xsc, v0, v1, live);
+}
+
+// this lane's fragment of GEMM column `vox` of the wave's row: channel group q of the K step (PAIR: group q & 1 of input column
+// vox + (q >> 1))
+template <class G>
+__device__ __forceinline__ const char* ds_lane_base(const char* slab, int wave, int vox, int q) {
+    return slab + (G::PAIR ? (q & 1) * G::GS + (q >> 1) * 16 : q * G::GS) + (wave * G::COLS + vox) * 16;
+}
+// (kd, kh) step `step` of a wave: taps (kd, kh, kw) read the staged input at offset (k == 0) per axis and add into the class with
+// bit (k != 1) per axis; w = that step's fragments
+template <class G, int NT>
+__device__ __forceinline__ void ds_kstep(int step, const char* lbase, const sph8 (&w)[G::NKW][G::KS][NT][2], spf4 (&acc)[G::NCLS][G::MT][NT]) {
+    constexpr int MT = G::MT;
+    const int kd = step / 3, kh = step % 3;
+    const int rowpix = ((kd == 0 ? DS_ROWS : 0) + (kh == 0)) * G::COLS;
+#pragma unroll
+    for (int kw = 0; kw < G::NKW; ++kw) {
+        const int cls = G::PAIR ? (((kd != 1) << 1) | (kh != 1)) : (((kd != 1) << 2) | ((kh != 1) << 1) | (kw != 1));
+        const int colpix = G::PAIR ? 0 : (kw == 0);
+#pragma unroll
+        for (int ks = 0; ks < G::KS; ++ks) {
+            sph8 xh[MT], xl[MT];
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                const char* a = lbase + ks * 4 * G::GS + (rowpix + colpix + m * 16) * 16;
+                xh[m] = *reinterpret_cast<const sph8*>(a);
+                xl[m] = *reinterpret_cast<const sph8*>(a + G::TERM);
+            }
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+#pragma unroll
+                for (int n = 0; n < NT; ++n) acc[cls][m][n] = split_mfma3(w[kw][ks][n][0], w[kw][ks][n][1], xh[m], xl[m], acc[cls][m][n]);
+        }
+    }
+}
+
+// class c -> the parities (pd, ph, pw) of its outputs: output voxel (2 zd + pd, 2 row + ph, 2 col + pw).  PAIR: a class is (pd, ph)
+// and pw = 0 here; the lane's rows are w-parity q >> 1, channels 4 (q & 1) .. + 3, which the kernels add
+template <class G>
+__device__ __forceinline__ void ds_class(int c, int& pd, int& ph, int& pw) {
+    pd = G::PAIR ? c >> 1 : c >> 2; ph = G::PAIR ? c & 1 : (c >> 1) & 1; pw = G::PAIR ? 0 : c & 1;
+}
+// the lane's float4 of 16-channel tile n: y = act(conv 2^(e + k_c) scale + shift) + skip.  (sk is a float4 and not an spf4: with the
+// skip values as a vector the compiler gives up the packed fp32 instructions of this whole chain)
+template <int NT>
+__device__ __forceinline__ spf4 ds_finish(const DSParams& p, spf4 a, const DSChan<NT>& c, int n, float4 sk) {
+    float r[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        // the two products are exact (powers of two) unless the result is a denormal
+        float val = fmaf(a[k] * c.mul[n][k] * c.mul2[n][k], c.sc[n][k], c.sh[n][k]);
+        if (p.relu) val = fmaxf(val, 0.f);
+        r[k] = val;
+    }
+    return spf4{r[0] + sk.x, r[1] + sk.y, r[2] + sk.z, r[3] + sk.w};
+}
+// max |y| over the lane's finite outputs so far
+__device__ __forceinline__ float ds_lane_max(float amax, spf4 out) {
+    return fmaxf(fmaxf(amax, fmaxf(finite_abs_or_zero(out[0]), finite_abs_or_zero(out[1]))),
+                 fmaxf(finite_abs_or_zero(out[2]), finite_abs_or_zero(out[3])));
+}
+// What the next split-operand layer scales its activations by: ONE atomic per workgroup.  wmax: the 16 bytes behind the slab, which
+// other waves may still read.  Against the slot as it was when the workgroup started (amax_seen, see raise_absmax_seen), and then
+// an atomic whose result nobody waits for: a second look at the slot (raise_absmax) is a dependent load at the very end of the
+// workgroup, and while the slot is still rising, in the first round of resident workgroups of every forward, all of them queue for
+// that one address.
+__device__ __forceinline__ void ds_raise(float amax, float* wmax, int tid, float* yamax, float amax_seen) {
+    const float m = workgroup_max(amax, wmax, tid);
+    if (tid == 0) {
+        if (m > amax_seen) atomicMax(reinterpret_cast<unsigned*>(yamax), __float_as_uint(m));
+    }
+}
+
+// One tile per workgroup.  Schedule: the first step's weights, the channel constants and the slab's loads go out together; one
+// barrier behind the staging; the weights of step s + 1 are requested ahead of the MFMAs of step s where both batches fit the
+// register file (AHEAD, as deconv3d_all_kernel); the skip values are read in the epilogue.  YAMAX: also max |y| (a variant of its
+// own, as conv0_split_kernel's), with the epilogue in two phases.
 template <int CIN, int NT, int MT, bool YAMAX>
 __global__ void __launch_bounds__(256) deconv3d_split_kernel(DSParams p) {
     const float amax_seen = absmax_seen(YAMAX ? p.yamax : nullptr);  // read now, used at the end (see raise_absmax_seen)
     using G = DSGeom<CIN, MT>;
     constexpr bool PAIR = G::PAIR;
-    constexpr int COLS = G::COLS, NG = G::NG, KS = G::KS, GS = G::GS, TERM = G::TERM, NCLS = G::NCLS, NFRAG = ds_nfrag(CIN);
+    constexpr int NKW = G::NKW, KS = G::KS, NCLS = G::NCLS, NIT = G::NIT;
     static_assert(!PAIR || NT == 1, "the pair form has one row tile");
     extern __shared__ __attribute__((aligned(16))) char dslab[];  // [term][channel group][plane 2][row][col] x 16 bytes
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int vox = lane & 15, q = lane >> 4;
-    int bx = blockIdx.x;
-    const int cb = bx % p.ncb; bx /= p.ncb;  // the channel blocks of a tile run next to each other: one input through one L2
-    const int tw = bx % p.tiles_w; bx /= p.tiles_w;
-    const int th = bx % p.tiles_h; bx /= p.tiles_h;
-    const int zd = bx % p.Di;
-    const int b = bx / p.Di;
-    const int r0 = th * DS_TH, c0 = tw * G::TW;
+    const DSTile tl = ds_tile<G>(p, blockIdx.x);
 
     float xsc, xsc_inv;
     split_xscale(p.xamax, xsc, xsc_inv);
 
-    // weight fragments of one (kd, kh) step in one batch, fetched one step ahead of the MFMAs that use them where both batches
-    // fit the register file (as deconv3d_all_kernel)
-    constexpr int NKW = PAIR ? 1 : 3;
-    const char* __restrict__ wl = p.wpk + (size_t)cb * NT * NFRAG * DS_FRAG_BYTES + lane * 16;
-    auto load_a = [&](int step, dsh8 (&dst)[NKW][KS][NT][2]) {
-#pragma unroll
-        for (int kw = 0; kw < NKW; ++kw)
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-                for (int n = 0; n < NT; ++n)
-#pragma unroll
-                    for (int t = 0; t < 2; ++t)
-                        dst[kw][ks][n][t] = *reinterpret_cast<const dsh8*>(
-                            wl + ((size_t)n * NFRAG + (step * NKW + kw) * KS + ks) * DS_FRAG_BYTES + t * 1024);
-    };
     constexpr bool AHEAD = 2 * NKW * KS * NT * 2 * 4 <= 112;
-    dsh8 af[NKW][KS][NT][2];
-    if constexpr (AHEAD) load_a(0, af);
-
-    // per-lane constants of this lane's 4 output channels: 2^(e + k_c) as TWO factors 2^floor(s/2) 2^(s - floor(s/2)) (e + k_c alone
-    // can leave fp32's exponent range, 2^-157 for activations of 1e-30 and weights of 1e-10, where the result does not),
-    // batch-norm scale and shift
-    float emul[NT][4], emul2[NT][4], esc[NT][4], esh[NT][4];
-    {
-        const float* __restrict__ eun = reinterpret_cast<const float*>(p.wpk + (size_t)p.ncb * NT * NFRAG * DS_FRAG_BYTES);
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int row = (cb * NT + n) * 16 + q * 4 + k;
-                const int ch = PAIR ? (row & 7) : row;
-                const int se = (int)((__float_as_uint(eun[row]) >> 23) & 0xffu) + (int)((__float_as_uint(xsc_inv) >> 23) & 0xffu) - 254;
-                emul[n][k] = __uint_as_float((unsigned)(127 + (se >> 1)) << 23);
-                emul2[n][k] = __uint_as_float((unsigned)(127 + se - (se >> 1)) << 23);
-                esc[n][k] = p.scale[ch];
-                esh[n][k] = p.shift[ch];
-            }
-    }
+    sph8 af[NKW][KS][NT][2];
+    if constexpr (AHEAD) ds_load_w<G, NT>(p, tl.cb, lane, 0, af);
+    DSChan<NT> kc;
+    ds_chan<G, NT>(p, tl.cb, q, xsc_inv, kc);
 
     // ---- stage input planes zd and zd + 1 (zero beyond the volume), split into the two fp16 terms on the way ----
     {
-        constexpr int NIT = G::NIT, C4 = CIN / 4;
-        const float4* __restrict__ x4 = reinterpret_cast<const float4*>(p.x) + (size_t)b * p.Di * p.hi * p.wi * C4;
-        float4 pf[NIT][2];
+        const spf4* __restrict__ x4 = reinterpret_cast<const spf4*>(p.x) + (size_t)tl.b * p.Di * p.hi * p.wi * G::C4;
+        spf4 pf[NIT][2];
         bool ok[NIT];
 #pragma unroll
         for (int i = 0; i < NIT; ++i) {
-            const int e = tid + 256 * i;
-            const int g = e % NG, pix = e / NG;
-            const int col = pix % COLS, r = pix / COLS;
-            const int pl = r / DS_ROWS, row = r - pl * DS_ROWS;
-            const int plane = zd + pl, gr = r0 + row, gc = c0 + col;
-            ok[i] = e < G::ITEMS && plane < p.Di && gr < p.hi && gc < p.wi;
-            const size_t o = ok[i] ? (((size_t)plane * p.hi + gr) * p.wi + gc) * C4 + 2 * g : 0;
+            const size_t o = ds_item_goff<G>(p, tl, ds_item<G>(tid + 256 * i), ok[i]);
             pf[i][0] = x4[o];
             pf[i][1] = x4[o + 1];
         }
 #pragma unroll
-        for (int i = 0; i < NIT; ++i) {
-            const int e = tid + 256 * i;
-            const int g = e % NG, pix = e / NG;
-            unsigned h[4], l[4];
-            split2(xsc, pf[i][0].x, pf[i][0].y, h[0], l[0]);
-            split2(xsc, pf[i][0].z, pf[i][0].w, h[1], l[1]);
-            split2(xsc, pf[i][1].x, pf[i][1].y, h[2], l[2]);
-            split2(xsc, pf[i][1].z, pf[i][1].w, h[3], l[3]);
-            dsu4 hv = {h[0], h[1], h[2], h[3]}, lv = {l[0], l[1], l[2], l[3]};
-            if (!ok[i]) { hv = dsu4{0, 0, 0, 0}; lv = dsu4{0, 0, 0, 0}; }
-            if (e < G::ITEMS) {
-                *reinterpret_cast<dsu4*>(dslab + g * GS + pix * 16) = hv;
-                *reinterpret_cast<dsu4*>(dslab + TERM + g * GS + pix * 16) = lv;
-            }
-        }
+        for (int i = 0; i < NIT; ++i) ds_stage_store<G>(dslab, ds_item<G>(tid + 256 * i).loff, xsc, pf[i][0], pf[i][1], ok[i]);
     }
     __syncthreads();
 
-    dsf4 acc[NCLS][MT][NT];
+    spf4 acc[NCLS][MT][NT];
 #pragma unroll
     for (int c = 0; c < NCLS; ++c)
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[c][m][n] = dsf4{0.f, 0.f, 0.f, 0.f};
+            for (int n = 0; n < NT; ++n) acc[c][m][n] = spf4{0.f, 0.f, 0.f, 0.f};
 
-    // this lane's fragment of GEMM column `vox` of the wave's row: channel group q of the K step (PAIR: group q & 1 of input
-    // column vox + (q >> 1))
-    const char* __restrict__ lbase = dslab + (PAIR ? (q & 1) * GS + (q >> 1) * 16 : q * GS) + (wave * COLS + vox) * 16;
-
+    const char* __restrict__ lbase = ds_lane_base<G>(dslab, wave, vox, q);
 #pragma unroll
     for (int step = 0; step < 9; ++step) {
-        const int kd = step / 3, kh = step % 3;
-        dsh8 af_next[NKW][KS][NT][2];
+        sph8 af_next[NKW][KS][NT][2];
         if constexpr (AHEAD) {
-            if (step + 1 < 9) load_a(step + 1, af_next);
+            if (step + 1 < 9) ds_load_w<G, NT>(p, tl.cb, lane, step + 1, af_next);
         } else {
-            load_a(step, af);
+            ds_load_w<G, NT>(p, tl.cb, lane, step, af);
         }
-        const int rowpix = ((kd == 0 ? DS_ROWS : 0) + (kh == 0)) * COLS;
-#pragma unroll
-        for (int kw = 0; kw < NKW; ++kw) {
-            const int cls = PAIR ? (((kd != 1) << 1) | (kh != 1)) : (((kd != 1) << 2) | ((kh != 1) << 1) | (kw != 1));
-            const int colpix = PAIR ? 0 : (kw == 0);
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                dsh8 xh[MT], xl[MT];
-#pragma unroll
-                for (int m = 0; m < MT; ++m) {
-                    const char* a = lbase + ks * 4 * GS + (rowpix + colpix + m * 16) * 16;
-                    xh[m] = *reinterpret_cast<const dsh8*>(a);
-                    xl[m] = *reinterpret_cast<const dsh8*>(a + TERM);
-                }
-#pragma unroll
-                for (int m = 0; m < MT; ++m)
-#pragma unroll
-                    for (int n = 0; n < NT; ++n) {
-                        acc[cls][m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[kw][ks][n][0], xh[m], acc[cls][m][n], 0, 0, 0);
-                        acc[cls][m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[kw][ks][n][1], xh[m], acc[cls][m][n], 0, 0, 0);
-                        acc[cls][m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[kw][ks][n][0], xl[m], acc[cls][m][n], 0, 0, 0);
-                    }
-            }
-        }
+        ds_kstep<G, NT>(step, lbase, af, acc);
         if constexpr (AHEAD) {
             if (step + 1 < 9) {
 #pragma unroll
@@ -267,40 +328,33 @@ __global__ void __launch_bounds__(256) deconv3d_split_kernel(DSParams p) {
         }
     }
 
-    // ---- epilogue: class (pd, ph, pw) -> output voxel (2 zd + pd, 2 row + ph, 2 col + pw); y = act(conv 2^(e + k_c) scale + shift) + skip.
-    // PAIR: the lane's rows are w-parity q >> 1, channels 4 (q & 1) .. + 3 ----
-    const int arow = r0 + wave;
+    // ---- epilogue: one 64-bit offset per output ----
+    const int arow = tl.r0 + wave;
     const bool row_ok = arow < p.hi;  // wave-uniform
     auto offset = [&](int c, int m, int n) {  // of the lane's float4 in y (and skip)
-        const int pd = PAIR ? c >> 1 : c >> 2, ph = PAIR ? c & 1 : (c >> 1) & 1, pw = PAIR ? q >> 1 : c & 1;
-        const size_t row_base = (((size_t)b * 2 * p.Di + 2 * zd + pd) * 2 * p.hi + 2 * arow + ph) * 2 * p.wi;
-        const int cbase = PAIR ? 4 * (q & 1) : (cb * NT + n) * 16 + q * 4;
-        return (row_base + 2 * (c0 + m * 16 + vox) + pw) * p.Cout + cbase;
+        int pd, ph, pw;
+        ds_class<G>(c, pd, ph, pw);
+        if (PAIR) pw = q >> 1;
+        const size_t row_base = (((size_t)tl.b * 2 * p.Di + 2 * tl.zd + pd) * 2 * p.hi + 2 * arow + ph) * 2 * p.wi;
+        const int cbase = PAIR ? 4 * (q & 1) : (tl.cb * NT + n) * 16 + q * 4;
+        return (row_base + 2 * (tl.c0 + m * 16 + vox) + pw) * p.Cout + cbase;
     };
     auto finish = [&](int c, int m, int n, size_t o) {
         float4 sk = make_float4(0.f, 0.f, 0.f, 0.f);
         if (p.skip) sk = *reinterpret_cast<const float4*>(p.skip + o);
-        float r[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            // the two products are exact (powers of two) unless the result is a denormal
-            float val = fmaf(acc[c][m][n][k] * emul[n][k] * emul2[n][k], esc[n][k], esh[n][k]);
-            if (p.relu) val = fmaxf(val, 0.f);
-            r[k] = val;
-        }
-        return dsf4{r[0] + sk.x, r[1] + sk.y, r[2] + sk.z, r[3] + sk.w};
+        return ds_finish(p, acc[c][m][n], kc, n, sk);
     };
-    if constexpr (!(YAMAX || DS_TWO_PHASE)) {
+    if constexpr (!YAMAX) {
         if (row_ok) {
 #pragma unroll
             for (int c = 0; c < NCLS; ++c)
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
-                    if (c0 + m * 16 + vox >= p.wi) continue;
+                    if (tl.c0 + m * 16 + vox >= p.wi) continue;
 #pragma unroll
                     for (int n = 0; n < NT; ++n) {
                         const size_t o = offset(c, m, n);
-                        *reinterpret_cast<dsf4*>(p.y + o) = finish(c, m, n, o);
+                        *reinterpret_cast<spf4*>(p.y + o) = finish(c, m, n, o);
                     }
                 }
         }
@@ -308,52 +362,39 @@ __global__ void __launch_bounds__(256) deconv3d_split_kernel(DSParams p) {
         // Two phases: every output value first (in place of its accumulator), then the stores.  max |y| is reduced between the
         // two: a barrier behind the stores would wait for them to be acknowledged (its release fence), and a wave that has
         // issued its stores otherwise just ends.
-        [[maybe_unused]] float amax = 0.f;  // max |y| over this lane's finite outputs
+        float amax = 0.f;
         if (row_ok) {
 #pragma unroll
             for (int c = 0; c < NCLS; ++c)
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
-                    if (c0 + m * 16 + vox >= p.wi) continue;
+                    if (tl.c0 + m * 16 + vox >= p.wi) continue;
 #pragma unroll
                     for (int n = 0; n < NT; ++n) {
-                        const dsf4 out = finish(c, m, n, offset(c, m, n));
-                        acc[c][m][n] = out;
-                        if constexpr (YAMAX)
-                            amax = fmaxf(fmaxf(amax, fmaxf(finite_abs_or_zero(out[0]), finite_abs_or_zero(out[1]))),
-                                         fmaxf(finite_abs_or_zero(out[2]), finite_abs_or_zero(out[3])));
+                        acc[c][m][n] = finish(c, m, n, offset(c, m, n));
+                        amax = ds_lane_max(amax, acc[c][m][n]);
                     }
                 }
         }
-        if constexpr (YAMAX) {  // what the next split-operand layer scales its activations by: ONE atomic per workgroup
-            // the four floats: 16 bytes behind the slab, which other waves may still read
-            const float m = workgroup_max(amax, reinterpret_cast<float*>(dslab + G::LDS), tid);
-            // Against the slot as it was when the workgroup started, and then an atomic whose result nobody waits for: a second
-            // look at the slot (raise_absmax) is a dependent load at the very end of the workgroup, and while the slot is still
-            // rising, in the first round of resident workgroups of every forward, all of them queue for that one address.
-            if (tid == 0) {
-                if (m > amax_seen) atomicMax(reinterpret_cast<unsigned*>(p.yamax), __float_as_uint(m));
-            }
-        }
+        ds_raise(amax, reinterpret_cast<float*>(dslab + G::LDS), tid, p.yamax, amax_seen);
         if (row_ok) {
 #pragma unroll
             for (int c = 0; c < NCLS; ++c)
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
-                    if (c0 + m * 16 + vox >= p.wi) continue;
+                    if (tl.c0 + m * 16 + vox >= p.wi) continue;
 #pragma unroll
-                    for (int n = 0; n < NT; ++n) *reinterpret_cast<dsf4*>(p.y + offset(c, m, n)) = acc[c][m][n];
+                    for (int n = 0; n < NT; ++n) *reinterpret_cast<spf4*>(p.y + offset(c, m, n)) = acc[c][m][n];
                 }
         }
     }
 }
 
 // The persistent, software-pipelined form: the same sums in the same order, bit for bit.  A workgroup walks the tiles t = blockIdx.x,
-// + gridDim.x, ... (a bound from the parameters alone: no ticket, no flag, no wait on another workgroup), decoded as above; with a
-// grid that is a multiple of ncb it keeps its channel block.  Once per workgroup: the activation scale, the per-lane channel
-// constants (again only where the channel block changes), and at the very end ONE workgroup_max
-// and atomic over everything the workgroup wrote: the lane maximum is carried across the tiles, so the epilogue has one phase and
-// no barrier.
+// + gridDim.x, ... (a bound from the parameters alone: no ticket, no flag, no wait on another workgroup); with a grid that is a
+// multiple of ncb it keeps its channel block.  Once per workgroup: the activation scale, the per-lane channel constants (again only
+// where the channel block changes), and at the very end ONE ds_raise over everything the workgroup wrote: the lane maximum is
+// carried across the tiles, so the epilogue has one phase and no barrier.
 //
 // Loads in flight.  vmcnt retires in order, so what a step waits for is requested ahead of what may stay outstanding:
 //   * weights: LA = 9 (the pair form: 18 fragments, 72 registers) keeps all of them for the life of the workgroup.  LA < 9 streams
@@ -367,16 +408,14 @@ __global__ void __launch_bounds__(256) deconv3d_split_kernel(DSParams p) {
 // For the wait counts to be static every load is unconditional: staging items outside the volume load the batch's first voxel and
 // are zeroed when they are split (a neighbour's inf or NaN cannot leak), lanes without an output load the skip of offset 0, a layer
 // without a skip reads y in its place and selects zero, and the last tile prefetches its own slab again.
-// PIXMAJOR: staging item e = (channel group, pixel) with the pixel running fastest, so that consecutive lanes write consecutive
-// 16-byte slots of one plane (no bank conflicts) and read 32 bytes each of consecutive voxels; otherwise the order of
-// deconv3d_split_kernel (consecutive lanes read consecutive bytes and write planes a multiple of 256 bytes apart).
-template <int CIN, int NT, int MT, bool YAMAX, int LA, int WAVES, bool SKIP_EARLY, bool PIXMAJOR>
+// Output offsets: a tile's scalar base plus offsets of 32 bits (with one 64-bit offset per output, as above, conv9 spilled 8 scalar
+// registers).
+template <int CIN, int NT, int MT, bool YAMAX, int LA, int WAVES, bool SKIP_EARLY>
 __global__ void __launch_bounds__(256, WAVES) deconv3d_split_persist_kernel(DSParams p) {
     const float amax_seen = absmax_seen(YAMAX ? p.yamax : nullptr);
     using G = DSGeom<CIN, MT>;
     constexpr bool PAIR = G::PAIR;
-    constexpr int COLS = G::COLS, NG = G::NG, KS = G::KS, GS = G::GS, TERM = G::TERM, NCLS = G::NCLS, NFRAG = ds_nfrag(CIN);
-    constexpr int NIT = G::NIT, C4 = CIN / 4, NKW = PAIR ? 1 : 3;
+    constexpr int NKW = G::NKW, KS = G::KS, NCLS = G::NCLS, NIT = G::NIT;
     static_assert(!PAIR || NT == 1, "the pair form has one row tile");
     static_assert(LA >= 1 && LA <= 9 && (LA < 9 || PAIR), "resident weights: the pair form (one channel block) only");
     static_assert(NIT <= 32, "one bit per staging item");
@@ -391,99 +430,45 @@ __global__ void __launch_bounds__(256, WAVES) deconv3d_split_persist_kernel(DSPa
     float xsc, xsc_inv;
     split_xscale(p.xamax, xsc, xsc_inv);
 
-    struct Tile { int cb, b, zd, r0, c0; };
-    auto tile_of = [&](int bx) {
-        Tile tl;
-        tl.cb = bx % p.ncb; bx /= p.ncb;
-        tl.c0 = (bx % p.tiles_w) * G::TW; bx /= p.tiles_w;
-        tl.r0 = (bx % p.tiles_h) * DS_TH; bx /= p.tiles_h;
-        tl.zd = bx % p.Di;
-        tl.b = bx / p.Di;
-        return tl;
-    };
-
-    // staging item i of this thread, e = tid + 256 i: where it goes in the slab (-1: beyond the items) and which voxel of a tile it
-    // is.  Worked out again where it is used (tz: a zero the compiler cannot see through), which is cheaper than 2 NIT registers
-    // held for the life of the workgroup.
-    struct Item { int loff, pl, row, col, g; };
-    auto item_of = [&](int i, int tz) {
-        const int e = tid + tz + 256 * i;
-        const int g = PIXMAJOR ? e / G::PIX : e % NG, pix = PIXMAJOR ? e % G::PIX : e / NG;
-        const int col = pix % COLS, r = pix / COLS;
-        const int pl = r / DS_ROWS;
-        return Item{e < G::ITEMS ? g * GS + pix * 16 : -1, pl, r - pl * DS_ROWS, col, g};
-    };
-    // the loads in flight for the next slab, and which of its items lie inside the volume
-    float4 pf[NIT][2];
+    // The loads in flight for the next slab, and which of its items lie inside the volume.  A thread's item i is e = tid + 256 i,
+    // worked out again where it is used (tz: a zero the compiler cannot see through), which is cheaper than 2 NIT registers held for
+    // the life of the workgroup.
+    spf4 pf[NIT][2];
     unsigned okm = 0;
-    auto prefetch = [&](const Tile& tl) {
-        const float4* __restrict__ x4 = reinterpret_cast<const float4*>(p.x) + (size_t)tl.b * p.Di * p.hi * p.wi * C4;
+    auto prefetch = [&](const DSTile& tl) {
+        const spf4* __restrict__ x4 = reinterpret_cast<const spf4*>(p.x) + (size_t)tl.b * p.Di * p.hi * p.wi * G::C4;
         okm = 0;
         int tz = 0;
         asm volatile("" : "+v"(tz));
 #pragma unroll
         for (int i = 0; i < NIT; ++i) {
-            const Item it = item_of(i, tz);
-            const int plane = tl.zd + it.pl, gr = tl.r0 + it.row, gc = tl.c0 + it.col;
-            const bool ok = it.loff >= 0 && plane < p.Di && gr < p.hi && gc < p.wi;
-            const size_t o = ok ? (((size_t)plane * p.hi + gr) * p.wi + gc) * C4 + 2 * it.g : 0;
+            bool ok;
+            const size_t o = ds_item_goff<G>(p, tl, ds_item<G>(tid + tz + 256 * i), ok);
             pf[i][0] = x4[o];
             pf[i][1] = x4[o + 1];
             okm |= (ok ? 1u : 0u) << i;
         }
     };
 
-    // weight fragments of step `step` of channel block cb
-    dsh8 w[9][NKW][KS][NT][2];
-    auto load_w = [&](int cb, int step) {
-        const char* __restrict__ wl = p.wpk + (size_t)cb * NT * NFRAG * DS_FRAG_BYTES + lane * 16;
-#pragma unroll
-        for (int kw = 0; kw < NKW; ++kw)
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-                for (int n = 0; n < NT; ++n)
-#pragma unroll
-                    for (int tm = 0; tm < 2; ++tm)
-                        w[step][kw][ks][n][tm] = *reinterpret_cast<const dsh8*>(
-                            wl + ((size_t)n * NFRAG + (step * NKW + kw) * KS + ks) * DS_FRAG_BYTES + tm * 1024);
-    };
-
-    // per-lane constants of this lane's 4 output channels (see deconv3d_split_kernel)
-    float emul[NT][4], emul2[NT][4], esc[NT][4], esh[NT][4];
-    auto load_consts = [&](int cb) {
-        const float* __restrict__ eun = reinterpret_cast<const float*>(p.wpk + (size_t)p.ncb * NT * NFRAG * DS_FRAG_BYTES);
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int row = (cb * NT + n) * 16 + q * 4 + k;
-                const int ch = PAIR ? (row & 7) : row;
-                const int se = (int)((__float_as_uint(eun[row]) >> 23) & 0xffu) + (int)((__float_as_uint(xsc_inv) >> 23) & 0xffu) - 254;
-                emul[n][k] = __uint_as_float((unsigned)(127 + (se >> 1)) << 23);
-                emul2[n][k] = __uint_as_float((unsigned)(127 + se - (se >> 1)) << 23);
-                esc[n][k] = p.scale[ch];
-                esh[n][k] = p.shift[ch];
-            }
-    };
-
-    const char* __restrict__ lbase = dslab + (PAIR ? (q & 1) * GS + (q >> 1) * 16 : q * GS) + (wave * COLS + vox) * 16;
+    sph8 w[9][NKW][KS][NT][2];  // the ring of weight fragments, by step
+    DSChan<NT> kc;
+    const char* __restrict__ lbase = ds_lane_base<G>(dslab, wave, vox, q);
     const float* __restrict__ skp = p.skip ? p.skip : p.y;
 
-    Tile tl = tile_of(t);
-    load_consts(tl.cb);
+    DSTile tl = ds_tile<G>(p, t);
+    ds_chan<G, NT>(p, tl.cb, q, xsc_inv, kc);
     int cb_have = tl.cb;
     prefetch(tl);
 #pragma unroll
-    for (int s = 0; s < LA; ++s) load_w(tl.cb, s);
+    for (int s = 0; s < LA; ++s) ds_load_w<G, NT>(p, tl.cb, lane, s, w[s]);
     [[maybe_unused]] float amax = 0.f;  // max |y| over this lane's finite outputs, all tiles
 
     for (;;) {
         const int tn = t + (int)gridDim.x;
         const bool more = tn < p.tiles;
-        Tile tnext;  // decoded where the requests for it begin (scalar registers)
+        DSTile tnext;  // decoded where the requests for it begin (scalar registers)
         if (tl.cb != cb_have) {
-            load_consts(tl.cb);
+            ds_chan<G, NT>(p, tl.cb, q, xsc_inv, kc);
             cb_have = tl.cb;
         }
 
@@ -493,7 +478,8 @@ __global__ void __launch_bounds__(256, WAVES) deconv3d_split_persist_kernel(DSPa
         const bool row_ok = arow < p.hi;  // wave-uniform
         const size_t obase = ((((size_t)tl.b * 2 * p.Di + 2 * tl.zd) * 2 * p.hi + 2 * arow) * 2 * p.wi + 2 * tl.c0) * p.Cout + (PAIR ? 0 : tl.cb * NT * 16);
         auto delta = [&](int c, int m, int n) {
-            const int pd = PAIR ? c >> 1 : c >> 2, ph = PAIR ? c & 1 : (c >> 1) & 1, pw = PAIR ? 0 : c & 1;
+            int pd, ph, pw;
+            ds_class<G>(c, pd, ph, pw);
             return ((pd * 2 * p.hi + ph) * 2 * p.wi + 32 * m + pw) * p.Cout + 16 * n;
         };
         const int lane_off = (2 * vox + (PAIR ? q >> 1 : 0)) * p.Cout + (PAIR ? 4 * (q & 1) : q * 4);
@@ -506,19 +492,7 @@ __global__ void __launch_bounds__(256, WAVES) deconv3d_split_persist_kernel(DSPa
         int tz = 0;
         asm volatile("" : "+v"(tz));
 #pragma unroll
-        for (int i = 0; i < NIT; ++i) {
-            const int lo = item_of(i, tz).loff;
-            if (lo < 0) continue;
-            unsigned h[4], l[4];
-            split2(xsc, pf[i][0].x, pf[i][0].y, h[0], l[0]);
-            split2(xsc, pf[i][0].z, pf[i][0].w, h[1], l[1]);
-            split2(xsc, pf[i][1].x, pf[i][1].y, h[2], l[2]);
-            split2(xsc, pf[i][1].z, pf[i][1].w, h[3], l[3]);
-            dsu4 hv = {h[0], h[1], h[2], h[3]}, lv = {l[0], l[1], l[2], l[3]};
-            if (!((okm >> i) & 1u)) { hv = dsu4{0, 0, 0, 0}; lv = dsu4{0, 0, 0, 0}; }
-            *reinterpret_cast<dsu4*>(dslab + lo) = hv;
-            *reinterpret_cast<dsu4*>(dslab + TERM + lo) = lv;
-        }
+        for (int i = 0; i < NIT; ++i) ds_stage_store<G>(dslab, ds_item<G>(tid + tz + 256 * i).loff, xsc, pf[i][0], pf[i][1], (okm >> i) & 1u);
         __builtin_amdgcn_sched_barrier(0);
 
         float4 sk[NCLS][MT][NT];
@@ -533,7 +507,7 @@ __global__ void __launch_bounds__(256, WAVES) deconv3d_split_persist_kernel(DSPa
         };
         auto request_skip_and_slab = [&]() {
             if constexpr (SKIP_EARLY) request_skip();
-            tnext = tile_of(more ? tn : t);
+            tnext = ds_tile<G>(p, more ? tn : t);
             prefetch(tnext);
         };
         if constexpr (LA == 9) {
@@ -542,84 +516,45 @@ __global__ void __launch_bounds__(256, WAVES) deconv3d_split_persist_kernel(DSPa
         }
         __syncthreads();
 
-        dsf4 acc[NCLS][MT][NT];
+        spf4 acc[NCLS][MT][NT];
 #pragma unroll
         for (int c = 0; c < NCLS; ++c)
 #pragma unroll
             for (int m = 0; m < MT; ++m)
 #pragma unroll
-                for (int n = 0; n < NT; ++n) acc[c][m][n] = dsf4{0.f, 0.f, 0.f, 0.f};
+                for (int n = 0; n < NT; ++n) acc[c][m][n] = spf4{0.f, 0.f, 0.f, 0.f};
 
 #pragma unroll
         for (int step = 0; step < 9; ++step) {
-            const int kd = step / 3, kh = step % 3;
             if constexpr (LA < 9) {
-                if (step + LA < 9) load_w(tl.cb, step + LA);
-                else load_w(tnext.cb, step + LA - 9);
+                if (step + LA < 9) ds_load_w<G, NT>(p, tl.cb, lane, step + LA, w[step + LA]);
+                else ds_load_w<G, NT>(p, tnext.cb, lane, step + LA - 9, w[step + LA - 9]);
                 if (step == 8 - LA) request_skip_and_slab();
                 __builtin_amdgcn_sched_barrier(0);
             }
-            const int rowpix = ((kd == 0 ? DS_ROWS : 0) + (kh == 0)) * COLS;
-#pragma unroll
-            for (int kw = 0; kw < NKW; ++kw) {
-                const int cls = PAIR ? (((kd != 1) << 1) | (kh != 1)) : (((kd != 1) << 2) | ((kh != 1) << 1) | (kw != 1));
-                const int colpix = PAIR ? 0 : (kw == 0);
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    dsh8 xh[MT], xl[MT];
-#pragma unroll
-                    for (int m = 0; m < MT; ++m) {
-                        const char* a = lbase + ks * 4 * GS + (rowpix + colpix + m * 16) * 16;
-                        xh[m] = *reinterpret_cast<const dsh8*>(a);
-                        xl[m] = *reinterpret_cast<const dsh8*>(a + TERM);
-                    }
-#pragma unroll
-                    for (int m = 0; m < MT; ++m)
-#pragma unroll
-                        for (int n = 0; n < NT; ++n) {
-                            acc[cls][m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[step][kw][ks][n][0], xh[m], acc[cls][m][n], 0, 0, 0);
-                            acc[cls][m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[step][kw][ks][n][1], xh[m], acc[cls][m][n], 0, 0, 0);
-                            acc[cls][m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[step][kw][ks][n][0], xl[m], acc[cls][m][n], 0, 0, 0);
-                        }
-                }
-            }
+            ds_kstep<G, NT>(step, lbase, w[step], acc);
         }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (!SKIP_EARLY) request_skip();
 
-        // ---- epilogue, as deconv3d_split_kernel's: y = act(conv 2^(e + k_c) scale + shift) + skip ----
+        // ---- epilogue: one phase, the stores go out as the values are ready ----
 #pragma unroll
         for (int c = 0; c < NCLS; ++c)
 #pragma unroll
             for (int m = 0; m < MT; ++m)
 #pragma unroll
                 for (int n = 0; n < NT; ++n) {
-                    float r[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        float val = fmaf(acc[c][m][n][k] * emul[n][k] * emul2[n][k], esc[n][k], esh[n][k]);
-                        if (p.relu) val = fmaxf(val, 0.f);
-                        r[k] = val;
-                    }
-                    const float4 s4 = p.skip ? sk[c][m][n] : make_float4(0.f, 0.f, 0.f, 0.f);
-                    const dsf4 out = {r[0] + s4.x, r[1] + s4.y, r[2] + s4.z, r[3] + s4.w};
+                    const spf4 out = ds_finish(p, acc[c][m][n], kc, n, p.skip ? sk[c][m][n] : make_float4(0.f, 0.f, 0.f, 0.f));
                     if (has[m]) {
-                        if constexpr (YAMAX)
-                            amax = fmaxf(fmaxf(amax, fmaxf(finite_abs_or_zero(out[0]), finite_abs_or_zero(out[1]))),
-                                         fmaxf(finite_abs_or_zero(out[2]), finite_abs_or_zero(out[3])));
-                        *reinterpret_cast<dsf4*>(p.y + obase + (unsigned)(delta(c, m, n) + lane_off)) = out;
+                        if constexpr (YAMAX) amax = ds_lane_max(amax, out);
+                        *reinterpret_cast<spf4*>(p.y + obase + (unsigned)(delta(c, m, n) + lane_off)) = out;
                     }
                 }
         if (!more) break;
         t = tn;
         tl = tnext;
     }
-    if constexpr (YAMAX) {  // ONE atomic per workgroup, against the slot as it was when the workgroup started
-        const float m = workgroup_max(amax, reinterpret_cast<float*>(dslab + G::LDS), tid);
-        if (tid == 0) {
-            if (m > amax_seen) atomicMax(reinterpret_cast<unsigned*>(p.yamax), __float_as_uint(m));
-        }
-    }
+    if constexpr (YAMAX) ds_raise(amax, reinterpret_cast<float*>(dslab + G::LDS), tid, p.yamax, amax_seen);
 }
 
 // The layers of the persistent form: the tile each runs at (the entry point's choice below) and, per layer, how far ahead its weights
@@ -659,8 +594,7 @@ static long long ds_persist_grid(int layer, long long tiles, int ncb, long long 
 template <int CIN, int NT, int MT, bool YAMAX, int LA, int WAVES, bool SKIP_EARLY>
 static int ds_launch_persist(const DSParams& p, long long grid, hipStream_t st) {
     using G = DSGeom<CIN, MT>;
-    hipLaunchKernelGGL((deconv3d_split_persist_kernel<CIN, NT, MT, YAMAX, LA, WAVES, SKIP_EARLY, DS_STAGE_PIXMAJOR != 0>), dim3((unsigned)grid), dim3(256),
-                       G::LDS + 16, st, p);
+    hipLaunchKernelGGL((deconv3d_split_persist_kernel<CIN, NT, MT, YAMAX, LA, WAVES, SKIP_EARLY>), dim3((unsigned)grid), dim3(256), G::LDS + 16, st, p);
     return launch_status("deconv3d_split: persistent");
 }
 
@@ -700,6 +634,7 @@ static int ds_launch(const DSParams& p, hipStream_t st) {
 static bool ds_shape_ok(int Cin, int Cout) {
     return ((Cin == 64 || Cin == 32) && Cout >= 16 && Cout <= 64 && Cout % 16 == 0) || (Cin == 16 && Cout == 8);
 }
+#define DS_SHAPES_BUILT "32 or 64 input channels with 16, 32, 48 or 64 output channels, or 16 -> 8, are built (got %d -> %d)"
 static int ds_row_tiles(int Cin, int Cout) { return Cin == 16 ? 1 : Cout / 16; }
 static size_t ds_frag_bytes(int Cin, int Cout) { return (size_t)ds_row_tiles(Cin, Cout) * mvd::ds_nfrag(Cin) * mvd::DS_FRAG_BYTES; }
 
@@ -711,8 +646,7 @@ size_t mvd_deconv3d_split_packed_weight_bytes(int Cin, int Cout) {
 
 int mvd_pack_deconv3d_weights_split(const float* w, int Cin, int Cout, void* packed, mvd_stream_t stream) {
     MVD_REQUIRE(w && packed, "pack_deconv3d_weights_split: NULL argument");
-    MVD_REQUIRE(ds_shape_ok(Cin, Cout), "pack_deconv3d_weights_split: 32 or 64 input channels with 16, 32, 48 or 64 output channels, or 16 -> 8, are built (got %d -> %d)",
-                Cin, Cout);
+    MVD_REQUIRE(ds_shape_ok(Cin, Cout), "pack_deconv3d_weights_split: " DS_SHAPES_BUILT, Cin, Cout);
     float* eun = reinterpret_cast<float*>(static_cast<char*>(packed) + ds_frag_bytes(Cin, Cout));
     const int rows = ds_row_tiles(Cin, Cout) * 16;
     mvd::split_wscale_launch(w, eun, Cin, Cout, 27, true, rows, rows, (hipStream_t)stream);
@@ -726,19 +660,24 @@ int mvd_deconv3d_bn_relu_f32_split(const float* x, const float* x_absmax, const 
                                    const float* skip, float* y, float* y_absmax, int B, int Di, int hi, int wi, int Cin, int Cout, int relu,
                                    mvd_stream_t stream) {
     MVD_REQUIRE(x && x_absmax && packed_w && scale && shift && y, "deconv3d_split: NULL argument");
-    MVD_REQUIRE(ds_shape_ok(Cin, Cout), "deconv3d_split: 32 or 64 input channels with 16, 32, 48 or 64 output channels, or 16 -> 8, are built (got %d -> %d)", Cin, Cout);
+    MVD_REQUIRE(ds_shape_ok(Cin, Cout), "deconv3d_split: " DS_SHAPES_BUILT, Cin, Cout);
     MVD_REQUIRE(B > 0 && Di > 0 && hi > 0 && wi > 0, "deconv3d_split: non-positive dimension");
     mvd::DSParams p{};
     p.x = x; p.xamax = x_absmax; p.wpk = (const char*)packed_w; p.scale = scale; p.shift = shift; p.skip = skip; p.y = y; p.yamax = y_absmax;
     p.B = B; p.Di = Di; p.hi = hi; p.wi = wi; p.Cout = Cout; p.relu = relu;
     hipStream_t st = (hipStream_t)stream;
-    // tile per layer, measured at the headline shapes (tools/bench_deconv_split.py); MVD_DS_CFG = 10 NT + MT picks another one in
-    // the experiments library
-    int cfg = 0;
-    if (const char* e = mvd::exp_env("MVD_DS_CFG")) cfg = atoi(e);
-    if (Cin == 16) return cfg % 10 == 3 ? mvd::ds_launch<16, 1, 3>(p, st) : mvd::ds_launch<16, 1, 2, true>(p, st);
-    if (Cin == 32) return cfg % 10 == 2 ? mvd::ds_launch<32, 1, 2>(p, st) : mvd::ds_launch<32, 1, 1, true>(p, st);
-    if (cfg / 10 == 2 && Cout % 32 == 0) return mvd::ds_launch<64, 2, 1>(p, st);
+    // tile per layer, measured at the headline shapes (tools/bench_deconv_split.py)
+#ifdef MVD_EXPERIMENTS  // DS_EXP: MVD_DS_CFG = 10 NT + MT picks one of the other tiles that were measured; no layer runs at one
+    if (const char* e = mvd::exp_env("MVD_DS_CFG")) {
+        const int cfg = atoi(e);
+        if (Cin == 16 && cfg % 10 == 3) return mvd::ds_launch<16, 1, 3>(p, st);
+        if (Cin == 32 && cfg % 10 == 2) return mvd::ds_launch<32, 1, 2>(p, st);
+        if (Cin == 64 && cfg / 10 == 2 && Cout % 32 == 0) return mvd::ds_launch<64, 2, 1>(p, st);
+    }
+#endif
+    if (Cin == 16) return mvd::ds_launch<16, 1, 2, true>(p, st);
+    if (Cin == 32) return mvd::ds_launch<32, 1, 1, true>(p, st);
     return mvd::ds_launch<64, 1, 1, true>(p, st);
 }
 }
+

@@ -7,7 +7,8 @@
 // hi = fp16(v), lo = fp16((v - hi) f); v - hi is exact in fp32.  f is the kernel's lo-term factor: 1 where the lo terms stay in
 // fp16's range as they are (the implicit-GEMM kernels), 2^11 where the kernel rescales them (conv0_split_kernel).  The epilogues
 // multiply by 2^(e + k_c); max |y| over the finite outputs (finite_abs_or_zero) reaches the next layer through raise_absmax
-// (mvd_common.h).
+// (mvd_common.h).  Below them, what the two implicit-GEMM files build their kernels from: the vector types, the store of a staged
+// item's two terms (split8_store), the hi / lo weight fragment pair (split_wpair) and the three-MFMA product (split_mfma3).
 #pragma once
 #include "mvd_common.h"
 
@@ -38,6 +39,37 @@ __device__ __forceinline__ void split2(float xsc, float a0, float a1, unsigned& 
     asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "+v"(lp) : "v"(t1), "s"(lo_factor));
     hi = hp;
     lo = lp;
+}
+
+// The implicit-GEMM kernels' vectors (conv2d_split.hip, deconv3d_split.hip): an MFMA operand fragment, an accumulator or four
+// consecutive floats, 16 bytes of packed halves
+typedef _Float16 sph8 __attribute__((ext_vector_type(8)));
+typedef float spf4 __attribute__((ext_vector_type(4)));
+typedef unsigned int spu4 __attribute__((ext_vector_type(4)));
+
+// the two fp16 terms of eight floats -> the same 16 bytes of a staged patch's hi and lo plane (`plane` bytes apart).  !live: zeros
+// instead, for an item outside the volume whose load went out all the same: nothing of what it read gets through, inf and NaN included
+__device__ __forceinline__ void split8_store(char* dst, int plane, float xsc, spf4 v0, spf4 v1, bool live = true) {
+    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
+    split2(xsc, v0[0], v0[1], h0, l0);
+    split2(xsc, v0[2], v0[3], h1, l1);
+    split2(xsc, v1[0], v1[1], h2, l2);
+    split2(xsc, v1[2], v1[3], h3, l3);
+    spu4 hv = {h0, h1, h2, h3}, lv = {l0, l1, l2, l3};
+    if (!live) { hv = spu4{0, 0, 0, 0}; lv = spu4{0, 0, 0, 0}; }
+    *reinterpret_cast<spu4*>(dst) = hv;
+    *reinterpret_cast<spu4*>(dst + plane) = lv;
+}
+// the hi and lo fragment of one K step of the packed weights, w = the lane's 16 bytes of the hi fragment (the lo one follows it)
+__device__ __forceinline__ void split_wpair(const char* w, sph8& hi, sph8& lo) {
+    hi = *reinterpret_cast<const sph8*>(w);
+    lo = *reinterpret_cast<const sph8*>(w + 1024);
+}
+// acc += w x for a 16 x 16 block and K = 32: w_hi x_hi + w_lo x_hi + w_hi x_lo, in this order, into the one accumulator
+__device__ __forceinline__ spf4 split_mfma3(sph8 wh, sph8 wl, sph8 xh, sph8 xl, spf4 acc) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh, acc, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl, acc, 0, 0, 0);
 }
 
 // the two fp16 terms of a weight already divided by its channel's 2^k_c (the pack kernels)

@@ -5,7 +5,8 @@ ahead, one max-|y| atomic at its end).
 Experiments library: the forms selected by MVD_DS_PERSIST (1 = the product rule, 3 = three workgroups, which cross plane, batch and
 channel-block boundaries and get unequal tile counts) and MVD_DS_LA (the layer's other look-ahead) are bit-identical to one tile per
 workgroup (MVD_DS_PERSIST=0), max |y| included, because every output is the same sum in the same order; with one inf and one NaN
-input exactly the same outputs are non-finite.
+input exactly the same outputs are non-finite.  The tiles no layer runs at (MVD_DS_CFG: three column tiles per wave, two at 32
+channels, two channel tiles per workgroup) give the bits of the layer's own tile, one tile per workgroup each.
 
 Product library: per channel pair a long, narrow volume with more tiles than any persistent grid holds (at most 256 CUs x 4
 workgroups = 1024), with a ragged row tile and a ragged column tile, against the float64 transposed convolution with the gate of
@@ -74,6 +75,38 @@ def test_persistent_forms_equal_one_tile_per_workgroup(cin, cout, shape, use_ski
             assert torch.equal(torch.isfinite(got.view(torch.float32)), finite), what
             if with_absmax:
                 assert torch.equal(amax, ref_amax), what
+
+
+# (cin, cout, MVD_DS_CFG = 10 NT + MT): the tiles of the experiments library that no layer runs at: MT = 3, MT = 2 at 32 channels, NT = 2
+OTHER_TILES = [(16, 8, 13), (32, 16, 12), (64, 32, 21)]
+# (1, 2, 5, 50): for 48 input columns per tile a whole tile whose halo column lies inside the volume and a tile with two live
+# columns, for 32 columns per tile 32 + 18; five rows leave a row tile with one live row
+TILE_SHAPES = SHAPES + [(1, 2, 5, 50)]
+
+
+@pytest.mark.parametrize("bad", [False, True])
+@pytest.mark.parametrize("shape", TILE_SHAPES)
+@pytest.mark.parametrize("cin,cout,cfg", OTHER_TILES)
+def test_other_tiles_equal_shipped_tile(cin, cout, cfg, shape, bad, dev, monkeypatch):
+    """One tile per workgroup (MVD_DS_PERSIST=0), with the skip and max |y|: the tile MVD_DS_CFG selects gives the bits of the
+    layer's own tile, max |y| included, and with one inf and one NaN input the same outputs are non-finite.  NT and MT decide which
+    wave holds an output, not its sum: the K content and the order of an output's MFMAs are fixed by (step, kw, K step)."""
+    L = _exp_or_skip()
+    c = case(cin, cout, shape, 1.0, 1.0, bad)
+    relu = not bad  # fmaxf(NaN, 0) is 0: without the ReLU the bad input reaches the output
+    monkeypatch.setenv("MVD_DS_PERSIST", "0")
+    monkeypatch.delenv("MVD_DS_LA", raising=False)
+    monkeypatch.delenv("MVD_DS_CFG", raising=False)
+    with L.use_experiments_library():
+        ref, ref_amax = _run(c, cin, cout, relu, True, True, dev)
+    finite = torch.isfinite(ref.view(torch.float32))
+    assert bool(finite.any()) and bool((~finite).any()) == bad
+    monkeypatch.setenv("MVD_DS_CFG", str(cfg))
+    with L.use_experiments_library():
+        got, amax = _run(c, cin, cout, relu, True, True, dev)
+    assert torch.equal(got, ref)  # as int32: NaN counts
+    assert torch.equal(torch.isfinite(got.view(torch.float32)), finite)
+    assert torch.equal(amax, ref_amax)
 
 
 # (cin, cout) -> (Di, hi, wi): Di planes of 2 x 2 tiles (conv11: 3 x 2), the last row tile and the last column tile ragged, and
