@@ -53,7 +53,7 @@ __global__ void __launch_bounds__(256) warp_variance_backward_kernel(WarpBwdPara
     const float4 k = *reinterpret_cast<const float4*>(p.key + b * img + self);
 
     auto locate = [&](int v, float depth) {
-        return sample_cell(sample_position_rcp(p.M + ((size_t)v * p.B + b) * 12, fx, fy, depth, sx, sy, xhi, yhi), W2, C, q * 4);
+        return sample_cell(sample_position<false>(p.M + ((size_t)v * p.B + b) * 12, fx, fy, depth, sx, sy, xhi, yhi), W2, C, q * 4);
     };
 
     // Planes in chunks of DZ: the chunk's means stay in registers, then each view walks the chunk with one PendingCell of tap

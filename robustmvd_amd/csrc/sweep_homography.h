@@ -1,9 +1,9 @@
 // The plane-homography family's sampling, defined ONCE: where a key pixel's sample on a depth plane lands in a source view, the
 // 2 x 2 cell and bilinear weights of that position, the 4-tap blend, the pending-cell scatter of the VJPs and the running
-// variance.  Users: the K3 backward (backward.hip scatter, warp_variance_backward_gather.hip gather), the generic sweep
-// reduction (sweep_modes.hip, all three kernels) and its backward (sweep_modes_backward.hip).  A VJP scatters into exactly
-// the taps its forward gathered, and the scatter and gather forms of one VJP agree bit for bit, because they call the functions
-// below.  Source maps are zero-bordered channel-last copies (h+3, w+3, C), pixel (y, x) at (y+1, x+1), W2 = w + 3.
+// variance.  Users: the K3 forward (warp_variance*.hip through warp_variance_common.h: position, cell weights, variance), the K3
+// backward (backward.hip scatter, warp_variance_backward_gather.hip gather), the generic sweep reduction (sweep_modes.hip, all
+// three kernels) and its backward (sweep_modes_backward.hip).  A VJP scatters into exactly the taps its forward gathered, and
+// the scatter and gather forms of one VJP agree bit for bit, because they call the functions below.  Source maps are zero-bordered channel-last copies (h+3, w+3, C), pixel (y, x) at (y+1, x+1), W2 = w + 3.
 // (K1's epipolar sweep has its own, different float chains: sweep_epipolar.h.)
 #pragma once
 #include "mvd_common.h"
@@ -13,18 +13,42 @@ namespace mvd {
 // Sampling position of key pixel (fx, fy) on the plane at `depth` in a source view with [R | t] = M (12 floats):
 // (X,Y,Z) = R (fx, fy, 1)^T depth + t, clamped to [-1, w] x [-1, h] (xhi = w, yhi = h).  A clamped coordinate (NaN -> -1) puts
 // every tap on the zero border (weight 0 on every interior tap), like the reference's zero padding.
-struct SamplePos { float ix, iy; };
+struct SamplePos { float ix, iy, Z; };  // Z: the sample's depth in the source view (the tile kernel's probe tests its sign)
 
-// K3's form, index = X * rcp(Z) * sx - 0.5: the folded arithmetic of the tuned forward tile kernel (warp_variance_tile.hip,
-// v_rcp_f32, 1 ulp), which K3's backward must reproduce to hit the forward's taps.
-__device__ __forceinline__ SamplePos sample_position_rcp(const float* __restrict__ M, float fx, float fy, float depth, float sx,
-                                                         float sy, float xhi, float yhi) {
-    const float ax = fmaf(M[0], fx, fmaf(M[1], fy, M[2])), ay = fmaf(M[4], fx, fmaf(M[5], fy, M[6]));
-    const float az = fmaf(M[8], fx, fmaf(M[9], fy, M[10]));
-    const float X = fmaf(ax, depth, M[3]), Y = fmaf(ay, depth, M[7]), Z = fmaf(az, depth, M[11]);
-    const float rz = __builtin_amdgcn_rcpf(Z);
-    float ix = fmaf(X * rz, sx, -0.5f), iy = fmaf(Y * rz, sy, -0.5f);
+// K3's two grid scales for a map n pixels a side: folded n/(n-1), EXACT the reference's divisor (n-1)/2.  Callers compute them once.
+template <bool EXACT>
+__device__ __forceinline__ float grid_scale(int n) {
+    return EXACT ? (float)(n - 1) / 2.0f : (float)n / (float)(n - 1);
+}
+
+// K3's form, forward and backward (sx = grid_scale<EXACT>(w), sy likewise of h).  Folded: index = X * rcp(Z) * sx - 0.5, i.e.
+// homo_warp's normalisation /((W-1)/2) - 1 followed by grid_sample's ((g+1)*W-1)/2 (utils.py:256-264) with 1/Z from v_rcp_f32
+// (1 ulp; within 1e-4 px of the exact chain) -- the tuned forward's arithmetic, which K3's backward calls too (<false>), so a
+// VJP hits the forward's taps.  EXACT (a template parameter: as a run-time branch its operands stay live through the callers'
+// loops, 16+ VGPRs): the reference's own chain, one rounding per step: R @ (x*d, y*d, d) + T (utils.py:246-250), IEEE
+// perspective divide, /((W-1)/2) - 1 (:256-257), then grid_sample's unnormalisation.
+template <bool EXACT>
+__device__ __forceinline__ SamplePos sample_position(const float* __restrict__ M, float fx, float fy, float depth, float sx, float sy,
+                                                     float xhi, float yhi) {
+    float ix, iy;
     SamplePos P;
+    if constexpr (EXACT) {
+        const float gx = fx * depth, gy = fy * depth;
+        const float X = ((M[0] * gx + M[1] * gy) + M[2] * depth) + M[3];
+        const float Y = ((M[4] * gx + M[5] * gy) + M[6] * depth) + M[7];
+        P.Z = ((M[8] * gx + M[9] * gy) + M[10] * depth) + M[11];
+        ix = unnormalize_coord((X / P.Z) / sx - 1.0f, xhi);
+        iy = unnormalize_coord((Y / P.Z) / sy - 1.0f, yhi);
+    } else {
+        const float ax = fmaf(M[0], fx, fmaf(M[1], fy, M[2])), ay = fmaf(M[4], fx, fmaf(M[5], fy, M[6]));
+        const float az = fmaf(M[8], fx, fmaf(M[9], fy, M[10]));
+        const float X = fmaf(ax, depth, M[3]), Y = fmaf(ay, depth, M[7]);
+        P.Z = fmaf(az, depth, M[11]);
+        const float rz = __builtin_amdgcn_rcpf(P.Z);
+        ix = fmaf(X * rz, sx, -0.5f);
+        iy = fmaf(Y * rz, sy, -0.5f);
+    }
+    // v_med3_f32: one instruction; with a NaN operand it returns the minimum of the others, i.e. -1 like fminf(fmaxf(NaN, -1), hi)
     P.ix = __builtin_amdgcn_fmed3f(ix, -1.0f, xhi);
     P.iy = __builtin_amdgcn_fmed3f(iy, -1.0f, yhi);
     return P;
@@ -39,19 +63,38 @@ __device__ __forceinline__ SamplePos sample_position_div(const float* __restrict
     const float X = fmaf(ax, depth, M[3]), Y = fmaf(ay, depth, M[7]), Z = fmaf(az, depth, M[11]);
     float ix = fmaf(X / Z, scale_x, bias), iy = fmaf(Y / Z, scale_y, bias);
     SamplePos P;
+    P.Z = Z;
     P.ix = __builtin_amdgcn_fmed3f(ix, -1.0f, xhi);
     P.iy = __builtin_amdgcn_fmed3f(iy, -1.0f, yhi);
     return P;
 }
 
+// Floor, fractions and the four bilinear weights (taps nw, ne, sw, se) of a clamped position; (xf, yf) + 1 is the first tap in the
+// bordered map.  Every K3 kernel and sample_cell take them from here; what each makes of (xf, yf) as an offset stays with the
+// kernel.  (The products are member functions, not fields, so that a caller's offset arithmetic can stand between the fractions
+// and the products as it did when each kernel wrote this out: the backward and sweep kernels compile to the same code as before.)
+struct CellWeights {
+    float xf, yf, wx, wy, ux, uy;
+    __device__ __forceinline__ float w00() const { return ux * uy; }
+    __device__ __forceinline__ float w10() const { return wx * uy; }
+    __device__ __forceinline__ float w01() const { return ux * wy; }
+    __device__ __forceinline__ float w11() const { return wx * wy; }
+    __device__ __forceinline__ float4 all() const { return make_float4(ux * uy, wx * uy, ux * wy, wx * wy); }
+};
+__device__ __forceinline__ CellWeights cell_weights(float ix, float iy) {
+    CellWeights c;
+    c.xf = floorf(ix); c.yf = floorf(iy);
+    c.wx = ix - c.xf; c.wy = iy - c.yf; c.ux = 1.0f - c.wx; c.uy = 1.0f - c.wy;
+    return c;
+}
+
 // The 2 x 2 cell of a position: offset of its top-left tap (channels c0 .. c0+3) in the bordered map and the four bilinear weights.
 struct SampleCell { size_t o; float w00, w10, w01, w11; };
 __device__ __forceinline__ SampleCell sample_cell(SamplePos P, int W2, int C, int c0) {
-    const float xf = floorf(P.ix), yf = floorf(P.iy);
-    const float wx = P.ix - xf, wy = P.iy - yf, ux = 1.0f - wx, uy = 1.0f - wy;
+    const CellWeights c = cell_weights(P.ix, P.iy);
     SampleCell L;
-    L.o = ((size_t)((int)yf + 1) * W2 + ((int)xf + 1)) * C + c0;
-    L.w00 = ux * uy; L.w10 = wx * uy; L.w01 = ux * wy; L.w11 = wx * wy;
+    L.o = ((size_t)((int)c.yf + 1) * W2 + ((int)c.xf + 1)) * C + c0;
+    L.w00 = c.w00(); L.w10 = c.w10(); L.w01 = c.w01(); L.w11 = c.w11();
     return L;
 }
 // bilinear blend of the cell's four taps, 4 channels
@@ -106,6 +149,13 @@ struct PendingCell {
     }
 };
 
+// variance of key + V sources from their sum s1 and sum of squares s2 (mvsnet.py:135), 4 channels; inv_nv = 1 / (V + 1)
+__device__ __forceinline__ float4 variance_finish(float4 s1, float4 s2, float inv_nv) {
+    const float mx = s1.x * inv_nv, my = s1.y * inv_nv, mz = s1.z * inv_nv, mw = s1.w * inv_nv;
+    return make_float4(fmaf(s2.x, inv_nv, -mx * mx), fmaf(s2.y, inv_nv, -my * my), fmaf(s2.z, inv_nv, -mz * mz),
+                       fmaf(s2.w, inv_nv, -mw * mw));
+}
+
 // Running variance over key + V sources (mvsnet.py:124-135), 4 channels: s1 = sum, s2 = sum of squares.  keysq: the reference's
 // aliasing in CVP-MVSNet (MVD_REDUCE_VARIANCE_KEYSQ), where both sums start from key^2.
 struct VarianceSums {
@@ -119,11 +169,7 @@ struct VarianceSums {
         s2.x = fmaf(sv.x, sv.x, s2.x); s2.y = fmaf(sv.y, sv.y, s2.y);
         s2.z = fmaf(sv.z, sv.z, s2.z); s2.w = fmaf(sv.w, sv.w, s2.w);
     }
-    __device__ __forceinline__ float4 finish(float inv_nv) const {  // inv_nv = 1 / (V + 1)
-        const float mx = s1.x * inv_nv, my = s1.y * inv_nv, mz = s1.z * inv_nv, mw = s1.w * inv_nv;
-        return make_float4(fmaf(s2.x, inv_nv, -mx * mx), fmaf(s2.y, inv_nv, -my * my), fmaf(s2.z, inv_nv, -mz * mz),
-                           fmaf(s2.w, inv_nv, -mw * mw));
-    }
+    __device__ __forceinline__ float4 finish(float inv_nv) const { return variance_finish(s1, s2, inv_nv); }
 };
 
 }  // namespace mvd

@@ -84,12 +84,7 @@ __device__ __forceinline__ void gather_blend_4planes(float4 (&s1)[4], float4 (&s
     u32x4 f[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        if (i == 0 || ((MASK >> (i - 1)) & 1)) {
-            f[i][0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[i], 0, 0);
-            f[i][1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[i] + pix, 0, 0);
-            f[i][2] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[i] + rowb, 0, 0);
-            f[i][3] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[i] + rowb + pix, 0, 0);
-        }
+        if (i == 0 || ((MASK >> (i - 1)) & 1)) gather_cell<RowPitch::in_voffset>(f[i], rsrc, off[i], rowb, pix);
     }
     int src = 0;
 #pragma unroll
@@ -99,71 +94,17 @@ __device__ __forceinline__ void gather_blend_4planes(float4 (&s1)[4], float4 (&s
     }
 }
 
-// The same for four waves per SIMD (128 VGPRs): the bilinear weights stay in the locating lane until a plane's
-// arithmetic needs them (4 DPP broadcasts right there instead of 16 registers held through the gathers), and at most
-// three cells are in flight — when all four planes re-gather, plane 3's loads are issued after plane 0's arithmetic
-// into the registers it frees.
-template <int MASK, int I>
-__device__ __forceinline__ void blend_plane_late(float4 (&s1)[4], float4 (&s2)[4], float m00, float m10, float m01, float m11,
-                                                 const u32x4 (&f)[4]) {
-    float w[4];
-    w[0] = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(m00), I * 0x55, 0xf, 0xf, true));  // quad_perm:[I,I,I,I]
-    w[1] = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(m10), I * 0x55, 0xf, 0xf, true));
-    w[2] = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(m01), I * 0x55, 0xf, 0xf, true));
-    w[3] = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(m11), I * 0x55, 0xf, 0xf, true));
-    accumulate_cell(s1[I], s2[I], w, f);
-}
-
-__device__ __forceinline__ void gather_cell(u32x4 (&f)[4], __amdgpu_buffer_rsrc_t rsrc, unsigned o, unsigned rowb, unsigned pix) {
-    f[0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o, 0, 0);
-    f[1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + pix, 0, 0);
-    f[2] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + rowb, 0, 0);
-    f[3] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + rowb + pix, 0, 0);
-}
-
-template <int MASK>
-__device__ __forceinline__ void gather_blend_4planes_late(float4 (&s1)[4], float4 (&s2)[4], float m00, float m10, float m01,
-                                                          float m11, const unsigned (&off)[4], __amdgpu_buffer_rsrc_t rsrc,
-                                                          unsigned rowb, unsigned pix) {
-    constexpr bool G1 = MASK & 1, G2 = (MASK >> 1) & 1, G3 = (MASK >> 2) & 1;
-    u32x4 a[4], b[4], c[4];  // three register sets
-    gather_cell(a, rsrc, off[0], rowb, pix);
-    if constexpr (MASK == 7) {
-        gather_cell(b, rsrc, off[1], rowb, pix);
-        gather_cell(c, rsrc, off[2], rowb, pix);
-        blend_plane_late<MASK, 0>(s1, s2, m00, m10, m01, m11, a);
-        gather_cell(a, rsrc, off[3], rowb, pix);  // into the set plane 0 just released
-        blend_plane_late<MASK, 1>(s1, s2, m00, m10, m01, m11, b);
-        blend_plane_late<MASK, 2>(s1, s2, m00, m10, m01, m11, c);
-        blend_plane_late<MASK, 3>(s1, s2, m00, m10, m01, m11, a);
-    } else {
-        // at most two of planes 1..3 re-gather: sets b and c take them in order
-        if constexpr (G1) gather_cell(b, rsrc, off[1], rowb, pix);
-        if constexpr (G2) gather_cell(G1 ? c : b, rsrc, off[2], rowb, pix);
-        if constexpr (G3) gather_cell((G1 || G2) ? c : b, rsrc, off[3], rowb, pix);
-        blend_plane_late<MASK, 0>(s1, s2, m00, m10, m01, m11, a);
-        const u32x4 (&p1)[4] = G1 ? b : a;
-        blend_plane_late<MASK, 1>(s1, s2, m00, m10, m01, m11, p1);
-        const u32x4 (&p2)[4] = G2 ? (G1 ? c : b) : p1;
-        blend_plane_late<MASK, 2>(s1, s2, m00, m10, m01, m11, p2);
-        const u32x4 (&p3)[4] = G3 ? ((G1 || G2) ? c : b) : p2;
-        blend_plane_late<MASK, 3>(s1, s2, m00, m10, m01, m11, p3);
-    }
-}
-
 // Work decomposition (the part that decides where the tap gathers are served from):
 //   * a workgroup owns one row segment of PPB key pixels and DPB consecutive depth planes; for each view
 //     it computes the DPB sample positions, issues all 4*DPB gathers back to back (buffer loads: SGPR
 //     descriptor + one 32-bit offset per sample, the 4 taps at constant strides from it) and only then
 //     accumulates, so the gathers of a view overlap each other and consecutive planes touch (nearly) the
 //     same source lines;
-//   * the 1-D grid is decoded XCD-first (blocks b and b+8 share an XCD, MI355X_MICROARCH.md): each XCD
-//     owns a contiguous band of key rows for ALL planes, so its private 4 MiB L2 only ever sees the
-//     matching band of each source image (1/8 of 7 MB per view) instead of whole images per plane —
-//     with a plane-major grid every XCD streamed all V source images per plane and the gathers were
-//     served by the Infinity Cache (measured 2.8 ms at the headline shape, profiles/r01_*).
+//   * the 1-D grid is decoded XCD-first (decode_xcd_first): each XCD owns a contiguous band of key rows for ALL planes --
+//     with a plane-major grid every XCD streamed all V source images per plane and the gathers were served by the Infinity
+//     Cache (measured 2.8 ms at the headline shape, profiles/r01_*).
 // Placement only affects speed; results do not depend on it.
-template <int LPP, bool WARP_ONLY, int DPB, int MINW, int REUSE = 0, bool EXACT = false>
+template <int LPP, bool WARP_ONLY, int DPB, int MINW, Reuse REUSE = Reuse::none, bool EXACT = false>
 __global__ void __launch_bounds__(256, MINW) warp_variance_kernel(WarpParams p) {
     constexpr int PPB = 256 / LPP;  // pixels per block
     constexpr int C = LPP * 4;
@@ -175,35 +116,28 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_kernel(WarpParams p) 
     const int px = tid / LPP;  // pixel within the block
     const int h = p.h, w = p.w, D = p.D;
 
-    // ---- decode the block index: xcd | (d-chunk fastest, then tile within the XCD's band, then batch) ----
-    const int xcd = blockIdx.x & 7;
-    int j = blockIdx.x >> 3;
-    const int dchunks = (D + DPB - 1) / DPB;
-    const int dc = j % dchunks; j /= dchunks;
-    const int tile_in = j % p.tiles_per_xcd;
-    const int b = j / p.tiles_per_xcd;
-    const int tile = xcd * p.tiles_per_xcd + tile_in;
-    if (tile >= p.tiles_x * h) return;  // block-uniform
-    const int y = tile / p.tiles_x;
-    const int x0 = (tile - y * p.tiles_x) * PPB;
+    // ---- decode: one row segment of PPB key pixels, DPB planes ----
+    const BlockWork blk = decode_xcd_first(blockIdx.x, (D + DPB - 1) / DPB, p.tiles_per_xcd);
+    const int b = blk.b;
+    if (blk.tile >= p.tiles_x * h) return;  // block-uniform
+    const int y = blk.tile / p.tiles_x;
+    const int x0 = (blk.tile - y * p.tiles_x) * PPB;
     const int x = x0 + px;
-    const int d0 = dc * DPB;
+    const int d0 = blk.chunk * DPB;
     const bool active = x < w;
     const int xc = active ? x : w - 1;
 
-    // sample index = (X/Z) * w/(w-1) - 0.5: homo_warp's normalisation /((W-1)/2) - 1 followed by
-    // grid_sample's ((g+1)*W-1)/2 (utils.py:256-264), folded, with 1/Z from v_rcp_f32 (1 ulp).  Path B has
-    // no in-bounds mask, so the few-ulp difference moves a sample by < 1e-4 px and the output continuously.
-    const float sx = (float)w / (float)(w - 1), sy = (float)h / (float)(h - 1);
+    // Path B has no in-bounds mask, so the folded grid's few-ulp difference moves a sample by < 1e-4 px and the output continuously
+    const float sx = grid_scale<EXACT>(w), sy = grid_scale<EXACT>(h);
     const float fx = (float)xc, fy = (float)y;
     const float xhi = (float)w, yhi = (float)h;
-    const float half_w = (float)(w - 1) / 2.0f, half_h = (float)(h - 1) / 2.0f;
     const int W2 = w + 3;
     const float W2f = (float)W2;
     const unsigned rowb = (unsigned)W2 * PIX;                    // bytes per padded row
     const unsigned img_bytes = (unsigned)(h + 3) * rowb;         // bytes per padded image
     const unsigned org = rowb + PIX + (unsigned)q * 16;          // padded (1,1) + this lane's channel quad
 
+    // ---- key: both sums start from the key features ----
     float4 s1[DPB], s2[DPB];
     if constexpr (!WARP_ONLY) {
         const float4 k = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(p.key) + (size_t)b * img_bytes +
@@ -238,105 +172,63 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_kernel(WarpParams p) 
         for (int k = 0; k < 12; ++k) M[k] = Mn[k];
         const char* srcv = srcn;
         fetch_view(min(v + 1, p.V - 1));
-        // (X,Y,Z)(d) = R (x,y,1)^T d + T  (utils.py:246-250)
-        const float ax = fmaf(M[0], fx, fmaf(M[1], fy, M[2]));
-        const float ay = fmaf(M[4], fx, fmaf(M[5], fy, M[6]));
-        const float az = fmaf(M[8], fx, fmaf(M[9], fy, M[10]));
-        const float tx = M[3], ty = M[7], tz = M[11];
         const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<char*>(srcv + (size_t)b * img_bytes), 0, (int)img_bytes,
             0x00020000);
         unsigned off[DPB];
         float wt[DPB][4];  // bilinear weights of the taps nw, ne, sw, se
-        bool moved[DPB];   // REUSE: the 2x2 source cell of plane i differs from plane i-1's
-        // position of one plane: clamp into the zero border (a sample outside the image lands on zero taps; NaN from
-        // Z == 0 clamps to -1), split into cell and fraction
-        auto locate = [&](float depth, float& fwx, float& fwy, unsigned& pixoff) {
-            float ix, iy;
-            if constexpr (EXACT) {  // a template parameter: as a run-time branch its operands stay live through the loop (16+ VGPRs)
-                // the reference's own chain, one rounding per step: R @ (x*d, y*d, d) + T (utils.py:246-250), perspective
-                // divide, /((W-1)/2) - 1 (:256-257), grid_sample's ((g+1)*W-1)/2
-                const float gx = fx * depth, gy = fy * depth;
-                const float X = ((M[0] * gx + M[1] * gy) + M[2] * depth) + tx;
-                const float Y = ((M[4] * gx + M[5] * gy) + M[6] * depth) + ty;
-                const float Z = ((M[8] * gx + M[9] * gy) + M[10] * depth) + tz;
-                ix = unnormalize_coord((X / Z) / half_w - 1.0f, xhi);
-                iy = unnormalize_coord((Y / Z) / half_h - 1.0f, yhi);
-            } else {
-                const float X = fmaf(ax, depth, tx), Y = fmaf(ay, depth, ty), Z = fmaf(az, depth, tz);
-                const float rz = __builtin_amdgcn_rcpf(Z);
-                ix = fmaf(X * rz, sx, -0.5f);
-                iy = fmaf(Y * rz, sy, -0.5f);
-            }
-            // v_med3_f32: one instruction; with a NaN operand it returns the minimum of the others, i.e. -1 like
-            // fminf(fmaxf(NaN, -1), hi)
-            ix = __builtin_amdgcn_fmed3f(ix, -1.0f, xhi);
-            iy = __builtin_amdgcn_fmed3f(iy, -1.0f, yhi);
-            const float xf = floorf(ix), yf = floorf(iy);
-            fwx = ix - xf;
-            fwy = iy - yf;
-            // (yf+1, xf+1) in the padded image once `org` is added.  With 32 channels the padded map has < 2^24 pixels
-            // (checked on the host), so yf*W2 + xf is exact in fp32 and replaces a quarter-rate integer multiply.
-            if constexpr (LPP == 8) pixoff = (unsigned)(int)fmaf(yf, W2f, xf) * PIX;
-            else pixoff = (unsigned)((int)yf * W2 + (int)xf) * PIX;
+
+        // ---- locate: a plane's cell weights; returns the byte offset of (yf, xf), which is (yf+1, xf+1) in the padded image once
+        // `org` is added.  With 32 channels the padded map has < 2^24 pixels (checked on the host), so yf*W2 + xf is exact in
+        // fp32 and replaces a quarter-rate integer multiply.
+        auto locate = [&](float depth, CellWeights& c) {
+            const SamplePos P = sample_position<EXACT>(M, fx, fy, depth, sx, sy, xhi, yhi);
+            c = cell_weights(P.ix, P.iy);
+            if constexpr (LPP == 8) return (unsigned)(int)fmaf(c.yf, W2f, c.xf) * PIX;
+            else return (unsigned)((int)c.yf * W2 + (int)c.xf) * PIX;
         };
         if constexpr (DPB == 4 && LPP % 4 == 0) {
             // the LPP lanes of a pixel would each repeat this arithmetic for all 4 planes; instead lane (q & 3) of every
-            // quad does plane (q & 3) and the quad exchanges the three results with DPP quad_perm broadcasts
-            float mwx, mwy;
-            unsigned mpo;
-            locate(mydep, mwx, mwy, mpo);
-            const float mux = 1.0f - mwx, muy = 1.0f - mwy;
-            const float m00 = mux * muy, m10 = mwx * muy, m01 = mux * mwy, m11 = mwx * mwy;
-            if constexpr (REUSE == 4) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) off[i] = 0;
-                off[0] = org + (unsigned)__builtin_amdgcn_mov_dpp((int)mpo, 0 * 0x55, 0xf, 0xf, true);
-                off[1] = org + (unsigned)__builtin_amdgcn_mov_dpp((int)mpo, 1 * 0x55, 0xf, 0xf, true);
-                off[2] = org + (unsigned)__builtin_amdgcn_mov_dpp((int)mpo, 2 * 0x55, 0xf, 0xf, true);
-                off[3] = org + (unsigned)__builtin_amdgcn_mov_dpp((int)mpo, 3 * 0x55, 0xf, 0xf, true);
-                const unsigned mask = (__builtin_amdgcn_ballot_w64(off[1] != off[0]) != 0 ? 1u : 0u) |
-                                      (__builtin_amdgcn_ballot_w64(off[2] != off[1]) != 0 ? 2u : 0u) |
-                                      (__builtin_amdgcn_ballot_w64(off[3] != off[2]) != 0 ? 4u : 0u);
-                switch (mask) {
-                    case 0: gather_blend_4planes_late<0>(s1, s2, m00, m10, m01, m11, off, rsrc, rowb, PIX); break;
-                    case 1: gather_blend_4planes_late<1>(s1, s2, m00, m10, m01, m11, off, rsrc, rowb, PIX); break;
-                    case 2: gather_blend_4planes_late<2>(s1, s2, m00, m10, m01, m11, off, rsrc, rowb, PIX); break;
-                    case 3: gather_blend_4planes_late<3>(s1, s2, m00, m10, m01, m11, off, rsrc, rowb, PIX); break;
-                    case 4: gather_blend_4planes_late<4>(s1, s2, m00, m10, m01, m11, off, rsrc, rowb, PIX); break;
-                    case 5: gather_blend_4planes_late<5>(s1, s2, m00, m10, m01, m11, off, rsrc, rowb, PIX); break;
-                    case 6: gather_blend_4planes_late<6>(s1, s2, m00, m10, m01, m11, off, rsrc, rowb, PIX); break;
-                    default: gather_blend_4planes_late<7>(s1, s2, m00, m10, m01, m11, off, rsrc, rowb, PIX); break;
-                }
+            // quad does plane (q & 3) and the quad exchanges the results with DPP quad_perm broadcasts
+            CellWeights m;
+            const unsigned mpo = locate(mydep, m);
+            if constexpr (REUSE == Reuse::wave_uniform_late) {
+                off[0] = org + quad_bcast<0>(mpo); off[1] = org + quad_bcast<1>(mpo);
+                off[2] = org + quad_bcast<2>(mpo); off[3] = org + quad_bcast<3>(mpo);
+                // four waves per SIMD (128 VGPRs): the weights stay in the locating lane until a plane's arithmetic needs them (4
+                // DPP broadcasts right there instead of 16 registers held through the gathers), at most three cells in flight
+                dispatch_mask(cell_change_mask(off), [&](auto mask) {
+                    gather_blend_4planes_3sets<decltype(mask)::value>(
+                        s1, s2, off,
+                        [&](auto I) {
+                            constexpr int i = decltype(I)::value;
+                            return make_float4(quad_bcast<i>(m.w00()), quad_bcast<i>(m.w10()), quad_bcast<i>(m.w01()), quad_bcast<i>(m.w11()));
+                        },
+                        [&](u32x4 (&f)[4], unsigned o) { gather_cell<RowPitch::in_voffset>(f, rsrc, o, rowb, PIX); });
+                });
                 continue;
             }
-#define MVD_QB(V, I) __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(V), (I) * 0x55, 0xf, 0xf, true))
-#define MVD_QUAD_BCAST(I)                                                                                          \
-    wt[I][0] = MVD_QB(m00, I); wt[I][1] = MVD_QB(m10, I); wt[I][2] = MVD_QB(m01, I); wt[I][3] = MVD_QB(m11, I);     \
-    off[I] = org + (unsigned)__builtin_amdgcn_mov_dpp((int)mpo, (I) * 0x55, 0xf, 0xf, true);  /* quad_perm:[I,I,I,I] */
-            MVD_QUAD_BCAST(0) MVD_QUAD_BCAST(1) MVD_QUAD_BCAST(2) MVD_QUAD_BCAST(3)
-#undef MVD_QUAD_BCAST
-#undef MVD_QB
-#pragma unroll
-            for (int i = 0; i < 4; ++i) moved[i] = i == 0 || off[i] != off[i - 1];
+            auto bcast = [&](auto I) {
+                constexpr int i = decltype(I)::value;
+                wt[i][0] = quad_bcast<i>(m.w00()); wt[i][1] = quad_bcast<i>(m.w10()); wt[i][2] = quad_bcast<i>(m.w01()); wt[i][3] = quad_bcast<i>(m.w11());
+                off[i] = org + quad_bcast<i>(mpo);
+            };
+            bcast(std::integral_constant<int, 0>{}); bcast(std::integral_constant<int, 1>{});
+            bcast(std::integral_constant<int, 2>{}); bcast(std::integral_constant<int, 3>{});
         } else {
 #pragma unroll
             for (int i = 0; i < DPB; ++i) {
-                unsigned po;
-                float fwx, fwy;
-                locate(dep[i], fwx, fwy, po);
-                const float ux = 1.0f - fwx, uy = 1.0f - fwy;
-                wt[i][0] = ux * uy; wt[i][1] = fwx * uy; wt[i][2] = ux * fwy; wt[i][3] = fwx * fwy;
-                off[i] = org + po;
-                moved[i] = i == 0 || off[i] != off[i - 1];
+                CellWeights c;
+                off[i] = org + locate(dep[i], c);
+                wt[i][0] = c.w00(); wt[i][1] = c.w10(); wt[i][2] = c.w01(); wt[i][3] = c.w11();
             }
         }
-        if constexpr (REUSE == 2 && DPB == 4) {
-            // wave-uniform re-gather pattern (see gather_blend_4planes)
-            const unsigned mask = (__builtin_amdgcn_ballot_w64(moved[1]) != 0 ? 1u : 0u) |
-                                  (__builtin_amdgcn_ballot_w64(moved[2]) != 0 ? 2u : 0u) |
-                                  (__builtin_amdgcn_ballot_w64(moved[3]) != 0 ? 4u : 0u);
-            switch (mask) {
+
+        // ---- pattern and gather-blend ----
+        if constexpr (REUSE == Reuse::wave_uniform && DPB == 4) {
+            // (its own switch, not dispatch_mask: through the closure the compiler sinks the eight cases' final adds into one
+            // tail block, which changes both product instances throughout and costs the warp-only one 4 VGPRs, 118 -> 122)
+            switch (cell_change_mask(off)) {
                 case 0: gather_blend_4planes<0>(s1, s2, wt, off, rsrc, rowb, PIX); break;
                 case 1: gather_blend_4planes<1>(s1, s2, wt, off, rsrc, rowb, PIX); break;
                 case 2: gather_blend_4planes<2>(s1, s2, wt, off, rsrc, rowb, PIX); break;
@@ -349,18 +241,15 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_kernel(WarpParams p) 
             continue;
         }
         u32x4 f[DPB][4];
-        if constexpr (REUSE == 1) {
+        if constexpr (REUSE == Reuse::per_lane) {
             // Sweep coherence: from one plane to the next a sample moves a fraction of a pixel, so its 2x2 cell is
             // usually the previous plane's.  Only lanes whose cell moved gather again (exec-masked loads, all issued
             // before the first use); the others take the previous plane's registers.
+            bool moved[DPB];
 #pragma unroll
             for (int i = 0; i < DPB; ++i) {
-                if (moved[i]) {
-                    f[i][0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[i], 0, 0);
-                    f[i][1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[i] + PIX, 0, 0);
-                    f[i][2] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[i] + rowb, 0, 0);
-                    f[i][3] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[i] + rowb + PIX, 0, 0);
-                }
+                moved[i] = i == 0 || off[i] != off[i - 1];
+                if (moved[i]) gather_cell<RowPitch::in_voffset>(f[i], rsrc, off[i], rowb, PIX);
             }
 #pragma unroll
             for (int i = 1; i < DPB; ++i)
@@ -373,43 +262,20 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_kernel(WarpParams p) 
                 }
         } else {
 #pragma unroll
-            for (int i = 0; i < DPB; ++i) {
-                f[i][0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[i], 0, 0);
-                f[i][1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[i] + PIX, 0, 0);
-                f[i][2] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[i] + rowb, 0, 0);
-                f[i][3] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[i] + rowb + PIX, 0, 0);
-            }
+            for (int i = 0; i < DPB; ++i) gather_cell<RowPitch::in_voffset>(f[i], rsrc, off[i], rowb, PIX);
         }
 #pragma unroll
-        for (int i = 0; i < DPB; ++i) {
-            float4 acc = make_float4(0, 0, 0, 0);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                acc.x = fmaf(__uint_as_float(f[i][k].x), wt[i][k], acc.x);
-                acc.y = fmaf(__uint_as_float(f[i][k].y), wt[i][k], acc.y);
-                acc.z = fmaf(__uint_as_float(f[i][k].z), wt[i][k], acc.z);
-                acc.w = fmaf(__uint_as_float(f[i][k].w), wt[i][k], acc.w);
-            }
-            s1[i].x += acc.x; s1[i].y += acc.y; s1[i].z += acc.z; s1[i].w += acc.w;
-            s2[i].x = fmaf(acc.x, acc.x, s2[i].x); s2[i].y = fmaf(acc.y, acc.y, s2[i].y);
-            s2[i].z = fmaf(acc.z, acc.z, s2[i].z); s2[i].w = fmaf(acc.w, acc.w, s2[i].w);
-        }
+        for (int i = 0; i < DPB; ++i) accumulate_cell(s1[i], s2[i], wt[i], f[i]);
     }
 
+    // ---- finish and store ----
     const float inv_nv = 1.0f / (float)(p.V + 1);  // mvsnet.py:135, V there counts the key view
     const size_t plane = (size_t)h * w;
 #pragma unroll
     for (int i = 0; i < DPB; ++i) {
         const int d = d0 + i;
         if (d >= D) break;  // block-uniform
-        float4 r;
-        if constexpr (WARP_ONLY) {
-            r = s1[i];
-        } else {
-            const float mx = s1[i].x * inv_nv, my = s1[i].y * inv_nv, mz = s1[i].z * inv_nv, mw = s1[i].w * inv_nv;
-            r = make_float4(fmaf(s2[i].x, inv_nv, -mx * mx), fmaf(s2[i].y, inv_nv, -my * my),
-                            fmaf(s2[i].z, inv_nv, -mz * mz), fmaf(s2[i].w, inv_nv, -mw * mw));
-        }
+        const float4 r = WARP_ONLY ? s1[i] : variance_finish(s1[i], s2[i], inv_nv);
         if (p.layout == MVD_LAYOUT_NDHWC) {
             if (active)
                 *reinterpret_cast<float4*>(p.out + ((((size_t)b * D + d) * h + y) * w + x) * C + q * 4) = r;
@@ -472,22 +338,34 @@ int launch_gather(const WarpParams& p0, int lpp, int dpb, WarpKernel kernel, hip
 }
 
 // The product's forms of the gather kernel: 4 planes per workgroup, 3 waves per SIMD (tuned on MI355X); with
-// 8 lanes per pixel (C = 32) on the folded grid, a plane's cell is gathered again only where the wave needs it (REUSE = 2)
+// 8 lanes per pixel (C = 32) on the folded grid, a plane's cell is gathered again only where the wave needs it
 template <bool WARP_ONLY, bool EXACT>
 static WarpKernel gather_kernel(int lpp) {
     switch (lpp) {
-        case 1: return warp_variance_kernel<1, WARP_ONLY, 4, 3, 0, EXACT>;
-        case 2: return warp_variance_kernel<2, WARP_ONLY, 4, 3, 0, EXACT>;
-        case 4: return warp_variance_kernel<4, WARP_ONLY, 4, 3, 0, EXACT>;
-        case 8: return warp_variance_kernel<8, WARP_ONLY, 4, 3, EXACT ? 0 : 2, EXACT>;
-        default: return warp_variance_kernel<16, WARP_ONLY, 4, 3, 0, EXACT>;  // C = 64
+        case 1: return warp_variance_kernel<1, WARP_ONLY, 4, 3, Reuse::none, EXACT>;
+        case 2: return warp_variance_kernel<2, WARP_ONLY, 4, 3, Reuse::none, EXACT>;
+        case 4: return warp_variance_kernel<4, WARP_ONLY, 4, 3, Reuse::none, EXACT>;
+        case 8: return warp_variance_kernel<8, WARP_ONLY, 4, 3, EXACT ? Reuse::none : Reuse::wave_uniform, EXACT>;
+        default: return warp_variance_kernel<16, WARP_ONLY, 4, 3, Reuse::none, EXACT>;  // C = 64
     }
 }
 
 int launch_warp_gather(const WarpParams& p, int C, bool warp_only, hipStream_t st) {  // C = 4, 8, 16, 32 or 64 (checked)
     const int lpp = C / 4;
-    const WarpKernel k = p.exact_grid ? (warp_only ? gather_kernel<true, true>(lpp) : gather_kernel<false, true>(lpp))
-                                      : (warp_only ? gather_kernel<true, false>(lpp) : gather_kernel<false, false>(lpp));
+    WarpKernel k;
+    if (!p.exact_grid) {
+        k = warp_only ? gather_kernel<true, false>(lpp) : gather_kernel<false, false>(lpp);
+    } else if (!warp_only) {
+        k = gather_kernel<false, true>(lpp);
+    } else {
+#ifdef MVD_EXPERIMENTS
+        k = gather_kernel<true, true>(lpp);
+#else
+        // homo_warp has no exact-grid flag (mvd_homo_warp_f32 passes a plain layout): the product does not compile these
+        set_error("homo_warp: the exact grid is not compiled into the product library");
+        return MVD_ERR_INVALID_ARG;
+#endif
+    }
     return launch_gather(p, lpp, 4, k, st);
 }
 
@@ -542,13 +420,14 @@ static int launch_k3(const WarpParams& p0, int C, bool warp_only, bool f16, hipS
     WarpParams p = p0;
 #ifdef MVD_EXPERIMENTS
     // experiments library: MVD_K3_CFG selects the kernel (warp_variance_exp.hip).  The gather kernel's other forms
-    // (REUSE, planes per workgroup, min waves per SIMD; C = 32 on the folded grid) are instantiated here, with its template.
+    // (Reuse, planes per workgroup, min waves per SIMD; C = 32 on the folded grid) are instantiated here, with its template.
     if (const char* e = exp_env("MVD_K3_CFG")) {
-#define MVD_G(R, DPB, MW) {R, DPB, MW, warp_only ? warp_variance_kernel<8, true, DPB, MW, R> : warp_variance_kernel<8, false, DPB, MW, R>}
-        const GatherForm forms[] = {MVD_G(0, 1, 8), MVD_G(0, 2, 4), MVD_G(0, 2, 6), MVD_G(0, 2, 8), MVD_G(0, 4, 2), MVD_G(0, 4, 3),
-                                    MVD_G(0, 4, 4), MVD_G(0, 8, 2), MVD_G(0, 8, 3), MVD_G(1, 2, 4), MVD_G(1, 2, 6), MVD_G(1, 4, 2),
-                                    MVD_G(1, 4, 3), MVD_G(1, 4, 4), MVD_G(1, 8, 2), MVD_G(2, 4, 2), MVD_G(2, 4, 3), MVD_G(2, 4, 4),
-                                    MVD_G(4, 4, 2), MVD_G(4, 4, 3), MVD_G(4, 4, 4)};
+#define MVD_G(R, DPB, MW) {Reuse::R, DPB, MW, warp_only ? warp_variance_kernel<8, true, DPB, MW, Reuse::R> : warp_variance_kernel<8, false, DPB, MW, Reuse::R>}
+        const GatherForm forms[] = {MVD_G(none, 1, 8), MVD_G(none, 2, 4), MVD_G(none, 2, 6), MVD_G(none, 2, 8), MVD_G(none, 4, 2),
+                                    MVD_G(none, 4, 3), MVD_G(none, 4, 4), MVD_G(none, 8, 2), MVD_G(none, 8, 3), MVD_G(per_lane, 2, 4),
+                                    MVD_G(per_lane, 2, 6), MVD_G(per_lane, 4, 2), MVD_G(per_lane, 4, 3), MVD_G(per_lane, 4, 4),
+                                    MVD_G(per_lane, 8, 2), MVD_G(wave_uniform, 4, 2), MVD_G(wave_uniform, 4, 3), MVD_G(wave_uniform, 4, 4),
+                                    MVD_G(wave_uniform_late, 4, 2), MVD_G(wave_uniform_late, 4, 3), MVD_G(wave_uniform_late, 4, 4)};
 #undef MVD_G
         return warp_variance_experiment(e, p, C, warp_only, f16, st, forms, (int)(sizeof(forms) / sizeof(forms[0])));
     }

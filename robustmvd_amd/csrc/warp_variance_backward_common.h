@@ -1,5 +1,5 @@
 // What the two K3 backward implementations share: the scatter kernel (backward.hip, float atomics) and the gather kernels
-// (warp_variance_backward_gather.hip, fixed summation order).  Both sample through sweep_homography.h (sample_position_rcp,
+// (warp_variance_backward_gather.hip, fixed summation order).  Both sample through sweep_homography.h (sample_position<false>,
 // sample_cell, sample_blend): the bilinear weights of a key pixel's sample are bit-identical in the two paths, and so is the
 // key gradient.
 #pragma once

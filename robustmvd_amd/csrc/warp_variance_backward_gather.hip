@@ -94,7 +94,7 @@ __global__ void __launch_bounds__(256) warp_variance_gather_stage_a_kernel(Gathe
         const float4 g = *reinterpret_cast<const float4*>(p.gvar + vox);
         float4 sum = k;
         for (int v = 0; v < V; ++v) {
-            const SamplePos P = sample_position_rcp(p.M + ((size_t)v * p.B + b) * 12, fx, fy, depth, sx, sy, xhi, yhi);
+            const SamplePos P = sample_position<false>(p.M + ((size_t)v * p.B + b) * 12, fx, fy, depth, sx, sy, xhi, yhi);
             const SampleCell L = sample_cell(P, W2, C, q * 4);
             const float4 xv = sample_blend(p.src.p[v] + b * img, L, W2, C);
             sum.x += xv.x; sum.y += xv.y; sum.z += xv.z; sum.w += xv.w;
@@ -163,7 +163,7 @@ __global__ void __launch_bounds__(256) warp_variance_gather_stage_b_kernel(Gathe
             const int px = cx - GR + i % GW, py = cy - GR + i / GW;
             bool hit = false;
             if (i < GW * GW && px >= 0 && px < w && py >= 0 && py < h) {
-                const SamplePos P = sample_position_rcp(M, (float)px, (float)py, depth, sx, sy, xhi, yhi);
+                const SamplePos P = sample_position<false>(M, (float)px, (float)py, depth, sx, sy, xhi, yhi);
                 const unsigned dx = (unsigned)(qx - (int)floorf(P.ix)), dy = (unsigned)(qy - (int)floorf(P.iy));
                 hit = dx < 2u && dy < 2u;
             }
@@ -175,7 +175,7 @@ __global__ void __launch_bounds__(256) warp_variance_gather_stage_b_kernel(Gathe
             const int i = __builtin_ctzll(hits);
             hits &= hits - 1;
             const int px = cx - GR + i % GW, py = cy - GR + i / GW;
-            const SamplePos P = sample_position_rcp(M, (float)px, (float)py, depth, sx, sy, xhi, yhi);
+            const SamplePos P = sample_position<false>(M, (float)px, (float)py, depth, sx, sy, xhi, yhi);
             const SampleCell L = sample_cell(P, W2, C, sub * 4);
             const bool right = qx != (int)floorf(P.ix), low = qy != (int)floorf(P.iy);
             const float wt = right ? (low ? L.w11 : L.w10) : (low ? L.w01 : L.w00);

@@ -3,7 +3,6 @@
 // (the product's K3 before the tile kernel), and warp_variance_experiment(), which reads the MVD_K3_CFG selector.
 // NOT part of libmvd_hip.so: compiled only into robustmvd_amd/lib_exp/libmvd_hip_exp.so (`make exp`, -DMVD_EXPERIMENTS),
 // which tools/ and tests/test_hip_shapes.py::test_warp_variance_experimental_variants_match_default load explicitly.
-#include <type_traits>
 #include "warp_variance_common.h"
 
 namespace mvd {
@@ -61,17 +60,12 @@ __global__ void __launch_bounds__(256, 2) warp_variance_lds_kernel(WarpParams p)
     const int lx = slot & 7, ly0 = slot >> 3;
     const int h = p.h, w = p.w, D = p.D;
 
-    const int xcd = blockIdx.x & 7;
-    int j = blockIdx.x >> 3;
-    const int dchunks = (D + ND - 1) / ND;
-    const int dc = j % dchunks; j /= dchunks;
-    const int tile_in = j % p.tiles_per_xcd;
-    const int b = j / p.tiles_per_xcd;
-    const int tile = xcd * p.tiles_per_xcd + tile_in;
+    const BlockWork blk = decode_xcd_first(blockIdx.x, (D + ND - 1) / ND, p.tiles_per_xcd);
+    const int b = blk.b, tile = blk.tile;
     if (tile >= p.tiles_x * p.tiles_y) return;  // block-uniform
     const int tyi = tile / p.tiles_x;
     const int x0 = (tile - tyi * p.tiles_x) * TX, y0 = tyi * TY;
-    const int d0 = dc * ND;
+    const int d0 = blk.chunk * ND;
     const int dl = min(d0 + ND, D) - 1;
 
     const float sx = (float)w / (float)(w - 1), sy = (float)h / (float)(h - 1);
@@ -107,19 +101,12 @@ __global__ void __launch_bounds__(256, 2) warp_variance_lds_kernel(WarpParams p)
         float bx0 = 3e38f, bx1 = -3e38f, by0 = 3e38f, by1 = -3e38f, zmin = 3e38f;
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
-            const float cx = cxs[a & 1], cy = cys[a >> 1];
-            const float ax = fmaf(M[0], cx, fmaf(M[1], cy, M[2])), ay = fmaf(M[4], cx, fmaf(M[5], cy, M[6]));
-            const float az = fmaf(M[8], cx, fmaf(M[9], cy, M[10]));
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
-                const float cd = e ? dlast : dfirst;
-                const float X = fmaf(ax, cd, M[3]), Y = fmaf(ay, cd, M[7]), Z = fmaf(az, cd, M[11]);
-                const float rz = __builtin_amdgcn_rcpf(Z);
-                const float ix = fminf(fmaxf(fmaf(X * rz, sx, -0.5f), -1.0f), xhi);
-                const float iy = fminf(fmaxf(fmaf(Y * rz, sy, -0.5f), -1.0f), yhi);
-                bx0 = fminf(bx0, ix); bx1 = fmaxf(bx1, ix);
-                by0 = fminf(by0, iy); by1 = fmaxf(by1, iy);
-                zmin = fminf(zmin, Z);
+                const SamplePos c = sample_position<false>(M, cxs[a & 1], cys[a >> 1], e ? dlast : dfirst, sx, sy, xhi, yhi);
+                bx0 = fminf(bx0, c.ix); bx1 = fmaxf(bx1, c.ix);
+                by0 = fminf(by0, c.iy); by1 = fmaxf(by1, c.iy);
+                zmin = fminf(zmin, c.Z);
             }
         }
         Box bx;
@@ -149,56 +136,33 @@ __global__ void __launch_bounds__(256, 2) warp_variance_lds_kernel(WarpParams p)
                                          nxt.rw * Q, nxt.rh, wave, lane);
         }
         const float* __restrict__ M = p.M + ((size_t)v * p.B + b) * 12;
-        const float4* __restrict__ reg = region[v & 1];
+        const u32x4* __restrict__ reg = reinterpret_cast<const u32x4*>(region[v & 1]);
         const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<char*>(reinterpret_cast<const char*>(p.src.p[v]) + (size_t)b * img_bytes), 0, (int)img_bytes,
             0x00020000);
 #pragma unroll
         for (int pi = 0; pi < 1; ++pi) {
             const float fy = (float)ys[pi];
-            const float ax = fmaf(M[0], fxs, fmaf(M[1], fy, M[2]));
-            const float ay = fmaf(M[4], fxs, fmaf(M[5], fy, M[6]));
-            const float az = fmaf(M[8], fxs, fmaf(M[9], fy, M[10]));
 #pragma unroll
             for (int i = 0; i < ND; ++i) {
-                const float X = fmaf(ax, dep[i], M[3]), Y = fmaf(ay, dep[i], M[7]), Z = fmaf(az, dep[i], M[11]);
-                const float rz = __builtin_amdgcn_rcpf(Z);
-                const float ix = fminf(fmaxf(fmaf(X * rz, sx, -0.5f), -1.0f), xhi);
-                const float iy = fminf(fmaxf(fmaf(Y * rz, sy, -0.5f), -1.0f), yhi);
-                const float xf = floorf(ix), yf = floorf(iy);
-                const float wx = ix - xf, wy = iy - yf;
-                float4 f00, f10, f01, f11;
+                const SamplePos sp = sample_position<false>(M, fxs, fy, dep[i], sx, sy, xhi, yhi);
+                const CellWeights cw = cell_weights(sp.ix, sp.iy);
+                u32x4 f[4];
                 if (cur.staged) {
                     // padded coordinates relative to the staged box, clamped into it
-                    const int xi = (int)xf + 1 - cur.x0, yi = (int)yf + 1 - cur.y0;
+                    const int xi = (int)cw.xf + 1 - cur.x0, yi = (int)cw.yf + 1 - cur.y0;
                     const int xa = min(max(xi, 0), cur.rw - 1), xb = min(max(xi + 1, 0), cur.rw - 1);
                     const int ya = min(max(yi, 0), cur.rh - 1), yb = min(max(yi + 1, 0), cur.rh - 1);
                     const int ra = ya * LDS_ROWQ + q, rb = yb * LDS_ROWQ + q;
-                    f00 = reg[ra + xa * Q];
-                    f10 = reg[ra + xb * Q];
-                    f01 = reg[rb + xa * Q];
-                    f11 = reg[rb + xb * Q];
+                    f[0] = reg[ra + xa * Q];
+                    f[1] = reg[ra + xb * Q];
+                    f[2] = reg[rb + xa * Q];
+                    f[3] = reg[rb + xb * Q];
                 } else {
-                    const unsigned off = rowb + PIX + (unsigned)q * 16 + (unsigned)((int)yf * W2 + (int)xf) * PIX;
-                    const u32x4 a0 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
-                    const u32x4 a1 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + PIX, 0, 0);
-                    const u32x4 a2 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + rowb, 0, 0);
-                    const u32x4 a3 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + rowb + PIX, 0, 0);
-                    f00 = make_float4(__uint_as_float(a0.x), __uint_as_float(a0.y), __uint_as_float(a0.z), __uint_as_float(a0.w));
-                    f10 = make_float4(__uint_as_float(a1.x), __uint_as_float(a1.y), __uint_as_float(a1.z), __uint_as_float(a1.w));
-                    f01 = make_float4(__uint_as_float(a2.x), __uint_as_float(a2.y), __uint_as_float(a2.z), __uint_as_float(a2.w));
-                    f11 = make_float4(__uint_as_float(a3.x), __uint_as_float(a3.y), __uint_as_float(a3.z), __uint_as_float(a3.w));
+                    gather_cell<RowPitch::in_voffset>(f, rsrc, rowb + PIX + (unsigned)q * 16 + (unsigned)((int)cw.yf * W2 + (int)cw.xf) * PIX, rowb, PIX);
                 }
-                const float ux = 1.0f - wx, uy = 1.0f - wy;
-                const float w00 = ux * uy, w10 = wx * uy, w01 = ux * wy, w11 = wx * wy;
-                float4 acc;  // same accumulation order as the direct kernel (bit-identical results)
-                acc.x = fmaf(f11.x, w11, fmaf(f01.x, w01, fmaf(f10.x, w10, fmaf(f00.x, w00, 0.0f))));
-                acc.y = fmaf(f11.y, w11, fmaf(f01.y, w01, fmaf(f10.y, w10, fmaf(f00.y, w00, 0.0f))));
-                acc.z = fmaf(f11.z, w11, fmaf(f01.z, w01, fmaf(f10.z, w10, fmaf(f00.z, w00, 0.0f))));
-                acc.w = fmaf(f11.w, w11, fmaf(f01.w, w01, fmaf(f10.w, w10, fmaf(f00.w, w00, 0.0f))));
-                s1[pi][i].x += acc.x; s1[pi][i].y += acc.y; s1[pi][i].z += acc.z; s1[pi][i].w += acc.w;
-                s2[pi][i].x = fmaf(acc.x, acc.x, s2[pi][i].x); s2[pi][i].y = fmaf(acc.y, acc.y, s2[pi][i].y);
-                s2[pi][i].z = fmaf(acc.z, acc.z, s2[pi][i].z); s2[pi][i].w = fmaf(acc.w, acc.w, s2[pi][i].w);
+                const float w[4] = {cw.w00(), cw.w10(), cw.w01(), cw.w11()};
+                accumulate_cell(s1[pi][i], s2[pi][i], w, f);  // same accumulation order as the direct kernel (bit-identical results)
             }
         }
         __syncthreads();  // (drains the LDS-DMA) buffer (v+1)&1 is complete; buffer v&1 is free for view v+2
@@ -214,11 +178,7 @@ __global__ void __launch_bounds__(256, 2) warp_variance_lds_kernel(WarpParams p)
         for (int i = 0; i < ND; ++i) {
             const int d = d0 + i;
             if (d >= D) break;
-            const float mx = s1[pi][i].x * inv_nv, my = s1[pi][i].y * inv_nv, mz = s1[pi][i].z * inv_nv,
-                        mw = s1[pi][i].w * inv_nv;
-            const float4 r = make_float4(fmaf(s2[pi][i].x, inv_nv, -mx * mx), fmaf(s2[pi][i].y, inv_nv, -my * my),
-                                         fmaf(s2[pi][i].z, inv_nv, -mz * mz), fmaf(s2[pi][i].w, inv_nv, -mw * mw));
-            *reinterpret_cast<float4*>(p.out + ((((size_t)b * D + d) * h + y) * w + x) * C + q * 4) = r;
+            *reinterpret_cast<float4*>(p.out + ((((size_t)b * D + d) * h + y) * w + x) * C + q * 4) = variance_finish(s1[pi][i], s2[pi][i], inv_nv);
         }
     }
 }
@@ -246,18 +206,13 @@ __global__ void __launch_bounds__(256, 2) warp_variance_wave_kernel(WarpParams p
     float4* __restrict__ mybuf = wlds + wave * 2 * BUF;
 
     // ---- task decode: xcd | d-chunk fastest | tile group (4 x-adjacent wave tiles per workgroup) | batch ----
-    const int xcd = blockIdx.x & 7;
-    int j = blockIdx.x >> 3;
-    const int dchunks = (D + ND - 1) / ND;
-    const int dc = j % dchunks; j /= dchunks;
-    const int grp_in = j % p.tiles_per_xcd;
-    const int b = j / p.tiles_per_xcd;
-    const int grp = xcd * p.tiles_per_xcd + grp_in;   // group of 4 wave tiles = 16 x 2 pixels
+    const BlockWork blk = decode_xcd_first(blockIdx.x, (D + ND - 1) / ND, p.tiles_per_xcd);
+    const int b = blk.b, grp = blk.tile;               // group of 4 wave tiles = 16 x 2 pixels
     if (grp >= p.tiles_x * p.tiles_y) return;          // block-uniform
     const int gy = grp / p.tiles_x;
     const int x0 = (grp - gy * p.tiles_x) * (4 * TXW) + wave * TXW, y0 = gy * TYW;
     if (x0 >= w) return;                               // wave-uniform (ragged right edge)
-    const int d0 = dc * ND;
+    const int d0 = blk.chunk * ND;
     const int dl = min(d0 + ND, D) - 1;
 
     const float sx = (float)w / (float)(w - 1), sy = (float)h / (float)(h - 1);
@@ -290,19 +245,12 @@ __global__ void __launch_bounds__(256, 2) warp_variance_wave_kernel(WarpParams p
         float bx0 = 3e38f, bx1 = -3e38f, by0 = 3e38f, by1 = -3e38f, zmin = 3e38f;
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
-            const float cx = cxs[a & 1], cy = cys[a >> 1];
-            const float ax = fmaf(M[0], cx, fmaf(M[1], cy, M[2])), ay = fmaf(M[4], cx, fmaf(M[5], cy, M[6]));
-            const float az = fmaf(M[8], cx, fmaf(M[9], cy, M[10]));
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
-                const float cd = e ? dlast : dfirst;
-                const float X = fmaf(ax, cd, M[3]), Y = fmaf(ay, cd, M[7]), Z = fmaf(az, cd, M[11]);
-                const float rz = __builtin_amdgcn_rcpf(Z);
-                const float ix = fminf(fmaxf(fmaf(X * rz, sx, -0.5f), -1.0f), xhi);
-                const float iy = fminf(fmaxf(fmaf(Y * rz, sy, -0.5f), -1.0f), yhi);
-                bx0 = fminf(bx0, ix); bx1 = fmaxf(bx1, ix);
-                by0 = fminf(by0, iy); by1 = fmaxf(by1, iy);
-                zmin = fminf(zmin, Z);
+                const SamplePos c = sample_position<false>(M, cxs[a & 1], cys[a >> 1], e ? dlast : dfirst, sx, sy, xhi, yhi);
+                bx0 = fminf(bx0, c.ix); bx1 = fmaxf(bx1, c.ix);
+                by0 = fminf(by0, c.iy); by1 = fmaxf(by1, c.iy);
+                zmin = fminf(zmin, c.Z);
             }
         }
         Box bx;
@@ -351,52 +299,29 @@ __global__ void __launch_bounds__(256, 2) warp_variance_wave_kernel(WarpParams p
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
         const float* __restrict__ M = p.M + ((size_t)v * p.B + b) * 12;
-        const float4* __restrict__ reg = mybuf + (v & 1) * BUF;
+        const u32x4* __restrict__ reg = reinterpret_cast<const u32x4*>(mybuf + (v & 1) * BUF);
         const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<char*>(reinterpret_cast<const char*>(p.src.p[v]) + (size_t)b * img_bytes), 0, (int)img_bytes,
             0x00020000);
-        const float ax = fmaf(M[0], fxs, fmaf(M[1], fys, M[2]));
-        const float ay = fmaf(M[4], fxs, fmaf(M[5], fys, M[6]));
-        const float az = fmaf(M[8], fxs, fmaf(M[9], fys, M[10]));
 #pragma unroll
         for (int i = 0; i < ND; ++i) {
-            const float X = fmaf(ax, dep[i], M[3]), Y = fmaf(ay, dep[i], M[7]), Z = fmaf(az, dep[i], M[11]);
-            const float rz = __builtin_amdgcn_rcpf(Z);
-            const float ix = fminf(fmaxf(fmaf(X * rz, sx, -0.5f), -1.0f), xhi);
-            const float iy = fminf(fmaxf(fmaf(Y * rz, sy, -0.5f), -1.0f), yhi);
-            const float xf = floorf(ix), yf = floorf(iy);
-            const float wx = ix - xf, wy = iy - yf;
-            float4 f00, f10, f01, f11;
+            const SamplePos sp = sample_position<false>(M, fxs, fys, dep[i], sx, sy, xhi, yhi);
+            const CellWeights cw = cell_weights(sp.ix, sp.iy);
+            u32x4 f[4];
             if (cur.staged) {
-                const int xi = (int)xf + 1 - cur.x0, yi = (int)yf + 1 - cur.y0;
+                const int xi = (int)cw.xf + 1 - cur.x0, yi = (int)cw.yf + 1 - cur.y0;
                 const int xa = min(max(xi, 0), cur.rw - 1), xb = min(max(xi + 1, 0), cur.rw - 1);
                 const int ya = min(max(yi, 0), cur.rh - 1), yb = min(max(yi + 1, 0), cur.rh - 1);
                 const int ra = ya * ROWQ + q, rb = yb * ROWQ + q;
-                f00 = reg[ra + xa * Q];
-                f10 = reg[ra + xb * Q];
-                f01 = reg[rb + xa * Q];
-                f11 = reg[rb + xb * Q];
+                f[0] = reg[ra + xa * Q];
+                f[1] = reg[ra + xb * Q];
+                f[2] = reg[rb + xa * Q];
+                f[3] = reg[rb + xb * Q];
             } else {
-                const unsigned off = rowb + PIX + (unsigned)q * 16 + (unsigned)((int)yf * W2 + (int)xf) * PIX;
-                const u32x4 a0 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
-                const u32x4 a1 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + PIX, 0, 0);
-                const u32x4 a2 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + rowb, 0, 0);
-                const u32x4 a3 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + rowb + PIX, 0, 0);
-                f00 = make_float4(__uint_as_float(a0.x), __uint_as_float(a0.y), __uint_as_float(a0.z), __uint_as_float(a0.w));
-                f10 = make_float4(__uint_as_float(a1.x), __uint_as_float(a1.y), __uint_as_float(a1.z), __uint_as_float(a1.w));
-                f01 = make_float4(__uint_as_float(a2.x), __uint_as_float(a2.y), __uint_as_float(a2.z), __uint_as_float(a2.w));
-                f11 = make_float4(__uint_as_float(a3.x), __uint_as_float(a3.y), __uint_as_float(a3.z), __uint_as_float(a3.w));
+                gather_cell<RowPitch::in_voffset>(f, rsrc, rowb + PIX + (unsigned)q * 16 + (unsigned)((int)cw.yf * W2 + (int)cw.xf) * PIX, rowb, PIX);
             }
-            const float ux = 1.0f - wx, uy = 1.0f - wy;
-            const float w00 = ux * uy, w10 = wx * uy, w01 = ux * wy, w11 = wx * wy;
-            float4 acc;  // same accumulation order as the direct kernel (bit-identical results)
-            acc.x = fmaf(f11.x, w11, fmaf(f01.x, w01, fmaf(f10.x, w10, fmaf(f00.x, w00, 0.0f))));
-            acc.y = fmaf(f11.y, w11, fmaf(f01.y, w01, fmaf(f10.y, w10, fmaf(f00.y, w00, 0.0f))));
-            acc.z = fmaf(f11.z, w11, fmaf(f01.z, w01, fmaf(f10.z, w10, fmaf(f00.z, w00, 0.0f))));
-            acc.w = fmaf(f11.w, w11, fmaf(f01.w, w01, fmaf(f10.w, w10, fmaf(f00.w, w00, 0.0f))));
-            s1[i].x += acc.x; s1[i].y += acc.y; s1[i].z += acc.z; s1[i].w += acc.w;
-            s2[i].x = fmaf(acc.x, acc.x, s2[i].x); s2[i].y = fmaf(acc.y, acc.y, s2[i].y);
-            s2[i].z = fmaf(acc.z, acc.z, s2[i].z); s2[i].w = fmaf(acc.w, acc.w, s2[i].w);
+            const float w[4] = {cw.w00(), cw.w10(), cw.w01(), cw.w11()};
+            accumulate_cell(s1[i], s2[i], w, f);  // same accumulation order as the direct kernel (bit-identical results)
         }
         cur = nxt;
     }
@@ -408,10 +333,7 @@ __global__ void __launch_bounds__(256, 2) warp_variance_wave_kernel(WarpParams p
         for (int i = 0; i < ND; ++i) {
             const int d = d0 + i;
             if (d >= D) break;
-            const float mx = s1[i].x * inv_nv, my = s1[i].y * inv_nv, mz = s1[i].z * inv_nv, mw = s1[i].w * inv_nv;
-            const float4 r = make_float4(fmaf(s2[i].x, inv_nv, -mx * mx), fmaf(s2[i].y, inv_nv, -my * my),
-                                         fmaf(s2[i].z, inv_nv, -mz * mz), fmaf(s2[i].w, inv_nv, -mw * mw));
-            *reinterpret_cast<float4*>(p.out + ((((size_t)b * D + d) * h + y) * w + x) * C + q * 4) = r;
+            *reinterpret_cast<float4*>(p.out + ((((size_t)b * D + d) * h + y) * w + x) * C + q * 4) = variance_finish(s1[i], s2[i], inv_nv);
         }
     }
 }
@@ -453,13 +375,9 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_q8_kernel(WarpParams 
     const int px = tid >> 2;  // 0..63: 32 columns x 2 rows
     const int h = p.h, w = p.w, D = p.D;
 
-    const int xcd = blockIdx.x & 7;
-    int j = blockIdx.x >> 3;
-    const int dchunks = (D + 2 * CPB - 1) / (2 * CPB);  // CPB chunks of 2 planes per workgroup: one index decode and key fetch for all
-    const int dc = j % dchunks; j /= dchunks;
-    const int tile_in = j % p.tiles_per_xcd;
-    const int b = j / p.tiles_per_xcd;
-    const int tile = xcd * p.tiles_per_xcd + tile_in;
+    // CPB chunks of 2 planes per workgroup: one index decode and key fetch for all
+    const BlockWork blk = decode_xcd_first(blockIdx.x, (D + 2 * CPB - 1) / (2 * CPB), p.tiles_per_xcd);
+    const int dc = blk.chunk, b = blk.b, tile = blk.tile;
     if (tile >= p.tiles_x * p.tiles_y) return;  // block-uniform
     const int ty = tile / p.tiles_x;
     const int x = (tile - ty * p.tiles_x) * 32 + (px & 31);
@@ -511,28 +429,12 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_q8_kernel(WarpParams 
         for (int k = 0; k < 12; ++k) M[k] = Mn[k];
         const char* srcv = srcn;
         fetch_view(min(v + 1, p.V - 1));
-        const float ax = fmaf(M[0], fx, fmaf(M[1], fy, M[2]));
-        const float ay = fmaf(M[4], fx, fmaf(M[5], fy, M[6]));
-        const float az = fmaf(M[8], fx, fmaf(M[9], fy, M[10]));
-        const float X = fmaf(ax, mydep, M[3]), Y = fmaf(ay, mydep, M[7]), Z = fmaf(az, mydep, M[11]);
-        const float rz = __builtin_amdgcn_rcpf(Z);
-        float ix = fmaf(X * rz, sx, -0.5f), iy = fmaf(Y * rz, sy, -0.5f);
-        ix = __builtin_amdgcn_fmed3f(ix, -1.0f, xhi);
-        iy = __builtin_amdgcn_fmed3f(iy, -1.0f, yhi);
-        const float xf = floorf(ix), yf = floorf(iy);
-        const float mwx = ix - xf, mwy = iy - yf;
-        const unsigned mpo = (unsigned)(int)fmaf(yf, W2f, xf) * PIX;
-        const float mux = 1.0f - mwx, muy = 1.0f - mwy;
-        const float m00 = mux * muy, m10 = mwx * muy, m01 = mux * mwy, m11 = mwx * mwy;
-        float wt[2][4];
-        unsigned off[2];
-#define MVD_QB(V, I) __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(V), (I) * 0x55, 0xf, 0xf, true))
-#define MVD_QUAD_BCAST(I)                                                                                          \
-    wt[I][0] = MVD_QB(m00, I); wt[I][1] = MVD_QB(m10, I); wt[I][2] = MVD_QB(m01, I); wt[I][3] = MVD_QB(m11, I);     \
-    off[I] = org + (unsigned)__builtin_amdgcn_mov_dpp((int)mpo, (I) * 0x55, 0xf, 0xf, true);  /* quad_perm:[I,I,I,I] */
-        MVD_QUAD_BCAST(0) MVD_QUAD_BCAST(1)
-#undef MVD_QUAD_BCAST
-#undef MVD_QB
+        const SamplePos sp = sample_position<false>(M, fx, fy, mydep, sx, sy, xhi, yhi);
+        const CellWeights m = cell_weights(sp.ix, sp.iy);
+        const unsigned mpo = (unsigned)(int)fmaf(m.yf, W2f, m.xf) * PIX;  // exact in fp32 (checked on the host)
+        const float wt[2][4] = {{quad_bcast<0>(m.w00()), quad_bcast<0>(m.w10()), quad_bcast<0>(m.w01()), quad_bcast<0>(m.w11())},
+                                {quad_bcast<1>(m.w00()), quad_bcast<1>(m.w10()), quad_bcast<1>(m.w01()), quad_bcast<1>(m.w11())}};
+        const unsigned off[2] = {org + quad_bcast<0>(mpo), org + quad_bcast<1>(mpo)};
         const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<char*>(srcv + (size_t)b * img_bytes), 0, (int)img_bytes, 0x00020000);
         if (__builtin_amdgcn_ballot_w64(off[1] != off[0]) != 0) step_q8<true>(s1, s2, wt[0], wt[1], off[0], off[1], rsrc, rowb);
@@ -547,9 +449,7 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_q8_kernel(WarpParams 
         float4* op = reinterpret_cast<float4*>(p.out + ((((size_t)b * D + d) * h + y) * w + x) * 32 + q * 8);
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
-            const float mx = s1[i][hf].x * inv_nv, my = s1[i][hf].y * inv_nv, mz = s1[i][hf].z * inv_nv, mw = s1[i][hf].w * inv_nv;
-            op[hf] = make_float4(fmaf(s2[i][hf].x, inv_nv, -mx * mx), fmaf(s2[i][hf].y, inv_nv, -my * my),
-                                 fmaf(s2[i][hf].z, inv_nv, -mz * mz), fmaf(s2[i][hf].w, inv_nv, -mw * mw));
+            op[hf] = variance_finish(s1[i][hf], s2[i][hf], inv_nv);
         }
     }
     }
@@ -653,59 +553,26 @@ __device__ __forceinline__ void blend_plane_lds(float4 (&s1)[4], float4 (&s2)[4]
     accumulate_cell(s1[I], s2[I], w, f);
 }
 
-// taps of one cell: nw at `o`, ne at +128 (folds into the instruction's immediate), sw / se one padded row further
-// (the row pitch rides in the scalar offset operand: no per-lane address arithmetic besides `o` itself)
-__device__ __forceinline__ void gather_cell_s(u32x4 (&f)[4], __amdgpu_buffer_rsrc_t rsrc, unsigned o, unsigned rowb) {
-    f[0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o, 0, 0);
-    f[1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + 128u, 0, 0);
-    f[2] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o, rowb, 0);
-    f[3] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + 128u, rowb, 0);
-}
-// fp16 features: 64 bytes per pixel, 8 per lane
-__device__ __forceinline__ void gather_cell_s(u32x2 (&f)[4], __amdgpu_buffer_rsrc_t rsrc, unsigned o, unsigned rowb) {
-    f[0] = load_b64(rsrc, o, 0);
-    f[1] = load_b64(rsrc, o + 64u, 0);
-    f[2] = load_b64(rsrc, o, rowb);
-    f[3] = load_b64(rsrc, o + 64u, rowb);
+// the cell's taps with the row pitch in the scalar offset operand; C = 32: a pixel is 8 lanes wide
+template <class TAP>
+__device__ __forceinline__ void gather_cell_s(TAP (&f)[4], __amdgpu_buffer_rsrc_t rsrc, unsigned o, unsigned rowb) {
+    gather_cell<RowPitch::in_soffset>(f, rsrc, o, rowb, 8u * (unsigned)sizeof(TAP));
 }
 
+// the three-set schedule with plane I's weights in LDS at wl[32 I] (broadcast reads: they land long before the gathers do)
 template <int MASK, int KO = 0>
 __device__ __forceinline__ void gather_blend_4planes_lds(float4 (&s1)[4], float4 (&s2)[4], const float4* __restrict__ wl,
                                                          const unsigned (&off)[4], __amdgpu_buffer_rsrc_t rsrc, unsigned rowb) {
-    constexpr bool G1 = MASK & 1, G2 = (MASK >> 1) & 1, G3 = (MASK >> 2) & 1;
-    auto gather_cell_s = [](u32x4 (&f)[4], __amdgpu_buffer_rsrc_t r, unsigned o, unsigned rb) {
-        if constexpr (KO & 2) {  // knock-out: taps from registers, no memory access
-            f[0] = u32x4{o, o + 1, o + 2, o + 3}; f[1] = u32x4{o + 4, o + 5, o + 6, o + 7};
-            f[2] = u32x4{o + rb, o + 9, o + 10, o + 11}; f[3] = u32x4{o + rb + 4, o + 13, o + 14, o + 15};
-        } else {
-            mvd::gather_cell_s(f, r, o, rb);
-        }
-    };
-    u32x4 a[4], b[4], c[4];  // three register sets
-    gather_cell_s(a, rsrc, off[0], rowb);
-    if constexpr (MASK == 7) {
-        gather_cell_s(b, rsrc, off[1], rowb);
-        gather_cell_s(c, rsrc, off[2], rowb);
-        const float4 w0 = wl[0], w1 = wl[32], w2 = wl[64], w3 = wl[96];  // LDS: lands long before the gathers do
-        blend_plane_lds<MASK, 0>(s1, s2, w0, a);
-        gather_cell_s(a, rsrc, off[3], rowb);  // into the set plane 0 just released
-        blend_plane_lds<MASK, 1>(s1, s2, w1, b);
-        blend_plane_lds<MASK, 2>(s1, s2, w2, c);
-        blend_plane_lds<MASK, 3>(s1, s2, w3, a);
-    } else {
-        // at most two of planes 1..3 re-gather: sets b and c take them in order
-        if constexpr (G1) gather_cell_s(b, rsrc, off[1], rowb);
-        if constexpr (G2) gather_cell_s(G1 ? c : b, rsrc, off[2], rowb);
-        if constexpr (G3) gather_cell_s((G1 || G2) ? c : b, rsrc, off[3], rowb);
-        const float4 w0 = wl[0], w1 = wl[32], w2 = wl[64], w3 = wl[96];
-        blend_plane_lds<MASK, 0>(s1, s2, w0, a);
-        const u32x4 (&p1)[4] = G1 ? b : a;
-        blend_plane_lds<MASK, 1>(s1, s2, w1, p1);
-        const u32x4 (&p2)[4] = G2 ? (G1 ? c : b) : p1;
-        blend_plane_lds<MASK, 2>(s1, s2, w2, p2);
-        const u32x4 (&p3)[4] = G3 ? ((G1 || G2) ? c : b) : p2;
-        blend_plane_lds<MASK, 3>(s1, s2, w3, p3);
-    }
+    gather_blend_4planes_3sets<MASK>(
+        s1, s2, off, [&](auto I) { return wl[32 * decltype(I)::value]; },
+        [&](u32x4 (&f)[4], unsigned o) {
+            if constexpr (KO & 2) {  // knock-out: taps from registers, no memory access
+                f[0] = u32x4{o, o + 1, o + 2, o + 3}; f[1] = u32x4{o + 4, o + 5, o + 6, o + 7};
+                f[2] = u32x4{o + rowb, o + 9, o + 10, o + 11}; f[3] = u32x4{o + rowb + 4, o + 13, o + 14, o + 15};
+            } else {
+                gather_cell_s(f, rsrc, o, rowb);
+            }
+        });
 }
 
 // KO != 0: knock-out builds that time parts of the kernel (they compute wrong results):
@@ -721,18 +588,12 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_located_kernel(WarpPa
     const int tid = threadIdx.x;
     const int h = p.h, w = p.w, D = p.D;
 
-    // ---- decode the block index: xcd | (d-chunk fastest, then tile within the XCD's band, then batch) ----
-    const int xcd = blockIdx.x & 7;
-    int j = blockIdx.x >> 3;
-    const int dchunks = (D + DPB - 1) / DPB;
-    const int dc = j % dchunks; j /= dchunks;
-    const int tile_in = j % p.tiles_per_xcd;
-    const int b = j / p.tiles_per_xcd;
-    const int tile = xcd * p.tiles_per_xcd + tile_in;
+    const BlockWork blk = decode_xcd_first(blockIdx.x, (D + DPB - 1) / DPB, p.tiles_per_xcd);
+    const int b = blk.b, tile = blk.tile;
     if (tile >= p.tiles_x * h) return;  // block-uniform
     const int y = tile / p.tiles_x;
     const int x0 = (tile - y * p.tiles_x) * PPB;
-    const int d0 = dc * DPB;
+    const int d0 = blk.chunk * DPB;
 
     const int W2 = w + 3;
     const unsigned rowb = (unsigned)W2 * PIX;             // bytes per padded row
@@ -748,21 +609,11 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_located_kernel(WarpPa
         const float W2f = (float)W2;
         const float depth = p.depth[(size_t)b * D + min(d0 + li, D - 1)];
         for (int v = __builtin_amdgcn_readfirstlane(tid >> 7); v < ((KO & 1) ? 0 : V); v += 2) {  // wave-uniform view
-            const float* __restrict__ M = p.M + ((size_t)v * p.B + b) * 12;       // scalar loads
-            const float ax = fmaf(M[0], fx, fmaf(M[1], fy, M[2]));
-            const float ay = fmaf(M[4], fx, fmaf(M[5], fy, M[6]));
-            const float az = fmaf(M[8], fx, fmaf(M[9], fy, M[10]));
-            const float X = fmaf(ax, depth, M[3]), Y = fmaf(ay, depth, M[7]), Z = fmaf(az, depth, M[11]);
-            const float rz = __builtin_amdgcn_rcpf(Z);
-            float ix = fmaf(X * rz, sx, -0.5f), iy = fmaf(Y * rz, sy, -0.5f);
-            ix = __builtin_amdgcn_fmed3f(ix, -1.0f, xhi);
-            iy = __builtin_amdgcn_fmed3f(iy, -1.0f, yhi);
-            const float xf = floorf(ix), yf = floorf(iy);
-            const float wx = ix - xf, wy = iy - yf;
-            const float ux = 1.0f - wx, uy = 1.0f - wy;
+            const SamplePos sp = sample_position<false>(p.M + ((size_t)v * p.B + b) * 12, fx, fy, depth, sx, sy, xhi, yhi);  // scalar loads
+            const CellWeights cw = cell_weights(sp.ix, sp.iy);
             const int slot = (v * DPB + li) * PPB + lpx;
-            lds_loc[slot] = make_float4(ux * uy, wx * uy, ux * wy, wx * wy);
-            lds_off[slot] = (unsigned)(int)fmaf(yf, W2f, xf) * PIX;  // exact in fp32 (checked on the host)
+            lds_loc[slot] = cw.all();
+            lds_off[slot] = (unsigned)(int)fmaf(cw.yf, W2f, cw.xf) * PIX;  // exact in fp32 (checked on the host)
         }
     }
 
@@ -798,20 +649,7 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_located_kernel(WarpPa
             const_cast<char*>(srcn + (size_t)b * img_bytes), 0, (int)img_bytes, 0x00020000);
         const float4* __restrict__ wl = lds_loc + v * (DPB * PPB) + px;
         fetch_view(min(v + 1, V - 1));
-        // wave-uniform re-gather pattern: bit i-1 set = some lane's 2x2 cell differs between plane i-1 and plane i
-        const unsigned mask = (__builtin_amdgcn_ballot_w64(off[1] != off[0]) != 0 ? 1u : 0u) |
-                              (__builtin_amdgcn_ballot_w64(off[2] != off[1]) != 0 ? 2u : 0u) |
-                              (__builtin_amdgcn_ballot_w64(off[3] != off[2]) != 0 ? 4u : 0u);
-        switch (mask) {
-            case 0: gather_blend_4planes_lds<0, KO>(s1, s2, wl, off, rsrc, rowb); break;
-            case 1: gather_blend_4planes_lds<1, KO>(s1, s2, wl, off, rsrc, rowb); break;
-            case 2: gather_blend_4planes_lds<2, KO>(s1, s2, wl, off, rsrc, rowb); break;
-            case 3: gather_blend_4planes_lds<3, KO>(s1, s2, wl, off, rsrc, rowb); break;
-            case 4: gather_blend_4planes_lds<4, KO>(s1, s2, wl, off, rsrc, rowb); break;
-            case 5: gather_blend_4planes_lds<5, KO>(s1, s2, wl, off, rsrc, rowb); break;
-            case 6: gather_blend_4planes_lds<6, KO>(s1, s2, wl, off, rsrc, rowb); break;
-            default: gather_blend_4planes_lds<7, KO>(s1, s2, wl, off, rsrc, rowb); break;
-        }
+        dispatch_mask(cell_change_mask(off), [&](auto mask) { gather_blend_4planes_lds<decltype(mask)::value, KO>(s1, s2, wl, off, rsrc, rowb); });
     }
 
     const float inv_nv = 1.0f / (float)(p.V + 1);  // mvsnet.py:135, V there counts the key view
@@ -820,9 +658,7 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_located_kernel(WarpPa
         for (int i = 0; i < DPB; ++i) {
             const int d = d0 + i;
             if (d >= D) break;  // block-uniform
-            const float mx = s1[i].x * inv_nv, my = s1[i].y * inv_nv, mz = s1[i].z * inv_nv, mw = s1[i].w * inv_nv;
-            const float4 r = make_float4(fmaf(s2[i].x, inv_nv, -mx * mx), fmaf(s2[i].y, inv_nv, -my * my),
-                                         fmaf(s2[i].z, inv_nv, -mz * mz), fmaf(s2[i].w, inv_nv, -mw * mw));
+            const float4 r = variance_finish(s1[i], s2[i], inv_nv);
             if ((KO & 4) && r.x != 123.456f) continue;
             *reinterpret_cast<float4*>(p.out + ((((size_t)b * D + d) * h + y) * w + (x0 + px)) * 32 + q * 4) = r;
         }
@@ -937,15 +773,9 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_march_kernel(WarpPara
     const int tid = threadIdx.x;
     const int h = p.h, w = p.w, D = p.D;
 
-    // ---- decode the block index: xcd | (chunk group fastest, then tile within the XCD's band, then batch) ----
-    const int xcd = blockIdx.x & 7;
-    int j = blockIdx.x >> 3;
     const int dchunks = (D + DPB - 1) / DPB;
-    const int dgroups = (dchunks + nch - 1) / nch;
-    const int dg = j % dgroups; j /= dgroups;
-    const int tile_in = j % p.tiles_per_xcd;
-    const int b = j / p.tiles_per_xcd;
-    const int tile = xcd * p.tiles_per_xcd + tile_in;
+    const BlockWork blk = decode_xcd_first(blockIdx.x, (dchunks + nch - 1) / nch, p.tiles_per_xcd);  // chunk groups
+    const int dg = blk.chunk, b = blk.b, tile = blk.tile;
     if (tile >= p.tiles_x * h) return;  // block-uniform
     const int y = tile / p.tiles_x;
     const int x0 = (tile - y * p.tiles_x) * PPB;
@@ -990,20 +820,12 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_march_kernel(WarpPara
         const float depth = wpi == 0 ? e0 : wpi == 1 ? e1 : wpi == 2 ? e2 : e3;
         for (int v = wvp; v < V; v += 2) {
             const float4 m0 = mtab[v * 3], m1 = mtab[v * 3 + 1], m2 = mtab[v * 3 + 2];
-            const float ax = fmaf(m0.x, wfx, fmaf(m0.y, lfy, m0.z));
-            const float ay = fmaf(m1.x, wfx, fmaf(m1.y, lfy, m1.z));
-            const float az = fmaf(m2.x, wfx, fmaf(m2.y, lfy, m2.z));
-            const float X = fmaf(ax, depth, m0.w), Y = fmaf(ay, depth, m1.w), Z = fmaf(az, depth, m2.w);
-            const float rz = __builtin_amdgcn_rcpf(Z);
-            float ix = fmaf(X * rz, sx, -0.5f), iy = fmaf(Y * rz, sy, -0.5f);
-            ix = __builtin_amdgcn_fmed3f(ix, -1.0f, xhi);
-            iy = __builtin_amdgcn_fmed3f(iy, -1.0f, yhi);
-            const float xf = floorf(ix), yf = floorf(iy);
-            const float wx = ix - xf, wy = iy - yf;
-            const float ux = 1.0f - wx, uy = 1.0f - wy;
+            const float M[12] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w};
+            const SamplePos sp = sample_position<false>(M, wfx, lfy, depth, sx, sy, xhi, yhi);
+            const CellWeights cw = cell_weights(sp.ix, sp.iy);
             const int slot = (v * DPB + wpi) * PPB + wpx;
-            loc[slot] = make_float4(ux * uy, wx * uy, ux * wy, wx * wy);
-            offs[slot] = (unsigned)(int)fmaf(yf, W2f, xf) * PIX;
+            loc[slot] = cw.all();
+            offs[slot] = (unsigned)(int)fmaf(cw.yf, W2f, cw.xf) * PIX;
         }
     };
     auto locate = [&](int c, int buf) {
@@ -1016,21 +838,13 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_march_kernel(WarpPara
                     e3 = dvals[min(d0 + 3, D - 1)];
         const float depth = li == 0 ? e0 : li == 1 ? e1 : li == 2 ? e2 : e3;
         for (int v = v_first; v < V; v += 2) {
-            cfloat* M = (cfloat*)(p.M + ((size_t)v * p.B + b) * 12);  // scalar loads
-            const float ax = fmaf(M[0], lfx, fmaf(M[1], lfy, M[2]));
-            const float ay = fmaf(M[4], lfx, fmaf(M[5], lfy, M[6]));
-            const float az = fmaf(M[8], lfx, fmaf(M[9], lfy, M[10]));
-            const float X = fmaf(ax, depth, M[3]), Y = fmaf(ay, depth, M[7]), Z = fmaf(az, depth, M[11]);
-            const float rz = __builtin_amdgcn_rcpf(Z);
-            float ix = fmaf(X * rz, sx, -0.5f), iy = fmaf(Y * rz, sy, -0.5f);
-            ix = __builtin_amdgcn_fmed3f(ix, -1.0f, xhi);
-            iy = __builtin_amdgcn_fmed3f(iy, -1.0f, yhi);
-            const float xf = floorf(ix), yf = floorf(iy);
-            const float wx = ix - xf, wy = iy - yf;
-            const float ux = 1.0f - wx, uy = 1.0f - wy;
+            cfloat* Mc = (cfloat*)(p.M + ((size_t)v * p.B + b) * 12);  // scalar loads
+            const float M[12] = {Mc[0], Mc[1], Mc[2], Mc[3], Mc[4], Mc[5], Mc[6], Mc[7], Mc[8], Mc[9], Mc[10], Mc[11]};
+            const SamplePos sp = sample_position<false>(M, lfx, lfy, depth, sx, sy, xhi, yhi);
+            const CellWeights cw = cell_weights(sp.ix, sp.iy);
             const int slot = (v * DPB + li) * PPB + lpx;
-            loc[slot] = make_float4(ux * uy, wx * uy, ux * wy, wx * wy);
-            offs[slot] = (unsigned)(int)fmaf(yf, W2f, xf) * PIX;  // exact in fp32 (checked on the host)
+            loc[slot] = cw.all();
+            offs[slot] = (unsigned)(int)fmaf(cw.yf, W2f, cw.xf) * PIX;  // exact in fp32 (checked on the host)
         }
     };
 
@@ -1108,41 +922,29 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_march_kernel(WarpPara
                 const unsigned* __restrict__ ol = offs + v * (DPB * PPB) + px;
 #pragma unroll
                 for (int i = 0; i < DPB; ++i) off[i] = ol[i * PPB] + org;
-                mask = (__builtin_amdgcn_ballot_w64(off[1] != off[0]) != 0 ? 1u : 0u) |
-                       (__builtin_amdgcn_ballot_w64(off[2] != off[1]) != 0 ? 2u : 0u) |
-                       (__builtin_amdgcn_ballot_w64(off[3] != off[2]) != 0 ? 4u : 0u);
+                mask = cell_change_mask(off);
                 const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
                     const_cast<char*>(reinterpret_cast<const char*>(p.src.p[v]) + (size_t)b * img_bytes), 0, (int)img_bytes, 0x00020000);
                 gather_cell_s(X, r, off[0], rowb);
                 return r;
             };
-#define MVD_BLEND(Mk, Xs, Ys, offs_, rs_, v_) \
-    case Mk: blend_view_prefetched<Mk, TAP>(s1, s2, loc + (v_) * (DPB * PPB) + px, Xs, Ys, offs_, rs_, rowb); break;
-#define MVD_BLEND_ALL(mask_, Xs, Ys, offs_, rs_, v_)                                                                      \
-    switch (mask_) {                                                                                                     \
-        MVD_BLEND(0, Xs, Ys, offs_, rs_, v_) MVD_BLEND(1, Xs, Ys, offs_, rs_, v_) MVD_BLEND(2, Xs, Ys, offs_, rs_, v_)  \
-        MVD_BLEND(3, Xs, Ys, offs_, rs_, v_) MVD_BLEND(4, Xs, Ys, offs_, rs_, v_) MVD_BLEND(5, Xs, Ys, offs_, rs_, v_)  \
-        MVD_BLEND(6, Xs, Ys, offs_, rs_, v_)                                                                             \
-        default: blend_view_prefetched<7, TAP>(s1, s2, loc + (v_) * (DPB * PPB) + px, Xs, Ys, offs_, rs_, rowb); break;   \
-    }
+            auto blend_view = [&](unsigned mask, TAP (&X)[4], TAP (&Y)[4], const unsigned (&off)[DPB], __amdgpu_buffer_rsrc_t rs, int v) {
+                dispatch_mask(mask, [&](auto m) { blend_view_prefetched<decltype(m)::value, TAP>(s1, s2, loc + v * (DPB * PPB) + px, X, Y, off, rs, rowb); });
+            };
             // Every path between a request and the first use of its taps is straight-line code: behind a conditional request
             // the compiler must assume the smaller number of outstanding loads and would wait for the prefetch it just issued.
             ra = open_view(0, offa, ma, X0);
             for (int v = 0; v + 1 < V; v += 2) {
                 rb = open_view(v + 1, offb, mb, X1);
-                MVD_BLEND_ALL(ma, X0, Y0, offa, ra, v)
+                blend_view(ma, X0, Y0, offa, ra, v);
                 if (v + 2 < V) {
                     ra = open_view(v + 2, offa, ma, X0);
-                    MVD_BLEND_ALL(mb, X1, Y1, offb, rb, v + 1)
+                    blend_view(mb, X1, Y1, offb, rb, v + 1);
                 } else {
-                    MVD_BLEND_ALL(mb, X1, Y1, offb, rb, v + 1)
+                    blend_view(mb, X1, Y1, offb, rb, v + 1);
                 }
             }
-            if (V & 1) {  // the last view of an odd count was opened by the iteration before it (or above, V = 1)
-                MVD_BLEND_ALL(ma, X0, Y0, offa, ra, V - 1)
-            }
-#undef MVD_BLEND_ALL
-#undef MVD_BLEND
+            if (V & 1) blend_view(ma, X0, Y0, offa, ra, V - 1);  // the last view of an odd count was opened by the iteration before it (or above, V = 1)
         } else {
             unsigned offn[DPB];
             const char* srcn;
@@ -1161,51 +963,23 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_march_kernel(WarpPara
                     const_cast<char*>(srcn + (size_t)b * img_bytes), 0, (int)img_bytes, 0x00020000);
                 const float4* __restrict__ wl = loc + v * (DPB * PPB) + px;
                 fetch_view(min(v + 1, V - 1));
-                const unsigned mask = (__builtin_amdgcn_ballot_w64(off[1] != off[0]) != 0 ? 1u : 0u) |
-                                      (__builtin_amdgcn_ballot_w64(off[2] != off[1]) != 0 ? 2u : 0u) |
-                                      (__builtin_amdgcn_ballot_w64(off[3] != off[2]) != 0 ? 4u : 0u);
-    #define MVD_CASE(Mk)                                                                                   \
-        if constexpr (F16) gather_blend_4planes_2sets<Mk, u32x2>(s1, s2, wl, off, rsrc, rowb);             \
-        else if constexpr (NSETS == 2) gather_blend_4planes_2sets<Mk, u32x4>(s1, s2, wl, off, rsrc, rowb); \
-        else gather_blend_4planes_lds<Mk>(s1, s2, wl, off, rsrc, rowb);                                   \
-        break;
-    #define MVD_CASE_HOOK(Mk) gather_blend_4planes_2sets<Mk, u32x4>(s1, s2, wl, off, rsrc, rowb, drain_v0); break;
-                if constexpr (PARK) {  // the previous chunk's parked results leave behind the first view's last gather request
-                    const bool first = v == 0;  // wave-uniform
-                    auto drain_v0 = [&]() { if (first) drain(); };
-                    switch (mask) {
-                        case 0: MVD_CASE_HOOK(0)
-                        case 1: MVD_CASE_HOOK(1)
-                        case 2: MVD_CASE_HOOK(2)
-                        case 3: MVD_CASE_HOOK(3)
-                        case 4: MVD_CASE_HOOK(4)
-                        case 5: MVD_CASE_HOOK(5)
-                        case 6: MVD_CASE_HOOK(6)
-                        default: MVD_CASE_HOOK(7)
-                    }
-                } else {
-                    switch (mask) {
-                        case 0: MVD_CASE(0)
-                        case 1: MVD_CASE(1)
-                        case 2: MVD_CASE(2)
-                        case 3: MVD_CASE(3)
-                        case 4: MVD_CASE(4)
-                        case 5: MVD_CASE(5)
-                        case 6: MVD_CASE(6)
-                        default: MVD_CASE(7)
-                    }
-                }
-    #undef MVD_CASE_HOOK
-    #undef MVD_CASE
+                // PARK: the previous chunk's parked results leave behind the first view's last gather request
+                const bool first = v == 0;  // wave-uniform
+                auto drain_v0 = [&]() { if (first) drain(); };
+                dispatch_mask(cell_change_mask(off), [&](auto m) {
+                    constexpr int Mk = decltype(m)::value;
+                    if constexpr (PARK) gather_blend_4planes_2sets<Mk, u32x4>(s1, s2, wl, off, rsrc, rowb, drain_v0);
+                    else if constexpr (F16) gather_blend_4planes_2sets<Mk, u32x2>(s1, s2, wl, off, rsrc, rowb);
+                    else if constexpr (NSETS == 2) gather_blend_4planes_2sets<Mk, u32x4>(s1, s2, wl, off, rsrc, rowb);
+                    else gather_blend_4planes_lds<Mk>(s1, s2, wl, off, rsrc, rowb);
+                });
             }
         }
         const int d0 = c * DPB;
 #pragma unroll
         for (int i = 0; i < DPB; ++i) {
             if (d0 + i >= D) break;  // block-uniform (only in the last chunk of a D that is not a multiple of 4)
-            const float mx = s1[i].x * inv_nv, my = s1[i].y * inv_nv, mz = s1[i].z * inv_nv, mw = s1[i].w * inv_nv;
-            const float4 r = make_float4(fmaf(s2[i].x, inv_nv, -mx * mx), fmaf(s2[i].y, inv_nv, -my * my),
-                                         fmaf(s2[i].z, inv_nv, -mz * mz), fmaf(s2[i].w, inv_nv, -mw * mw));
+            const float4 r = variance_finish(s1[i], s2[i], inv_nv);
             if constexpr (PARK) {
                 park_base[i * 256 + tid] = r;
                 continue;
@@ -1335,12 +1109,13 @@ int warp_variance_experiment(const char* e, const WarpParams& p, int C, bool war
         if (e[0] == 'w') { int nd = 8; sscanf(e, "wave,%d", &nd); return launch_warp_wave(p, st, nd); }
     }
     if (C != 32 || exact) return launch_warp_gather(p, C, warp_only, st);
-    // (planes per workgroup, min waves per SIMD, REUSE); a selector of another kind keeps the product's (4, 3, 2)
-    int dpb = 4, minw = 3, reuse = 2;
-    if (e[0] >= '0' && e[0] <= '9') { sscanf(e, "%d,%d", &dpb, &minw); reuse = 0; }
-    if (e[0] == 'r') { sscanf(e, "r%d,%d", &dpb, &minw); reuse = 1; }
-    if (e[0] == 'u') { sscanf(e, "u%d,%d", &dpb, &minw); reuse = 2; }
-    if (e[0] == 'v') { sscanf(e, "v%d,%d", &dpb, &minw); reuse = 4; }
+    // (planes per workgroup, min waves per SIMD, Reuse); a selector of another kind keeps the product's (4, 3, wave_uniform)
+    int dpb = 4, minw = 3;
+    Reuse reuse = Reuse::wave_uniform;
+    if (e[0] >= '0' && e[0] <= '9') { sscanf(e, "%d,%d", &dpb, &minw); reuse = Reuse::none; }
+    if (e[0] == 'r') { sscanf(e, "r%d,%d", &dpb, &minw); reuse = Reuse::per_lane; }
+    if (e[0] == 'u') { sscanf(e, "u%d,%d", &dpb, &minw); reuse = Reuse::wave_uniform; }
+    if (e[0] == 'v') { sscanf(e, "v%d,%d", &dpb, &minw); reuse = Reuse::wave_uniform_late; }
     for (int i = 0; i < nforms; ++i)
         if (forms[i].reuse == reuse && forms[i].dpb == dpb && forms[i].minw == minw) return launch_gather(p, 8, dpb, forms[i].kernel, st);
     set_error("warp_variance: MVD_K3_CFG=%s is not a compiled variant", e);

@@ -28,8 +28,6 @@
 // The two passes are separate loops on purpose: one loop with both tap sources makes every accumulator a phi of two
 // definitions, which this compiler does not coalesce (168 VGPRs + spills instead of 126).  LDS use: 2 windows + 10.6 KiB +
 // 8 bytes per (chunk, view) of a workgroup's march.
-#include "mvd_common.h"
-#include <type_traits>
 #include "warp_variance_common.h"
 
 namespace mvd {
@@ -133,14 +131,10 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_tile_kernel(WarpParam
     const unsigned DEP0 = VIEW0 + (unsigned)V * sizeof(ViewRec), UNIT0 = DEP0 + (unsigned)nch * 32;
 
     // ---- decode the block index: xcd | (chunk group fastest, then tile within the XCD's band, then batch) ----
-    const int xcd = blockIdx.x & 7;
-    int j = blockIdx.x >> 3;
     const int dchunks = (D + P - 1) / P;
     const int dgroups = (dchunks + nch - 1) / nch;
-    const int dg = j % dgroups; j /= dgroups;
-    const int tile_in = j % p.tiles_per_xcd;
-    const int b = j / p.tiles_per_xcd;
-    const int tile = xcd * p.tiles_per_xcd + tile_in;
+    const BlockWork blk = decode_xcd_first(blockIdx.x, dgroups, p.tiles_per_xcd);
+    const int dg = blk.chunk, b = blk.b, tile = blk.tile;
     if (tile >= p.tiles_x * p.tiles_y) return;  // block-uniform
     const int tyi = tile / p.tiles_x;
     const int x0 = (tile - tyi * p.tiles_x) * TW, y0 = tyi * (NPX / TW);
@@ -188,38 +182,17 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_tile_kernel(WarpParam
                                                  0, (int)img_bytes, 0x00020000);
     };
 
-    // w/(w-1), h/(h-1) of the folded grid arithmetic: two IEEE divisions, done once and kept in scalar registers (left inside
-    // `position` the compiler redoes them, 12 vector instructions each, for every unit)
-    const float sx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)w / (float)(w - 1))));
-    const float sy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)h / (float)(h - 1))));
-    // sampling position of key pixel (fx, fy) at `depth` under the composed transform M (12 floats) of a source view,
-    // clamped into the zero border (a sample outside the image lands on zero taps; v_med3_f32 sends NaN to -1); returns Z
-    auto position = [&](const float (&M)[12], float fx, float fy, float depth, float& ix, float& iy) -> float {
-        float Z;
-        if constexpr (EXACT) {
-            // the reference's own chain, one rounding per step: R @ (x*d, y*d, d) + T (utils.py:246-250), perspective divide
-            // (IEEE), /((W-1)/2) - 1 (:256-257), then grid_sample's ((g+1)*W-1)/2
-            const float half_w = (float)(w - 1) / 2.0f, half_h = (float)(h - 1) / 2.0f;
-            const float gx = fx * depth, gy = fy * depth;
-            const float X = ((M[0] * gx + M[1] * gy) + M[2] * depth) + M[3];
-            const float Y = ((M[4] * gx + M[5] * gy) + M[6] * depth) + M[7];
-            Z = ((M[8] * gx + M[9] * gy) + M[10] * depth) + M[11];
-            ix = unnormalize_coord((X / Z) / half_w - 1.0f, (float)w);
-            iy = unnormalize_coord((Y / Z) / half_h - 1.0f, (float)h);
-        } else {
-            // folded: ix = (X/Z) * w/(w-1) - 0.5 with 1/Z from v_rcp_f32 (within 1e-4 px of the chain above)
-            const float ax = fmaf(M[0], fx, fmaf(M[1], fy, M[2]));
-            const float ay = fmaf(M[4], fx, fmaf(M[5], fy, M[6]));
-            const float az = fmaf(M[8], fx, fmaf(M[9], fy, M[10]));
-            const float X = fmaf(ax, depth, M[3]), Y = fmaf(ay, depth, M[7]);
-            Z = fmaf(az, depth, M[11]);
-            const float rz = __builtin_amdgcn_rcpf(Z);
-            ix = fmaf(X * rz, sx, -0.5f);
-            iy = fmaf(Y * rz, sy, -0.5f);
-        }
-        ix = __builtin_amdgcn_fmed3f(ix, -1.0f, (float)w);
-        iy = __builtin_amdgcn_fmed3f(iy, -1.0f, (float)h);
-        return Z;
+    // The grid scales of sample_position<EXACT>.  Folded, w/(w-1) and h/(h-1) are two IEEE divisions: done once and kept in scalar
+    // registers (left to the compiler they are redone, 12 vector instructions each, for every unit)
+    float sx = grid_scale<EXACT>(w), sy = grid_scale<EXACT>(h);
+    if constexpr (!EXACT) {
+        sx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sx)));
+        sy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sy)));
+    }
+    // sampling position of key pixel (fx, fy) at `depth` under the composed transform M (12 floats) of a source view, clamped
+    // into the zero border (a sample outside the image lands on zero taps; NaN goes to -1)
+    auto position = [&](const float (&M)[12], float fx, float fy, float depth) {
+        return sample_position<EXACT>(M, fx, fy, depth, sx, sy, (float)w, (float)h);
     };
 
     // ---- PROBE: per (chunk, view) the box of the tile's samples, from its 8 corner samples, one cell wider on every side
@@ -251,10 +224,10 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_tile_kernel(WarpParam
         __syncthreads();
         for (int jc = 0; jc < nchunks; ++jc) {
             const float depth = *reinterpret_cast<const float*>(lds + DEP0 + (jc * P + ((co & 4) ? P - 1 : 0)) * 4);
-            float ix, iy;
-            const float Z = position(M, cfx, cfy, depth, ix, iy);
-            const unsigned cell = ((unsigned)((int)floorf(iy) + 1) << 16) | (unsigned)((int)floorf(ix) + 1);
-            const bool ok = Z > 0.0f;  // false for NaN too: then the box is the whole map (does not fit)
+            const SamplePos sp = position(M, cfx, cfy, depth);
+            // packed 16-bit box coordinates (padded), so that min and max over the corners are one v_pk_min / max_u16 each
+            const unsigned cell = ((unsigned)((int)floorf(sp.iy) + 1) << 16) | (unsigned)((int)floorf(sp.ix) + 1);
+            const bool ok = sp.Z > 0.0f;  // false for NaN too: then the box is the whole map (does not fit)
             unsigned mn = ok ? cell : 0u, mx = ok ? cell : 0xffffffffu;
             mn = pk_min_u16(mn, row_shr<1>(mn)); mx = pk_max_u16(mx, row_shr<1>(mx));
             mn = pk_min_u16(mn, row_shr<2>(mn)); mx = pk_max_u16(mx, row_shr<2>(mx));
@@ -304,14 +277,12 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_tile_kernel(WarpParam
         const float4 m0 = *reinterpret_cast<const float4*>(vr->M), m1 = *reinterpret_cast<const float4*>(vr->M + 4),
                      m2 = *reinterpret_cast<const float4*>(vr->M + 8);
         const float M[12] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w};
-        float ix, iy;
-        position(M, lfx, lfy, depth, ix, iy);
-        const float xf = floorf(ix), yf = floorf(iy);
-        const float wx = ix - xf, wy = iy - yf;
-        const float ux = 1.0f - wx, uy = 1.0f - wy;
-        *reinterpret_cast<float4*>(lds + TABW0 + slot * 4096 + t * 16) = make_float4(ux * uy, wx * uy, ux * wy, wx * wy);
+        const SamplePos sp = position(M, lfx, lfy, depth);
+        const CellWeights cw = cell_weights(sp.ix, sp.iy);
+        *reinterpret_cast<float4*>(lds + TABW0 + slot * 4096 + t * 16) = cw.all();
         unsigned* const ent = reinterpret_cast<unsigned*>(lds + TABO0 + slot * 1024 + (lpx * P + li) * 4);
-        const int cx = (int)xf + 1, cy = (int)yf + 1;  // padded coordinates of the cell's first tap
+        // padded coordinates of the cell's first tap, as integers: pass 0 places the cell in the unit's window
+        const int cx = (int)cw.xf + 1, cy = (int)cw.yf + 1;
         if (wb < 0) {  // wave-uniform
             *ent = (unsigned)(cy * W2 + cx) * PIXB;
         } else {
@@ -369,8 +340,8 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_tile_kernel(WarpParam
         if constexpr (LDSTAPS) pitch = *reinterpret_cast<const unsigned*>(lds + UNIT0 + (jc * V + v) * sizeof(UnitRec) + 8);
         else rsrc = src_rsrc(v);
         auto weights = [&](int i) { return *reinterpret_cast<const float4*>(tw + i * (NPX * 16)); };
-        auto taps = [&](int i, TAP (&f)[4]) {
-            const unsigned o = ofs[i] + q_b;
+        // the four taps of the cell whose first tap is at `o` (window address, or byte offset in the source map)
+        auto read_taps = [&](unsigned o, TAP (&f)[4]) {
             if constexpr ((MVD_K3T_KO & 2) != 0) {
                 if constexpr (F16) { f[0] = u32x2{o, o + 1}; f[1] = u32x2{o + 2, o + 3}; f[2] = u32x2{o + pitch, o + 5}; f[3] = u32x2{o + 6, o + 7}; }
                 else { f[0] = u32x4{o, o + 1, o + 2, o + 3}; f[1] = u32x4{o + 4, o + 5, o + 6, o + 7};
@@ -380,16 +351,11 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_tile_kernel(WarpParam
                 f[1] = *reinterpret_cast<const TAP*>(lds + o + PIXB);
                 f[2] = *reinterpret_cast<const TAP*>(lds + o + pitch);
                 f[3] = *reinterpret_cast<const TAP*>(lds + o + pitch + PIXB);
-            } else if constexpr (F16) {
-                f[0] = load_b64(rsrc, o, 0); f[1] = load_b64(rsrc, o + PIXB, 0);
-                f[2] = load_b64(rsrc, o, rowb); f[3] = load_b64(rsrc, o + PIXB, rowb);
             } else {
-                f[0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o, 0, 0);
-                f[1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + PIXB, 0, 0);
-                f[2] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o, rowb, 0);
-                f[3] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + PIXB, rowb, 0);
+                gather_cell<RowPitch::in_soffset>(f, rsrc, o, rowb, PIXB);
             }
         };
+        auto taps = [&](int i, TAP (&f)[4]) { read_taps(ofs[i] + q_b, f); };
         // Sweep coherence: between planes a sample moves a fraction of a pixel, so the 2x2 cell of plane i is often the cell of
         // plane i-2 for every pixel of the wave (host count at the headline poses: 54 % of the tap fetches remain).  Plane i
         // uses tap set i & 1; the set is re-read only when some lane's cell differs (wave-uniform branch, registers refreshed
@@ -402,22 +368,8 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_tile_kernel(WarpParam
             unsigned oi = ofs[i];
             asm volatile("" : "+v"(done.a1[0]), "+v"(done.a1[1]), "+v"(done.a2[0]), "+v"(done.a2[1]), "+v"(oi));
             if (__builtin_amdgcn_ballot_w64(oi != ofs[i - SETS]) != 0) {
-                const unsigned o = oi + q_b;
-                if constexpr ((MVD_K3T_KO & 2) != 0) { taps(i, f); }
-                else if constexpr (LDSTAPS) {
-                    f[0] = *reinterpret_cast<const TAP*>(lds + o);
-                    f[1] = *reinterpret_cast<const TAP*>(lds + o + PIXB);
-                    f[2] = *reinterpret_cast<const TAP*>(lds + o + pitch);
-                    f[3] = *reinterpret_cast<const TAP*>(lds + o + pitch + PIXB);
-                } else if constexpr (F16) {
-                    f[0] = load_b64(rsrc, o, 0); f[1] = load_b64(rsrc, o + PIXB, 0);
-                    f[2] = load_b64(rsrc, o, rowb); f[3] = load_b64(rsrc, o + PIXB, rowb);
-                } else {
-                    f[0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o, 0, 0);
-                    f[1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + PIXB, 0, 0);
-                    f[2] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o, rowb, 0);
-                    f[3] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + PIXB, rowb, 0);
-                }
+                if constexpr ((MVD_K3T_KO & 2) != 0) taps(i, f);
+                else read_taps(oi + q_b, f);
             }
         };
         if constexpr (SETS == 2) {
@@ -475,9 +427,8 @@ __global__ void __launch_bounds__(256, MINW) warp_variance_tile_kernel(WarpParam
         const int nvalid = drop ? 0 : min(P, D - c * P);  // planes of this chunk that exist (and are kept)
 #pragma unroll
         for (int i = 0; i < P; ++i) {
-            const float mx = sm[i].a1[0].x * inv_nv, my = sm[i].a1[0].y * inv_nv, mz = sm[i].a1[1].x * inv_nv, mw = sm[i].a1[1].y * inv_nv;
-            const float4 r = make_float4(fmaf(sm[i].a2[0].x, inv_nv, -mx * mx), fmaf(sm[i].a2[0].y, inv_nv, -my * my),
-                                         fmaf(sm[i].a2[1].x, inv_nv, -mz * mz), fmaf(sm[i].a2[1].y, inv_nv, -mw * mw));
+            const float4 r = variance_finish(make_float4(sm[i].a1[0].x, sm[i].a1[0].y, sm[i].a1[1].x, sm[i].a1[1].y),
+                                             make_float4(sm[i].a2[0].x, sm[i].a2[0].y, sm[i].a2[1].x, sm[i].a2[1].y), inv_nv);
             const unsigned long long pb = plane0 + (i < nvalid ? (unsigned long long)i * plane_bytes : 0ull);
             const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(pb), 0, i < nvalid ? (int)plane_bytes : 0, 0x00020000);
             if constexpr ((MVD_K3T_KO & 4) != 0) { if (r.x != 123.456f) continue; }
@@ -631,6 +582,7 @@ int launch_warp_tile(const WarpParams& p0, hipStream_t st, int tw, int win, int 
     const dim3 grid((unsigned)nblk);
     int rc = MVD_ERR_INVALID_ARG;
     timing_begin(st);
+#ifdef MVD_EXPERIMENTS
 #define MVD_T(TW_, WIN_, MW_, SETS_)                                                                                   \
     if (tw == TW_ && win == WIN_ && sets == SETS_) {                                                                  \
         rc = f16 ? (exact ? launch_tile_variant<TW_, WIN_, true, true, MW_, SETS_>(p, grid, st, nch)                  \
@@ -638,14 +590,22 @@ int launch_warp_tile(const WarpParams& p0, hipStream_t st, int tw, int win, int 
                  : (exact ? launch_tile_variant<TW_, WIN_, false, true, MW_, SETS_>(p, grid, st, nch)                 \
                           : launch_tile_variant<TW_, WIN_, false, false, MW_, SETS_>(p, grid, st, nch));              \
     }
-    MVD_T(8, 104, 4, 1) MVD_T(8, 128, 4, 1)  // product: fp32 maps, fp16 maps (half the window bytes)
-#ifdef MVD_EXPERIMENTS
-    MVD_T(8, 128, 3, 2) MVD_T(8, 96, 4, 1) MVD_T(16, 128, 3, 2) MVD_T(16, 104, 4, 1) MVD_T(16, 96, 4, 1) MVD_T(32, 128, 3, 2) MVD_T(32, 104, 4, 1)
-#endif
+    MVD_T(8, 104, 4, 1) MVD_T(8, 128, 4, 1) MVD_T(8, 128, 3, 2) MVD_T(8, 96, 4, 1) MVD_T(16, 128, 3, 2) MVD_T(16, 104, 4, 1)
+    MVD_T(16, 96, 4, 1) MVD_T(32, 128, 3, 2) MVD_T(32, 104, 4, 1)
 #undef MVD_T
+#else
+    // the product's three: fp32 maps on either grid, fp16 maps (half the window bytes) on the folded grid (launch_k3)
+    if (tw == 8 && sets == 1 && !f16 && win == 104) {
+        rc = exact ? launch_tile_variant<8, 104, false, true, 4, 1>(p, grid, st, nch)
+                   : launch_tile_variant<8, 104, false, false, 4, 1>(p, grid, st, nch);
+    } else if (tw == 8 && sets == 1 && f16 && win == 128 && !exact) {
+        rc = launch_tile_variant<8, 128, true, false, 4, 1>(p, grid, st, nch);
+    }
+#endif
     timing_end(st);
     if (rc == MVD_ERR_INVALID_ARG) {
-        set_error("warp_variance: tile variant tw=%d win=%d sets=%d is not compiled", tw, win, sets);
+        set_error("warp_variance: tile variant tw=%d win=%d sets=%d (%s maps, %s grid) is not compiled", tw, win, sets, f16 ? "fp16" : "fp32",
+                  exact ? "exact" : "folded");
         return rc;
     }
     if (rc) return rc;
