@@ -235,6 +235,21 @@ int mvd_conv3d_bn_relu_absmax_f32(const float* x, const float* packed_w, const f
  * partials in a fixed order, so two calls on the same inputs give bit-identical gw.  gw is written, not accumulated.
  * The measurement hook (mvd_arm_kernel_timing) brackets the two kernels. */
 size_t mvd_conv3d_weight_grad_workspace_bytes(int B, int Di, int hi, int wi, int Cin, int Cout, int mode);
+/* One field of the launch plan mvd_conv3d_weight_grad_f32 follows for these arguments, from the same planning code as the launch
+ * (for tests and tools that must know which path a size takes; the values are a tuning matter and may change between versions).
+ * A workgroup marches over DZ depth planes of the tiled tensor per work item; `items` work items are walked by PARTIALS
+ * workgroups per channel block (items > PARTIALS: a workgroup takes several items and keeps summing); the kernel instantiation
+ * is <COT, CIT, S> (16-channel tiles per 32-channel block on the tiled and on the haloed side, stride of the taps) and
+ * CS_BLOCKS x CG_BLOCKS channel blocks.  0 for unsupported arguments (where the workspace size is 0) or an unknown field. */
+#define MVD_WGRAD_PLAN_DZ 0
+#define MVD_WGRAD_PLAN_ITEMS 1
+#define MVD_WGRAD_PLAN_PARTIALS 2
+#define MVD_WGRAD_PLAN_COT 3
+#define MVD_WGRAD_PLAN_CIT 4
+#define MVD_WGRAD_PLAN_S 5
+#define MVD_WGRAD_PLAN_CS_BLOCKS 6
+#define MVD_WGRAD_PLAN_CG_BLOCKS 7
+size_t mvd_conv3d_weight_grad_plan_field(int B, int Di, int hi, int wi, int Cin, int Cout, int mode, int field);
 int mvd_conv3d_weight_grad_f32(const float* x, const float* gy, float* gw, int B, int Di, int hi, int wi, int Cin, int Cout,
                                int mode, void* workspace, size_t workspace_bytes, mvd_stream_t stream);
 

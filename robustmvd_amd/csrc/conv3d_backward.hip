@@ -334,6 +334,22 @@ size_t mvd_conv3d_weight_grad_workspace_bytes(int B, int Di, int hi, int wi, int
     return mvd::wgrad_plan(B, Di, hi, wi, Cin, Cout, mode, pl) ? 0 : pl.bytes;
 }
 
+size_t mvd_conv3d_weight_grad_plan_field(int B, int Di, int hi, int wi, int Cin, int Cout, int mode, int field) {
+    mvd::WGradPlan pl;
+    if (mvd::wgrad_plan(B, Di, hi, wi, Cin, Cout, mode, pl)) return 0;
+    switch (field) {
+        case MVD_WGRAD_PLAN_DZ: return (size_t)pl.p.DZ;
+        case MVD_WGRAD_PLAN_ITEMS: return (size_t)pl.p.items;
+        case MVD_WGRAD_PLAN_PARTIALS: return (size_t)pl.P;
+        case MVD_WGRAD_PLAN_COT: return (size_t)pl.COT;
+        case MVD_WGRAD_PLAN_CIT: return (size_t)pl.CIT;
+        case MVD_WGRAD_PLAN_S: return (size_t)pl.S;
+        case MVD_WGRAD_PLAN_CS_BLOCKS: return (size_t)pl.cs_blocks;
+        case MVD_WGRAD_PLAN_CG_BLOCKS: return (size_t)pl.p.cg_blocks;
+        default: return 0;
+    }
+}
+
 int mvd_conv3d_weight_grad_f32(const float* x, const float* gy, float* gw, int B, int Di, int hi, int wi, int Cin, int Cout, int mode,
                                void* workspace, size_t workspace_bytes, mvd_stream_t stream) {
     using namespace mvd;
