@@ -777,6 +777,76 @@ int mvd_cloud_pair_sums_f32(const float* source, long long n, const double* tran
                             void* workspace, size_t workspace_bytes, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Point-cloud clean-up: the neighbours within a radius, the k nearest, PCA normals and outlier removal.  The reference has NO
+ * counterpart: the definition is robustmvd_amd/cloud_clean.py (neighbourhood_numpy, knn_numpy, list_moments_numpy,
+ * normals_from_moments_numpy, remove_outliers_numpy) and DESIGN.md, restated here.  No entry uses an atomic.
+ *
+ * Pair distance of a query q and a target p, in float32 and in exactly this order, without contraction:
+ *   dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z,  d2 = (dx dx + dy dy) + dz dz
+ * which are float32 numpy's bits, so membership and order are exact integers.  (mvd_cloud_nearest_f32 contracts to FMAs: another d2.)
+ * p is a NEIGHBOUR of q iff both are valid and d2 < r2 (strict), r2 = radius * radius in float32.  exclude_self != 0: the queries ARE
+ * the targets (the same records), and a point is not its own neighbour, by index; its duplicates are, at distance 0.
+ * Records, keys, origin and inv are mvd_cloud_grid_build_f32's and mvd_cloud_nearest_f32's; the cell edge 1 / inv must be at least
+ * radius (1 + 2^-10) (the 27-cell argument for d2 < r2 is in csrc/cloud_clean.hip).  Outputs are in the queries' ORIGINAL order.
+ * n == 0 writes nothing; m == 0 gives empty neighbourhoods.
+ *
+ * Radius moments.  count (n) int32; sum_dist (n) float64 = sum of double(sqrtf(d2)); moments (n,9) float64: with
+ * v = (double(p.x) - double(q.x), double(p.y) - double(q.y), double(p.z) - double(q.z)), relative to the QUERY, sum v (3) then
+ * sum v_a v_b for a <= b (6, row-major).  ORDER: every sum starts from +0.0 and adds the neighbours one after the other in ascending
+ * position of the target grid's sorted order, that is by (cell key, original index).  An invalid query or one without neighbours
+ * gives 0 and zeros. */
+#define MVD_CLOUD_KNN_MAX 16
+int mvd_cloud_radius_moments_f32(const float* query_records, long long n, const float* target_records, const long long* target_keys,
+                                 long long m, double origin_x, double origin_y, double origin_z, double inv, float radius,
+                                 int exclude_self, int* count, double* sum_dist, double* moments, mvd_stream_t stream);
+
+/* The up-to-k neighbours within max_dist that are smallest in (bits of d2, original index), 1 <= k <= MVD_CLOUD_KNN_MAX, n k < 2^31:
+ * index (n,k) int32 ascending in that order and -1 past the found ones; dist (n,k) float32 = sqrtf(d2), max_dist past them; count (n)
+ * int32.  The list is kept in registers at a capacity of 4, 8 or 16: a k in between is served by the next capacity. */
+int mvd_cloud_knn_f32(const float* query_records, long long n, const float* target_records, const long long* target_keys, long long m,
+                      double origin_x, double origin_y, double origin_z, double inv, float max_dist, int k, int exclude_self,
+                      int* index, float* dist, int* count, mvd_stream_t stream);
+
+/* mvd_cloud_radius_moments_f32's outputs over each query's list instead: queries (n,3), targets (m,3), index and dist (n,k) of
+ * mvd_cloud_knn_f32; the entries are added in LIST order up to the first index outside [0, m), sum_dist from double(dist). */
+int mvd_cloud_list_moments_f32(const float* queries, long long n, const float* targets, long long m, const int* index, const float* dist,
+                               int k, int* count, double* sum_dist, double* moments, mvd_stream_t stream);
+
+/* Normals from moments, one lane per point, float64.  The PCA is over the neighbours AND the point itself, which adds zeros:
+ * N = count + 1, mean = sum v / N, C = sum v v^T / N - mean mean^T (each entry: one division, one product, one difference).
+ * l0 <= l1 <= l2: C's eigenvalues (cyclic Jacobi, a fixed number of sweeps); normal (n,3) float32 = the unit eigenvector of l0;
+ * curvature (n) float32 = l0 / ((l0 + l1) + l2), the surface variation, 0 when the sum is 0.  The normal is (0,0,0) and the curvature NaN
+ * where count < min_neighbours (at least 2), where l1 <= 1e-9 l2 (collinear or coincident neighbours) or where the point is invalid.
+ * Orientation, on the float64 unit vector u before it is rounded: orient 1: w = (toward_x, toward_y, toward_z) - double(q);
+ * 2: w = double(toward[i]) - double(q); 3: w = double(toward[i]) (reference normals); dot = (u.x w.x + u.y w.y) + u.z w.z; u is
+ * flipped when dot < 0.  orient 0, or a dot that is 0 or NaN: flipped when its component of largest magnitude (the first among
+ * equals) is negative.  toward (n,3) float32: orient 2 and 3 only, else NULL. */
+int mvd_cloud_normals_f64(const float* points, long long n, const int* count, const double* moments, int min_neighbours, int orient,
+                          double toward_x, double toward_y, double toward_z, const float* toward, float* normal, float* curvature,
+                          mvd_stream_t stream);
+
+/* The verdicts of outlier removal, keep (n) bytes 0 / 1; an invalid point is always dropped.
+ * Density: keep iff the point is valid and count >= min_neighbours.
+ * Statistical: mean (n) float64 = (sum over the list of double(dist), in list order from +0.0) / k where count == k (a FULL list), NaN
+ * elsewhere; result (32 bytes, device, 8-byte aligned) = the float64 sum of those means, the float64 sum of their squares, their
+ * number as int64 and a zero, added in the two-level order of mvd_cloud_scores_f32 (2048 consecutive points per workgroup).  The host
+ * forms the threshold; keep iff mean <= threshold.  workspace: mvd_cloud_knn_mean_sums_workspace_bytes(n). */
+int mvd_cloud_keep_density(const float* points, const int* count, long long n, int min_neighbours, unsigned char* keep,
+                           mvd_stream_t stream);
+size_t mvd_cloud_knn_mean_sums_workspace_bytes(long long n);
+int mvd_cloud_knn_mean_sums_f32(const float* dist, const int* count, long long n, int k, double* mean, void* result, void* workspace,
+                                size_t workspace_bytes, mvd_stream_t stream);
+int mvd_cloud_keep_threshold(const double* mean, long long n, double threshold, unsigned char* keep, mvd_stream_t stream);
+
+/* The kept points of a keep mask: kept (n) int32 receives their original indices in ascending order, remap (n) int32 the new index of
+ * every point or -1, total (device, 8-byte aligned) their number.  A deterministic compaction (ballot counts, one workgroup's scan,
+ * rank in the ballot), as mvd_voxel_reduce_f32's; rows then move through mvd_mesh_gather_rows_f32 with remap.
+ * workspace: mvd_cloud_select_workspace_bytes(n). */
+size_t mvd_cloud_select_workspace_bytes(long long n);
+int mvd_cloud_select(const unsigned char* keep, long long n, int* kept, int* remap, long long* total, void* workspace,
+                     size_t workspace_bytes, mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * TSDF volume: the views' depth maps averaged into a truncated signed distance volume, and its surface as a triangle mesh.  The
  * reference has NO counterpart: the definition is robustmvd_amd/tsdf.py (its docstring, integrate_numpy, extract_numpy) and DESIGN.md.
  *

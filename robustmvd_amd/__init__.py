@@ -27,6 +27,10 @@ from .cloud_eval import (PointCloudEvaluation, CloudScore, evaluate_scene, read_
                          cloud_scores_numpy, voxel_downsample_numpy)
 from . import cloud_register  # noqa: F401,E402
 from .cloud_register import register_clouds, register_numpy, Registration  # noqa: F401,E402
+from . import cloud_clean  # noqa: F401,E402
+from .cloud_clean import (cloud_knn, cloud_neighbourhood, estimate_normals, remove_outliers, cloud_spacing, knn_numpy,  # noqa: F401,E402
+                          neighbourhood_numpy, list_moments_numpy, normals_from_moments_numpy, estimate_normals_numpy,
+                          remove_outliers_numpy, KNN, Neighbourhood)
 from . import tsdf  # noqa: F401,E402
 from .mesh import Mesh  # noqa: F401,E402
 from .tsdf import TSDFVolume, integrate_numpy, extract_numpy, bounds_from_points  # noqa: F401,E402

@@ -101,7 +101,7 @@ class CloudScore:
     points of the evaluated prediction (after thinning) and of the ground truth; dist_pred (n,), dist_gt (m,) float32: the truncated
     distances per point, for colouring an error cloud (GPU tensors on the device path); pred_points, pred_colors: the evaluated
     prediction, i.e. the thinned (and, with align, registered) cloud that dist_pred belongs to; registration: the
-    cloud_register.Registration that aligned it, or None."""
+    cloud_register.Registration that aligned it, or None; n_removed: the points that clean= took out of the thinned prediction."""
     accuracy: float
     completeness: float
     overall: float
@@ -117,6 +117,7 @@ class CloudScore:
     pred_points: object = None
     pred_colors: object = None
     registration: object = None
+    n_removed: int = 0
 
 
 def combine_scores(sum_p, n_p, cnt_p, sum_g, n_g, cnt_g, **fields):
@@ -204,9 +205,14 @@ class PointCloudEvaluation:
     max_dist defaults to 4 x the largest threshold.  With voxel, the prediction is thinned first (its colours with it).
     align = "rigid", "similarity" or "plane": the thinned prediction is registered onto the ground truth first
     (cloud_register.register_clouds, at the radii align_max_dist, by default (4, 2, 1) x max_dist; "plane" needs gt_normals (m,3), given
-    here or per call) and the ALIGNED prediction is scored; the score's `registration` tells how it went."""
+    here or per call) and the ALIGNED prediction is scored; the score's `registration` tells how it went.
+    gt_normals="estimate": the ground truth's normals are estimated (cloud_clean.estimate_normals) from its neighbours within
+    normal_radius, by default 4 x the largest threshold: a scan read without normals can serve align="plane".
+    clean=dict(...): cloud_clean.remove_outliers' keywords; the prediction is filtered after the thinning and before registration and
+    scoring, and the score's n_removed tells how many points that took."""
 
-    def __init__(self, thresholds, max_dist=None, voxel=None, align=None, align_max_dist=None, gt_normals=None):
+    def __init__(self, thresholds, max_dist=None, voxel=None, align=None, align_max_dist=None, gt_normals=None, clean=None,
+                 normal_radius=None):
         self.thresholds, self.max_dist = check_thresholds(thresholds, max_dist)
         if voxel is not None and not (np.float32(voxel) > 0 and np.isfinite(np.float32(voxel))):
             raise ValueError(f"voxel must be finite and > 0, got {voxel}")
@@ -220,6 +226,28 @@ class PointCloudEvaluation:
                                          else align_max_dist)
         elif align_max_dist is not None or gt_normals is not None:
             raise ValueError("align_max_dist and gt_normals belong to align=...")
+        if isinstance(gt_normals, str) and gt_normals != "estimate":
+            raise ValueError(f"gt_normals must be (m,3) normals or 'estimate', got {gt_normals!r}")
+        if normal_radius is not None and not (isinstance(gt_normals, str) and np.float32(normal_radius) > 0
+                                              and np.isfinite(np.float32(normal_radius))):
+            raise ValueError(f"normal_radius must be finite and > 0 and belongs to gt_normals='estimate', got {normal_radius}")
+        self.normal_radius = float(np.float32(4.0) * self.thresholds.max() if normal_radius is None else np.float32(normal_radius))
+        self.clean = None
+        if clean is not None:
+            from .cloud_clean import _outlier_rule
+            self.clean = dict(clean)
+            unknown = sorted(set(self.clean) - {"radius", "min_neighbours", "k", "std_ratio", "max_dist"})
+            if unknown:
+                raise ValueError(f"clean: unexpected {unknown}")
+            _outlier_rule(*[self.clean.get(a) for a in ("radius", "min_neighbours", "k", "std_ratio", "max_dist")])
+
+    def _clean(self, pred, colors):
+        """-> (the filtered prediction, its colours, the points removed), or the inputs and 0 without clean"""
+        if self.clean is None:
+            return pred, colors, 0
+        from .cloud_clean import remove_outliers
+        out = remove_outliers(pred, colors, **self.clean)
+        return out.points, out.colors, int(pred.shape[0] - out.points.shape[0])
 
     def _register(self, pred, gt, gt_normals):
         """-> (the aligned prediction, the Registration), or (pred, None) without align"""
@@ -231,6 +259,11 @@ class PointCloudEvaluation:
         normals = self.gt_normals if gt_normals is None else gt_normals
         if self.align == "plane" and normals is None:
             raise ValueError("align='plane' needs gt_normals")
+        if isinstance(normals, str):  # "estimate": only the plane mode reads them
+            normals = None
+            if self.align == "plane":
+                from .cloud_clean import estimate_normals
+                normals, _ = estimate_normals(gt, radius=self.normal_radius)
         if normals is not None and place(normals) != place(gt):
             if place(gt) == "host":
                 normals = to_numpy(normals)
@@ -251,9 +284,10 @@ class PointCloudEvaluation:
         pred, gt = host_points(pred, "pred_points"), host_points(gt, "gt_points")
         if self.voxel is not None:
             pred, colors, _ = voxel_downsample_numpy(pred, self.voxel, colors)
+        pred, colors, removed = self._clean(pred, colors)
         pred, reg = self._register(pred, gt, gt_normals)
         score = cloud_scores_numpy(pred, gt, self.thresholds, self.max_dist)
-        score.pred_colors, score.registration = colors, reg
+        score.pred_colors, score.registration, score.n_removed = colors, reg, removed
         return score
 
     def _run_device(self, pred, gt, colors, gt_normals=None):
@@ -268,6 +302,7 @@ class PointCloudEvaluation:
         if self.voxel is not None:
             pred, colors, _ = ops.voxel_downsample(pred, self.voxel, colors)
         pred, gt = ops.cloud_points(pred, "pred_points"), ops.cloud_points(gt, "gt_points", dev)
+        pred, colors, removed = self._clean(pred, colors)
         pred, reg = self._register(pred, gt, gt_normals)
         md, T = float(self.max_dist), len(self.thresholds)
         cell = md * ops.CLOUD_CELL_MARGIN
@@ -285,7 +320,7 @@ class PointCloudEvaluation:
         sp, np_, cp = ops.cloud_scores_read(blocks[0], T)
         sg, ng, cg = ops.cloud_scores_read(blocks[1], T)
         return combine_scores(sp, np_, cp, sg, ng, cg, dist_pred=dp, dist_gt=dg, thresholds=self.thresholds, max_dist=md, pred_points=pred,
-                        pred_colors=colors, registration=reg)
+                        pred_colors=colors, registration=reg, n_removed=removed)
 
 
 def evaluate_scene(model, images, intrinsics, poses, gt_points, fusion=None, num_sources=None, evaluation=None, gt_normals=None,
@@ -293,7 +328,7 @@ def evaluate_scene(model, images, intrinsics, poses, gt_points, fusion=None, num
     """model -> depth maps -> fused cloud -> CloudScore: DepthFusion.reconstruct chained into PointCloudEvaluation, so that a registered
     model reaches the fusion and the scoring kernels end to end.  images, intrinsics, poses, num_sources: reconstruct's; fusion: a
     DepthFusion (default DepthFusion()); evaluation: a PointCloudEvaluation, or its arguments as keywords (thresholds=..., voxel=...,
-    align=..., align_max_dist=...); gt_normals: the ground truth's normals for align="plane".
+    align=..., align_max_dist=..., clean=...); gt_normals: the ground truth's normals for align="plane", or "estimate".
     The scene is fused where reconstruct puts it (the model's GPU; a ground truth that is a GPU tensor asks for its device) and the
     ground truth is taken there."""
     if evaluation is None:

@@ -1565,6 +1565,183 @@ def voxel_downsample(points, voxel, colors=None, origin=None):
     return xyz[:k].clone(), None if rgb is None else rgb[:k].clone(), counts[:k].clone()
 
 
+CLOUD_KNN_MAX = L.CLOUD_KNN_MAX  # the largest k of cloud_knn
+
+
+def _neighbour_query(query, grid, radius, name):
+    """The shared front of cloud_radius_moments and cloud_knn -> (query records, exclude_self, radius as the float32 the kernel
+    squares).  query: None or the grid itself (every point of the grid's cloud asks, and is not its own neighbour), another
+    CloudGrid of the same origin and cell, or (n,3) points."""
+    if not isinstance(grid, CloudGrid):
+        raise ValueError(f"grid: expected a CloudGrid (ops.cloud_grid), got {type(grid).__name__}")
+    dev = grid.points.device
+    radius = float(torch.tensor(float(radius), dtype=torch.float32))
+    if not 0.0 < radius < float("inf"):
+        raise ValueError(f"{name} must be finite and > 0, got {radius}")
+    if grid.cell < radius * CLOUD_CELL_MARGIN * (1 - 1e-12):
+        raise ValueError(f"the grid's cell {grid.cell:g} is below {name} * (1 + 2^-10) = {radius * CLOUD_CELL_MARGIN:g}")
+    if query is None or query is grid:
+        return grid.records, 1, radius
+    if isinstance(query, CloudGrid):
+        if query.origin != grid.origin or query.cell != grid.cell or query.points.device != dev:
+            raise ValueError("query and target grids differ in origin, cell or device")
+        return query.records, 0, radius
+    return cloud_grid(cloud_points(query, "query", dev), grid.origin, grid.cell, check=False).records, 0, radius
+
+
+@inference_only
+def cloud_radius_moments(query, grid, radius):
+    """Per query the targets of the grid's cloud with d2 < radius^2 (include/mvd.h: mvd_cloud_radius_moments_f32) -> (count (n) int32,
+    sum_dist (n) float64, moments (n,9) float64) in the query's original order.  query None or the grid itself: the cloud against
+    itself, a point not its own neighbour."""
+    rec, self_query, radius = _neighbour_query(query, grid, radius, "radius")
+    dev, n, m = grid.points.device, rec.shape[0], grid.points.shape[0]
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    sum_dist = torch.empty(n, dtype=torch.float64, device=dev)
+    moments = torch.empty((n, 9), dtype=torch.float64, device=dev)
+    call("mvd_cloud_radius_moments_f32", dev, rec, n, grid.records, grid.keys, m, grid.origin[0], grid.origin[1], grid.origin[2], grid.inv,
+         radius, self_query, count, sum_dist, moments)
+    return count, sum_dist, moments
+
+
+@inference_only
+def cloud_knn(query, grid, k, max_dist):
+    """Per query the up-to-k nearest targets of the grid's cloud within max_dist (include/mvd.h: mvd_cloud_knn_f32) -> (index (n,k)
+    int32, dist (n,k) float32, count (n) int32) in the query's original order.  query None or the grid itself: the cloud against
+    itself, a point not its own neighbour."""
+    k = int(k)
+    if not 1 <= k <= CLOUD_KNN_MAX:
+        raise ValueError(f"k = {k}, supported 1..{CLOUD_KNN_MAX}")
+    rec, self_query, max_dist = _neighbour_query(query, grid, max_dist, "max_dist")
+    dev, n, m = grid.points.device, rec.shape[0], grid.points.shape[0]
+    if n * k >= 2 ** 31:
+        raise ValueError(f"{n} queries of {k} neighbours: n k must be below 2^31")
+    index = torch.empty((n, k), dtype=torch.int32, device=dev)
+    dist = torch.empty((n, k), dtype=torch.float32, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    call("mvd_cloud_knn_f32", dev, rec, n, grid.records, grid.keys, m, grid.origin[0], grid.origin[1], grid.origin[2], grid.inv, max_dist, k,
+         self_query, index, dist, count)
+    return index, dist, count
+
+
+@inference_only
+def cloud_list_moments(points, targets, index, dist):
+    """cloud_radius_moments' outputs over the lists of cloud_knn (include/mvd.h: mvd_cloud_list_moments_f32): points (n,3), targets
+    (m,3), index and dist (n,k) -> (count (n) int32, sum_dist (n) float64, moments (n,9) float64)."""
+    idx = L.as_dtype(torch.int32, False, index, "index")
+    if idx.dim() != 2 or not 1 <= idx.shape[1] <= CLOUD_KNN_MAX:
+        raise ValueError(f"index must be (n,k) with k in 1..{CLOUD_KNN_MAX}, got {tuple(idx.shape)}")
+    dev, (n, k) = idx.device, idx.shape
+    d = L.as_dtype(torch.float32, False, dist, "dist", (n, k), dev)
+    p = L.as_dtype(torch.float32, False, cloud_points(points, "points", dev), "points", (n, 3))
+    t = cloud_points(targets, "targets", dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    sum_dist = torch.empty(n, dtype=torch.float64, device=dev)
+    moments = torch.empty((n, 9), dtype=torch.float64, device=dev)
+    call("mvd_cloud_list_moments_f32", dev, p, n, t if t.shape[0] else None, t.shape[0], idx, d, k, count, sum_dist, moments)
+    return count, sum_dist, moments
+
+
+@inference_only
+def cloud_normals(points, count, moments, min_neighbours=5, toward=None, like=None):
+    """Normals and surface variation from the moments (include/mvd.h: mvd_cloud_normals_f64) -> (normals (n,3) float32, curvature (n)
+    float32).  toward: a viewpoint of 3 numbers or (n,3) per-point viewpoints on the device; like: (n,3) reference normals; at most
+    one of them."""
+    p = cloud_points(points, "points")
+    n, dev = p.shape[0], p.device
+    cnt = L.as_dtype(torch.int32, False, count, "count", (n,), dev)
+    mom = L.as_dtype(torch.float64, False, moments, "moments", (n, 9), dev)
+    min_neighbours = int(min_neighbours)
+    if min_neighbours < 2:
+        raise ValueError(f"min_neighbours = {min_neighbours}, at least 2")
+    if toward is not None and like is not None:
+        raise ValueError("toward and like: at most one of them")
+    orient, w, per_point = 0, [0.0, 0.0, 0.0], None
+    if like is not None:
+        orient, per_point = 3, L.as_f32(like, "like", (n, 3), dev)
+    elif isinstance(toward, torch.Tensor) and toward.dim() == 2:
+        orient, per_point = 2, L.as_f32(toward, "toward", (n, 3), dev)
+    elif toward is not None:
+        orient, w = 1, _cloud_origin(toward, "toward")
+    normals = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    curvature = torch.empty(n, dtype=torch.float32, device=dev)
+    call("mvd_cloud_normals_f64", dev, p, n, cnt, mom, min_neighbours, orient, w[0], w[1], w[2], per_point, normals, curvature)
+    return normals, curvature
+
+
+@inference_only
+def cloud_keep_density(points, count, min_neighbours):
+    """keep (n) uint8: the point is valid and has at least min_neighbours neighbours (include/mvd.h: mvd_cloud_keep_density)."""
+    p = cloud_points(points, "points")
+    n, dev = p.shape[0], p.device
+    cnt = L.as_dtype(torch.int32, False, count, "count", (n,), dev)
+    min_neighbours = int(min_neighbours)
+    if min_neighbours < 0:
+        raise ValueError(f"min_neighbours = {min_neighbours}, at least 0")
+    keep = torch.empty(n, dtype=torch.uint8, device=dev)
+    call("mvd_cloud_keep_density", dev, p, cnt, n, min_neighbours, keep)
+    return keep
+
+
+@inference_only
+def cloud_knn_mean_sums(dist, count, result=None):
+    """The statistical rule's first half (include/mvd.h: mvd_cloud_knn_mean_sums_f32): dist (n,k), count (n) of cloud_knn -> (mean (n)
+    float64, NaN without a full list; a device int64 tensor of 4 words: the bits of the float64 sum of the means and of their
+    squares, and their number; read it with cloud_knn_mean_sums_read)."""
+    d = L.as_dtype(torch.float32, False, dist, "dist")
+    if d.dim() != 2 or not 1 <= d.shape[1] <= CLOUD_KNN_MAX:
+        raise ValueError(f"dist must be (n,k) with k in 1..{CLOUD_KNN_MAX}, got {tuple(d.shape)}")
+    dev, (n, k) = d.device, d.shape
+    cnt = L.as_dtype(torch.int32, False, count, "count", (n,), dev)
+    mean = torch.empty(n, dtype=torch.float64, device=dev)
+    result = _result_block(result, 4, dev, "dist's")
+    nbytes = L.load().mvd_cloud_knn_mean_sums_workspace_bytes(n)
+    ws = workspace(nbytes, dev)
+    call("mvd_cloud_knn_mean_sums_f32", dev, d, cnt, n, k, mean, result, ws, int(nbytes))
+    return mean, result
+
+
+def cloud_knn_mean_sums_read(result):
+    """cloud_knn_mean_sums' block on the host -> (sum of the means, sum of their squares, their number): the one read of the rule."""
+    r = result.cpu()
+    s = r[:2].view(torch.float64)
+    return float(s[0]), float(s[1]), int(r[2])
+
+
+@inference_only
+def cloud_keep_threshold(mean, threshold):
+    """keep (n) uint8: mean <= threshold, 0 for a NaN mean (include/mvd.h: mvd_cloud_keep_threshold)."""
+    mu = L.as_dtype(torch.float64, False, mean, "mean")
+    if mu.dim() != 1:
+        raise ValueError(f"mean must be (n,), got {tuple(mu.shape)}")
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("threshold is NaN")
+    keep = torch.empty(mu.shape[0], dtype=torch.uint8, device=mu.device)
+    call("mvd_cloud_keep_threshold", mu.device, mu, mu.shape[0], threshold, keep)
+    return keep
+
+
+@inference_only
+def cloud_select(keep):
+    """The kept points of keep (n) uint8 (include/mvd.h: mvd_cloud_select) -> (kept (K) int32: their indices ascending, remap (n) int32:
+    the new index or -1, K); the count is the one read.  Rows follow through mesh_gather_rows(src, remap, K)."""
+    kp = L.as_dtype(torch.uint8, False, keep, "keep")
+    if kp.dim() != 1:
+        raise ValueError(f"keep must be (n,), got {tuple(kp.shape)}")
+    n, dev = kp.shape[0], kp.device
+    if n >= 2 ** 31:
+        raise ValueError(f"keep: {n} points, supported below 2^31")
+    kept = torch.empty(n, dtype=torch.int32, device=dev)
+    remap = torch.empty(n, dtype=torch.int32, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    nbytes = L.load().mvd_cloud_select_workspace_bytes(n)
+    ws = workspace(nbytes, dev)
+    call("mvd_cloud_select", dev, kp, n, kept, remap, total, ws, int(nbytes))
+    K = int(total.item())
+    return kept[:K].clone(), remap, K
+
+
 MESH_MAX_PAIRS = 1 << 28    # mesh_grid's default bound on the (cell, triangle) pairs: 2^28 pairs are 15 GB of keys, permutation and records
 MESH_MAX_SAMPLES = 1 << 28  # mesh_sample's default bound on the samples
 _MESH_HARD_LIMIT = 2 ** 31 - 1
