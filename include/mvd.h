@@ -487,7 +487,8 @@ int mvd_softmax_regress_pp_f32(const float* cost, const float* depth_hypos, int 
  *   grid_sample, i.e. the sample index to [((1 - c) w - 1) / 2, ((1 + c) w - 1) / 2]: on maps narrower than 10 pixels a sample far
  *   outside the map then still takes a part of the rim pixel (at w = 8 the index stops at 7.9).  The kernel clamps the index to that
  *   interval (within its own [-1, w]); on wider maps it changes nothing.  grid_clamp <= 0: no such clamp (mvd_sweep_reduce_f32's values).
- *   C a multiple of 4 up to 64, C / groups a multiple of 4; all maps 16-byte aligned (MVD_ERR_INVALID_ARG otherwise).
+ *   C a multiple of 4 up to 64, C / groups a multiple of 4; key_feat, src_feat[v] and out[0] 16-byte aligned, out[v > 0] 4-byte (the
+ *   slices that follow out[0] in one buffer are not 16-byte aligned when B D h w groups is no multiple of 4) (MVD_ERR_INVALID_ARG otherwise).
  * No workspace, no repacking launches; without grid_clamp bit-identical to mvd_sweep_reduce_f32's group correlation on the same
  * values, permuted. */
 int mvd_sweep_groupcorr_nhwc_f32(const float* key_feat, const float* const* src_feat, const float* const* M, const float* depth,

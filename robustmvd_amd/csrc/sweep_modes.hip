@@ -80,12 +80,7 @@ __global__ void __launch_bounds__(256) sweep_reduce_tile_kernel(ReduceParams p, 
                 const long long po = pix0 + p4;
                 float* o = p.out.p[0] + (((size_t)b * C + ch) * D + d) * dplane + po;
                 const float4 r = *reinterpret_cast<const float4*>(tile[buf] + ch * ppw + p4);
-                if (po + 3 < npix) *reinterpret_cast<float4*>(o) = r;
-                else {
-                    if (po < npix) o[0] = r.x;
-                    if (po + 1 < npix) o[1] = r.y;
-                    if (po + 2 < npix) o[2] = r.z;
-                }
+                if (po < npix) *reinterpret_cast<float4*>(o) = r;  // npix and po are multiples of 4: the four pixels are inside together
             } else {
                 for (int e = tid; e < 1024; e += 256) {
                     const int ch = e / ppw, pp = e % ppw;
@@ -258,7 +253,10 @@ int mvd_sweep_groupcorr_nhwc_f32(const float* key_feat, const float* const* src_
     ReduceParams p{};
     for (int v = 0; v < V; ++v) {
         MVD_REQUIRE(src_feat[v] && M[v] && out[v], "sweep_groupcorr_nhwc: NULL view %d", v);
-        MVD_REQUIRE((((uintptr_t)src_feat[v] | (uintptr_t)out[v]) & 15) == 0, "sweep_groupcorr_nhwc: src_feat[%d] and out[%d] must be 16-byte aligned", v, v);
+        MVD_REQUIRE(((uintptr_t)src_feat[v] & 15) == 0, "sweep_groupcorr_nhwc: src_feat[%d] must be 16-byte aligned", v);
+        // out[0] like every map; the further volumes may be the slices that follow it in one buffer, which are only float-aligned
+        // when B D h w groups is no multiple of 4 (the kernel stores them one float at a time)
+        MVD_REQUIRE(((uintptr_t)out[v] & (v == 0 ? 15 : 3)) == 0, "sweep_groupcorr_nhwc: out[%d] must be %d-byte aligned", v, v == 0 ? 16 : 4);
         p.src.p[v] = src_feat[v];
         p.M.p[v] = M[v];
         p.out.p[v] = out[v];

@@ -7,6 +7,7 @@ import torch
 
 from conftest import load_golden
 import gen_common as gc
+from sweep_reduce_cases import sweep_inputs
 from test_vis_mvsnet_cpu import (CASES, FUSE_SHAPES, SA_SHAPES, fuse_inputs, fuse_reference, golden_state_dict, groupcorr_reference, sa_inputs,
                                  sa_reference)
 
@@ -34,30 +35,6 @@ def bordered(x):
     buf = torch.zeros((B, h + 3, w + 3, C), dtype=torch.float32, device=x.device)
     buf[:, 1:h + 1, 1:w + 1, :] = x.permute(0, 2, 3, 1)
     return buf
-
-
-def sweep_inputs(B, C, h, w, D, V, seed, dev):
-    """features, [R|t] per view, and hypotheses that push samples across every border and behind the camera: planes from a negative
-    depth over depths close to the camera (large parallax) to far ones, where the source camera's 3 x longer focal length pushes the
-    map's rim out through all four borders; per pixel spread by +-50 %."""
-    rng = np.random.default_rng(seed)
-    feats = [T(rng.standard_normal((B, C, h, w)).astype(np.float32), dev) for _ in range(V + 1)]
-    K = gc.synthetic_intrinsics(h, w).astype(np.float64)
-    Ksrc = K.copy()
-    Ksrc[0, 0] *= 3.0
-    Ksrc[1, 1] *= 3.0
-    Ms = []
-    for v in range(V):
-        m = []
-        for b in range(B):
-            P = gc.synthetic_pose(rng, 0.1, 0.3).astype(np.float64)
-            P[:3, 3] *= np.array([1, -1, 1]) * (-1) ** (v + b)
-            m.append((Ksrc @ P[:3, :4] @ np.linalg.inv(np.vstack([np.hstack([K, np.zeros((3, 1))]), [0, 0, 0, 1]])))[:3, :4])
-        Ms.append(T(np.stack(m).astype(np.float32), dev))
-    planes = np.concatenate(([-0.7], np.geomspace(1.5, 20.0, D - 1))) if D > 1 else np.array([1.0])
-    shared = T(np.stack([planes * (1 + 0.1 * b) for b in range(B)]).astype(np.float32), dev)
-    per_pixel = (shared[:, :, None, None] * (0.5 + torch.from_numpy(rng.random((B, D, h, w)).astype(np.float32)).to(dev))).contiguous()
-    return feats, Ms, shared, per_pixel
 
 
 def border_crossings(Ms, shared, h, w):

@@ -11,8 +11,8 @@
     channel count without a backward kernel at the call;
 (c) the inference entries still refuse an input that requires grad (ops.inference_only).
 
-The restatement computes the sampling positions in float32 with the kernels' formulas (a fused multiply-add is taken as the
-float64 product and sum rounded to float32) and gathers by index in float64 under autograd."""
+The restatement computes the sampling positions in float32 with the kernels' formulas (a fused multiply-add is the exact product and
+sum rounded once to float32: _fma) and gathers by index in float64 under autograd."""
 import ctypes
 
 import numpy as np
@@ -27,7 +27,18 @@ f32 = np.float32
 
 # ------------------------------------------------------------------------------------------------ the restatement
 def _fma(a, b, c):
-    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(f32)
+    """fmaf of float32 operands, rounded ONCE.  The product is exact in float64; its sum with c is rounded to float64 (s) and
+    then to float32, which is the single rounding of the exact value unless s lies exactly half-way between two float32 and the
+    float64 rounding error e (Knuth's two-sum, exact) is not zero: then e's sign decides, not the tie rule."""
+    p, c = np.asarray(a, np.float64) * np.asarray(b, np.float64), np.asarray(c, np.float64)
+    with np.errstate(all="ignore"):
+        s = p + c
+        r = s.astype(f32)
+        bb = s - p
+        e = (p - (s - bb)) + (c - bb)
+        lo, hi = np.nextafter(s, -np.inf).astype(f32), np.nextafter(s, np.inf).astype(f32)
+        tie = np.isfinite(s) & (lo != hi) & (lo.astype(np.float64) * 0.5 + hi.astype(np.float64) * 0.5 == s) & (e != 0)
+    return np.where(tie, np.where(e > 0, hi, lo), r).astype(f32)
 
 
 def reduce_positions(M, depth, h, w, pix_offset, stretch):
@@ -61,18 +72,23 @@ def _gather4(src, cell_y, cell_x, wts):
     return torch.stack(out)
 
 
-def reduce_sample(src, M, depth, pix_offset, stretch):
+def reduce_sample(src, M, depth, pix_offset, stretch, bounds=None):
+    """bounds: (xlo, xhi, ylo, yhi) float32 within [-1, w] x [-1, h], sweep_groupcorr_nhwc_kernel's second clamp of the position."""
     h, w = src.shape[-2:]
     ix, iy = reduce_positions(M, depth, h, w, pix_offset, stretch)
+    if bounds is not None:
+        xlo, xhi, ylo, yhi = (f32(v) for v in bounds)
+        ix, iy = np.clip(ix, xlo, xhi), np.clip(iy, ylo, yhi)
     xf, yf = np.floor(ix), np.floor(iy)
     wx, wy = ix - xf, iy - yf
     ux, uy = f32(1) - wx, f32(1) - wy
     return _gather4(src, yf.astype(np.int64) + 1, xf.astype(np.int64) + 1, (ux * uy, wx * uy, ux * wy, wx * wy))
 
 
-def sweep_reduce_restated(key, srcs, Ms, depth, mode, groups=1, pix_offset=0.0, stretch=True):
-    """key, srcs: float64 tensors (B,C,h,w); Ms, depth: float32 arrays.  mode "variance" | "keysq" | "groupcorr"."""
-    sv = [reduce_sample(s, M, depth, pix_offset, stretch) for s, M in zip(srcs, Ms)]
+def sweep_reduce_restated(key, srcs, Ms, depth, mode, groups=1, pix_offset=0.0, stretch=True, bounds=None):
+    """key, srcs: float64 tensors (B,C,h,w); Ms, depth: float32 arrays.  mode "variance" | "keysq" | "groupcorr".
+    bounds: reduce_sample's (the group correlation's grid_clamp; None: the kernels' clamp to [-1, w] x [-1, h] alone)."""
+    sv = [reduce_sample(s, M, depth, pix_offset, stretch, bounds) for s, M in zip(srcs, Ms)]
     k = key.unsqueeze(2)
     if mode == "groupcorr":
         B, C, D, h, w = sv[0].shape
